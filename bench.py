@@ -12,7 +12,7 @@ canonical length 40, beam 10, lm_alpha 0.  `--workload greedy32` runs configs[1]
 The headline `value` carries `--fuse` (default 8) reference batches per launch sequence (every utterance full length).  The
 reference masks nothing, so an utterance's result depends on its batch's padded lengths; mdd_forward_fused carries batches of
 DIFFERENT padded lengths in one launch sequence with per-row (T_g, L_g), bit-identical to running each batch alone.  What real
-(ragged) data gets is reported in the same JSON line under `variants` (same run, rank 0, N=1): `ragged` (len ~ U[0.5,1] x 10 s,
+(ragged) data gets is reported in the same JSON line under `variants` (same run with `--full`, rank 0, N=1): `ragged` (len ~ U[0.5,1] x 10 s,
 every batch padded to its own maximum, 8 such batches per fused pass, frames counted UNPADDED), `ragged_fuse1` / `fuse1` (a lone
 B=64 batch per pass: the latency-bound case), `bf16x3_mode` (the flagged split-bf16 arithmetic, narrower than the reference's:
 MDD_PRECISION=bf16x3), `greedy32_h256` (configs[1]) and `train32_f32` / `train32_bf16x3` (configs[4]'s per-GPU shard: a full training
@@ -29,8 +29,11 @@ over RCCL/xGMI each step on a stream of their own, behind the next pass's forwar
 names: 2.9 MB per rank and batch, 23 MB per rank and 8-batch pass), or -- the default, since nothing downstream of the decode
 consumes the other ranks' posteriors -- the decoded ids (`--gather ids`: [B, T'] int32 + lengths, 0.5 MB per rank and pass).
 
-Prints ONE JSON line on rank 0 (see the driver contract in the task statement) including `roofline`
-for the dominant kernel and a `cpu_baseline` measured in the same run on the host cores.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times `--steps` steps and prints the headline (`metric`, `value`,
+`unit`, `higher_is_better`, `dtype`, `ms_per_step`).  Everything else takes runs of its own and is measured only with `--full`: the
+`roofline` of the dominant kernel (stage replay), the `cpu_baseline` and `accuracy` on the host cores, the `variants`, the check of the
+N>1 exchange (`gather_verified`) and the train32 stage split.  `--dump-outputs DIR` writes what the last timed pass returned to its
+caller as DIR/<name>.npy (float32, float64 where the path computes in float64); the inputs are seeded, so two builds can be compared.
 """
 import argparse
 import json
@@ -49,6 +52,25 @@ PEAK_BF16_MATRIX_TFLOPS = 2500.0 # dense bf16 MFMA peak (not the 2:1-sparsity fi
 PEAK_HBM_GBS = 8000.0
 PMC_FILE = os.path.join(ROOT, "profiles", "round3_pmc_traffic.json")
 T_RAW, D_RAW, L_CANON, BEAM_W, N_CLASS = 1000, 81, 40, 10, 45
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays, utt_axis):
+    """--dump-outputs: every array as <path>/<name>.npy, float32 (float64 where the path computes in float64).  utt_axis names each
+    array's utterance axis (None: the array has none).  Over DUMP_BYTES in all, a fixed seeded sample of the utterances is kept;
+    `utterance` holds the indices of the utterances written."""
+    arrays = {n: np.asarray(a, dtype=np.float64 if np.asarray(a).dtype == np.float64 else np.float32) for n, a in arrays.items()}
+    n_utt = next(a.shape[utt_axis[n]] for n, a in arrays.items() if utt_axis[n] is not None)
+    per_utt = 4 + sum(a.nbytes for n, a in arrays.items() if utt_axis[n] is not None) // n_utt    # 4: its entry in `utterance`
+    fixed = 4096 + sum(a.nbytes for n, a in arrays.items() if utt_axis[n] is None)              # 4096: the .npy headers
+    keep = np.arange(n_utt)
+    if fixed + per_utt * n_utt > DUMP_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(n_utt, (DUMP_BYTES - fixed) // per_utt, replace=False))
+        arrays = {n: a if utt_axis[n] is None else np.take(a, keep, axis=utt_axis[n]) for n, a in arrays.items()}
+    arrays["utterance"] = keep.astype(np.float32)
+    os.makedirs(path, exist_ok=True)
+    for n, a in arrays.items():
+        np.save(os.path.join(path, n + ".npy"), a)
 
 
 def parse():
@@ -63,14 +85,21 @@ def parse():
     ap.add_argument("--fuse", type=int, default=8, help="reference-sized batches carried by one launch sequence")
     ap.add_argument("--ragged", action="store_true", help="headline on the ragged set (per-batch padding, unpadded frames counted)")
     ap.add_argument("--precision", default=None, choices=[None, "f32", "f32x6", "bf16x3"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-variants", action="store_true", help="skip the fuse1 / ragged / f32_mode / greedy32_h256 lines")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what takes runs of its own: roofline, CPU baseline and accuracy, variants, N>1 exchange check, train32 stage split")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed pass returned as DIR/<name>.npy (float32 / float64, at most 64 MB: a seeded sample of utterances beyond)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and accuracy")
+    ap.add_argument("--no-variants", action="store_true", help="with --full: skip the fuse1 / ragged / f32_mode / greedy32_h256 lines")
     ap.add_argument("--gather", default="ids", choices=["ids", "posteriors", "none"],
                     help="what the ranks exchange per pass at N>1 (own stream, overlapped with the next forward): decoded ids (default) or the posteriors")
     ap.add_argument("--no-gather", action="store_true", help="same as --gather none")
     ap.add_argument("--decoder", default=None, choices=[None, "beam", "greedy", "none"], help="diagnostic override of the decode stage")
-    ap.add_argument("--no-roofline", action="store_true", help="skip the stage-replay pass (for clean traces)")
-    return ap.parse_args()
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the stage-replay pass (for clean traces)")
+    args = ap.parse_args()
+    if args.ragged and args.fuse > 1 and args.steps % args.fuse:
+        ap.error("--ragged runs whole passes of --fuse batches: --steps must be a multiple of --fuse")
+    return args
 
 
 class Ctx(object):
@@ -309,10 +338,11 @@ class DecodeJob(object):
         if self.gather is not None and self.last_slot == ((q - 1) & 3):   # idle time of the forward stream between two consecutive passes
             self.fwd_gap_ms.append(self.ev_tf1[self.last_slot].elapsed_time(self.ev_tf0[q]))
         self.last_slot = q
-        tot = 0
+        tot, d = 0, None
         if self.decoder_kind != "none":
             d = align_ids_batch(bf.h_ids[k].numpy(), bf.h_n[k].numpy(), bf.canon, bf.canon_len)[0]   # one native call per pass
             tot = int(d[d >= 0].sum())
+        self.last = (bf, k, d)
         self.aligned.append(tot)
         self.frames_done += bf.frames
 
@@ -369,6 +399,27 @@ class DecodeJob(object):
             self.ctx.dist.all_reduce(t, op=self.ctx.dist.ReduceOp.MAX)
             dt = float(t.item())
         return dt, self.frames_done
+
+    def last_outputs(self):
+        """What the last finished pass handed its caller: log-probs [T', b, C] (frames past a row's own batch length zeroed: a fused
+        pass leaves them unwritten), and with a decoder the decoded ids [b, T'] (-1 past each row's length), their lengths, the beam's
+        status and score, and the edit distance to the canonical phonemes [b]."""
+        bf, k, dist = self.last
+        torch.cuda.synchronize()
+        logp = bf.logp[k].cpu().numpy()
+        if self.ragged:
+            frames = bf.bframes.cpu().numpy()
+            logp[np.arange(logp.shape[0])[:, None] >= frames[None, :]] = 0.0
+        out = {"log_probs": logp}
+        if self.decoder_kind != "none":
+            dev = [t.cpu().numpy() for t in bf.dev_out[k]]
+            ids, n = dev[0], dev[1]
+            out["decoded_ids"] = np.where(np.arange(ids.shape[1])[None, :] < n[:, None], ids, -1)
+            out["decoded_len"] = n
+            if self.decoder_kind == "beam":
+                out["beam_status"], out["beam_score"] = dev[2], dev[3]
+            out["edit_distance"] = dist
+        return out
 
     def verify_gather(self):
         """N>1: every rank's slice of the last exchanged buffers equals its own results, and the slices of the other ranks
@@ -515,7 +566,8 @@ def ctc_workload(ctx, args):
     dt = time.perf_counter() - t0
     kern_ms = e0.elapsed_time(e1) / args.steps
     alg_bytes = 2.0 * T * B * Cn * 4
-    return dt, B * T * args.steps, {"kernel": "ctc_kernel", "bound": "hbm", "achieved": round(alg_bytes / (kern_ms * 1e-3) / 1e9, 2),
+    outs = {"nll": nll.cpu().numpy(), "grad": grad.cpu().numpy()} if args.dump_outputs else None
+    return dt, B * T * args.steps, outs, {"kernel": "ctc_kernel", "bound": "hbm", "achieved": round(alg_bytes / (kern_ms * 1e-3) / 1e9, 2),
                                     "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": round(alg_bytes / (kern_ms * 1e-3) / 1e9 / PEAK_HBM_GBS, 4),
                                     "traffic": None, "avg_launch_us": round(kern_ms * 1e3, 2), "bytes_per_launch": alg_bytes,
                                     "note": "lattice recurrences are T' dependent steps per utterance: latency-, not bandwidth-bound at B=256"}
@@ -547,11 +599,13 @@ def train_workload(ctx, args):
     tl = torch.full((B,), L, dtype=torch.int64).cuda()
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
     stage = np.zeros(4)
+    held = {}
 
     def step(timed):
         if timed:
             ev[0].record()
         out = model(xd, x1d)
+        held["log_probs"] = out
         if timed:
             ev[1].record()
         loss = loss_fn(out, tg, il, tl) / B
@@ -577,15 +631,18 @@ def train_workload(ctx, args):
         last = step(False)
     ctx.barrier()
     dt = time.perf_counter() - t0
-    for _ in range(3):                                              # stage split, outside the timed region (it synchronises per step)
-        step(True)
+    outs = {"loss": np.float64(float(last)), "log_probs": held["log_probs"].detach().cpu().numpy()} if args.dump_outputs else None
+    info = {"loss_first": round(float(first), 4), "loss_last": round(float(last), 4), "batch_per_gpu": B}
+    if args.full:
+        for _ in range(3):                                          # stage split, outside the timed region (it synchronises per step)
+            step(True)
+        info.update({"forward_ms": round(stage[0] / 3, 3), "loss_backward_ms": round(stage[1] / 3, 3),
+                     "allreduce_ms": round(stage[2] / 3, 3), "adam_ms": round(stage[3] / 3, 3)})
     if ctx.dist is not None:
         t = torch.tensor([dt], dtype=torch.float64, device="cpu" if ctx.dist.get_backend() == "gloo" else "cuda")
         ctx.dist.all_reduce(t, op=ctx.dist.ReduceOp.MAX)
         dt = float(t.item())
-    return dt, B * (T // 2) * args.steps, {"forward_ms": round(stage[0] / 3, 3), "loss_backward_ms": round(stage[1] / 3, 3),
-                                              "allreduce_ms": round(stage[2] / 3, 3), "adam_ms": round(stage[3] / 3, 3),
-                                              "loss_first": round(float(first), 4), "loss_last": round(float(last), 4), "batch_per_gpu": B}
+    return dt, B * (T // 2) * args.steps, outs, info
 
 
 def main():
@@ -596,7 +653,9 @@ def main():
     rank, world = ctx.rank, ctx.world
 
     if args.workload == "ctc256":
-        dt, frames, roof = ctc_workload(ctx, args)
+        dt, frames, outs, roof = ctc_workload(ctx, args)
+        if rank == 0 and outs is not None:
+            dump_outputs(args.dump_outputs, outs, {"nll": 0, "grad": 1})
         if rank == 0:
             print(json.dumps({"metric": "phoneme-frames/sec CTC loss+grad lattice", "value": round(world * frames / dt, 1), "unit": "phoneme-frames/s",
                               "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 4),
@@ -606,7 +665,9 @@ def main():
         return
 
     if args.workload == "train32":
-        dt, frames, info = train_workload(ctx, args)
+        dt, frames, outs, info = train_workload(ctx, args)
+        if rank == 0 and outs is not None:
+            dump_outputs(args.dump_outputs, outs, {"loss": None, "log_probs": 1})
         if rank == 0:
             flop = 3.0 * 38.2e6 * (frames / args.steps)             # forward + ~2x for the backward, per step (38.2 MFLOP / frame)
             print(json.dumps({"metric": "phoneme-frames/sec training step (fwd + CTC + bwd + all-reduce + Adam)", "value": round(world * frames / dt, 1),
@@ -630,6 +691,9 @@ def main():
     job = DecodeJob(ctx, args, hidden=args.hidden, joint=joint, fuse=args.fuse, ragged=args.ragged, precision=args.precision,
                     decoder_kind=args.decoder, gather="none" if args.no_gather else args.gather)
     dt, frames = job.timed(args.steps, args.warmup)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, job.last_outputs(), {"log_probs": 1, "decoded_ids": 0, "decoded_len": 0, "beam_status": 0,
+                                                             "beam_score": 0, "edit_distance": 0})
     G = max(1, min(args.fuse, args.steps))
     if ctx.dist is not None:
         ft = torch.tensor([frames], dtype=torch.float64, device="cpu" if ctx.dist.get_backend() == "gloo" else "cuda")
@@ -640,7 +704,7 @@ def main():
     value = frames_all / dt
     precision = job.model.precision
     checksum = int(sum(job.aligned))
-    gather_ok = job.verify_gather()
+    gather_ok = job.verify_gather() if args.full else None
     gather_kind = job.gather
     gather_timing = None
     if job.gather is not None and job.gather_ms:
@@ -649,12 +713,12 @@ def main():
                          "note": "gap = idle time of the forward stream between consecutive passes (device timestamps); the exchange of pass i runs on "
                                  "its own stream beside the forward of pass i+1"}
 
-    roof = job.roofline(G) if (rank == 0 and not args.no_roofline) else None
+    roof = job.roofline(G) if (rank == 0 and args.full and not args.no_roofline) else None
 
     # ---- CPU baseline: the torch-CPU + Python-beam port of the reference path on a bounded sample
     cpu = None
     accuracy = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.ragged:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and not args.ragged:
         from oracle import ref_port
         from ctc_attention_mispronunciation_amd.utils.data_loader import stack_features
         ncores = min(os.cpu_count() or 1, 16)
@@ -687,7 +751,7 @@ def main():
 
     # ---- the same hot path in the configurations real data and the other BASELINE configs get (rank 0, N=1 only)
     variants = None
-    if rank == 0 and world == 1 and not args.no_variants and joint and not args.ragged:
+    if rank == 0 and world == 1 and args.full and not args.no_variants and joint and not args.ragged:
         variants = {
             "fuse1": variant(ctx, args, "fuse1", hidden=args.hidden, joint=True, fuse=1, ragged=False, precision=args.precision, steps=32, warmup=8),
             "ragged": variant(ctx, args, "ragged", hidden=args.hidden, joint=True, fuse=args.fuse, ragged=True, precision=args.precision, steps=64, warmup=16),
@@ -700,8 +764,8 @@ def main():
                                            steps=32, warmup=8),
         }
         for mode in ("f32", "bf16x3"):          # BASELINE configs[4]'s per-GPU shard: one full training step (--workload train32 has the stage split)
-            targs = argparse.Namespace(**dict(vars(args), steps=10, warmup=3, train_precision=mode))
-            tdt, tframes, tinfo = train_workload(ctx, targs)
+            targs = argparse.Namespace(**dict(vars(args), steps=10, warmup=3, train_precision=mode, dump_outputs=None))
+            tdt, tframes, _, tinfo = train_workload(ctx, targs)
             variants["train32_" + mode] = {"value": round(tframes / tdt, 1), "unit": "phoneme-frames/s", "ms_per_step": round(tdt / targs.steps * 1e3, 3),
                                            "steps": targs.steps, "batch": 32, "precision": mode, "forward_ms": tinfo["forward_ms"],
                                            "loss_backward_ms": tinfo["loss_backward_ms"], "adam_ms": tinfo["adam_ms"]}
@@ -729,7 +793,7 @@ def main():
             "roofline": roof, "cpu_baseline": cpu, "accuracy": accuracy, "variants": variants,
             "edit_distance_checksum": checksum,
         }
-        if gather_ok is not None:
+        if gather_kind is not None:
             line["gather_verified"] = gather_ok
             line["gather_timing"] = gather_timing
         if variants:

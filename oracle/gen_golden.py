@@ -19,6 +19,7 @@ What is imported:
   all of the above chained as AA/infer.py:294-342 does, at T'=250 -> G9 (g9_chain.*)
   the same chain for each of the 20 words of egs/vocabulary/single, canonicals from AA/dict/phonetic_dict.py's CMU lookup -> G12
   torch.nn.CTCLoss(reduction='sum') as called at AA/steps/train_ctc.py:72,186 -> G5
+  G2's and G11's cases again with the model in float64 (module.double()) -> g2_ref64.npz, g11_train64.npz
 
 Usage:  python oracle/gen_golden.py            (writes tests/golden/*)
 """
@@ -737,6 +738,51 @@ def gen_words_goldens():
     json.dump(meta, open(os.path.join(OUT, "g12_words.json"), "w"))
 
 
+# ----------------------------------------------------------------------------- G2 / G11 in float64
+def gen_float64_goldens():
+    """G2 and G11 again with the REFERENCE model and its inputs in float64 (module.double()).  ATen's fp32 kernels round differently
+    with the CPU's vector width and thread count, so a port's fp32 output matches the fp32 goldens only to within that drift; in
+    float64 the same graph agrees to ~1e-12 on any CPU, which pins oracle/ref_port's graph tightly wherever the suite runs."""
+    out = {}
+    for meta in json.load(open(os.path.join(OUT, "g2_ref.json"))):
+        geom = synth.Geometry(**meta["geom"])
+        sd = synth.synth_state_dict(geom, seed=meta["seed"])
+        x, x1, _, _ = synth.synth_batch(geom, B=meta["B"], T=meta["T"], L=meta["L"], seed=meta["seed"])
+        m = build_reference_model(geom, sd).double()
+        with torch.no_grad():
+            out[meta["tag"] + "_logp"] = m(torch.from_numpy(x).double(), torch.from_numpy(x1)).numpy()
+    np.savez_compressed(os.path.join(OUT, "g2_ref64.npz"), **out)
+    arrays = {}
+    g32 = np.load(os.path.join(OUT, "g11_train.npz"))
+    for rec in json.load(open(os.path.join(OUT, "g11_train.json"))):
+        tag = rec["tag"]
+        geom = synth.Geometry(**rec["geom"])
+        sd, x, x1, masks, tg, il, tl = synth.train_case(geom, rec["seed"], rec["B"], rec["T"], rec["L"], rec["Lt"])
+        m = build_reference_model(geom, sd).double()
+        m.train()
+        drops = [m.conv[0], m.conv[1]] + [m.rnns[i] for i in range(geom.layers)]
+        for mod, mk in zip(drops, masks):
+            mod.dropout = GivenDropout(mk, 0.2)
+            mod.dropout.noise = mod.dropout.noise.double()
+        with torch.enable_grad():
+            o = m(torch.from_numpy(x).double(), torch.from_numpy(x1))
+            loss = nn.CTCLoss(reduction="sum")(o, torch.from_numpy(tg), torch.from_numpy(il), torch.from_numpy(tl)) / rec["B"]
+            loss.backward()
+        arrays[tag + "_logp"] = o.detach().numpy()
+        arrays[tag + "_loss"] = np.float64(loss.item())
+        for k, prm in m.named_parameters():
+            if tag + "_grad_" + k in g32.files:
+                arrays["%s_grad_%s" % (tag, k)] = prm.grad.numpy()
+            else:                                                  # the entries G11 samples
+                arrays["%s_gval_%s" % (tag, k)] = prm.grad.numpy().ravel()[g32["%s_gidx_%s" % (tag, k)]]
+            arrays["%s_gnorm_%s" % (tag, k)] = np.float64(np.sqrt((prm.grad.numpy() ** 2).sum()))
+        for k, bufv in m.named_buffers():
+            if "running_" in k:
+                arrays["%s_run_%s" % (tag, k)] = bufv.numpy().copy()
+        print("G2/G11 float64", tag, "loss %.12f (fp32 golden %.6f)" % (loss.item(), rec["loss"]))
+    np.savez_compressed(os.path.join(OUT, "g11_train64.npz"), **arrays)
+
+
 # ----------------------------------------------------------------------------- G11 (SURVEY 8(f) #3: one training step)
 class GivenDropout(nn.Module):
     """nn.Dropout with the mask handed in: y = x * (mask / (1-p)), the arithmetic of ATen's dropout with a fixed noise tensor."""
@@ -793,7 +839,7 @@ def gen_train_goldens():
 
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
-    which = sys.argv[1:] or ["model", "decode", "align", "eval", "ctc", "input", "chain", "aug", "train", "words"]
+    which = sys.argv[1:] or ["model", "decode", "align", "eval", "ctc", "input", "chain", "aug", "train", "words", "float64"]
     with torch.no_grad():
         if "model" in which:
             gen_model_goldens()
@@ -815,3 +861,5 @@ if __name__ == "__main__":
         gen_train_goldens()
     if "words" in which:
         gen_words_goldens()
+    if "float64" in which:                   # after "model" and "train": reads their case lists and G11's sampled indices
+        gen_float64_goldens()

@@ -922,7 +922,7 @@ def test_bench_two_ranks_rehearsal(what):
     env = dict(os.environ, MDD_DIST_BACKEND="gloo", MDD_LSTM="step", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--fuse", "1",
-           "--no-cpu-baseline", "--no-roofline", "--gather", what]
+           "--full", "--no-cpu-baseline", "--no-roofline", "--gather", what]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -946,7 +946,7 @@ def test_bench_exchange_runs_beside_the_next_forward():
     env = dict(os.environ, MDD_FORCE_DIST="1", MDD_LSTM="step", MDD_BENCH_GATHER_DELAY_MS="12", HSA_ENABLE_IPC_MODE_LEGACY="0",
                MASTER_ADDR="127.0.0.1", MASTER_PORT="29571", RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2", "--fuse", "1",
-           "--no-cpu-baseline", "--no-roofline", "--no-variants", "--gather", "posteriors"]
+           "--full", "--no-cpu-baseline", "--no-roofline", "--no-variants", "--gather", "posteriors"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -955,6 +955,45 @@ def test_bench_exchange_runs_beside_the_next_forward():
     assert out["gather_verified"] is True and gt["what"] == "posteriors"
     assert gt["gather_ms_median"] > 4.0                          # the stretched exchange
     assert gt["forward_stream_gap_ms_median"] < 0.25 * gt["gather_ms_median"] and gt["forward_stream_gap_ms_median"] < 1.0
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain bench.py run (no --full): the headline line with exactly --steps timed steps and none of --full's extras; with
+    --dump-outputs, the last timed pass's results as float arrays.  --steps 3 --fuse 2 makes the passes [2 batches, 1 batch], so the
+    last pass is the first 64 seeded utterances alone: its log-probs equal a lone forward_raw of them, its decoded ids stop at
+    their lengths, and its edit distances to the 40 canonical phonemes lie within the bounds their lengths allow."""
+    import subprocess
+    import sys
+    from tests.helpers import ROOT
+    from ctc_attention_mispronunciation_amd.hip_model import HipModel
+    dump = tmp_path / "out"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--fuse", "2",
+           "--dump-outputs", str(dump)]
+    r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    out = json.loads(lines[0])
+    assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["value"] > 0 and out["higher_is_better"] is True
+    assert out["unit"] == "phoneme-frames/s" and out["dtype"].startswith("f32")
+    assert out["roofline"] is None and out["cpu_baseline"] is None and out["accuracy"] is None and out["variants"] is None
+    got = {p.stem: np.load(p) for p in dump.glob("*.npy")}
+    assert set(got) == {"log_probs", "decoded_ids", "decoded_len", "beam_status", "beam_score", "edit_distance", "utterance"}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert sum(p.stat().st_size for p in dump.glob("*.npy")) <= 64 << 20
+    B, Tp = 64, 250
+    assert got["log_probs"].shape == (Tp, B, 45) and got["decoded_ids"].shape == (B, Tp)
+    np.testing.assert_array_equal(got["utterance"], np.arange(B))
+    n, ids, d = got["decoded_len"].astype(int), got["decoded_ids"], got["edit_distance"].astype(int)
+    assert all(((ids[b, :n[b]] > 0) & (ids[b, :n[b]] < 45)).all() and (ids[b, n[b]:] == -1).all() for b in range(B))
+    assert all(abs(n[b] - 40) <= d[b] <= max(n[b], 40) if n[b] else d[b] == -1 for b in range(B))     # canonical length 40
+    geom = synth.Geometry(feat=243, hidden=384, layers=4, num_class=45)
+    raw = synth.synth_raw_features(128, 1000, 81, seed=1234)[:B]
+    x1 = synth.synth_batch(geom, B=128, T=500, L=40, seed=1234, ragged=False)[1][:B]
+    m = HipModel(geom, synth.synth_state_dict(geom, seed=1234), device=0)
+    want = m.forward_raw(_cuda(raw), _cuda(x1), sync_errors=True).cpu().numpy()
+    m.close()
+    np.testing.assert_allclose(got["log_probs"], want, rtol=0, atol=1e-6)
 
 
 @pytest.mark.parametrize("L,T,B", [(40, 250, 8), (100, 300, 3), (200, 420, 2), (63, 130, 4), (64, 130, 4), (1, 5, 3)])

@@ -331,3 +331,36 @@ def test_asm_mfma_hazards(tmp_path):
         r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "check_mfma_hazards.py"), out] + pat, capture_output=True, text=True)
         assert r.returncode == 0 and " 0 finding(s)" in r.stdout, unit + ":\n" + r.stdout[:3000]
         assert not r.stdout.startswith("0 kernel(s)"), unit
+
+
+def test_bench_dump_outputs_types_budget_and_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs' writer: integers and float32 as float32, float64 kept; within the byte budget every utterance,
+    beyond it the same fixed seeded sample of utterances from every array (each along its own utterance axis), files within budget."""
+    import bench
+    rs = np.random.default_rng(3)
+    arrays = {"log_probs": rs.standard_normal((50, 40, 45)).astype(np.float32), "ids": rs.integers(0, 45, size=(40, 50)).astype(np.int32),
+              "score": rs.standard_normal(40), "loss": np.float64(1.5)}
+    axes = {"log_probs": 1, "ids": 0, "score": 0, "loss": None}
+
+    def written(d):
+        return {p.stem: np.load(p) for p in d.glob("*.npy")}, sum(p.stat().st_size for p in d.glob("*.npy"))
+    bench.dump_outputs(str(tmp_path / "all"), arrays, axes)
+    got, _ = written(tmp_path / "all")
+    assert {k: v.dtype for k, v in got.items()} == {"log_probs": np.float32, "ids": np.float32, "score": np.float64, "loss": np.float64,
+                                                    "utterance": np.float32}
+    np.testing.assert_array_equal(got["utterance"], np.arange(40))
+    for k in arrays:
+        np.testing.assert_array_equal(got[k], arrays[k])
+    monkeypatch.setattr(bench, "DUMP_BYTES", 200000)
+    for sub in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / sub), arrays, axes)
+    got, size = written(tmp_path / "s1")
+    again, _ = written(tmp_path / "s2")
+    keep = got["utterance"].astype(int)
+    assert size <= 200000 and 0 < len(keep) < 40 and (np.diff(keep) > 0).all()
+    for k in got:
+        np.testing.assert_array_equal(got[k], again[k])
+    np.testing.assert_array_equal(got["log_probs"], arrays["log_probs"][:, keep])
+    np.testing.assert_array_equal(got["ids"], arrays["ids"][keep])
+    np.testing.assert_array_equal(got["score"], arrays["score"][keep])
+    assert float(got["loss"]) == 1.5

@@ -119,14 +119,26 @@ def test_g6_stack_skip_and_lengths():
 
 
 # ---------------------------------------------------------------------------- the torch/Python port (CPU baseline)
+def _within_fp32_envelope(port32, ref32, ref64, what):
+    """fp32 log-probs no farther from the float64 reference than twice the reference's own fp32 run (max and mean): ATen's fp32
+    rounding moves with the CPU's vector width and thread count, so the fp32 goldens pin an fp32 port only to within that drift."""
+    d_port, d_ref = np.abs(port32.astype(np.float64) - ref64), np.abs(ref32.astype(np.float64) - ref64)
+    assert d_port.max() <= 2 * d_ref.max() and d_port.mean() <= 2 * d_ref.mean(), (what, d_port.max(), d_ref.max(), d_port.mean(), d_ref.mean())
+
+
 def test_ref_port_forward_matches_goldens():
+    """G2: the port's graph in float64 against the reference model run in float64 (g2_ref64, to 1e-10: on every CPU the two agree to
+    ~1e-14), and its fp32 run inside the reference's own fp32 error (g2_ref)."""
+    import torch
     from oracle import ref_port
-    g = npz("g2_ref.npz")
+    g, g64 = npz("g2_ref.npz"), npz("g2_ref64.npz")
     for meta in jload("g2_ref.json"):
         geom = synth.Geometry(**meta["geom"])
         sd = synth.synth_state_dict(geom, seed=meta["seed"])
         x, x1, _, _ = synth.synth_batch(geom, B=meta["B"], T=meta["T"], L=meta["L"], seed=meta["seed"])
-        np.testing.assert_allclose(ref_port.forward(sd, x, x1).numpy(), g[meta["tag"] + "_logp"], rtol=0, atol=2e-6)
+        ref64 = g64[meta["tag"] + "_logp"]
+        np.testing.assert_allclose(ref_port.forward(sd, x, x1, dtype=torch.float64).numpy(), ref64, rtol=0, atol=1e-10)
+        _within_fp32_envelope(ref_port.forward(sd, x, x1).numpy(), g[meta["tag"] + "_logp"], ref64, meta["tag"])
 
 
 def test_ref_port_decoders_match_goldens():
@@ -267,23 +279,27 @@ def test_g12_vocabulary_single_words_through_the_oracle():
 def test_g11_train_step_restatement(idx):
     """G11: the reference model in train mode (batch-statistics BatchNorm, given dropout masks), CTCLoss(sum)/B, backward --
     log-probs, loss, every parameter gradient, updated running statistics.  This pins oracle/ref_port.train_step (the torch
-    restatement that checks the HIP training step on shapes without a golden)."""
+    restatement that checks the HIP training step on shapes without a golden): in float64 against the reference model run in
+    float64 (g11_train64; on every CPU the two agree to ~1e-13), and its fp32 log-probs inside the reference's own fp32 error."""
+    import torch
     from oracle import ref_port
     meta = jload("g11_train.json")[idx]
-    g = npz("g11_train.npz")
+    g, g64 = npz("g11_train.npz"), npz("g11_train64.npz")
     tag = meta["tag"]
     geom = synth.Geometry(**meta["geom"])
     sd, x, x1, masks, tg, il, tl = synth.train_case(geom, meta["seed"], meta["B"], meta["T"], meta["L"], meta["Lt"])
-    logp, loss, grads, run = ref_port.train_step(sd, x, x1, masks, tg, il, tl, 0.2)
-    np.testing.assert_allclose(logp, g[tag + "_logp"], rtol=0, atol=2e-6)
-    assert abs(loss - meta["loss"]) <= 1e-5 * abs(meta["loss"])
+    logp, loss, grads, run = ref_port.train_step(sd, x, x1, masks, tg, il, tl, 0.2, dtype=torch.float64)
+    np.testing.assert_allclose(logp, g64[tag + "_logp"], rtol=0, atol=1e-10)
+    assert abs(loss - float(g64[tag + "_loss"])) <= 1e-12 * abs(float(g64[tag + "_loss"]))
     assert set(grads) == set(meta["tensors"])
     for k, info in meta["tensors"].items():
-        tol = 2e-6 * max(1.0, info["absmax"])
-        if tag + "_grad_" + k in g.files:
-            np.testing.assert_allclose(grads[k], g[tag + "_grad_" + k], rtol=0, atol=tol, err_msg=k)
+        tol = 1e-10 * max(1.0, info["absmax"])
+        if tag + "_grad_" + k in g64.files:
+            np.testing.assert_allclose(grads[k], g64[tag + "_grad_" + k], rtol=0, atol=tol, err_msg=k)
         else:
-            np.testing.assert_allclose(grads[k].ravel()[g[tag + "_gidx_" + k]], g[tag + "_gval_" + k], rtol=0, atol=tol, err_msg=k)
-        assert abs(np.sqrt((grads[k].astype(np.float64) ** 2).sum()) - info["norm"]) <= 1e-4 * max(info["norm"], 1e-6), k
+            np.testing.assert_allclose(grads[k].ravel()[g[tag + "_gidx_" + k]], g64[tag + "_gval_" + k], rtol=0, atol=tol, err_msg=k)
+        want = float(g64[tag + "_gnorm_" + k])
+        assert abs(np.sqrt((grads[k] ** 2).sum()) - want) <= 1e-10 * max(want, 1.0), k
     for k, v in run.items():
-        np.testing.assert_allclose(v, g["%s_run_%s" % (tag, k)], rtol=0, atol=1e-6, err_msg=k)
+        np.testing.assert_allclose(v, g64["%s_run_%s" % (tag, k)], rtol=0, atol=1e-12, err_msg=k)
+    _within_fp32_envelope(ref_port.train_step(sd, x, x1, masks, tg, il, tl, 0.2)[0], g[tag + "_logp"], g64[tag + "_logp"], tag)

@@ -9,10 +9,10 @@ OUT=$R/gpurun_out
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 LEAN="--no-variants --no-cpu-baseline"
-python3 $R/bench.py 2> $OUT/${TAG}_bench.err | tee $OUT/${TAG}_bench.json
+python3 $R/bench.py --full 2> $OUT/${TAG}_bench.err | tee $OUT/${TAG}_bench.json
 stats() {   # stats <name> <bench args...>
   local name=$1; shift
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_${name}_stats -o ${TAG} -- python3 $R/bench.py "$@" > $OUT/${TAG}_${name}_profiled.json 2> $OUT/${TAG}_${name}_stats.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_${name}_stats -o ${TAG} -- python3 $R/bench.py --full "$@" > $OUT/${TAG}_${name}_profiled.json 2> $OUT/${TAG}_${name}_stats.err
   find $OUT/${TAG}_${name}_stats -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $OUT/${TAG}_${name}_kernel_stats.csv
 }
 stats joint $LEAN
