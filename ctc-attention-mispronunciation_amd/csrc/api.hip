@@ -96,6 +96,7 @@ struct mdd_model {
     bool lstm_persist_f32 = true;
     bool lstm_persist_x6 = true;     // MDD_LSTM_X6=0: mode 2 runs the exact-fp32 layer kernel instead (diagnostic); =force: lstm_x6.hip wherever it can run
     bool lstm_x6_force = false;
+    bool conv_rowwise = false;       // MDD_CONV=rowwise: mode 2's front end runs the row-at-a-time conv kernel (diagnostic; bit-identical)
     // the f32x6 recurrence (lstm_x6.hip) where it is the faster of the two reference-width layer kernels (tools/lstm_kernel_choice.py,
     // profiles/round3_lstm_x6_notes.txt): at H = 384 for every batch size (0.60 - 0.93 of the exact-fp32 kernel's time), at H = 256 up to
     // 128 rows (0.83; beyond, the fp32 kernel's shorter products win: 1.07 - 1.5)
@@ -255,7 +256,7 @@ static int run_stage(mdd_model *m, int si, const float *x, int B, int T, const i
         info->flops = 2.0 * 9 * c.channels * (double)B * Tp * m->W2() * (c.channels + 6.0);
         if (m->x6())   // fp32-grade form: three K-tile-major planes straight into the projection GEMM's operand buffer
             return launch_conv_fused3(x, m->w_conv0, m->sc0, m->sh0, m->w_conv1_3, m->sc1, m->sh1, reinterpret_cast<unsigned short *>(m->p3.p),
-                                      m->taps ? m->seq0.p : nullptr, B, T, m->raw_T, st);
+                                      m->taps ? m->seq0.p : nullptr, B, T, m->raw_T, st, m->conv_rowwise);
         return launch_conv_fused(x, m->w_conv0, m->sc0, m->sh0, m->w_conv1_s, m->sc1, m->sh1, split_view(m->seq0_s, rows * m->rnn_in()),
                                  nullptr, B, T, m->raw_T, st);
     }
@@ -443,6 +444,7 @@ extern "C" int mdd_create(const mdd_config *cfg, int device, mdd_model **out) {
     if (!persistent_grid_fits(m->n_cu)) m->lstm_persist = false;   // per-step kernels instead (smaller partitions, other gfx950 SKUs)
     if (!persistent_f32_grid_fits(m->n_cu)) m->lstm_persist_f32 = false;
     if (!persistent_x6_grid_fits(m->n_cu)) m->lstm_persist_x6 = false;
+    { const char *cv = getenv("MDD_CONV"); m->conv_rowwise = cv && !strcmp(cv, "rowwise"); }
     { const char *e6 = getenv("MDD_LSTM_X6"); if (e6 && e6[0] == '0') m->lstm_persist_x6 = false; if (e6 && e6[0] == 'f') m->lstm_x6_force = true; }
     hipError_t e = hipMalloc((void **)&m->err_flag, sizeof(int));
     if (e == hipSuccess) e = hipMemset(m->err_flag, 0, sizeof(int));

@@ -413,6 +413,234 @@ __global__ __launch_bounds__(256, NP == 2 ? 2 : 1) void conv_fused_kernel(const 
 
 size_t conv_fused_smem(int np) { return 5 * CF_XLD * 4 + (size_t)np * CF_YPLANE + 2048 * 4 + (size_t)np * 1952 * 2; }
 
+// ---------------------------------------------------------------- fused conv0 -> conv1, f32x6 form, R output rows per pass
+// The same arithmetic as conv_fused_kernel<3> (the same six products in the same order per MFMA, the same MFMA shapes and k order, the
+// two K halves accumulated apart and added last), reorganised so that the per-row bookkeeping around the small MFMA groups is paid
+// once per R output rows:
+//  * the x tile holds the 2R+3 x rows of R output rows (2tp-2 .. 2tp+2R); the next block's rows are requested right after conv0 has
+//    read the tile, so they travel while conv1 runs instead of queueing behind the output stores;
+//  * the conv0 tile holds 2R+1 rows in rotating slots; after a segment's first block only its 2R new rows are computed (R x 122
+//    positions = 4 tiles of 32 per wave, one unrolled group);
+//  * 8 waves, two per SIMD (one wave's VALU runs beside the other's MFMAs); conv1: wave = (output row jr, M tile mt, K half kh2) with
+//    its 9 k-steps of W1's three planes resident.  (All of K per wave needs 216 registers for W1 alone: measured slower, the rest of
+//    the kernel then lives in AGPR copies -- profiles/round4_conv_notes.txt.)
+//  * the R output rows are transposed into LDS together and written as 16-byte granules of the K-tile-major planes.
+// LDS (R = 2): conv0 tile 3 planes x [5 slots][124 cols][64 B] (32 channels bf16; the four 16-byte chunks of a column are XOR-swizzled
+// by column bits 2..3: 2-way-conflict fragment reads, as the padded layout of the row-wise kernel) | x tile [7][248] f32, whose bytes
+// later stage the output rows [R][3 planes][1952] | K-half partial sums [2R tiles][16][64] f32 | conv0's folded BN (kept out of
+// registers: with it there the kernel spills).
+constexpr int CM_R = 2, CM_NY = 2 * CM_R + 1, CM_NX = 2 * CM_R + 3;
+constexpr int CM_YPLANE = CM_NY * CF_NCOL * 64;                                    // 39680 B
+constexpr int CM_XT = CM_NX * CF_XLD * 4, CM_OST = CM_R * 3 * 1952 * 2;             // 6944 B, 23424 B
+constexpr int CM_RED = 2 * CM_R * 16 * 64 * 4;                                      // 16384 B: K-half partial sums of the 2R output tiles
+constexpr size_t conv_multirow_smem() { return 3 * (size_t)CM_YPLANE + (CM_XT > CM_OST ? CM_XT : CM_OST) + CM_RED + 256; }   // 159104 B
+
+__device__ __forceinline__ int cm_yoff(int slot, int col, int chunk) { return (slot * CF_NCOL + col) * 64 + ((chunk ^ ((col >> 2) & 3)) << 4); }
+
+template <int NP, int R>
+__global__ __launch_bounds__(512, 1) void conv_fused_kernel(const float *__restrict__ x, const float *__restrict__ w0,
+                                                            const float *__restrict__ sc0, const float *__restrict__ sh0,
+                                                            const unsigned short *__restrict__ w1_3, const float *__restrict__ sc1,
+                                                            const float *__restrict__ sh1, unsigned short *__restrict__ out3,
+                                                            float *__restrict__ out_f32, int B, int T, int Traw, int S, int seg) {
+    static_assert(NP == 3 && R == CM_R, "multi-row form: f32x6 planes, CM_R rows (LDS layout above)");
+    constexpr int F = 243, W1 = 122, W2 = 61, CH = 32, ROW = CH * W2;   // 1952
+    constexpr int D0 = F / 3;
+    constexpr int NY = 2 * R + 1, NX = 2 * R + 3;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    unsigned char *yh = smem, *ym = yh + CM_YPLANE, *yl = ym + CM_YPLANE;
+    float *xs = reinterpret_cast<float *>(yl + CM_YPLANE);                         // [NX][CF_XLD]
+    unsigned short *ost = reinterpret_cast<unsigned short *>(yl + CM_YPLANE);      // [R][hi, mid, lo][ROW] (after conv0 has read xs)
+    float *red = reinterpret_cast<float *>(yl + CM_YPLANE + (CM_XT > CM_OST ? CM_XT : CM_OST));   // [2R tiles][16][64]
+    float *bn0 = red + CM_RED / 4;                                                 // conv0's folded BN: scale [32] | shift [32]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int li = lane & 31, half = lane >> 5;
+    const int kh2 = wave >> 2, jr = (wave >> 1) & 1, mt = wave & 1;              // conv1: output row tp + jr, M tile mt, K half kh2
+    const int Tp = T / 2;
+    const size_t mrows = (size_t)Tp * B;
+
+    // resident B fragments: W1[co = li][k], this wave's 9 k-steps of 16, three planes
+    bf16x8 bwh[9], bwm[9], bwl[9];
+#pragma unroll
+    for (int i = 0; i < 9; i++) {
+        const size_t o = (size_t)li * 288 + (kh2 * 9 + i) * 16 + half * 8;
+        bwh[i] = *reinterpret_cast<const bf16x8 *>(w1_3 + o);
+        bwm[i] = *reinterpret_cast<const bf16x8 *>(w1_3 + CH * 288 + o);
+        bwl[i] = *reinterpret_cast<const bf16x8 *>(w1_3 + 2 * CH * 288 + o);
+    }
+    bf16x8 w0h, w0m, w0l;
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+        const int tap = half * 8 + j;
+        const float wv = tap < 9 ? w0[li * 9 + tap] : 0.f;
+        w0h[j] = (__bf16)wv;
+        const float r1 = wv - (float)w0h[j];
+        w0m[j] = (__bf16)r1; w0l[j] = (__bf16)(r1 - (float)w0m[j]);
+    }
+    if (tid < 64) bn0[tid] = tid < 32 ? sc0[tid] : sh0[tid - 32];               // (read behind the loop's first barrier)
+    const float s1 = sc1[li], h1 = sh1[li];
+    // zero the left pad column (col 0 = conv0 column -1) of every slot of the three planes once
+    for (int i = tid; i < 3 * NY * 16; i += 512) {
+        const int pl = i / (NY * 16), rem = i - pl * (NY * 16);
+        reinterpret_cast<unsigned int *>(smem + pl * CM_YPLANE + (rem >> 4) * CF_NCOL * 64)[rem & 15] = 0u;
+    }
+
+    const int b = blockIdx.x / S, sidx = blockIdx.x - b * S;                      // utterance b, segment sidx of S
+    const int tp_begin = sidx * seg, tp_end = min(Tp, tp_begin + seg);
+    constexpr int XPT = (NX * CF_XLD + 511) / 512;
+    auto load_x = [&](int tp, float (&dst)[XPT]) {   // x rows 2tp-2 .. 2tp+2R, columns -1 .. 246 (zero outside)
+#pragma unroll
+        for (int k = 0; k < XPT; k++) {
+            const int i = tid + 512 * k, r = i / CF_XLD, c = i - r * CF_XLD - 1, ti = 2 * tp - 2 + r;
+            float v = 0.f;
+            if (i < NX * CF_XLD) {
+                if (Traw == 0) {
+                    if (ti >= 0 && ti < T && c >= 0 && c < F) v = x[((size_t)b * T + ti) * F + c];
+                } else {   // raw frames: see conv_fused_kernel<NP>
+                    const int j = c / D0, fr = min(2 * ti + j, Traw - 1);
+                    if (ti >= 0 && 2 * ti < Traw && c >= 0 && c < F) v = x[((size_t)b * Traw + fr) * D0 + (c - j * D0)];
+                }
+            }
+            dst[k] = v;
+        }
+    };
+    float xnext[XPT];
+    if (tp_begin < tp_end) load_x(tp_begin, xnext);
+    int rot = 0;                                                                   // logical conv0 row r lives in slot (r + rot) % NY
+    for (int tp = tp_begin; tp < tp_end; tp += R) {
+        const bool fresh = tp == tp_begin;
+        if (!fresh) rot = rot == 0 ? NY - 1 : rot - 1;                             // old logical row NY-1 becomes row 0
+        __syncthreads();                                                           // previous block's tile and staged rows consumed
+#pragma unroll
+        for (int k = 0; k < XPT; k++) if (tid + 512 * k < NX * CF_XLD) xs[tid + 512 * k] = xnext[k];
+        __syncthreads();
+        // ---- conv0 (as in conv_fused_kernel<3>): logical rows 0 .. NY-1 = conv0 rows 2tp-1 .. 2tp+2R-1; positions p = r * W1 + wc
+        auto conv0_tile = [&](int p) {
+            const int pc = min(p, NY * W1 - 1);
+            const int r = pc / W1, wc = pc - r * W1, ti = 2 * tp - 1 + r;
+            const int rs = r + rot >= NY ? r + rot - NY : r + rot;
+            const bool inb = p < NY * W1, rowok = ti >= 0 && ti < T && inb;
+            float v[8];
+#pragma unroll
+            for (int j = 0; j < 8; j++) {
+                const int tap = half * 8 + j, kh = tap / 3, kw = tap - kh * 3;
+                v[j] = (tap < 9) ? xs[(r + kh) * CF_XLD + 2 * wc + kw] : 0.f;
+            }
+            bf16x8 bh, bm, bl;
+#pragma unroll
+            for (int j = 0; j < 8; j++) {
+                bh[j] = (__bf16)v[j];
+                const float r1 = v[j] - (float)bh[j];
+                bm[j] = (__bf16)r1; bl[j] = (__bf16)(r1 - (float)bm[j]);
+            }
+            f32x16 d;
+#pragma unroll
+            for (int q = 0; q < 16; q++) d[q] = 0.f;
+            d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0m, bm, d, 0, 0, 0);
+            d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0h, bl, d, 0, 0, 0);
+            d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0l, bh, d, 0, 0, 0);
+            d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0h, bm, d, 0, 0, 0);
+            d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0m, bh, d, 0, 0, 0);
+            d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0h, bh, d, 0, 0, 0);
+            if (inb) {
+#pragma unroll
+                for (int g = 0; g < 4; g++) {      // registers 4g..4g+3 = channels 8g + 4*half + 0..3 = 16-byte chunk g, bytes 8*half..
+                    unsigned short hb[4], mb[4], lb[4];
+                    const float4 c0s = *reinterpret_cast<const float4 *>(bn0 + 8 * g + 4 * half);
+                    const float4 c0h = *reinterpret_cast<const float4 *>(bn0 + 32 + 8 * g + 4 * half);
+                    const float cs[4] = {c0s.x, c0s.y, c0s.z, c0s.w}, chh[4] = {c0h.x, c0h.y, c0h.z, c0h.w};
+#pragma unroll
+                    for (int e = 0; e < 4; e++) {
+                        float a = d[4 * g + e] * cs[e] + chh[e];
+                        a = (rowok && a > 0.f) ? a : 0.f;
+                        __bf16 h = (__bf16)a;
+                        const float r1 = a - (float)h;
+                        __bf16 mm_ = (__bf16)r1, l = (__bf16)(r1 - (float)mm_);
+                        hb[e] = *reinterpret_cast<unsigned short *>(&h);
+                        mb[e] = *reinterpret_cast<unsigned short *>(&mm_); lb[e] = *reinterpret_cast<unsigned short *>(&l);
+                    }
+                    const int o = cm_yoff(rs, wc + 1, g) + 8 * half;
+                    *reinterpret_cast<uint2 *>(yh + o) = make_uint2(hb[0] | ((unsigned)hb[1] << 16), hb[2] | ((unsigned)hb[3] << 16));
+                    *reinterpret_cast<uint2 *>(ym + o) = make_uint2(mb[0] | ((unsigned)mb[1] << 16), mb[2] | ((unsigned)mb[3] << 16));
+                    *reinterpret_cast<uint2 *>(yl + o) = make_uint2(lb[0] | ((unsigned)lb[1] << 16), lb[2] | ((unsigned)lb[3] << 16));
+                }
+            }
+        };
+        {   // a fresh block computes all NY rows (5 x 122 positions = 20 tiles), a continuing one the 2R new rows (16 tiles; row 0 is
+            // the previous block's row NY-1)
+            const int p0 = fresh ? 0 : W1;
+            conv0_tile(p0 + wave * 32 + li);
+            conv0_tile(p0 + (wave + 8) * 32 + li);
+            if (fresh && wave < 4) conv0_tile((16 + wave) * 32 + li);
+        }
+        if (tp + R < tp_end) load_x(tp + R, xnext);                                // the next block's x rows travel during conv1
+        __syncthreads();
+        // ---- conv1: this wave = output row tp + jr (logical conv0 rows 2jr .. 2jr+2), M tile mt, k-steps 9 kh2 .. 9 kh2 + 8
+        f32x16 acc;
+#pragma unroll
+        for (int r = 0; r < 16; r++) acc[r] = 0.f;
+        const int m = min(mt * 32 + li, W2 - 1);                                   // rows >= 61 recompute row 60, never stored
+        int slot[3];
+#pragma unroll
+        for (int kh = 0; kh < 3; kh++) { const int r = 2 * jr + kh + rot; slot[kh] = r >= NY ? r - NY : r; }
+#pragma unroll
+        for (int i = 0; i < 9; i++) {
+            const int kb = kh2 * 9 + i, kk = kb >> 1, kh = kk / 3, kw = kk - kh * 3;
+            const int off = cm_yoff(slot[kh], 2 * m + kw, (kb & 1) * 2 + half);   // col index = (2m+kw-1)+1
+            const bf16x8 ah = *reinterpret_cast<const bf16x8 *>(yh + off);
+            const bf16x8 am = *reinterpret_cast<const bf16x8 *>(ym + off);
+            const bf16x8 al = *reinterpret_cast<const bf16x8 *>(yl + off);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bwm[i], acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bwl[i], acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bwh[i], acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bwm[i], acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bwh[i], acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bwh[i], acc, 0, 0, 0);
+        }
+        // ---- sum of the K halves, BN + ReLU + three-plane split, transposed into the staged output row jr (xs is dead: the barrier above
+        // followed conv0)
+        float *rt = red + (jr * 2 + mt) * 16 * 64;
+        if (kh2 == 1) {
+#pragma unroll
+            for (int r = 0; r < 16; r++) rt[r * 64 + lane] = acc[r];
+        }
+        __syncthreads();
+        if (kh2 == 0 && tp + jr < tp_end) {
+            unsigned short *oh = ost + jr * 3 * ROW, *om = oh + ROW, *ol = om + ROW;
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                const int wo = mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;         // C/D: row = w', col = lane&31 = co
+                if (wo < W2) {
+                    float v = (acc[r] + rt[r * 64 + lane]) * s1 + h1;
+                    v = v > 0.f ? v : 0.f;
+                    __bf16 hb = (__bf16)v;
+                    const float r1 = v - (float)hb;
+                    __bf16 mb = (__bf16)r1, lb = (__bf16)(r1 - (float)mb);
+                    oh[li * W2 + wo] = *reinterpret_cast<unsigned short *>(&hb);
+                    om[li * W2 + wo] = *reinterpret_cast<unsigned short *>(&mb);
+                    ol[li * W2 + wo] = *reinterpret_cast<unsigned short *>(&lb);
+                }
+            }
+        }
+        __syncthreads();
+        // ---- stores: 16-byte chunk q of plane pl of staged row jj = columns 8q .. 8q+7 = K-tile q / 4, offset (q % 4) * 8
+        const int nr = min(R, tp_end - tp);
+        for (int i = tid; i < nr * 3 * 244; i += 512) {
+            const int jj = i / (3 * 244), rem = i - jj * (3 * 244), pl = rem / 244, q = rem - pl * 244;
+            const size_t rowid = (size_t)(tp + jj) * B + b;
+            unsigned short *dst = out3 + pl * mrows * ROW + ((size_t)(q >> 2) * mrows + rowid) * 32 + (q & 3) * 8;
+            *reinterpret_cast<u32x4 *>(dst) = *reinterpret_cast<const u32x4 *>(ost + (jj * 3 + pl) * ROW + q * 8);
+        }
+        if (out_f32)
+            for (int i = tid; i < nr * ROW; i += 512) {
+                const int jj = i / ROW, c = i - jj * ROW;
+                const unsigned short *oh = ost + jj * 3 * ROW;
+                out_f32[((size_t)(tp + jj) * B + b) * ROW + c] =
+                    (__uint_as_float((unsigned)oh[c] << 16) + __uint_as_float((unsigned)oh[ROW + c] << 16)) + __uint_as_float((unsigned)oh[2 * ROW + c] << 16);
+            }
+    }
+}
+
 int launch_conv_fused(const float *x, const float *w0, const float *sc0, const float *sh0, SplitPtr w1, const float *sc1,
                       const float *sh1, SplitPtr out, float *out_f32, int B, int T, int Traw, hipStream_t st) {
     // segments of consecutive output rows per utterance: about 1024 workgroups (two rounds of the 512 that fit the chip)
@@ -430,13 +658,22 @@ int launch_conv_fused(const float *x, const float *w0, const float *sc0, const f
 
 // f32x6 form: w1_3 = conv1 weights [co][kh][kw][ci] as three consecutive row-major planes (hi | mid | lo, 32 * 288 elements each);
 // out3 = three consecutive K-tile-major planes of (T/2 * B) x 1952 elements (the A operand of launch_gemm_f32x6)
+// rowwise: the row-at-a-time kernel (MDD_CONV=rowwise, diagnostic); otherwise conv_fused_kernel<3, CM_R>, bit-identical to it.
 int launch_conv_fused3(const float *x, const float *w0, const float *sc0, const float *sh0, const unsigned short *w1_3, const float *sc1,
-                       const float *sh1, unsigned short *out3, float *out_f32, int B, int T, int Traw, hipStream_t st) {
+                       const float *sh1, unsigned short *out3, float *out_f32, int B, int T, int Traw, hipStream_t st, bool rowwise) {
     const int Tp = T / 2;
     if (Tp <= 0 || B <= 0) return MDD_OK;
-    int S = (512 + B - 1) / B;                                                     // one workgroup per CU (114 KB of LDS): two rounds of 256
+    int S = (512 + B - 1) / B;                                                     // one workgroup per CU (114 / 159 KB of LDS): two rounds of 256
     S = S < 1 ? 1 : (S > Tp ? Tp : S);
-    const int seg = (Tp + S - 1) / S;
+    int seg = (Tp + S - 1) / S;
+    if (!rowwise) {
+        seg = (seg + CM_R - 1) / CM_R * CM_R;                                      // whole blocks of CM_R rows except at the utterance's end
+        S = (Tp + seg - 1) / seg;
+        hipLaunchKernelGGL((conv_fused_kernel<3, CM_R>), dim3(B * S), dim3(512), conv_multirow_smem(), st, x, w0, sc0, sh0, w1_3, sc1, sh1,
+                           out3, out_f32, B, T, Traw, S, seg);
+        MDD_LAUNCH_CHECK();
+        return MDD_OK;
+    }
     S = (Tp + seg - 1) / seg;
     const size_t plane = (size_t)Tp * B * 1952;
     hipLaunchKernelGGL(conv_fused_kernel<3>, dim3(B * S), dim3(256), conv_fused_smem(3), st, x, w0, sc0, sh0, w1_3, w1_3 + 32 * 288, sc1, sh1,
@@ -448,6 +685,7 @@ int launch_conv_fused3(const float *x, const float *w0, const float *sc0, const 
 int init_conv_attributes() {
     MDD_HIP_CHECK(hipFuncSetAttribute((const void *)conv_fused_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
     MDD_HIP_CHECK(hipFuncSetAttribute((const void *)conv_fused_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
+    MDD_HIP_CHECK(hipFuncSetAttribute((const void *)conv_fused_kernel<3, CM_R>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)conv_multirow_smem()));
     return MDD_OK;
 }
 
