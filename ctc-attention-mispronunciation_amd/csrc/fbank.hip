@@ -30,17 +30,12 @@ struct FbankTables {           // device pointers
 #define FB_WAVE_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); \
                             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); } while (0)
 
-__global__ __launch_bounds__(256) void fbank_kernel(const float *__restrict__ wav, int nframes, FbankTables tb,
-                                                    const float *__restrict__ cscale, const float *__restrict__ coffset,
-                                                    float *__restrict__ out) {
-    __shared__ float2 buf[4][FB_P];
-    __shared__ float raw[4][FB_N];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int f = blockIdx.x * 4 + wave;
-    if (f >= nframes) return;                      // wave-uniform: waves never meet at a workgroup barrier
-    float2 *z = buf[wave];
-    float *xr = raw[wave];
-    const float *src = wav + (size_t)f * FB_S;
+// One frame of 400 samples at `src` -> its 81 output columns, computed by one wave in the LDS scratch z / xr of that wave.
+// Lane l returns mel[0] = column 1 + l and, for l < 16, mel[1] = column 65 + l; every lane returns column 0 in `energy`.
+// Shared by fbank_kernel and fbank_batch_kernel, so both give the same bits for the same frame.
+__device__ __forceinline__ void fbank_frame(const float *__restrict__ src, const FbankTables &tb,
+                                            const float *__restrict__ cscale, const float *__restrict__ coffset,
+                                            float2 *z, float *xr, int lane, float mel[2], float &energy) {
     // 1. samples, DC offset, raw energy
     float v[7], sum = 0.f;
 #pragma unroll
@@ -93,18 +88,84 @@ __global__ __launch_bounds__(256) void fbank_kernel(const float *__restrict__ wa
         xr[k] = c.x * c.x + c.y * c.y;
     }
     FB_WAVE_SYNC();
-    // 5. mel energies, log, CMVN, row store
-    float *orow = out + (size_t)f * FB_D;
-    for (int b = lane; b < FB_BINS; b += 64) {
-        const int first = tb.first[b], n = tb.count[b];
-        const float *w = tb.weights + tb.woff[b];
-        float acc = 0.f;
-        for (int k = 0; k < n; k++) acc += w[k] * xr[first + k];
-        float val = logf(fmaxf(acc, 1.1920929e-07f));
-        if (cscale) val = val * cscale[1 + b] + coffset[1 + b];
-        orow[1 + b] = val;
+    // 5. mel energies, log, CMVN
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+        const int b = lane + 64 * h;
+        float val = 0.f;
+        if (b < FB_BINS) {
+            const int first = tb.first[b], n = tb.count[b];
+            const float *w = tb.weights + tb.woff[b];
+            float acc = 0.f;
+            for (int k = 0; k < n; k++) acc += w[k] * xr[first + k];
+            val = logf(fmaxf(acc, 1.1920929e-07f));
+            if (cscale) val = val * cscale[1 + b] + coffset[1 + b];
+        }
+        mel[h] = val;
     }
-    if (lane == 0) orow[0] = cscale ? log_energy * cscale[0] + coffset[0] : log_energy;
+    energy = cscale ? log_energy * cscale[0] + coffset[0] : log_energy;
+}
+
+// The 81 columns of one frame, as fbank_frame left them in the wave's registers, to one output row.
+__device__ __forceinline__ void fbank_store_row(float *__restrict__ orow, int lane, const float mel[2], float energy) {
+    orow[1 + lane] = mel[0];
+    if (lane < FB_BINS - 64) orow[65 + lane] = mel[1];
+    if (lane == 0) orow[0] = energy;
+}
+
+__global__ __launch_bounds__(256) void fbank_kernel(const float *__restrict__ wav, int nframes, FbankTables tb,
+                                                    const float *__restrict__ cscale, const float *__restrict__ coffset,
+                                                    float *__restrict__ out) {
+    __shared__ float2 buf[4][FB_P];
+    __shared__ float raw[4][FB_N];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int f = blockIdx.x * 4 + wave;
+    if (f >= nframes) return;                      // wave-uniform: waves never meet at a workgroup barrier
+    float mel[2], energy;
+    fbank_frame(wav + (size_t)f * FB_S, tb, cscale, coffset, buf[wave], raw[wave], lane, mel, energy);
+    fbank_store_row(out + (size_t)f * FB_D, lane, mel, energy);
+}
+
+// B utterances -> the padded, stacked batch of create_input (AA/utils/data_loader.py:123-181) in one launch.
+// Wave (x, b) owns raw frame s = 4 * blockIdx.x + wave of utterance b: it computes the frame once (fbank_frame) and stores
+// its 81 columns into every stacked slot (i, r) that reads it, min(i * skip + r, T_raw_b - 1) == s (make_context(., 0, right)
+// repeats the last frame: AA/utils/tools.py:207-216; skip_feat keeps rows i * skip: :218-227).  The same wave also zeroes
+// stacked row s when s lies in [kept_b, T_out) -- the even-pad row of data_loader.py:138-142 and the batch padding -- so every
+// element of out [B, T_out, (right + 1) * 81] is written exactly once by this launch.  The grid's x extent covers
+// max(T_raw_b) <= T_out * skip and T_out.
+__global__ __launch_bounds__(256) void fbank_batch_kernel(const float *__restrict__ wav, const int64_t *__restrict__ offsets,
+                                                          int T_out, FbankTables tb, const float *__restrict__ cscale,
+                                                          const float *__restrict__ coffset, int right, int skip,
+                                                          float *__restrict__ out) {
+    __shared__ float2 buf[4][FB_P];
+    __shared__ float raw[4][FB_N];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int s = blockIdx.x * 4 + wave, b = blockIdx.y;
+    const int64_t n = offsets[b + 1] - offsets[b];
+    const int T_raw = n < FB_N ? 0 : (int)(1 + (n - FB_N) / FB_S);
+    const int kept = (T_raw + skip - 1) / skip;
+    const int W = (right + 1) * FB_D;
+    float *ub = out + (size_t)b * T_out * W;
+    if (s >= kept && s < T_out) {                  // a padding row: wave-uniform, no barrier follows
+        float *orow = ub + (size_t)s * W;
+        for (int j = lane; j < W; j += 64) orow[j] = 0.f;
+    }
+    if (s >= T_raw) return;                        // wave-uniform: waves never meet at a workgroup barrier
+    float mel[2], energy;
+    fbank_frame(wav + offsets[b] + (size_t)s * FB_S, tb, cscale, coffset, buf[wave], raw[wave], lane, mel, energy);
+    for (int r = 0; r <= right; r++) {
+        // rows i with i * skip + r == s, or, for the last frame, every i * skip + r >= s (the edge repeat)
+        int i0, i1;
+        if (s < T_raw - 1) {
+            if (s < r || (s - r) % skip) continue;
+            i0 = i1 = (s - r) / skip;
+        } else {
+            i0 = s > r ? (s - r + skip - 1) / skip : 0;
+            i1 = kept - 1;
+        }
+        if (i1 >= T_out) i1 = T_out - 1;           // a T_out below the batch's stack length loses rows, never writes past them
+        for (int i = i0; i <= i1; i++) fbank_store_row(ub + (size_t)i * W + r * FB_D, lane, mel, energy);
+    }
 }
 
 static std::mutex g_fb_mutex;
@@ -180,6 +241,45 @@ extern "C" int mdd_fbank(const float *wav_dev, int64_t n_samples, const float *c
     if (int rc = fbank_tables(dev, &tb)) return rc;
     hipLaunchKernelGGL(fbank_kernel, dim3((nframes + 3) / 4), dim3(256), 0, (hipStream_t)stream, wav_dev, nframes, tb,
                        cmvn_scale_dev, cmvn_offset_dev, out_dev);
+    MDD_LAUNCH_CHECK();
+    return MDD_OK;
+}
+
+extern "C" int32_t mdd_fbank_batch_len(const int64_t *n_samples, int32_t B, int32_t skip, int32_t n_down) {
+    if (!n_samples || B <= 0 || skip < 1) { set_error("mdd_fbank_batch_len: bad argument"); return -1; }
+    int32_t t_out = 0;
+    for (int32_t b = 0; b < B; b++) {
+        const int32_t T_raw = mdd_fbank_num_frames(n_samples[b]);
+        if (T_raw == 0) {
+            set_error("mdd_fbank_batch_len: utterance %d has %lld samples, fewer than one %d-sample window", b,
+                      (long long)n_samples[b], FB_N);
+            return -1;
+        }
+        const int32_t t = mdd_stack_len(T_raw, skip, n_down);
+        if (t > t_out) t_out = t;
+    }
+    return t_out;
+}
+
+extern "C" int mdd_fbank_batch(const float *wav_dev, const int64_t *offsets_dev, int32_t B, int32_t T_out,
+                               const float *cmvn_scale_dev, const float *cmvn_offset_dev, int32_t right, int32_t skip,
+                               int32_t n_down, float *out_dev, void *stream) {
+    if (B <= 0 || T_out < 0 || right < 0 || skip < 1 || n_down < 1 ||
+        ((cmvn_scale_dev == nullptr) != (cmvn_offset_dev == nullptr))) {
+        set_error("mdd_fbank_batch: bad argument (B=%d T_out=%d right=%d skip=%d n_down=%d, cmvn pointers must come as a pair)",
+                  B, T_out, right, skip, n_down);
+        return MDD_ERR_ARG;
+    }
+    if (T_out == 0) return MDD_OK;
+    if (!wav_dev || !offsets_dev || !out_dev) { set_error("mdd_fbank_batch: null buffer"); return MDD_ERR_ARG; }
+    if ((int64_t)T_out * skip > INT32_MAX - 4 || B > 65535) { set_error("mdd_fbank_batch: batch too large"); return MDD_ERR_ARG; }
+    int dev = 0;
+    MDD_HIP_CHECK(hipGetDevice(&dev));
+    FbankTables tb;
+    if (int rc = fbank_tables(dev, &tb)) return rc;
+    const int rows = T_out * skip > T_out ? T_out * skip : T_out;   // covers every raw frame (T_raw_b <= T_out * skip) and row
+    hipLaunchKernelGGL(fbank_batch_kernel, dim3((rows + 3) / 4, B), dim3(256), 0, (hipStream_t)stream, wav_dev, offsets_dev,
+                       T_out, tb, cmvn_scale_dev, cmvn_offset_dev, right, skip, out_dev);
     MDD_LAUNCH_CHECK();
     return MDD_OK;
 }

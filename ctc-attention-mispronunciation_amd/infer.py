@@ -1,0 +1,166 @@
+"""Batch inference over a folder of WAVs and word transcripts -- the package's form of the reference's user-facing program
+(AA/infer.py:435-598, ``main``), run as
+
+    python -m ctc_attention_mispronunciation_amd.infer --conf CONF --wav_transcript_path DIR [-p cmudict] [-f cmu]
+        [--cmvn PATH] [--cmudict PATH] [--precision f32x6|f32|bf16x3] [--decode_seq PATH]
+
+The conf YAML is read as ``infer_init`` reads it (AA/infer.py:211-261): the checkpoint
+``checkpoint_dir/exp_name/ctc_best_model.pkl``, ``vocab_file``, ``decode_type``, ``beam_width``, ``lm_path``, ``lm_alpha``,
+``batch_size``, ``right_ctx``, ``n_skip_frame`` (and ``n_downsample``, default 2).  Utterances are the ``N.wav`` files with an
+``N.txt`` beside them, in sorted order of ``N`` as a string (the reference takes ``os.listdir`` order; the order changes only
+the order of the printed blocks).  The WAVs go to the GPU once and become the padded batches in one kernel launch per batch
+(``WavBatchLoader`` / ``fbank_batch``); the loop is ``infer_core.infer``.
+
+What the reference does that needs services absent offline is left out, and says so: no denoiser (``eeo_apm_test``), no
+resampler (non-16 kHz audio exits with status 2), canonical phones from the CMU dictionary only (``-p g2p|phonemizer|
+transcript`` and ``-f ipa`` exit with status 2; a word the dictionary lacks is skipped with one line), no ECDICT translation
+(line 4 of each block is empty).  Nothing is written into the input folder.
+"""
+import argparse
+import os
+import sys
+import time
+
+MAX_SAMPLES = 3 * 60 * 16000          # AA/infer.py:510-512: no more than 3 minutes (the length of its silence.wav)
+REFUSED_PHONETIC = {"g2p": "g2p_en", "phonemizer": "phonemizer / espeak", "transcript": "textgrid (TextGrid input)"}
+
+
+class _Conf(object):
+    """steps/train_ctc.py Config: attributes set from the YAML (AA/infer.py:218-220)."""
+    batch_size = 4
+    dropout = 0.1
+    n_downsample = 2
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(description="infer with only wav and transcript")
+    ap.add_argument("--conf", required=True, help="conf file with the checkpoint, vocabulary and decoder settings")
+    ap.add_argument("--wav_transcript_path", required=True, help="folder of N.wav / N.txt pairs")
+    ap.add_argument("-p", "--phonetic", default="cmudict", help="canonical phone source (only cmudict exists offline)")
+    ap.add_argument("-f", "--phonetic_format", default="cmu", help="phone display format (only cmu exists offline)")
+    ap.add_argument("--cmvn", default=os.path.join("data", "global_fbank_cmvn.txt"),
+                    help="Kaldi global CMVN stats (the reference's data/global_fbank_cmvn.txt)")
+    ap.add_argument("--cmudict", default=None, help="CMU pronouncing dictionary (default: dict/cmudict.dict or $MDD_CMUDICT)")
+    ap.add_argument("--precision", default=None, choices=("f32x6", "f32", "bf16x3"), help="arithmetic mode of the forward")
+    ap.add_argument("--decode_seq", default=None, help="write '<utt> <decoded phones>' lines here")
+    return ap.parse_args(argv)
+
+
+def refuse(msg):
+    print(msg, file=sys.stderr)
+    sys.exit(2)
+
+
+def load_model(opts, precision=None):
+    """infer_init's checkpoint load (AA/infer.py:227-254) onto the MI355X path."""
+    import torch
+    import torch.nn as nn  # noqa: F401  (a checkpoint pickles nn.LSTM / nn.ReLU by reference)
+    from .models.model_ctc import CTC_Model
+    if precision is not None:          # read by mdd_create when the model's handle is made
+        os.environ["MDD_PRECISION"] = precision
+    path = os.path.join(opts.checkpoint_dir, opts.exp_name, "ctc_best_model.pkl")
+    package = torch.load(path, map_location="cpu", weights_only=False)
+    model = CTC_Model(rnn_param=package["rnn_param"], add_cnn=package["add_cnn"], cnn_param=package["cnn_param"],
+                      num_class=package["num_class"], drop_out=package["_drop_out"])
+    model.load_state_dict(package["state_dict"])
+    model.eval()
+    return model
+
+
+def collect(folder, phonetic):
+    """(items, word_dict, transcripts, total seconds) over the N.wav / N.txt pairs of `folder`, sorted by N as a string."""
+    from .utils.fbank import read_wav, SAMPLE_RATE
+    items, word_dict, transcripts, total = [], {}, {}, 0.0
+    names = sorted(p for p in os.listdir(folder) if os.path.isfile(os.path.join(folder, p)) and p.endswith(".wav"))
+    for p in sorted(names, key=lambda q: q[:-4]):
+        utt = p[:-4]
+        txt = os.path.join(folder, utt + ".txt")
+        if not os.path.exists(txt):
+            continue
+        wav_path = os.path.normpath(os.path.join(folder, p))
+        samples, rate = read_wav(wav_path)
+        if rate != SAMPLE_RATE:
+            refuse("%s: %d Hz audio; resampling to %d Hz needs librosa, which is absent" % (wav_path, rate, SAMPLE_RATE))
+        if samples.size > MAX_SAMPLES:
+            print("{} skipped, currently wav length should be no more than 3 minutes!".format(wav_path))
+            continue
+        if samples.size < 400:
+            print("{} skipped, shorter than one 25 ms window".format(wav_path))
+            continue
+        with open(txt, "r") as f:
+            lines = f.readlines()
+        if not lines:
+            continue
+        utterance = lines[-1].rstrip("\n")
+        cmu = phonetic.api_word_phones_cmu(utterance)
+        if not cmu:
+            print("%s skipped: '%s' is not in the CMU dictionary" % (utt, utterance.strip()))
+            continue
+        items.append((utt, samples, phonetic.phones_for_model(cmu)))
+        word_dict[utt] = {"ipa": cmu, "cmu_phns": cmu}
+        transcripts[utt] = utterance
+        total += samples.size / float(SAMPLE_RATE)
+    return items, word_dict, transcripts, total
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    if args.phonetic in REFUSED_PHONETIC:
+        refuse("-p %s needs %s, which is not available offline; use -p cmudict" % (args.phonetic, REFUSED_PHONETIC[args.phonetic]))
+    if args.phonetic != "cmudict":
+        refuse("-p %s: unknown phone source; use -p cmudict" % args.phonetic)
+    if args.phonetic_format != "cmu":
+        refuse("-f %s needs the IPA tables of phonemizer / espeak, which are not available offline; use -f cmu"
+               % args.phonetic_format)
+    t0 = time.time()
+    import yaml
+    try:
+        conf = yaml.safe_load(open(args.conf, "r"))
+    except OSError:
+        print("Config file not exist!")
+        sys.exit(1)
+    opts = _Conf()
+    for k, v in conf.items():
+        setattr(opts, k, v)
+    if not os.path.exists(args.cmvn):
+        refuse("CMVN stats not found at %s (pass --cmvn)" % args.cmvn)
+    print(args.wav_transcript_path, False, args.phonetic)
+
+    from .dict.phonetic_dict import Phonetic
+    from .infer_core import infer
+    from .utils import fbank
+    from .utils.ctcDecoder import GreedyDecoder, BeamDecoder
+    from .utils.data_loader import Vocab, WavBatchLoader
+    import torch
+    phonetic = Phonetic(args.cmudict)
+    model = load_model(opts, args.precision)
+    vocab = Vocab(opts.vocab_file)
+    if opts.decode_type == "Greedy":
+        decoder = GreedyDecoder(vocab.index2word, space_idx=-1, blank_index=0)
+    else:
+        decoder = BeamDecoder(vocab.index2word, beam_width=opts.beam_width, blank_index=0, space_idx=-1, lm_path=opts.lm_path,
+                              lm_alpha=opts.lm_alpha)
+    t2 = time.time()
+    items, word_dict, transcripts, total_wav_time = collect(args.wav_transcript_path, phonetic)
+    cnt = len(items)
+    t3 = time.time()
+    cmvn = fbank.cmvn_scale_offset(fbank.read_cmvn_stats(args.cmvn))
+    loader = WavBatchLoader(items, vocab, opts.batch_size, cmvn=cmvn, right_ctx=opts.right_ctx, n_skip_frame=opts.n_skip_frame,
+                            n_downsample=getattr(opts, "n_downsample", 2))
+    device = torch.device("cuda", torch.cuda.current_device())
+    c1, c2, c3 = infer(phonetic, word_dict, loader, device, model, decoder, vocab, transcripts, False,
+                       decode_seq_path=args.decode_seq)
+    print(c1, c2, c3)
+    end = time.time()
+    total = max(total_wav_time, 1e-9)
+    rtf = (end - t0) / total
+    print("RTF: %.4f, time used for decode %d sentences: %.4f seconds, total wav length: %.4f seconds"
+          % (rtf, cnt, end - t0, total_wav_time))
+    print("init model time: %.4f, init phone time: %.4f, denoise time: %.4f, mdd infer time: %.4f"
+          % ((t2 - t0) / total, (t3 - t2) / total, 0.0, (end - t3) / total))
+    print("process time: %.4f" % ((end - t3) / total))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -4,8 +4,16 @@ decoded phoneme string and the canonical phoneme string into the printed diagnos
 Reference: AA/infer.py:155-209 (print_aligned_string, align_canonical_decoded), :405-433 (stastics),
 :304-342 (sil removal, 'err' stripping, score).  Pure Python on <= ~50 tokens per utterance; function
 names are the reference's so callers can switch by changing the import.
+
+``infer`` is the batch loop around them (AA/infer.py:282-372): model, decoder, diagnosis and the printed block per
+utterance, over any loader that yields the reference's 7-tuple (``SpeechDataLoader`` or ``WavBatchLoader``).
 """
 import math
+import sys
+
+import torch
+
+from .utils.data_loader import frames_from_fraction
 
 
 def print_aligned_string(s1, s2, l):
@@ -76,3 +84,52 @@ def diagnose(decoded, canonical, decoder, to_display=None):
     score, ok, ds = pronunciation_score(path, len(ins))
     return dict(decoded=ph_dec, canonical=ph_can, path=path, insertions=ins, substitutions=sub, deletions=dele,
                 correct=ok, del_sub=ds, score=score, printed=print_aligned_string(ph_dec, ph_can, path))
+
+
+def infer(phonetic, word_dict, test_loader, device, model, decoder, vocab, test_transcipt_dict, use_ipa, out=None,
+          decode_seq_path=None):
+    """AA/infer.py:282-372.  Per batch ``(inputs, input_sizes, _, _, trans, trans_sizes, utt_list)``: ``model(inputs, trans)``,
+    frame counts ``(input_sizes * T').long()``, ``decoder.decode``, then per utterance the 'sil' strip, 'err' removal, ``wer``,
+    alignment, fault lists and score (``diagnose``), printed as the reference's 13-line block to ``out`` (stdout by default).
+    Returns (total_correct_cnt, total_cnt, total_insertion_cnt).
+
+    Offline substitutions: line 3 prints ``word_dict[utt]['ipa']`` as given; line 4 is ``phonetic.api_word_translation(word)``
+    when ``phonetic`` has it (the reference asks ECDICT), else empty.  ``use_ipa`` needs ``phonetic.cmu_to_ipa_wiki``.  The
+    reference always writes '<utt> <decoded phones>' lines to decode_seq.txt in the input folder and main() deletes the file;
+    here they are written only when ``decode_seq_path`` is given."""
+    out = sys.stdout if out is None else out
+    to_display = phonetic.cmu_to_ipa_wiki if use_ipa else None
+    translate = getattr(phonetic, "api_word_translation", None)
+    total_correct_cnt = total_cnt = total_insertion_cnt = 0
+    w1 = open(decode_seq_path, "w+") if decode_seq_path else None
+    try:
+        with torch.no_grad():
+            for data in test_loader:
+                inputs, input_sizes, _, _, trans, trans_sizes, utt_list = data
+                inputs = inputs.to(device)
+                trans = trans.to(device)
+                probs = model(inputs, trans)
+                lens = frames_from_fraction(input_sizes, probs.size(0))
+                decoded = decoder.decode(probs, lens.numpy().tolist())
+                trans, trans_sizes = trans.cpu().numpy(), trans_sizes.numpy()
+                for x in range(len(decoded)):
+                    canonical = " ".join(vocab.index2word[num] for num in trans[x][:trans_sizes[x]])
+                    utterance = test_transcipt_dict[utt_list[x]]
+                    d = diagnose(decoded[x], canonical, decoder, to_display)
+                    tmp1, tmp2, tmp3 = d["printed"]
+                    block = ["id     : " + utt_list[x], utt_list[x] + ": " + utterance, str(word_dict[utt_list[x]]["ipa"]),
+                             str(translate(utterance)) if translate is not None else "", tmp2, tmp3, tmp1,
+                             "ins err: " + " ".join(d["insertions"]), "sub err: " + " ".join(d["substitutions"]),
+                             "del err: " + " ".join(d["deletions"]),
+                             "Comp.  : " + str(d["correct"]) + "/" + str(d["correct"] + d["del_sub"]),
+                             "score  : " + str(d["score"]), ""]
+                    out.write("\n".join(block) + "\n")
+                    total_correct_cnt += d["correct"]
+                    total_cnt += d["correct"] + d["del_sub"]
+                    total_insertion_cnt += len(d["insertions"])
+                    if w1 is not None:
+                        w1.write(utt_list[x] + " " + " ".join(d["decoded"]) + "\n")
+    finally:
+        if w1 is not None:
+            w1.close()
+    return total_correct_cnt, total_cnt, total_insertion_cnt

@@ -140,3 +140,39 @@ class SpeechDataLoader(DataLoader):
     def __init__(self, *args, **kwargs):
         super(SpeechDataLoader, self).__init__(*args, **kwargs)
         self.collate_fn = create_input
+
+
+class WavBatchLoader(object):
+    """Batches of WAVs in the shape of ``SpeechDataLoader(SpeechDataset(...), batch_size, shuffle=False)`` as AA/infer.py:278-279
+    builds them, straight from samples: ``items`` is a list of (utt, samples [16 kHz, int16 scale], canonical phones as a
+    space-separated string), taken in the given order.  Each batch is the reference's 7-tuple (inputs, input_sizes, labels,
+    label_sizes, trans, trans_sizes, utt_list): ``inputs`` / ``input_sizes`` come from ``fbank.fbank_batch`` (one kernel launch,
+    the features never pass through the host); trans ids are looked up as SpeechDataset does (unknown -> 'UNK') and padded as
+    create_input pads them; the label pair repeats them (infer.py reads its canonical file as the labels too, :273-276)."""
+
+    def __init__(self, items, vocab, batch_size, cmvn=None, right_ctx=2, n_skip_frame=2, n_downsample=2):
+        self.items = list(items)
+        self.vocab = vocab
+        self.batch_size = int(batch_size)
+        self.cmvn = cmvn
+        self.right_ctx, self.n_skip_frame, self.n_downsample = right_ctx, n_skip_frame, n_downsample
+
+    def __len__(self):
+        return (len(self.items) + self.batch_size - 1) // self.batch_size
+
+    def __iter__(self):
+        from .fbank import fbank_batch
+        unk = self.vocab.word2index["UNK"]
+        for start in range(0, len(self.items), self.batch_size):
+            chunk = self.items[start:start + self.batch_size]
+            inputs, input_sizes = fbank_batch([it[1] for it in chunk], cmvn=self.cmvn, right_ctx=self.right_ctx,
+                                              n_skip_frame=self.n_skip_frame, n_downsample=self.n_downsample)
+            ids = [[self.vocab.word2index.get(c, unk) for c in it[2].split()] for it in chunk]
+            l_max = max(len(t) for t in ids)
+            trans = torch.zeros(len(chunk), l_max)
+            trans_sizes = torch.zeros(len(chunk))
+            for i, t in enumerate(ids):
+                trans[i, :len(t)] = torch.tensor(t, dtype=torch.float32)
+                trans_sizes[i] = len(t)
+            trans, trans_sizes = trans.long(), trans_sizes.long()
+            yield inputs, input_sizes, trans.clone(), trans_sizes.clone(), trans, trans_sizes, [it[0] for it in chunk]

@@ -120,3 +120,49 @@ def load_mat(spec):
             raise ValueError("%s: not an uncompressed binary float matrix" % spec)
         rows, cols = struct.unpack_from("<i", head, 6)[0], struct.unpack_from("<i", head, 11)[0]
         return np.frombuffer(f.read(4 * rows * cols), dtype="<f4").reshape(rows, cols).copy()
+
+
+def fbank_batch(wavs, cmvn=None, right_ctx=2, n_skip_frame=2, n_downsample=2, out=None):
+    """B utterances -> the padded model input the reference's infer.py batches from them, in one kernel launch (mdd_fbank_batch):
+    fbank + CMVN per utterance, make_context(., 0, right_ctx) + skip_feat(., n_skip_frame) + zero rows up to a multiple of
+    n_downsample (AA/utils/data_loader.py:138-142), zero-padded to the longest (create_input, :151-181).
+
+    ``wavs``: list of 1-D sample arrays / tensors at 16 kHz on the int16 scale; ``cmvn``: None or the (scale, offset) pair of
+    ``cmvn_scale_offset``.  Returns (inputs [B, T_out, (right_ctx+1)*81] float32 CUDA, input_sizes [B] float32 CPU), where
+    input_sizes[b] is create_input's float32 ``feature_length / inputs_max_length``.  Each stored frame is bit-identical to
+    ``compute_fbank_feats`` of that utterance.  ``out`` (optional) is written whole, padding included."""
+    if len(wavs) == 0:
+        raise ValueError("fbank_batch: empty batch")
+    host = [np.asarray(w.detach().cpu().numpy() if torch.is_tensor(w) else w, dtype=np.float32).reshape(-1) for w in wavs]
+    B = len(host)
+    n = np.array([h.size for h in host], dtype=np.int64)
+    L = _lib.lib()
+    t_out = L.mdd_fbank_batch_len(n.ctypes.data_as(C.POINTER(C.c_int64)), B, n_skip_frame, n_downsample)
+    if t_out < 0:
+        short = [b for b in range(B) if n[b] < 400]
+        raise ValueError("fbank_batch: utterance %s is shorter than one 400-sample window (%s)"
+                         % (short[0] if short else "?", L.mdd_last_error().decode()))
+    _lib.require_gpu()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    offsets = np.concatenate([[0], np.cumsum(n)]).astype(np.int64)
+    wav = torch.from_numpy(np.concatenate(host)).to(dev)
+    off = torch.from_numpy(offsets).to(dev)
+    W = (right_ctx + 1) * NUM_COLS
+    if out is None:
+        out = torch.empty((B, t_out, W), dtype=torch.float32, device=dev)
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (B, t_out, W)
+    sc = of = None
+    if cmvn is not None:
+        sc = torch.as_tensor(cmvn[0]).to(dev, torch.float32).contiguous()
+        of = torch.as_tensor(cmvn[1]).to(dev, torch.float32).contiguous()
+        if sc.numel() != NUM_COLS or of.numel() != NUM_COLS:
+            raise ValueError("cmvn vectors must have %d entries" % NUM_COLS)
+    _lib.check(L.mdd_fbank_batch(C.c_void_p(wav.data_ptr()), C.c_void_p(off.data_ptr()), B, t_out,
+                                 C.c_void_p(sc.data_ptr()) if sc is not None else None,
+                                 C.c_void_p(of.data_ptr()) if of is not None else None,
+                                 right_ctx, n_skip_frame, n_downsample, C.c_void_p(out.data_ptr()), _lib.current_stream_ptr()))
+    lens = [L.mdd_stack_len(L.mdd_fbank_num_frames(int(k)), n_skip_frame, n_downsample) for k in n]
+    sizes = torch.zeros(B)
+    for b in range(B):
+        sizes[b] = lens[b] / t_out          # a Python true division stored into float32, as create_input does (:177)
+    return out, sizes

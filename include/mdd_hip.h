@@ -185,6 +185,19 @@ int mdd_align_batch(const int32_t *a, const int32_t *a_len, int32_t a_stride, co
 int32_t mdd_fbank_num_frames(int64_t n_samples);
 int mdd_fbank(const float *wav_dev, int64_t n_samples, const float *cmvn_scale_dev, const float *cmvn_offset_dev,
               float *out_dev, void *stream);
+/* The same front end for B utterances at once, up to the padded model input the reference's infer.py builds from them:
+ * fbank + CMVN (AA/infer.py:567-574), then per utterance make_context(., 0, right) + skip_feat(., skip) + zero rows up to a
+ * multiple of n_down (SpeechDataset.__getitem__, AA/utils/data_loader.py:123-146), then create_input's zero padding to the
+ * batch's longest utterance (:151-181), all in one launch.
+ * mdd_fbank_batch_len (host): T_out of that batch = max_b mdd_stack_len(mdd_fbank_num_frames(n_samples[b]), skip, n_down);
+ *   -1 (and mdd_last_error names the index) if any utterance is shorter than one 400-sample window.
+ * mdd_fbank_batch: wav_dev holds the B utterances back to back, utterance b at [offsets_dev[b], offsets_dev[b+1]) (int64,
+ *   device, B+1 entries); T_out must be mdd_fbank_batch_len's.  out_dev [B, T_out, (right+1)*81] is written whole (padding
+ *   rows included, no memset needed); every stored frame has the bits mdd_fbank gives it.  CMVN pointers as mdd_fbank. */
+int32_t mdd_fbank_batch_len(const int64_t *n_samples, int32_t B, int32_t skip, int32_t n_down);
+int mdd_fbank_batch(const float *wav_dev, const int64_t *offsets_dev, int32_t B, int32_t T_out,
+                    const float *cmvn_scale_dev, const float *cmvn_offset_dev,
+                    int32_t right, int32_t skip, int32_t n_down, float *out_dev, void *stream);
 
 /* ---- evaluation counts of a batch (AA/steps/test_ctc_nosil.py:33-60,218-298), host.
  * Row x of dec / lab / can (row pitch `stride` ids) holds the decoded, annotated and canonical phoneme ids of utterance x
