@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <memory>
 #include <mutex>
 #include <vector>
 
@@ -35,15 +36,39 @@ struct DeviceGate {
 };
 static DeviceGate g_gate[64];
 
-struct DevBuf {
-    float *p = nullptr;
-    size_t cap = 0;  // in floats
-};
-
 struct GraphKey {
     const void *x, *x1, *out, *tlen, *llen;
     int B, T, L, Traw;
     bool operator<(const GraphKey &o) const { return memcmp(this, &o, sizeof(GraphKey)) < 0; }
+};
+
+// The weights of one BiLSTM layer on the device; the text encoder's sit at index cfg.layers.
+struct LstmWeights {
+    float *wih = nullptr, *whh = nullptr;          // fp32, gate rows permuted (whh in the packed layout where use_packed)
+    SplitPtr wih_s{nullptr, nullptr}, whh_s{nullptr, nullptr};   // split-bf16 copies (whh row-major)
+    unsigned short *wih_3 = nullptr;               // three-plane (f32x6) copy of W_ih, K-tile-major
+    unsigned short *whh_3 = nullptr;               // Whh' [3][2][4H][H]: three row-major planes (f32x6 layer kernel)
+    float *scale = nullptr, *shift = nullptr;      // the BatchNorm of the layer's input (layers 1 .. cfg.layers - 1)
+};
+
+// Every device weight of one mdd_finalize_weights: built whole, read-only while in use, freed whole with the set.
+struct DecodeWeights {
+    float *w_conv0 = nullptr, *sc0 = nullptr, *sh0 = nullptr;
+    float *w_conv1t = nullptr, *sc1 = nullptr, *sh1 = nullptr;
+    SplitPtr w_conv1_s{nullptr, nullptr};
+    unsigned short *w_conv1_3 = nullptr;           // conv1 weights [co][kh][kw][ci] as three row-major planes
+    std::vector<LstmWeights> rnn;                  // cfg.layers + 1
+    float *emb = nullptr, *t_bias = nullptr;
+    float *w_score = nullptr, *fscale = nullptr, *fshift = nullptr, *w_fc = nullptr, *w_fcp = nullptr;
+    SplitPtr w_score_s{nullptr, nullptr};
+    std::vector<DeviceArray<unsigned char>> mem;   // the allocations behind every pointer above
+    template <class T> int alloc(T **p, size_t n) {
+        DeviceArray<unsigned char> b;
+        if (int rc = b.need(n * sizeof(T))) return rc;
+        *p = reinterpret_cast<T *>(b.p);
+        mem.push_back(std::move(b));
+        return MDD_OK;
+    }
 };
 
 }  // namespace mdd
@@ -55,39 +80,28 @@ struct mdd_model {
     int precision = 2;   // 2 (default): fp32-grade, the large contractions as f32x6 on the bf16 matrix cores (falls back to 0 when the geometry does not allow);
                          // 0: exact fp32 MFMA everywhere; 1: split-bf16 x3 for every contraction (narrower than fp32: flagged variant)
     std::map<std::string, std::vector<float>> host;  // state_dict entries as loaded
-    // device weights
-    float *w_conv0 = nullptr, *sc0 = nullptr, *sh0 = nullptr;
-    float *w_conv1t = nullptr, *sc1 = nullptr, *sh1 = nullptr;
-    std::vector<float *> wih, whh, bn_scale, bn_shift;  // per rnn layer (bn_* of layer n applies to layer n's INPUT)
-    float *emb = nullptr, *t_wih = nullptr, *t_whh = nullptr, *t_bias = nullptr;
-    float *w_score = nullptr, *fscale = nullptr, *fshift = nullptr, *w_fc = nullptr, *w_fcp = nullptr;
-    std::vector<mdd::SplitPtr> wih_s, whh_s;                // split-bf16 copies of the GEMM / recurrent weights
-    std::vector<unsigned short *> wih_3;                    // three-plane (f32x6) copies of the input-projection weights, K-tile-major
-    unsigned short *t_wih_3 = nullptr, *w_conv1_3 = nullptr; // (conv1 weights [co][kh][kw][ci] as three row-major planes)
-    std::vector<unsigned short *> whh_3;                    // Whh' [3][2][4H][H]: three row-major planes of the recurrent weights (f32x6 layer kernel)
-    unsigned short *t_whh_3 = nullptr;
-    mdd::SplitPtr t_whh_s{nullptr, nullptr};
-    mdd::SplitPtr t_wih_s{nullptr, nullptr}, w_score_s{nullptr, nullptr}, w_conv1_s{nullptr, nullptr};
-    std::vector<void *> owned;  // every hipMalloc'd weight pointer
+    std::unique_ptr<mdd::DecodeWeights> weights;   // the set of the last successful mdd_finalize_weights
     // workspace
-    mdd::DevBuf y0, seq0, gx, act[2], xraw, hbuf, cbuf, embo, text, key, S;
-    mdd::DevBuf seq0_s, act_s[2], x_s, embo_s, text_s, key_s, hsplit, hx;   // split-bf16 activations (hi plane, then lo plane)
-    mdd::DevBuf p3;             // f32x6 mode: the three bf16 planes of the projection GEMM's A operand (rewritten per GEMM)
-    std::vector<mdd::DevBuf> tap_rnn;
-    int *err_flag = nullptr;
+    mdd::DeviceBuf y0, seq0, gx, act[2], xraw, hbuf, cbuf, embo, text, key, S;
+    mdd::DeviceBuf seq0_s, act_s[2], x_s, embo_s, text_s, key_s, hsplit, hx;   // split-bf16 activations (hi plane, then lo plane)
+    mdd::DeviceBuf p3;          // f32x6 mode: the three bf16 planes of the projection GEMM's A operand (rewritten per GEMM)
+    std::vector<mdd::DeviceBuf> tap_rnn;
+    mdd::DeviceArray<int> err_flag;
     hipStream_t cap_stream = nullptr;  // graphs are captured here (the legacy default stream cannot capture)
     int lastB = 0, lastT = 0, lastL = 0;
     int raw_T = 0;              // > 0 while mdd_forward_raw runs the fused front-end straight on unstacked frames
     const int *tlen = nullptr, *llen = nullptr;   // set while mdd_forward_fused runs: per-row posterior frames / canonical length of the row's own batch
-    mdd::DevBuf xstack;         // mdd_forward_raw without the fused front-end: stacked copy
+    mdd::DeviceBuf xstack;      // mdd_forward_raw without the fused front-end: stacked copy
     std::map<mdd::GraphKey, hipGraphExec_t> graphs;
+    void drop_graphs() { for (auto &kv : graphs) (void)hipGraphExecDestroy(kv.second); graphs.clear(); }
+    ~mdd_model() { drop_graphs(); if (cap_stream) (void)hipStreamDestroy(cap_stream); }
     int W1() const { return (cfg.feat + 2 - 3) / 2 + 1; }
     int W2() const { return (W1() + 2 - 3) / 2 + 1; }
     int rnn_in() const { return cfg.channels * W2(); }
     int granule_max_b = 1024;   // batch rows the persistent kernel's teams cover (4 row tiles x 16 rows x 16 groups)
     bool lstm_persist = true;   // one persistent team-synchronised launch per BiLSTM layer (split-bf16 mode, >= 256 CUs, B <= 1024)
     int n_cu = 0;
-    unsigned int *sync_words = nullptr;
+    mdd::DeviceArray<unsigned int> sync_words;
     bool lstm_x3 = false;   // MDD_LSTM=x3: LDS-tiled split-bf16 step kernel (measured slower than the packed fp32 step; kept for study)
     bool conv_fused() const { return (x3() || x6()) && cfg.feat == 243 && cfg.channels == 32; }
     bool packed_h() const { return cfg.hidden == 384 || cfg.hidden == 256; }
@@ -113,9 +127,8 @@ struct mdd_model {
 
 namespace mdd {
 
-static int upload(mdd_model *m, const std::vector<float> &h, float **dev) {
-    MDD_HIP_CHECK(hipMalloc((void **)dev, h.size() * sizeof(float)));
-    m->owned.push_back(*dev);
+static int upload(DecodeWeights &w, const std::vector<float> &h, float **dev) {
+    if (int rc = w.alloc(dev, h.size())) return rc;
     MDD_HIP_CHECK(hipMemcpy(*dev, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
     return MDD_OK;
 }
@@ -127,7 +140,7 @@ static unsigned short host_bf16(float x) {   // round-to-nearest-even (weights a
 }
 static float host_bf16_f32(unsigned short b) { unsigned u = (unsigned)b << 16; float f; memcpy(&f, &u, 4); return f; }
 
-static int upload_split(mdd_model *m, const std::vector<float> &h, SplitPtr *out) {
+static int upload_split(DecodeWeights &w, const std::vector<float> &h, SplitPtr *out) {
     const size_t n = h.size();
     std::vector<unsigned short> buf(2 * n);
     for (size_t i = 0; i < n; i++) {
@@ -135,15 +148,14 @@ static int upload_split(mdd_model *m, const std::vector<float> &h, SplitPtr *out
         buf[n + i] = host_bf16(h[i] - host_bf16_f32(buf[i]));
     }
     unsigned short *d = nullptr;
-    MDD_HIP_CHECK(hipMalloc((void **)&d, 2 * n * sizeof(unsigned short)));
-    m->owned.push_back(d);
+    if (int rc = w.alloc(&d, 2 * n)) return rc;
     MDD_HIP_CHECK(hipMemcpy(d, buf.data(), 2 * n * sizeof(unsigned short), hipMemcpyHostToDevice));
     out->hi = d; out->lo = d + n;
     return MDD_OK;
 }
 
-// a DevBuf of n floats holds a split tensor of n elements: hi plane then lo plane
-static SplitPtr split_view(const DevBuf &b, size_t n) {
+// a DeviceBuf of n floats holds a split tensor of n elements: hi plane then lo plane
+static SplitPtr split_view(const DeviceBuf &b, size_t n) {
     SplitPtr s; s.hi = reinterpret_cast<unsigned short *>(b.p); s.lo = s.hi ? s.hi + n : nullptr; return s;
 }
 static const SplitPtr kNoSplit = {nullptr, nullptr};
@@ -157,12 +169,11 @@ static thread_local bool g_ws_moved = false;
 // stream depend on a capturing stream").  Both are rare (first call of a shape); graph REPLAYS never take this lock.
 static std::mutex g_prep_mu;
 
-static int ensure(DevBuf &b, size_t n, hipStream_t zero_stream) {
+static int ensure(DeviceBuf &b, size_t n, hipStream_t zero_stream) {
     if (b.cap >= n) return MDD_OK;
     g_ws_moved = true;
-    if (b.p) MDD_HIP_CHECK(hipFree(b.p));
-    b.p = nullptr; b.cap = 0;
-    MDD_HIP_CHECK(hipMalloc((void **)&b.p, n * sizeof(float)));
+    if (int rc = b.need(n)) return rc;
+    b.cap = 0;   // grown only once cleared
     MDD_HIP_CHECK(hipMemsetAsync(b.p, 0, n * sizeof(float), zero_stream));  // padded batch rows of the packed h exchange must be finite
     MDD_HIP_CHECK(hipStreamSynchronize(zero_stream));
     b.cap = n;
@@ -221,18 +232,101 @@ static void pack_whh(const std::vector<float> &w, int H, std::vector<float> &out
 }
 
 // fp32 matrix -> three bf16 planes (hi | mid | lo, same element order), on the device
-static int upload_split3(mdd_model *m, const std::vector<float> &w, unsigned short **out) {
-    const size_t n = w.size();
+static int upload_split3(DecodeWeights &w, const std::vector<float> &h, unsigned short **out) {
+    const size_t n = h.size();
     std::vector<unsigned short> buf(3 * n);
     for (size_t i = 0; i < n; i++) {
-        buf[i] = host_bf16(w[i]);
-        const float r1 = w[i] - host_bf16_f32(buf[i]);
+        buf[i] = host_bf16(h[i]);
+        const float r1 = h[i] - host_bf16_f32(buf[i]);
         buf[n + i] = host_bf16(r1);
         buf[2 * n + i] = host_bf16(r1 - host_bf16_f32(buf[n + i]));
     }
-    MDD_HIP_CHECK(hipMalloc((void **)out, 3 * n * sizeof(unsigned short)));
-    m->owned.push_back(*out);
+    if (int rc = w.alloc(out, 3 * n)) return rc;
     MDD_HIP_CHECK(hipMemcpy(*out, buf.data(), 3 * n * sizeof(unsigned short), hipMemcpyHostToDevice));
+    return MDD_OK;
+}
+
+// Build a complete weight set from the loaded state_dict into `w` (a fresh set: on failure it is discarded whole).
+static int build_weights(mdd_model *m, DecodeWeights &w) {
+    const mdd_config &c = m->cfg;
+    const int ch = c.channels, H = c.hidden;
+    int rc;
+    std::vector<float> sc, sh, tmp;
+    {   // conv0 / conv1: fold bias + BN into scale/shift; conv1 weights -> [ci][kh][kw][co]
+        const auto *w0 = get(m, "conv.0.conv.weight", (size_t)ch * 9), *b0 = get(m, "conv.0.conv.bias", ch);
+        const auto *w1 = get(m, "conv.1.conv.weight", (size_t)ch * ch * 9), *b1 = get(m, "conv.1.conv.bias", ch);
+        if (!w0 || !b0 || !w1 || !b1) return MDD_ERR_STATE;
+        if (!bn_fold(m, "conv.0.batch_norm", ch, sc, sh)) return MDD_ERR_STATE;
+        for (int i = 0; i < ch; i++) sh[i] += (*b0)[i] * sc[i];
+        if ((rc = upload(w, *w0, &w.w_conv0)) || (rc = upload(w, sc, &w.sc0)) || (rc = upload(w, sh, &w.sh0))) return rc;
+        if (!bn_fold(m, "conv.1.batch_norm", ch, sc, sh)) return MDD_ERR_STATE;
+        for (int i = 0; i < ch; i++) sh[i] += (*b1)[i] * sc[i];
+        tmp.assign((size_t)ch * 9 * ch, 0.f);
+        for (int co = 0; co < ch; co++)
+            for (int ci = 0; ci < ch; ci++)
+                for (int k = 0; k < 9; k++) tmp[((size_t)ci * 9 + k) * ch + co] = (*w1)[((size_t)co * ch + ci) * 9 + k];
+        if ((rc = upload(w, tmp, &w.w_conv1t)) || (rc = upload(w, sc, &w.sc1)) || (rc = upload(w, sh, &w.sh1))) return rc;
+        // conv1 weights for the fused MFMA front-end: [co][kh][kw][ci] (k = (kh*3+kw)*ch + ci), split-bf16, and the same matrix as
+        // three planes (hi | mid | lo, each [co][288] row-major) for the fp32-grade fused front-end
+        tmp.assign((size_t)ch * 9 * ch, 0.f);
+        for (int co = 0; co < ch; co++)
+            for (int ci = 0; ci < ch; ci++)
+                for (int k = 0; k < 9; k++) tmp[((size_t)co * 9 + k) * ch + ci] = (*w1)[((size_t)co * ch + ci) * 9 + k];
+        if ((rc = upload_split(w, tmp, &w.w_conv1_s)) || (rc = upload_split3(w, tmp, &w.w_conv1_3))) return rc;
+    }
+    w.rnn.resize(c.layers + 1);
+    for (int n = 0; n <= c.layers; n++) {   // the BiLSTM layers, then the text encoder
+        LstmWeights &lw = w.rnn[n];
+        char base[64];
+        if (n < c.layers) snprintf(base, sizeof(base), "rnns.%d.rnn.", n);
+        else snprintf(base, sizeof(base), "lstm_embeds.");
+        const int K = n == c.layers ? c.emb_dim : (n == 0 ? m->rnn_in() : 2 * H);
+        if (!pack_gate_rows(m, base, "weight_ih_l0", H, K, tmp)) return MDD_ERR_STATE;
+        if ((rc = upload(w, tmp, &lw.wih)) || (rc = upload_split(w, tmp, &lw.wih_s))) return rc;
+        // f32x6: hi | mid | lo planes in the kernel's K-tile-major order, made on the device from the fp32 copy
+        if (K % 32 == 0 && ((rc = w.alloc(&lw.wih_3, (size_t)3 * 8 * H * K)) || (rc = launch_split3(lw.wih, 8 * H, K, K, lw.wih_3, nullptr)))) return rc;
+        if (!pack_gate_rows(m, base, "weight_hh_l0", H, H, tmp)) return MDD_ERR_STATE;
+        if ((rc = upload_split(w, tmp, &lw.whh_s))) return rc;
+        if (use_packed(m) && (rc = upload_split3(w, tmp, &lw.whh_3))) return rc;
+        if (use_packed(m)) { std::vector<float> pk; pack_whh(tmp, H, pk); tmp.swap(pk); }
+        if ((rc = upload(w, tmp, &lw.whh))) return rc;
+        if (n > 0 && n < c.layers) {
+            snprintf(base, sizeof(base), "rnns.%d.batch_norm", n);
+            if (!bn_fold(m, base, 2 * H, sc, sh)) return MDD_ERR_STATE;
+            if ((rc = upload(w, sc, &lw.scale)) || (rc = upload(w, sh, &lw.shift))) return rc;
+        }
+    }
+    {   // text encoder: the embedding table; bias_ih + bias_hh folded into the input projection's epilogue
+        const auto *e = get(m, "embeds.weight", (size_t)c.emb_rows * c.emb_dim);
+        if (!e) return MDD_ERR_STATE;
+        if ((rc = upload(w, *e, &w.emb))) return rc;
+        std::vector<float> bi, bh;
+        if (!pack_gate_rows(m, "lstm_embeds.", "bias_ih_l0", H, 1, bi) || !pack_gate_rows(m, "lstm_embeds.", "bias_hh_l0", H, 1, bh)) return MDD_ERR_STATE;
+        for (size_t i = 0; i < bi.size(); i++) bi[i] += bh[i];
+        if ((rc = upload(w, bi, &w.t_bias))) return rc;
+    }
+    {
+        const auto *ws = get(m, "score.weight", (size_t)4 * H * H), *wf = get(m, "fc.1.weight", (size_t)c.num_class * 4 * H);
+        if (!ws || !wf) return MDD_ERR_STATE;
+        if (!bn_fold(m, "fc.0", 4 * H, sc, sh)) return MDD_ERR_STATE;
+        if ((rc = upload_split(w, *ws, &w.w_score_s))) return rc;
+        if ((rc = upload(w, *ws, &w.w_score)) || (rc = upload(w, *wf, &w.w_fc)) || (rc = upload(w, sc, &w.fscale)) ||
+            (rc = upload(w, sh, &w.fshift))) return rc;
+        const int D2 = 4 * H;
+        if (D2 % 64 == 0 && c.num_class <= 48) {   // consumer-order repack for attn_tail_mfma_kernel
+            const int J = D2 / 64;
+            std::vector<float> pk((size_t)4 * 3 * J * 64 * 4, 0.f);
+            for (int wv = 0; wv < 4; wv++)
+                for (int nt = 0; nt < 3; nt++)
+                    for (int j = 0; j < J; j++)
+                        for (int lane = 0; lane < 64; lane++)
+                            for (int mm = 0; mm < 4; mm++) {
+                                const int n = nt * 16 + (lane & 15), k = wv * (D2 / 4) + 16 * j + 4 * (lane >> 4) + mm;
+                                if (n < c.num_class) pk[((((size_t)wv * 3 + nt) * J + j) * 64 + lane) * 4 + mm] = (*wf)[(size_t)n * D2 + k];
+                            }
+            if ((rc = upload(w, pk, &w.w_fcp))) return rc;
+        }
+    }
     return MDD_OK;
 }
 
@@ -242,9 +336,24 @@ struct Stage { const char *name; int launches; double flops; };
 
 static int n_stages(const mdd_model *m) { return 2 + 2 * m->cfg.layers + 6; }
 
+// One BiLSTM layer: the caller sets a.T, a.B, a.seqlen and the outputs, the rest is filled here.  The persistent layer kernel where
+// it runs (f32x6, split-bf16 or exact-fp32 teams), else one launch per step.
+static int run_lstm(mdd_model *m, const LstmWeights &lw, LstmStepArgs &a, hipStream_t st, Stage *info) {
+    const bool x3 = m->x3();
+    a.gx = m->gx.p; a.whh = lw.whh; a.hbuf = m->hbuf.p; a.cbuf = m->cbuf.p;
+    a.H = m->cfg.hidden; a.packed = use_packed(m);
+    a.whh_split = lw.whh_s; a.hsplit = (x3 && m->lstm_x3) ? reinterpret_cast<unsigned short *>(m->hsplit.p) : nullptr;
+    if (!m->persist(a.B)) return launch_lstm_layer(a, st);
+    info->launches = 1;
+    unsigned short *hx = reinterpret_cast<unsigned short *>(m->hx.p);
+    if (m->lx6(a.B)) return launch_lstm_layer_x6(a, lw.whh_3, hx, m->sync_words.p, m->err_flag.p, st);
+    return x3 ? launch_lstm_layer_granule(a, hx, m->sync_words.p, m->err_flag.p, st) : launch_lstm_layer_f32(a, hx, m->sync_words.p, m->err_flag.p, st);
+}
+
 static int run_stage(mdd_model *m, int si, const float *x, int B, int T, const int64_t *x1, int L, float *logp,
                      hipStream_t st, Stage *info) {
     const mdd_config &c = m->cfg;
+    const DecodeWeights &w = *m->weights;
     const int H = c.hidden, H2 = 2 * H, G2 = 8 * H, Tp = T / 2, Lp = L, nl = c.layers;
     const bool x3 = m->x3();
     const size_t rows = (size_t)Tp * B, trows = (size_t)L * B;
@@ -255,16 +364,16 @@ static int run_stage(mdd_model *m, int si, const float *x, int B, int T, const i
         info->name = "conv_fused";
         info->flops = 2.0 * 9 * c.channels * (double)B * Tp * m->W2() * (c.channels + 6.0);
         if (m->x6())   // fp32-grade form: three K-tile-major planes straight into the projection GEMM's operand buffer
-            return launch_conv_fused3(x, m->w_conv0, m->sc0, m->sh0, m->w_conv1_3, m->sc1, m->sh1, reinterpret_cast<unsigned short *>(m->p3.p),
+            return launch_conv_fused3(x, w.w_conv0, w.sc0, w.sh0, w.w_conv1_3, w.sc1, w.sh1, reinterpret_cast<unsigned short *>(m->p3.p),
                                       m->taps ? m->seq0.p : nullptr, B, T, m->raw_T, st, m->conv_rowwise);
-        return launch_conv_fused(x, m->w_conv0, m->sc0, m->sh0, m->w_conv1_s, m->sc1, m->sh1, split_view(m->seq0_s, rows * m->rnn_in()),
+        return launch_conv_fused(x, w.w_conv0, w.sc0, w.sh0, w.w_conv1_s, w.sc1, w.sh1, split_view(m->seq0_s, rows * m->rnn_in()),
                                  nullptr, B, T, m->raw_T, st);
     }
     if (si == 1 && m->conv_fused()) { info->name = "conv1_in_fused"; info->launches = 0; return MDD_OK; }
     if (si == 0) { info->name = "conv0"; info->flops = 2.0 * 9 * c.channels * (double)B * T * m->W1();
-        return launch_conv0(x, m->w_conv0, m->sc0, m->sh0, m->y0.p, B, T, c.feat, c.channels, st); }
+        return launch_conv0(x, w.w_conv0, w.sc0, w.sh0, m->y0.p, B, T, c.feat, c.channels, st); }
     if (si == 1) { info->name = "conv1"; info->flops = 2.0 * 9 * c.channels * c.channels * (double)B * Tp * m->W2();
-        return launch_conv1(m->y0.p, m->w_conv1t, m->sc1, m->sh1, x3 ? nullptr : m->seq0.p,
+        return launch_conv1(m->y0.p, w.w_conv1t, w.sc1, w.sh1, x3 ? nullptr : m->seq0.p,
                             x3 ? split_view(m->seq0_s, rows * m->rnn_in()) : kNoSplit, B, T, m->W1(), c.channels, st); }
     si -= 2;
     if (si < 2 * nl) {
@@ -275,81 +384,64 @@ static int run_stage(mdd_model *m, int si, const float *x, int B, int T, const i
             info->flops = 2.0 * (double)Tp * B * G2 * K;
             if (x3) {
                 const SplitPtr in = n == 0 ? split_view(m->seq0_s, rows * K) : split_view(m->act_s[(n - 1) & 1], rows * K);
-                return launch_gemm_bf16x3(in, m->wih_s[n], nullptr, m->gx.p, nullptr, Tp * B, G2, K, K, K, G2, 1, 0, 0, 0, st);
+                return launch_gemm_bf16x3(in, w.rnn[n].wih_s, nullptr, m->gx.p, nullptr, Tp * B, G2, K, K, K, G2, 1, 0, 0, 0, st);
             }
             const float *in = n == 0 ? m->seq0.p : m->act[(n - 1) & 1].p;
             if (m->x6()) {   // fp32-grade arithmetic at 6/16 of the fp32 MFMA's cost (gemm_bf16x6.hip)
                 unsigned short *p3 = reinterpret_cast<unsigned short *>(m->p3.p);
                 if (!(n == 0 && m->conv_fused()))      // (layer 0: the fused front-end has written the planes already)
                     if (int rc = launch_split3(in, Tp * B, K, K, p3, st)) return rc;
-                return launch_gemm_f32x6(p3, (size_t)Tp * B * K, m->wih_3[n], (size_t)G2 * K, nullptr, m->gx.p, Tp * B, G2, K, G2, st);
+                return launch_gemm_f32x6(p3, (size_t)Tp * B * K, w.rnn[n].wih_3, (size_t)G2 * K, nullptr, m->gx.p, Tp * B, G2, K, G2, st);
             }
-            return launch_gemm_nt(in, m->wih[n], nullptr, m->gx.p, Tp * B, G2, K, K, K, G2, 1, 0, 0, 0, st);
+            return launch_gemm_nt(in, w.rnn[n].wih, nullptr, m->gx.p, Tp * B, G2, K, K, K, G2, 1, 0, 0, 0, st);
         }
         snprintf(namebuf, sizeof(namebuf), "lstm%d", n); info->name = namebuf;
         info->launches = Tp; info->flops = 2.0 * 2 * (double)B * H * 4 * H * Tp;
         LstmStepArgs a;
-        a.gx = m->gx.p; a.whh = m->whh[n]; a.hbuf = m->hbuf.p; a.cbuf = m->cbuf.p;
-        a.T = Tp; a.B = B; a.H = H; a.packed = use_packed(m);
-        a.whh_split = m->whh_s[n]; a.hsplit = (x3 && m->lstm_x3) ? reinterpret_cast<unsigned short *>(m->hsplit.p) : nullptr;
-        a.seqlen = m->tlen;
+        a.T = Tp; a.B = B; a.seqlen = m->tlen;
         if (n == nl - 1) {   // raw h: the attention queries X (fp32 for the tail, split for the score GEMM)
             a.out = m->xraw.p; a.out_raw = m->xraw.p; a.oscale = nullptr; a.oshift = nullptr;
             a.out_split = x3 ? split_view(m->x_s, rows * H2) : kNoSplit;
         } else {             // next layer's BatchNorm folded into the store
             a.out = x3 ? nullptr : m->act[n & 1].p; a.out_raw = m->taps ? m->tap_rnn[n].p : nullptr;
             a.out_split = x3 ? split_view(m->act_s[n & 1], rows * H2) : kNoSplit;
-            a.oscale = m->bn_scale[n + 1]; a.oshift = m->bn_shift[n + 1];
+            a.oscale = w.rnn[n + 1].scale; a.oshift = w.rnn[n + 1].shift;
         }
-        if (m->persist(B)) {
-            info->launches = 1;
-            if (m->lx6(B)) return launch_lstm_layer_x6(a, m->whh_3[n], reinterpret_cast<unsigned short *>(m->hx.p), m->sync_words, m->err_flag, st);
-            return x3 ? launch_lstm_layer_granule(a, reinterpret_cast<unsigned short *>(m->hx.p), m->sync_words, m->err_flag, st)
-                      : launch_lstm_layer_f32(a, reinterpret_cast<unsigned short *>(m->hx.p), m->sync_words, m->err_flag, st);
-        }
-        return launch_lstm_layer(a, st);
+        return run_lstm(m, w.rnn[n], a, st, info);
     }
     si -= 2 * nl;
+    const LstmWeights &tw = w.rnn[nl];   // the text encoder
     switch (si) {
     case 0:  // text encoder (model_ctc.py:193,198) and keys (:201)
         info->name = "embed";
-        return launch_embed(m->emb, c.emb_rows, c.emb_dim, x1, B, L, x3 ? nullptr : m->embo.p,
-                            x3 ? split_view(m->embo_s, trows * c.emb_dim) : kNoSplit, m->err_flag, st);
+        return launch_embed(w.emb, c.emb_rows, c.emb_dim, x1, B, L, x3 ? nullptr : m->embo.p,
+                            x3 ? split_view(m->embo_s, trows * c.emb_dim) : kNoSplit, m->err_flag.p, st);
     case 1:
         info->name = "gemm_text"; info->flops = 2.0 * (double)L * B * G2 * c.emb_dim;
-        if (x3) return launch_gemm_bf16x3(split_view(m->embo_s, trows * c.emb_dim), m->t_wih_s, m->t_bias, m->gx.p, nullptr, L * B, G2,
+        if (x3) return launch_gemm_bf16x3(split_view(m->embo_s, trows * c.emb_dim), tw.wih_s, w.t_bias, m->gx.p, nullptr, L * B, G2,
                                           c.emb_dim, c.emb_dim, c.emb_dim, G2, 1, 0, 0, 0, st);
         if (m->x6()) {
             unsigned short *p3 = reinterpret_cast<unsigned short *>(m->p3.p);
             if (int rc = launch_split3(m->embo.p, L * B, c.emb_dim, c.emb_dim, p3, st)) return rc;
-            return launch_gemm_f32x6(p3, (size_t)L * B * c.emb_dim, m->t_wih_3, (size_t)G2 * c.emb_dim, m->t_bias, m->gx.p, L * B, G2, c.emb_dim, G2, st);
+            return launch_gemm_f32x6(p3, (size_t)L * B * c.emb_dim, tw.wih_3, (size_t)G2 * c.emb_dim, w.t_bias, m->gx.p, L * B, G2, c.emb_dim, G2, st);
         }
-        return launch_gemm_nt(m->embo.p, m->t_wih, m->t_bias, m->gx.p, L * B, G2, c.emb_dim, c.emb_dim, c.emb_dim, G2, 1, 0, 0, 0, st);
+        return launch_gemm_nt(m->embo.p, tw.wih, w.t_bias, m->gx.p, L * B, G2, c.emb_dim, c.emb_dim, c.emb_dim, G2, 1, 0, 0, 0, st);
     case 2: {
         info->name = "lstm_text"; info->launches = L; info->flops = 2.0 * 2 * (double)B * H * 4 * H * L;
         LstmStepArgs a;
-        a.gx = m->gx.p; a.whh = m->t_whh; a.hbuf = m->hbuf.p; a.cbuf = m->cbuf.p;
+        a.T = L; a.B = B; a.seqlen = m->llen;
         a.out = m->text.p; a.out_raw = m->text.p; a.oscale = nullptr; a.oshift = nullptr;
         a.out_split = x3 ? split_view(m->text_s, trows * H2) : kNoSplit;
-        a.T = L; a.B = B; a.H = H; a.packed = use_packed(m);
-        a.whh_split = m->t_whh_s; a.hsplit = (x3 && m->lstm_x3) ? reinterpret_cast<unsigned short *>(m->hsplit.p) : nullptr;
-        a.seqlen = m->llen;
-        if (m->persist(B)) {
-            info->launches = 1;
-            if (m->lx6(B)) return launch_lstm_layer_x6(a, m->t_whh_3, reinterpret_cast<unsigned short *>(m->hx.p), m->sync_words, m->err_flag, st);
-            return x3 ? launch_lstm_layer_granule(a, reinterpret_cast<unsigned short *>(m->hx.p), m->sync_words, m->err_flag, st)
-                      : launch_lstm_layer_f32(a, reinterpret_cast<unsigned short *>(m->hx.p), m->sync_words, m->err_flag, st);
-        }
-        return launch_lstm_layer(a, st);
+        return run_lstm(m, tw, a, st, info);
     }
     case 3:
         info->name = "gemm_key"; info->flops = 2.0 * (double)L * B * H2 * H2;
         if (x3) {
             const SplitPtr ks = split_view(m->key_s, trows * H2);
-            return launch_gemm_bf16x3(split_view(m->text_s, trows * H2), m->w_score_s, nullptr, nullptr, &ks, L * B, H2, H2, H2, H2, H2,
+            return launch_gemm_bf16x3(split_view(m->text_s, trows * H2), w.w_score_s, nullptr, nullptr, &ks, L * B, H2, H2, H2, H2, H2,
                                       1, 0, 0, 0, st);
         }
-        return launch_gemm_nt(m->text.p, m->w_score, nullptr, m->key.p, L * B, H2, H2, H2, H2, H2, 1, 0, 0, 0, st);
+        return launch_gemm_nt(m->text.p, w.w_score, nullptr, m->key.p, L * B, H2, H2, H2, H2, H2, 1, 0, 0, 0, st);
     case 4:  // scores S[b][t][l] = X[t,b,:] . key[l,b,:]   (:204)
         info->name = "gemm_score"; info->flops = 2.0 * (double)B * Tp * L * H2;
         if (x3) return launch_gemm_bf16x3(split_view(m->x_s, rows * H2), split_view(m->key_s, trows * H2), nullptr, m->S.p, nullptr, Tp, L,
@@ -357,7 +449,7 @@ static int run_stage(mdd_model *m, int si, const float *x, int B, int T, const i
         return launch_gemm_nt(m->xraw.p, m->key.p, nullptr, m->S.p, Tp, L, H2, B * H2, B * H2, Lp, B, H2, H2, (long)Tp * Lp, st);
     default:
         info->name = "attn_tail"; info->flops = 2.0 * (double)B * Tp * ((double)L * H2 + 2.0 * H2 * c.num_class);
-        return launch_attn_tail(m->S.p, Lp, m->xraw.p, m->text.p, m->fscale, m->fshift, m->w_fc, m->w_fcp, logp, Tp, B, L, H2, c.num_class, st, m->llen);
+        return launch_attn_tail(m->S.p, Lp, m->xraw.p, m->text.p, w.fscale, w.fshift, w.w_fc, w.w_fcp, logp, Tp, B, L, H2, c.num_class, st, m->llen);
     }
 }
 
@@ -420,7 +512,7 @@ extern "C" int mdd_create(const mdd_config *cfg, int device, mdd_model **out) {
         set_error("libmdd_hip is built for gfx950 (MI355X) only; device %d is %s", device, prop.gcnArchName);
         return MDD_ERR_ARG;
     }
-    mdd_model *m = new mdd_model();
+    std::unique_ptr<mdd_model> m(new mdd_model());
     m->cfg = *cfg;
     m->device = device;
     const char *pr = getenv("MDD_PRECISION");
@@ -432,26 +524,26 @@ extern "C" int mdd_create(const mdd_config *cfg, int device, mdd_model **out) {
     if (lx && !strcmp(lx, "step")) m->lstm_persist = false;
     const char *g = getenv("MDD_GRAPH");
     m->use_graph = !(g && g[0] == '0');
-    if (int rc = init_kernel_attributes()) { delete m; return rc; }
-    if (int rc = init_lstm_attributes()) { delete m; return rc; }
-    if (int rc = init_granule_attributes()) { delete m; return rc; }
-    if (int rc = init_lstm_f32_attributes()) { delete m; return rc; }
-    if (int rc = init_lstm_x6_attributes()) { delete m; return rc; }
-    if (int rc = init_conv_attributes()) { delete m; return rc; }
-    if (int rc = init_gemm_attributes()) { delete m; return rc; }
-    if (int rc = init_gemm_x6_attributes()) { delete m; return rc; }
+    if (int rc = init_kernel_attributes()) return rc;
+    if (int rc = init_lstm_attributes()) return rc;
+    if (int rc = init_granule_attributes()) return rc;
+    if (int rc = init_lstm_f32_attributes()) return rc;
+    if (int rc = init_lstm_x6_attributes()) return rc;
+    if (int rc = init_conv_attributes()) return rc;
+    if (int rc = init_gemm_attributes()) return rc;
+    if (int rc = init_gemm_x6_attributes()) return rc;
     m->n_cu = prop.multiProcessorCount;
     if (!persistent_grid_fits(m->n_cu)) m->lstm_persist = false;   // per-step kernels instead (smaller partitions, other gfx950 SKUs)
     if (!persistent_f32_grid_fits(m->n_cu)) m->lstm_persist_f32 = false;
     if (!persistent_x6_grid_fits(m->n_cu)) m->lstm_persist_x6 = false;
     { const char *cv = getenv("MDD_CONV"); m->conv_rowwise = cv && !strcmp(cv, "rowwise"); }
     { const char *e6 = getenv("MDD_LSTM_X6"); if (e6 && e6[0] == '0') m->lstm_persist_x6 = false; if (e6 && e6[0] == 'f') m->lstm_x6_force = true; }
-    hipError_t e = hipMalloc((void **)&m->err_flag, sizeof(int));
-    if (e == hipSuccess) e = hipMemset(m->err_flag, 0, sizeof(int));
+    if (int rc = m->err_flag.need(1)) return rc;
+    if (int rc = m->sync_words.need(32)) return rc;
+    hipError_t e = hipMemset(m->err_flag.p, 0, sizeof(int));
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&m->cap_stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMalloc((void **)&m->sync_words, 32 * sizeof(unsigned int));
-    if (e != hipSuccess) { set_error("mdd_create: %s", hipGetErrorString(e)); delete m; return MDD_ERR_HIP; }
-    *out = m;
+    if (e != hipSuccess) { set_error("mdd_create: %s", hipGetErrorString(e)); return MDD_ERR_HIP; }
+    *out = m.release();
     return MDD_OK;
 }
 
@@ -459,15 +551,6 @@ extern "C" void mdd_destroy(mdd_model *m) {
     if (!m) return;
     (void)hipSetDevice(m->device);
     (void)hipDeviceSynchronize();
-    for (auto &kv : m->graphs) (void)hipGraphExecDestroy(kv.second);
-    for (void *p : m->owned) (void)hipFree(p);
-    DevBuf *bufs[] = {&m->y0, &m->seq0, &m->gx, &m->act[0], &m->act[1], &m->xraw, &m->hbuf, &m->cbuf, &m->embo, &m->text, &m->key, &m->S,
-                      &m->seq0_s, &m->act_s[0], &m->act_s[1], &m->x_s, &m->embo_s, &m->text_s, &m->key_s, &m->hsplit, &m->hx, &m->xstack, &m->p3};
-    for (DevBuf *b : bufs) if (b->p) (void)hipFree(b->p);
-    for (auto &b : m->tap_rnn) if (b.p) (void)hipFree(b.p);
-    if (m->err_flag) (void)hipFree(m->err_flag);
-    if (m->cap_stream) (void)hipStreamDestroy(m->cap_stream);
-    if (m->sync_words) (void)hipFree(m->sync_words);
     delete m;
 }
 
@@ -482,125 +565,16 @@ extern "C" int mdd_load_weight(mdd_model *m, const char *key, const float *data,
     return MDD_OK;
 }
 
+// Builds a whole new weight set, then swaps it in.  On failure the handle is left not finalized, still holding no pointer to freed memory.
 extern "C" int mdd_finalize_weights(mdd_model *m) {
     if (!m) { set_error("null model"); return MDD_ERR_ARG; }
+    m->finalized = false;
     MDD_HIP_CHECK(hipSetDevice(m->device));
-    const mdd_config &c = m->cfg;
-    const int ch = c.channels, H = c.hidden;
-    int rc;
-    for (void *p : m->owned) (void)hipFree(p);
-    m->owned.clear(); m->wih.clear(); m->whh.clear(); m->wih_s.clear(); m->whh_s.clear(); m->wih_3.clear(); m->t_wih_3 = nullptr;
-    m->bn_scale.assign(c.layers, nullptr); m->bn_shift.assign(c.layers, nullptr);
-    for (auto &kv : m->graphs) (void)hipGraphExecDestroy(kv.second);
-    m->graphs.clear();
-    std::vector<float> sc, sh, tmp;
-    {   // conv0 / conv1: fold bias + BN into scale/shift; conv1 weights -> [ci][kh][kw][co]
-        const auto *w0 = get(m, "conv.0.conv.weight", (size_t)ch * 9), *b0 = get(m, "conv.0.conv.bias", ch);
-        const auto *w1 = get(m, "conv.1.conv.weight", (size_t)ch * ch * 9), *b1 = get(m, "conv.1.conv.bias", ch);
-        if (!w0 || !b0 || !w1 || !b1) return MDD_ERR_STATE;
-        if (!bn_fold(m, "conv.0.batch_norm", ch, sc, sh)) return MDD_ERR_STATE;
-        for (int i = 0; i < ch; i++) sh[i] += (*b0)[i] * sc[i];
-        if ((rc = upload(m, *w0, &m->w_conv0)) || (rc = upload(m, sc, &m->sc0)) || (rc = upload(m, sh, &m->sh0))) return rc;
-        if (!bn_fold(m, "conv.1.batch_norm", ch, sc, sh)) return MDD_ERR_STATE;
-        for (int i = 0; i < ch; i++) sh[i] += (*b1)[i] * sc[i];
-        tmp.assign((size_t)ch * 9 * ch, 0.f);
-        for (int co = 0; co < ch; co++)
-            for (int ci = 0; ci < ch; ci++)
-                for (int k = 0; k < 9; k++) tmp[((size_t)ci * 9 + k) * ch + co] = (*w1)[((size_t)co * ch + ci) * 9 + k];
-        if ((rc = upload(m, tmp, &m->w_conv1t)) || (rc = upload(m, sc, &m->sc1)) || (rc = upload(m, sh, &m->sh1))) return rc;
-        // conv1 weights for the fused MFMA front-end: [co][kh][kw][ci] (k = (kh*3+kw)*ch + ci), split-bf16
-        tmp.assign((size_t)ch * 9 * ch, 0.f);
-        for (int co = 0; co < ch; co++)
-            for (int ci = 0; ci < ch; ci++)
-                for (int k = 0; k < 9; k++) tmp[((size_t)co * 9 + k) * ch + ci] = (*w1)[((size_t)co * ch + ci) * 9 + k];
-        if ((rc = upload_split(m, tmp, &m->w_conv1_s))) return rc;
-        {   // the same matrix as three planes (hi | mid | lo, each [co][288] row-major) for the fp32-grade fused front-end
-            const size_t n = tmp.size();
-            std::vector<unsigned short> buf(3 * n);
-            for (size_t i = 0; i < n; i++) {
-                buf[i] = host_bf16(tmp[i]);
-                const float r1 = tmp[i] - host_bf16_f32(buf[i]);
-                buf[n + i] = host_bf16(r1);
-                buf[2 * n + i] = host_bf16(r1 - host_bf16_f32(buf[n + i]));
-            }
-            MDD_HIP_CHECK(hipMalloc((void **)&m->w_conv1_3, 3 * n * sizeof(unsigned short)));
-            m->owned.push_back(m->w_conv1_3);
-            MDD_HIP_CHECK(hipMemcpy(m->w_conv1_3, buf.data(), 3 * n * sizeof(unsigned short), hipMemcpyHostToDevice));
-        }
-    }
-    for (int n = 0; n < c.layers; n++) {
-        char base[64];
-        snprintf(base, sizeof(base), "rnns.%d.rnn.", n);
-        const int K = n == 0 ? m->rnn_in() : 2 * H;
-        float *d = nullptr;
-        if (!pack_gate_rows(m, base, "weight_ih_l0", H, K, tmp)) return MDD_ERR_STATE;
-        if ((rc = upload(m, tmp, &d))) return rc;
-        m->wih.push_back(d);
-        { SplitPtr sp{nullptr, nullptr}; if ((rc = upload_split(m, tmp, &sp))) return rc; m->wih_s.push_back(sp); }
-        if (K % 32 == 0) {   // f32x6: hi | mid | lo planes in the kernel's K-tile-major order, made on the device from the fp32 copy
-            unsigned short *p3 = nullptr;
-            MDD_HIP_CHECK(hipMalloc((void **)&p3, (size_t)3 * 8 * H * K * sizeof(unsigned short)));
-            m->owned.push_back(p3);
-            if ((rc = launch_split3(d, 8 * H, K, K, p3, nullptr))) return rc;
-            m->wih_3.push_back(p3);
-        } else m->wih_3.push_back(nullptr);
-        if (!pack_gate_rows(m, base, "weight_hh_l0", H, H, tmp)) return MDD_ERR_STATE;
-        { SplitPtr sp{nullptr, nullptr}; if ((rc = upload_split(m, tmp, &sp))) return rc; m->whh_s.push_back(sp); }
-        { unsigned short *p3 = nullptr; if (use_packed(m) && (rc = upload_split3(m, tmp, &p3))) return rc; m->whh_3.push_back(p3); }
-        if (use_packed(m)) { std::vector<float> pk; pack_whh(tmp, H, pk); tmp.swap(pk); }
-        if ((rc = upload(m, tmp, &d))) return rc;
-        m->whh.push_back(d);
-        if (n > 0) {
-            snprintf(base, sizeof(base), "rnns.%d.batch_norm", n);
-            if (!bn_fold(m, base, 2 * H, sc, sh)) return MDD_ERR_STATE;
-            if ((rc = upload(m, sc, &m->bn_scale[n])) || (rc = upload(m, sh, &m->bn_shift[n]))) return rc;
-        }
-    }
-    {   // text encoder: bias_ih + bias_hh folded into the input projection's epilogue
-        const auto *e = get(m, "embeds.weight", (size_t)c.emb_rows * c.emb_dim);
-        if (!e) return MDD_ERR_STATE;
-        if ((rc = upload(m, *e, &m->emb))) return rc;
-        if (!pack_gate_rows(m, "lstm_embeds.", "weight_ih_l0", H, c.emb_dim, tmp)) return MDD_ERR_STATE;
-        if ((rc = upload(m, tmp, &m->t_wih)) || (rc = upload_split(m, tmp, &m->t_wih_s))) return rc;
-        if (c.emb_dim % 32 == 0) {
-            MDD_HIP_CHECK(hipMalloc((void **)&m->t_wih_3, (size_t)3 * 8 * H * c.emb_dim * sizeof(unsigned short)));
-            m->owned.push_back(m->t_wih_3);
-            if ((rc = launch_split3(m->t_wih, 8 * H, c.emb_dim, c.emb_dim, m->t_wih_3, nullptr))) return rc;
-        }
-        if (!pack_gate_rows(m, "lstm_embeds.", "weight_hh_l0", H, H, tmp)) return MDD_ERR_STATE;
-        if ((rc = upload_split(m, tmp, &m->t_whh_s))) return rc;
-        if (use_packed(m) && (rc = upload_split3(m, tmp, &m->t_whh_3))) return rc;
-        if (use_packed(m)) { std::vector<float> pk; pack_whh(tmp, H, pk); tmp.swap(pk); }
-        if ((rc = upload(m, tmp, &m->t_whh))) return rc;
-        std::vector<float> bi, bh;
-        if (!pack_gate_rows(m, "lstm_embeds.", "bias_ih_l0", H, 1, bi) || !pack_gate_rows(m, "lstm_embeds.", "bias_hh_l0", H, 1, bh)) return MDD_ERR_STATE;
-        for (size_t i = 0; i < bi.size(); i++) bi[i] += bh[i];
-        if ((rc = upload(m, bi, &m->t_bias))) return rc;
-    }
-    {
-        const auto *ws = get(m, "score.weight", (size_t)4 * H * H), *wf = get(m, "fc.1.weight", (size_t)c.num_class * 4 * H);
-        if (!ws || !wf) return MDD_ERR_STATE;
-        if (!bn_fold(m, "fc.0", 4 * H, sc, sh)) return MDD_ERR_STATE;
-        if ((rc = upload_split(m, *ws, &m->w_score_s))) return rc;
-        if ((rc = upload(m, *ws, &m->w_score)) || (rc = upload(m, *wf, &m->w_fc)) || (rc = upload(m, sc, &m->fscale)) ||
-            (rc = upload(m, sh, &m->fshift))) return rc;
-        m->w_fcp = nullptr;
-        const int D2 = 4 * H;
-        if (D2 % 64 == 0 && c.num_class <= 48) {   // consumer-order repack for attn_tail_mfma_kernel
-            const int J = D2 / 64;
-            std::vector<float> pk((size_t)4 * 3 * J * 64 * 4, 0.f);
-            for (int w = 0; w < 4; w++)
-                for (int nt = 0; nt < 3; nt++)
-                    for (int j = 0; j < J; j++)
-                        for (int lane = 0; lane < 64; lane++)
-                            for (int mm = 0; mm < 4; mm++) {
-                                const int n = nt * 16 + (lane & 15), k = w * (D2 / 4) + 16 * j + 4 * (lane >> 4) + mm;
-                                if (n < c.num_class) pk[((((size_t)w * 3 + nt) * J + j) * 64 + lane) * 4 + mm] = (*wf)[(size_t)n * D2 + k];
-                            }
-            if ((rc = upload(m, pk, &m->w_fcp))) return rc;
-        }
-    }
-    MDD_HIP_CHECK(hipDeviceSynchronize());
+    std::unique_ptr<DecodeWeights> w(new DecodeWeights());
+    if (int rc = build_weights(m, *w)) return rc;
+    m->drop_graphs();                         // captured graphs bake the old set's pointers
+    MDD_HIP_CHECK(hipDeviceSynchronize());    // (also: no forward still reads the old set)
+    m->weights.swap(w);
     m->finalized = true;
     return MDD_OK;
 }
@@ -608,8 +582,7 @@ extern "C" int mdd_finalize_weights(mdd_model *m) {
 extern "C" int mdd_enable_taps(mdd_model *m, int32_t on) {
     if (!m) return MDD_ERR_ARG;
     m->taps = on != 0;
-    for (auto &kv : m->graphs) (void)hipGraphExecDestroy(kv.second);
-    m->graphs.clear();
+    m->drop_graphs();
     return MDD_OK;
 }
 
@@ -617,8 +590,7 @@ extern "C" int mdd_set_precision(mdd_model *m, int32_t mode) {
     if (!m || mode < 0 || mode > 2) { set_error("mdd_set_precision: mode must be 0 (fp32 MFMA), 1 (split-bf16 x3) or 2 (f32x6 projections)"); return MDD_ERR_ARG; }
     if (m->precision != mode) {
         m->precision = mode;
-        for (auto &kv : m->graphs) (void)hipGraphExecDestroy(kv.second);
-        m->graphs.clear();
+        m->drop_graphs();
     }
     return MDD_OK;
 }
@@ -669,8 +641,7 @@ static int forward_prepare(mdd_model *m, const float *x_dev, int32_t B, int32_t 
     }
     m->lastB = B; m->lastT = T; m->lastL = L;
     if (g_ws_moved) {   // hipFree above synchronised the device, so no replay of an old graph is still running
-        for (auto &kv : m->graphs) (void)hipGraphExecDestroy(kv.second);
-        m->graphs.clear();
+        m->drop_graphs();
         g_ws_moved = false;
     }
     return MDD_OK;
@@ -693,7 +664,7 @@ extern "C" int mdd_forward(mdd_model *m, const float *x_dev, int32_t B, int32_t 
     key.x = x_dev; key.x1 = x1_dev; key.out = logp_dev; key.B = B; key.T = T; key.L = L; key.Traw = m->raw_T; key.tlen = m->tlen; key.llen = m->llen;
     auto it = m->graphs.find(key);
     if (it == m->graphs.end()) {
-        if (m->graphs.size() >= 8) { for (auto &kv : m->graphs) (void)hipGraphExecDestroy(kv.second); m->graphs.clear(); }
+        if (m->graphs.size() >= 8) m->drop_graphs();
         hipGraph_t graph = nullptr;
         std::lock_guard<std::mutex> prep_lock(g_prep_mu);
         MDD_HIP_CHECK(hipStreamBeginCapture(m->cap_stream, hipStreamCaptureModeRelaxed));
@@ -747,7 +718,7 @@ extern "C" int mdd_forward_raw(mdd_model *m, const float *raw_dev, int32_t B, in
         std::lock_guard<std::mutex> prep_lock(g_prep_mu);
         if (int rc = ensure(m->xstack, (size_t)B * T * m->cfg.feat, m->cap_stream)) return rc;
     }
-    if (g_ws_moved) { for (auto &kv : m->graphs) (void)hipGraphExecDestroy(kv.second); m->graphs.clear(); g_ws_moved = false; }
+    if (g_ws_moved) { m->drop_graphs(); g_ws_moved = false; }
     if (int rc = mdd_stack_skip(raw_dev, B, T_raw, D, 2, 2, 2, m->xstack.p, stream)) return rc;
     return mdd_forward(m, m->xstack.p, B, T, x1_dev, L, logp_dev, stream);
 }
@@ -818,7 +789,7 @@ extern "C" const float *mdd_tap(mdd_model *m, const char *name, int64_t *numel) 
     if (m->x3() && (n == "conv1" || n == "key")) {   // these stages exist only as split-bf16 planes: rebuild fp32 = hi + lo
         const bool cv = n == "conv1";
         ne = cv ? (int64_t)Tp * B * m->rnn_in() : (int64_t)L * B * H2;
-        DevBuf &dst = cv ? m->seq0 : m->key;
+        DeviceBuf &dst = cv ? m->seq0 : m->key;
         if (launch_unsplit(split_view(cv ? m->seq0_s : m->key_s, (size_t)ne), (size_t)ne, dst.p, nullptr) != MDD_OK) return nullptr;
         if (hipStreamSynchronize(nullptr) != hipSuccess) return nullptr;
         p = dst.p;
@@ -852,14 +823,14 @@ extern "C" int mdd_sync(mdd_model *m, void *stream) {
     if (!m) { set_error("null model"); return MDD_ERR_ARG; }
     MDD_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
     int flag = 0;
-    MDD_HIP_CHECK(hipMemcpy(&flag, m->err_flag, sizeof(int), hipMemcpyDeviceToHost));
+    MDD_HIP_CHECK(hipMemcpy(&flag, m->err_flag.p, sizeof(int), hipMemcpyDeviceToHost));
     if (flag == 2) {
-        MDD_HIP_CHECK(hipMemset(m->err_flag, 0, sizeof(int)));
+        MDD_HIP_CHECK(hipMemset(m->err_flag.p, 0, sizeof(int)));
         set_error("persistent BiLSTM kernel timed out waiting for its team (grid not fully resident?); set MDD_LSTM=step");
         return MDD_ERR_HIP;
     }
     if (flag) {
-        MDD_HIP_CHECK(hipMemset(m->err_flag, 0, sizeof(int)));
+        MDD_HIP_CHECK(hipMemset(m->err_flag.p, 0, sizeof(int)));
         set_error("index out of range in self");  // the message of the IndexError nn.Embedding raises
         return MDD_ERR_ARG;
     }

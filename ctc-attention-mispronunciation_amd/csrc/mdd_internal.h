@@ -5,6 +5,7 @@
 
 #include <map>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/mdd_hip.h"
@@ -23,6 +24,29 @@ void set_error(const char *fmt, ...);
     } while (0)
 
 #define MDD_LAUNCH_CHECK() MDD_HIP_CHECK(hipGetLastError())
+
+// A device array with exactly one owner: move-only, freed by its destructor.  need(n) grows it to at least n elements by freeing
+// and allocating afresh (the contents are not kept).
+template <class T> struct DeviceArray {
+    T *p = nullptr;
+    size_t cap = 0;   // in elements
+    DeviceArray() = default;
+    DeviceArray(const DeviceArray &) = delete;
+    DeviceArray &operator=(const DeviceArray &) = delete;
+    DeviceArray(DeviceArray &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    DeviceArray &operator=(DeviceArray &&o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); return *this; }
+    ~DeviceArray() { if (p) (void)hipFree(p); }
+    int need(size_t n) {
+        if (cap >= n) return MDD_OK;
+        T *old = p;
+        p = nullptr; cap = 0;
+        if (old) MDD_HIP_CHECK(hipFree(old));
+        MDD_HIP_CHECK(hipMalloc((void **)&p, n * sizeof(T)));
+        cap = n;
+        return MDD_OK;
+    }
+};
+using DeviceBuf = DeviceArray<float>;
 
 // A split-bf16 tensor: hi = bf16(x), lo = bf16(x - hi), two planes of the same [rows][ld] shape.
 struct SplitPtr { unsigned short *hi, *lo; };

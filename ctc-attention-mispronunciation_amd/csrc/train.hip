@@ -10,6 +10,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -19,19 +20,6 @@ struct mdd_train_ws;
 namespace mdd {
 
 struct TInfo { std::string key; int64_t numel; int is_buffer; };
-
-struct Buf {
-    float *p = nullptr; size_t cap = 0;
-    int need(size_t n) {
-        if (cap >= n) return MDD_OK;
-        if (p) MDD_HIP_CHECK(hipFree(p));
-        p = nullptr; cap = 0;
-        MDD_HIP_CHECK(hipMalloc((void **)&p, n * sizeof(float)));
-        cap = n;
-        return MDD_OK;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-};
 
 }  // namespace mdd
 
@@ -43,33 +31,24 @@ struct mdd_train_ws {
     int B = 0, T = 0, L = 0;          // shapes of the saved forward
     float p_drop = 0.f;
     // saved activations / scratch
-    mdd::Buf z0, a0, col1, w1r, z1, a1, seq0, gx, dgx, hb, cb, emb, text, key, att, cat, ycat, logits, logp;
-    mdd::Buf stats;                    // per-site mean / invstd
-    std::vector<mdd::Buf> xin, hraw, pd, gates, cst, wihp, whhp, whht;    // per rnn layer (index layers = the text encoder)
-    mdd::Buf tbias;
-    mdd::Buf d_a, d_b, d_c, part, dtext, dkey;      // backward temporaries
-    mdd::Buf whhs, hx;                 // flagged variant: W_hh' as hi/lo planes and the h exchange buffer of the persistent layer kernel
-    unsigned int *sync_words = nullptr;
+    mdd::DeviceBuf z0, a0, col1, w1r, z1, a1, seq0, gx, dgx, hb, cb, emb, text, key, att, cat, ycat, logits, logp;
+    mdd::DeviceBuf stats;              // per-site mean / invstd
+    std::vector<mdd::DeviceBuf> xin, hraw, pd, gates, cst, wihp, whhp, whht;    // per rnn layer (index layers = the text encoder)
+    mdd::DeviceBuf tbias;
+    mdd::DeviceBuf d_a, d_b, d_c, part, dtext, dkey;      // backward temporaries
+    mdd::DeviceBuf whhs, hx;           // flagged variant: W_hh' as hi/lo planes and the h exchange buffer of the persistent layer kernel
+    mdd::DeviceArray<unsigned int> sync_words;
     bool persist_ok = false;           // the device can hold the persistent layer kernel's grid
-    mdd::Buf xs_a, xs_b;               // split-bf16 operand planes of the flagged variant's GEMMs (hi plane, then lo plane)
+    mdd::DeviceBuf xs_a, xs_b;         // split-bf16 operand planes of the flagged variant's GEMMs (hi plane, then lo plane)
     int precision = 0;                 // 0: exact fp32 MFMA everywhere (the reference trains in fp32); 1: the large contractions as split-bf16 x3
-    int *err_flag = nullptr;           // set by the embedding gather on an id outside the table
-    mdd::Buf masks;                    // generated dropout masks (bytes)
+    mdd::DeviceArray<int> err_flag;    // set by the embedding gather on an id outside the table
+    mdd::DeviceBuf masks;              // generated dropout masks (bytes)
     std::vector<const unsigned char *> mask_ptr;
     const unsigned char *mask_rows[2] = {nullptr, nullptr};   // the two conv sites' masks in channels-last order
-    mdd::Buf maskt;
-    double *dacc = nullptr;            // fp64 column sums
+    mdd::DeviceBuf maskt;
+    mdd::DeviceArray<double> dacc;     // fp64 column sums
     const int64_t *ids = nullptr;      // canonical ids of the saved forward (caller memory, must stay valid until backward)
     const float *x = nullptr;
-    ~mdd_train_ws() {
-        mdd::Buf *all[] = {&z0, &a0, &col1, &w1r, &z1, &a1, &seq0, &gx, &dgx, &hb, &cb, &emb, &text, &key, &att, &cat, &ycat, &logits, &logp, &stats,
-                           &tbias, &d_a, &d_b, &d_c, &part, &masks, &dtext, &dkey, &xs_a, &xs_b, &whhs, &hx, &maskt};
-        for (auto *b : all) b->release();
-        for (auto *v : {&xin, &hraw, &pd, &gates, &cst, &wihp, &whhp, &whht}) for (auto &b : *v) b.release();
-        if (dacc) (void)hipFree(dacc);
-        if (err_flag) (void)hipFree(err_flag);
-        if (sync_words) (void)hipFree(sync_words);
-    }
 };
 
 namespace mdd {
@@ -166,7 +145,7 @@ static int lstm_forward_layer(mdd_train_ws *w, LstmStepArgs &a, hipStream_t st) 
         a.whh_split = SplitPtr{hi, lo};
         a.out = nullptr;
         if (int rc = w->hx.need((size_t)2 * 32 * granule_bg(a.B) * H * 2 + 64 + 256 * 6 * 2)) return rc;
-        return launch_lstm_layer_granule(a, reinterpret_cast<unsigned short *>(w->hx.p), w->sync_words, w->err_flag + 1, st);
+        return launch_lstm_layer_granule(a, reinterpret_cast<unsigned short *>(w->hx.p), w->sync_words.p, w->err_flag.p + 1, st);
     }
     return launch_lstm_layer_train(a, st);
 }
@@ -187,23 +166,22 @@ extern "C" int mdd_train_create(const mdd_config *cfg, int device, mdd_train_ws 
         set_error("mdd_train_create: unsupported geometry"); return MDD_ERR_ARG;
     }
     MDD_HIP_CHECK(hipSetDevice(device));
-    mdd_train_ws *w = new mdd_train_ws();
+    std::unique_ptr<mdd_train_ws> w(new mdd_train_ws());
     w->cfg = *cfg; w->device = device;
     { const char *pr = getenv("MDD_TRAIN_PRECISION"); if (pr && (!strcmp(pr, "bf16x3") || !strcmp(pr, "1"))) w->precision = 1; }
-    build_info(w);
+    build_info(w.get());
     const int nl = cfg->layers + 1;
     w->xin.resize(nl); w->hraw.resize(nl); w->pd.resize(nl); w->gates.resize(nl); w->cst.resize(nl); w->wihp.resize(nl); w->whhp.resize(nl); w->whht.resize(nl);
-    if (hipMalloc((void **)&w->dacc, sizeof(double) * 2 * 8192) != hipSuccess || hipMalloc((void **)&w->err_flag, 2 * sizeof(int)) != hipSuccess ||
-        hipMemset(w->err_flag, 0, 2 * sizeof(int)) != hipSuccess || hipMalloc((void **)&w->sync_words, 32 * sizeof(unsigned int)) != hipSuccess) {
-        delete w; set_error("mdd_train_create: out of memory"); return MDD_ERR_NOMEM;
+    if (w->dacc.need(2 * 8192) || w->err_flag.need(2) || hipMemset(w->err_flag.p, 0, 2 * sizeof(int)) != hipSuccess || w->sync_words.need(32)) {
+        set_error("mdd_train_create: out of memory"); return MDD_ERR_NOMEM;
     }
-    if (int rc = init_gemm_attributes()) { delete w; return rc; }
-    if (int rc = init_granule_attributes()) { delete w; return rc; }
-    if (int rc = init_conv1_attributes()) { delete w; return rc; }
+    if (int rc = init_gemm_attributes()) return rc;
+    if (int rc = init_granule_attributes()) return rc;
+    if (int rc = init_conv1_attributes()) return rc;
     { int n_cu = 0; w->persist_ok = hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && persistent_grid_fits(n_cu) &&
                                      !(getenv("MDD_LSTM") && !strcmp(getenv("MDD_LSTM"), "step")); }
-    if (8 * cfg->hidden > 8192) { delete w; set_error("mdd_train_create: hidden too large for the statistics scratch"); return MDD_ERR_ARG; }
-    *out = w;
+    if (8 * cfg->hidden > 8192) { set_error("mdd_train_create: hidden too large for the statistics scratch"); return MDD_ERR_ARG; }
+    *out = w.release();
     return MDD_OK;
 }
 extern "C" void mdd_train_destroy(mdd_train_ws *w) { if (w) { (void)hipSetDevice(w->device); (void)hipDeviceSynchronize(); delete w; } }
@@ -300,7 +278,7 @@ static int train_forward_enqueue(mdd_train_ws *w, float *const *tensors, const f
     TRY(launch_conv0_train_fwd(x_dev, P("conv.0.conv.weight"), P("conv.0.conv.bias"), w->z0.p, B, T, c.feat, ch, st));
     BnSite s0{w->mask_rows[0], scale};
     TRY(launch_bn_train_fwd(w->z0.p, R0, ch, P("conv.0.batch_norm.weight"), P("conv.0.batch_norm.bias"), eps, mom, P("conv.0.batch_norm.running_mean"),
-                            P("conv.0.batch_norm.running_var"), w->dacc, mean, invstd, &s0, w->a0.p, st));
+                            P("conv.0.batch_norm.running_var"), w->dacc.p, mean, invstd, &s0, w->a0.p, st));
     // ---- conv1 (im2col + GEMM) -> BN -> ReLU -> Dropout -> [T',B,ch*W2]
     TRY(launch_pack_w1(P("conv.1.conv.weight"), w->w1r.p, ch, true, st));
     if (direct1) {
@@ -311,7 +289,7 @@ static int train_forward_enqueue(mdd_train_ws *w, float *const *tensors, const f
     }
     BnSite s1{w->mask_rows[1], scale};
     TRY(launch_bn_train_fwd(w->z1.p, R1, ch, P("conv.1.batch_norm.weight"), P("conv.1.batch_norm.bias"), eps, mom, P("conv.1.batch_norm.running_mean"),
-                            P("conv.1.batch_norm.running_var"), w->dacc, mean + ch, invstd + ch, &s1, w->a1.p, st));
+                            P("conv.1.batch_norm.running_var"), w->dacc.p, mean + ch, invstd + ch, &s1, w->a1.p, st));
     TRY(launch_cnn_seq(w->a1.p, w->seq0.p, B, Tp, W2, ch, true, st));
     // ---- BatchRNN x layers
     for (int n = 0; n < nl; n++) {
@@ -320,7 +298,7 @@ static int train_forward_enqueue(mdd_train_ws *w, float *const *tensors, const f
         const float *xin = w->seq0.p;
         if (n > 0) {
             TRY(launch_bn_train_fwd(w->pd[n - 1].p, R, H2, P(r + ".batch_norm.weight"), P(r + ".batch_norm.bias"), eps, mom, P(r + ".batch_norm.running_mean"),
-                                    P(r + ".batch_norm.running_var"), w->dacc, mean + 2 * ch + (n - 1) * H2, invstd + 2 * ch + (n - 1) * H2, nullptr, w->xin[n].p, st));
+                                    P(r + ".batch_norm.running_var"), w->dacc.p, mean + 2 * ch + (n - 1) * H2, invstd + 2 * ch + (n - 1) * H2, nullptr, w->xin[n].p, st));
             xin = w->xin[n].p;
         }
         TRY(launch_pack_gates(P(r + ".rnn.weight_ih_l0"), P(r + ".rnn.weight_ih_l0_reverse"), w->wihp[n].p, H, K, st));
@@ -335,7 +313,7 @@ static int train_forward_enqueue(mdd_train_ws *w, float *const *tensors, const f
     }
     const float *X = w->pd[nl - 1].p;
     // ---- text encoder: Embedding -> BiLSTM (bias) ; key = score(text)
-    TRY(launch_embed(P("embeds.weight"), c.emb_rows, E, x1_dev, B, L, w->emb.p, SplitPtr{nullptr, nullptr}, w->err_flag, st));
+    TRY(launch_embed(P("embeds.weight"), c.emb_rows, E, x1_dev, B, L, w->emb.p, SplitPtr{nullptr, nullptr}, w->err_flag.p, st));
     TRY(launch_pack_gates(P("lstm_embeds.weight_ih_l0"), P("lstm_embeds.weight_ih_l0_reverse"), w->wihp[nl].p, H, E, st));
     TRY(launch_pack_gates(P("lstm_embeds.weight_hh_l0"), P("lstm_embeds.weight_hh_l0_reverse"), w->whhp[nl].p, H, H, st));
     TRY(launch_pack_gates(P("lstm_embeds.bias_ih_l0"), P("lstm_embeds.bias_ih_l0_reverse"), w->tbias.p, H, 1, st));
@@ -357,7 +335,7 @@ static int train_forward_enqueue(mdd_train_ws *w, float *const *tensors, const f
     TRY(launch_copy_cols(X, H2, 0, w->cat.p, 2 * H2, 0, R, H2, false, st));
     TRY(launch_gemm_f32(false, true, w->att.p, w->hraw[nl].p, nullptr, w->cat.p + H2, Tp, H2, L, L, B * H2, B * 2 * H2, B, (long)Tp * L, H2, 2 * H2, false, st));
     // ---- fc: BatchNorm1d(4H) -> Linear(4H -> C, no bias) -> log-softmax
-    TRY(launch_bn_train_fwd(w->cat.p, R, 2 * H2, P("fc.0.weight"), P("fc.0.bias"), eps, mom, P("fc.0.running_mean"), P("fc.0.running_var"), w->dacc,
+    TRY(launch_bn_train_fwd(w->cat.p, R, 2 * H2, P("fc.0.weight"), P("fc.0.bias"), eps, mom, P("fc.0.running_mean"), P("fc.0.running_var"), w->dacc.p,
                             mean + 2 * ch + nl * H2, invstd + 2 * ch + nl * H2, nullptr, w->ycat.p, st));
     {   // [R, 1536] x [45, 1536]^T: one column tile, 63 row tiles at R = 8000 -> the contraction is cut into partial products so the chip is busy
         const int Kfc = 2 * H2, tiles = (int)((R + 127) / 128) * ((C + 127) / 128);
@@ -390,7 +368,7 @@ static int lstm_backward(mdd_train_ws *w, int n, int Tn, int B, int K, const flo
         unsigned short *hi = reinterpret_cast<unsigned short *>(w->whhs.p), *lo = hi + nW;
         TRY(launch_split_rows(w->whht[n].p, G, (size_t)2 * H, G, G, hi, lo, st));
         TRY(w->hx.need(lstm_bwd_granule_hx_bytes(H) / 4));
-        TRY(launch_lstm_bwd_granule(dout, a.gates, a.cst, SplitPtr{hi, lo}, a.dg, Tn, B, H, reinterpret_cast<unsigned short *>(w->hx.p), w->sync_words, w->err_flag + 1, st));
+        TRY(launch_lstm_bwd_granule(dout, a.gates, a.cst, SplitPtr{hi, lo}, a.dg, Tn, B, H, reinterpret_cast<unsigned short *>(w->hx.p), w->sync_words.p, w->err_flag.p + 1, st));
     } else {
         TRY(launch_lstm_bwd(a, st));
     }
@@ -441,7 +419,7 @@ static int train_backward_enqueue(mdd_train_ws *w, float *const *tensors, const 
     TRY(gemm_tn(w, dlogits, C, w->ycat.p, 2 * H2, GR("fc.1.weight"), C, 2 * H2, (int)R, st));
     float *dycat = w->d_a.p, *dcat = w->d_c.p;
     TRY(launch_gemm_f32(false, true, dlogits, P("fc.1.weight"), nullptr, dycat, (int)R, 2 * H2, C, C, 2 * H2, 2 * H2, 1, 0, 0, 0, false, st));
-    TRY(launch_bn_train_bwd(w->cat.p, dycat, R, 2 * H2, P("fc.0.weight"), P("fc.0.bias"), mean + 2 * ch + nl * H2, invstd + 2 * ch + nl * H2, nullptr, w->dacc,
+    TRY(launch_bn_train_bwd(w->cat.p, dycat, R, 2 * H2, P("fc.0.weight"), P("fc.0.bias"), mean + 2 * ch + nl * H2, invstd + 2 * ch + nl * H2, nullptr, w->dacc.p,
                             dcat, GR("fc.0.weight"), GR("fc.0.bias"), st));
     // ---- attention
     float *dX = w->ycat.p;                                          // [R, 2H]  (ycat is free now)
@@ -460,7 +438,7 @@ static int train_backward_enqueue(mdd_train_ws *w, float *const *tensors, const 
     float *demb = w->d_c.p;
     TRY(lstm_backward(w, nl, L, B, E, dtext, w->emb.p, GR("lstm_embeds.weight_ih_l0"), GR("lstm_embeds.weight_ih_l0_reverse"), GR("lstm_embeds.weight_hh_l0"),
                       GR("lstm_embeds.weight_hh_l0_reverse"), demb, st));
-    TRY(launch_col_sum(w->dgx.p, Rt, G2, w->dacc, w->tbias.p, st));            // packed bias gradient (u*4+g order)
+    TRY(launch_col_sum(w->dgx.p, Rt, G2, w->dacc.p, w->tbias.p, st));            // packed bias gradient (u*4+g order)
     TRY(launch_unpack_gates(w->tbias.p, GR("lstm_embeds.bias_ih_l0"), GR("lstm_embeds.bias_ih_l0_reverse"), H, 1, st));
     TRY(launch_unpack_gates(w->tbias.p, GR("lstm_embeds.bias_hh_l0"), GR("lstm_embeds.bias_hh_l0_reverse"), H, 1, st));
     TRY(launch_embed_bwd(demb, w->ids, B, L, E, c.emb_rows, GR("embeds.weight"), st));
@@ -476,7 +454,7 @@ static int train_backward_enqueue(mdd_train_ws *w, float *const *tensors, const 
                           GR(r + ".rnn.weight_hh_l0"), GR(r + ".rnn.weight_hh_l0_reverse"), dxin, st));
         if (n > 0) {
             TRY(launch_bn_train_bwd(w->pd[n - 1].p, dxin, R, H2, P(r + ".batch_norm.weight"), P(r + ".batch_norm.bias"), mean + 2 * ch + (n - 1) * H2,
-                                    invstd + 2 * ch + (n - 1) * H2, nullptr, w->dacc, w->ycat.p, GR(r + ".batch_norm.weight"), GR(r + ".batch_norm.bias"), st));
+                                    invstd + 2 * ch + (n - 1) * H2, nullptr, w->dacc.p, w->ycat.p, GR(r + ".batch_norm.weight"), GR(r + ".batch_norm.bias"), st));
             dpd = w->ycat.p;
         }
     }
@@ -485,9 +463,9 @@ static int train_backward_enqueue(mdd_train_ws *w, float *const *tensors, const 
     TRY(launch_cnn_seq(da1, w->d_c.p, B, Tp, W2, ch, false, st));
     BnSite s1{w->mask_rows[1], scale};
     float *dz1 = w->d_a.p;
-    TRY(launch_bn_train_bwd(w->z1.p, da1, R1, ch, P("conv.1.batch_norm.weight"), P("conv.1.batch_norm.bias"), mean + ch, invstd + ch, &s1, w->dacc, dz1,
+    TRY(launch_bn_train_bwd(w->z1.p, da1, R1, ch, P("conv.1.batch_norm.weight"), P("conv.1.batch_norm.bias"), mean + ch, invstd + ch, &s1, w->dacc.p, dz1,
                             GR("conv.1.batch_norm.weight"), GR("conv.1.batch_norm.bias"), st));
-    TRY(launch_col_sum(dz1, R1, ch, w->dacc, GR("conv.1.conv.bias"), st));
+    TRY(launch_col_sum(dz1, R1, ch, w->dacc.p, GR("conv.1.conv.bias"), st));
     TRY(w->d_b.need((size_t)ch * 9 * ch));
     float *da0 = w->d_c.p;
     const bool direct1 = ch == 32 && W1 <= 128 && !getenv("MDD_TRAIN_CONV1_IM2COL");
@@ -507,9 +485,9 @@ static int train_backward_enqueue(mdd_train_ws *w, float *const *tensors, const 
     // ---- conv0
     BnSite s0{w->mask_rows[0], scale};
     float *dz0 = w->d_a.p;
-    TRY(launch_bn_train_bwd(w->z0.p, da0, R0, ch, P("conv.0.batch_norm.weight"), P("conv.0.batch_norm.bias"), mean, invstd, &s0, w->dacc, dz0,
+    TRY(launch_bn_train_bwd(w->z0.p, da0, R0, ch, P("conv.0.batch_norm.weight"), P("conv.0.batch_norm.bias"), mean, invstd, &s0, w->dacc.p, dz0,
                             GR("conv.0.batch_norm.weight"), GR("conv.0.batch_norm.bias"), st));
-    TRY(launch_conv0_train_bwd(w->x, dz0, w->dacc, GR("conv.0.conv.weight"), GR("conv.0.conv.bias"), B, T, c.feat, ch, st));
+    TRY(launch_conv0_train_bwd(w->x, dz0, w->dacc.p, GR("conv.0.conv.weight"), GR("conv.0.conv.bias"), B, T, c.feat, ch, st));
     return MDD_OK;
 }
 
@@ -518,8 +496,8 @@ extern "C" int mdd_train_sync(mdd_train_ws *w, void *stream) {
     if (!w) { set_error("null handle"); return MDD_ERR_ARG; }
     MDD_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
     int flag[2] = {0, 0};
-    MDD_HIP_CHECK(hipMemcpy(flag, w->err_flag, 2 * sizeof(int), hipMemcpyDeviceToHost));
-    if (flag[0] || flag[1]) MDD_HIP_CHECK(hipMemset(w->err_flag, 0, 2 * sizeof(int)));
+    MDD_HIP_CHECK(hipMemcpy(flag, w->err_flag.p, 2 * sizeof(int), hipMemcpyDeviceToHost));
+    if (flag[0] || flag[1]) MDD_HIP_CHECK(hipMemset(w->err_flag.p, 0, 2 * sizeof(int)));
     if (flag[1]) { set_error("persistent BiLSTM layer kernel gave up waiting for its team (was another persistent launch resident on this device?)"); return MDD_ERR_HIP; }
     if (flag[0]) { set_error("index out of range in self"); return MDD_ERR_ARG; }
     return MDD_OK;
