@@ -16,6 +16,7 @@ EXPORTS = (
     "mdd_last_error", "mdd_version", "mdd_create", "mdd_destroy", "mdd_load_weight", "mdd_finalize_weights",
     "mdd_set_precision", "mdd_get_precision", "mdd_stack_len", "mdd_stack_skip", "mdd_len_frames", "mdd_forward", "mdd_forward_fused", "mdd_forward_raw", "mdd_forward_num_stages", "mdd_forward_profile", "mdd_tap", "mdd_tap_copy", "mdd_enable_taps", "mdd_sync",
     "mdd_greedy", "mdd_beam", "mdd_ctc_loss", "mdd_ctc_workspace_bytes", "mdd_align", "mdd_align_batch", "mdd_eval_batch", "mdd_fbank_num_frames", "mdd_fbank", "mdd_fbank_batch_len", "mdd_fbank_batch",
+    "mdd_resample_len", "mdd_resample_filter", "mdd_resample_batch",
     "mdd_train_create", "mdd_train_destroy", "mdd_train_num_tensors", "mdd_train_tensor_info", "mdd_train_num_masks", "mdd_train_mask_bytes",
     "mdd_train_forward", "mdd_train_backward", "mdd_train_sync", "mdd_train_set_precision", "mdd_adam_step",
     "mdd_diag_gemm_ph8", "mdd_diag_gates", "mdd_diag_gemm", "mdd_diag_gemm_time",
@@ -84,6 +85,10 @@ def lib():
     L.mdd_fbank_batch_len.argtypes = [i64p, i32, i32, i32]
     L.mdd_fbank_batch_len.restype = i32
     L.mdd_fbank_batch.argtypes = [vp, vp, i32, i32, vp, vp, i32, i32, i32, vp, vp]
+    L.mdd_resample_len.argtypes = [C.c_int64, i32]
+    L.mdd_resample_len.restype = C.c_int64
+    L.mdd_resample_filter.argtypes = [i32, vp, vp, C.c_int64]
+    L.mdd_resample_batch.argtypes = [vp, vp, vp, i32, vp, vp, vp]
     L.mdd_train_create.argtypes = [C.POINTER(MddConfig), C.c_int, C.POINTER(vp)]
     L.mdd_train_destroy.argtypes = [vp]
     L.mdd_train_destroy.restype = None

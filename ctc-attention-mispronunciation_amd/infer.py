@@ -11,10 +11,16 @@ The conf YAML is read as ``infer_init`` reads it (AA/infer.py:211-261): the chec
 the order of the printed blocks).  The WAVs go to the GPU once and become the padded batches in one kernel launch per batch
 (``WavBatchLoader`` / ``fbank_batch``); the loop is ``infer_core.infer``.
 
-What the reference does that needs services absent offline is left out, and says so: no denoiser (``eeo_apm_test``), no
-resampler (non-16 kHz audio exits with status 2), canonical phones from the CMU dictionary only (``-p g2p|phonemizer|
-transcript`` and ``-f ipa`` exit with status 2; a word the dictionary lacks is skipped with one line), no ECDICT translation
-(line 4 of each block is empty).  Nothing is written into the input folder.
+WAVs at any rate from 1 to 384 kHz are accepted, in every format ``read_wav`` reads.  As the reference resamples every input
+that is not 16 kHz to 16-bit 16 kHz audio (``librosa.resample`` + ``sf.write``, AA/infer.py:498-501), a batch holding such an
+input is resampled and quantised to PCM16 on the GPU in one launch (``resample_batch``) and goes on to ``fbank_batch`` without
+leaving the device; the reference's rewrite of the input file is not done.  A 16 kHz file that is not 16-bit PCM is
+quantised to PCM16 by the same rule on the host (the reference hands it to its denoiser unchanged).  The 3-minute limit, the
+400-sample minimum and the total audio time count 16 kHz samples, as the reference counts them after resampling.
+
+What the reference does that needs services absent offline is left out, and says so: no denoiser (``eeo_apm_test``), canonical
+phones from the CMU dictionary only (``-p g2p|phonemizer|transcript`` and ``-f ipa`` exit with status 2; a word the dictionary
+lacks is skipped with one line), no ECDICT translation (line 4 of each block is empty).  Nothing is written into the input folder.
 """
 import argparse
 import os
@@ -68,8 +74,9 @@ def load_model(opts, precision=None):
 
 
 def collect(folder, phonetic):
-    """(items, word_dict, transcripts, total seconds) over the N.wav / N.txt pairs of `folder`, sorted by N as a string."""
-    from .utils.fbank import read_wav, SAMPLE_RATE
+    """(items, word_dict, transcripts, total seconds) over the N.wav / N.txt pairs of `folder`, sorted by N as a string.
+    Each item is (utt, samples, phones, sample rate); lengths and seconds are counted at 16 kHz."""
+    from .utils.fbank import read_wav, resample_len, quantize_pcm16, SAMPLE_RATE
     items, word_dict, transcripts, total = [], {}, {}, 0.0
     names = sorted(p for p in os.listdir(folder) if os.path.isfile(os.path.join(folder, p)) and p.endswith(".wav"))
     for p in sorted(names, key=lambda q: q[:-4]):
@@ -78,13 +85,17 @@ def collect(folder, phonetic):
         if not os.path.exists(txt):
             continue
         wav_path = os.path.normpath(os.path.join(folder, p))
-        samples, rate = read_wav(wav_path)
-        if rate != SAMPLE_RATE:
-            refuse("%s: %d Hz audio; resampling to %d Hz needs librosa, which is absent" % (wav_path, rate, SAMPLE_RATE))
-        if samples.size > MAX_SAMPLES:
+        samples, rate, pcm16 = read_wav(wav_path, with_format=True)
+        try:
+            n16 = resample_len(samples.size, rate)
+        except ValueError as e:
+            refuse("%s: %s" % (wav_path, e))
+        if rate == SAMPLE_RATE and not pcm16:
+            samples = quantize_pcm16(samples)
+        if n16 > MAX_SAMPLES:
             print("{} skipped, currently wav length should be no more than 3 minutes!".format(wav_path))
             continue
-        if samples.size < 400:
+        if n16 < 400:
             print("{} skipped, shorter than one 25 ms window".format(wav_path))
             continue
         with open(txt, "r") as f:
@@ -96,10 +107,10 @@ def collect(folder, phonetic):
         if not cmu:
             print("%s skipped: '%s' is not in the CMU dictionary" % (utt, utterance.strip()))
             continue
-        items.append((utt, samples, phonetic.phones_for_model(cmu)))
+        items.append((utt, samples, phonetic.phones_for_model(cmu), rate))
         word_dict[utt] = {"ipa": cmu, "cmu_phns": cmu}
         transcripts[utt] = utterance
-        total += samples.size / float(SAMPLE_RATE)
+        total += n16 / float(SAMPLE_RATE)
     return items, word_dict, transcripts, total
 
 

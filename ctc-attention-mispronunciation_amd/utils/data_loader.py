@@ -144,11 +144,12 @@ class SpeechDataLoader(DataLoader):
 
 class WavBatchLoader(object):
     """Batches of WAVs in the shape of ``SpeechDataLoader(SpeechDataset(...), batch_size, shuffle=False)`` as AA/infer.py:278-279
-    builds them, straight from samples: ``items`` is a list of (utt, samples [16 kHz, int16 scale], canonical phones as a
-    space-separated string), taken in the given order.  Each batch is the reference's 7-tuple (inputs, input_sizes, labels,
-    label_sizes, trans, trans_sizes, utt_list): ``inputs`` / ``input_sizes`` come from ``fbank.fbank_batch`` (one kernel launch,
-    the features never pass through the host); trans ids are looked up as SpeechDataset does (unknown -> 'UNK') and padded as
-    create_input pads them; the label pair repeats them (infer.py reads its canonical file as the labels too, :273-276)."""
+    builds them, straight from samples: ``items`` is a list of (utt, samples [int16 scale], canonical phones as a
+    space-separated string[, sample rate, default 16000]), taken in the given order.  Each batch is the reference's 7-tuple
+    (inputs, input_sizes, labels, label_sizes, trans, trans_sizes, utt_list): ``inputs`` / ``input_sizes`` come from
+    ``fbank.fbank_batch`` (one kernel launch, the features never pass through the host; a batch that holds any rate other than
+    16 kHz is first resampled to 16 kHz PCM16 by ``fbank.resample_batch``, AA/infer.py:498-501, and its samples stay on the
+    device); trans ids are looked up as SpeechDataset does (unknown -> 'UNK') and padded as create_input pads them; the label pair repeats them (infer.py reads its canonical file as the labels too, :273-276)."""
 
     def __init__(self, items, vocab, batch_size, cmvn=None, right_ctx=2, n_skip_frame=2, n_downsample=2):
         self.items = list(items)
@@ -161,12 +162,18 @@ class WavBatchLoader(object):
         return (len(self.items) + self.batch_size - 1) // self.batch_size
 
     def __iter__(self):
-        from .fbank import fbank_batch
+        from .fbank import SAMPLE_RATE, fbank_batch, resample_batch
         unk = self.vocab.word2index["UNK"]
         for start in range(0, len(self.items), self.batch_size):
             chunk = self.items[start:start + self.batch_size]
-            inputs, input_sizes = fbank_batch([it[1] for it in chunk], cmvn=self.cmvn, right_ctx=self.right_ctx,
-                                              n_skip_frame=self.n_skip_frame, n_downsample=self.n_downsample)
+            rates = [int(it[3]) if len(it) > 3 else SAMPLE_RATE for it in chunk]
+            if all(r == SAMPLE_RATE for r in rates):
+                inputs, input_sizes = fbank_batch([it[1] for it in chunk], cmvn=self.cmvn, right_ctx=self.right_ctx,
+                                                  n_skip_frame=self.n_skip_frame, n_downsample=self.n_downsample)
+            else:
+                wav, offsets = resample_batch([it[1] for it in chunk], rates)
+                inputs, input_sizes = fbank_batch(wav, cmvn=self.cmvn, right_ctx=self.right_ctx, n_skip_frame=self.n_skip_frame,
+                                                  n_downsample=self.n_downsample, offsets=offsets)
             ids = [[self.vocab.word2index.get(c, unk) for c in it[2].split()] for it in chunk]
             l_max = max(len(t) for t in ids)
             trans = torch.zeros(len(chunk), l_max)

@@ -11,7 +11,6 @@ format the data loader reads (``kaldiio.load_mat``, ``AA/utils/data_loader.py:12
 """
 import ctypes as C
 import struct
-import wave
 
 import numpy as np
 import torch
@@ -22,13 +21,65 @@ SAMPLE_RATE = 16000
 NUM_COLS = 81
 
 
-def read_wav(path):
-    """16-bit mono PCM WAV -> (float32 samples on the int16 scale, sample rate), as Kaldi's WaveData holds them."""
-    with wave.open(path, "rb") as w:
-        if w.getsampwidth() != 2:
-            raise ValueError("%s: only 16-bit PCM is supported" % path)
-        x = np.frombuffer(w.readframes(w.getnframes()), dtype="<i2").reshape(-1, w.getnchannels())
-        return x[:, 0].astype(np.float32), w.getframerate()
+_WAVE_FORMAT_PCM, _WAVE_FORMAT_IEEE_FLOAT, _WAVE_FORMAT_EXTENSIBLE = 1, 3, 0xFFFE
+
+
+def read_wav(path, with_format=False):
+    """WAV -> (float32 samples of channel 0 on the int16 scale, sample rate), as Kaldi's WaveData holds 16-bit PCM.
+
+    Reads what ``sf.read`` reads in a plain WAV (AA/infer.py:497): 8-bit (unsigned), 16-, 24- and 32-bit PCM, IEEE float32 and
+    float64, in a plain or a ``WAVE_FORMAT_EXTENSIBLE`` header.  The value is libsndfile's normalised sample (PCM: the integer
+    over 2^(bits-1), 8-bit centred on 128; float: as stored) times 32768, so 16-bit PCM comes back as the integers themselves.
+    32-bit PCM and float64 keep float32's 24 significant bits.  ``with_format=True`` adds a third value, True when the file is
+    16-bit PCM."""
+    with open(path, "rb") as f:
+        data = f.read()
+    if len(data) < 12 or data[:4] != b"RIFF" or data[8:12] != b"WAVE":
+        raise ValueError("%s: not a RIFF/WAVE file" % path)
+    fmt = body = None
+    pos = 12
+    while pos + 8 <= len(data) and (fmt is None or body is None):
+        cid, size = data[pos:pos + 4], struct.unpack_from("<I", data, pos + 4)[0]
+        chunk = data[pos + 8:pos + 8 + size]
+        if cid == b"fmt ":
+            fmt = chunk
+        elif cid == b"data":
+            body = chunk
+        pos += 8 + size + (size & 1)
+    if fmt is None or body is None or len(fmt) < 16:
+        raise ValueError("%s: no fmt or data chunk" % path)
+    tag, channels, rate, _, align, bits = struct.unpack_from("<HHIIHH", fmt, 0)
+    if tag == _WAVE_FORMAT_EXTENSIBLE:
+        if len(fmt) < 26:
+            raise ValueError("%s: truncated WAVE_FORMAT_EXTENSIBLE header" % path)
+        tag = struct.unpack_from("<H", fmt, 24)[0]          # the first two bytes of the sub-format GUID
+    width = bits // 8
+    if channels < 1 or bits % 8 or align != channels * width:
+        raise ValueError("%s: unsupported layout (%d channels, %d bits, block align %d)" % (path, channels, bits, align))
+    frames = len(body) // align
+    raw = np.frombuffer(body, dtype=np.uint8, count=frames * align).reshape(frames, align)[:, :width]
+    if tag == _WAVE_FORMAT_PCM and bits == 16:
+        x = raw.copy().view("<i2")[:, 0].astype(np.float32)
+    elif tag == _WAVE_FORMAT_PCM and bits == 8:
+        x = ((raw[:, 0].astype(np.float64) - 128.0) * 256.0).astype(np.float32)
+    elif tag == _WAVE_FORMAT_PCM and bits == 24:
+        v = raw[:, 0].astype(np.int32) | (raw[:, 1].astype(np.int32) << 8) | (raw[:, 2].astype(np.int32) << 16)
+        x = ((v - ((v & 0x800000) << 1)).astype(np.float64) / 256.0).astype(np.float32)
+    elif tag == _WAVE_FORMAT_PCM and bits == 32:
+        x = (raw.copy().view("<i4")[:, 0].astype(np.float64) / 65536.0).astype(np.float32)
+    elif tag == _WAVE_FORMAT_IEEE_FLOAT and bits in (32, 64):
+        x = (raw.copy().view("<f4" if bits == 32 else "<f8")[:, 0].astype(np.float64) * 32768.0).astype(np.float32)
+    else:
+        raise ValueError("%s: unsupported WAV sample format (tag %d, %d bits)" % (path, tag, bits))
+    pcm16 = tag == _WAVE_FORMAT_PCM and bits == 16
+    return (x, rate, pcm16) if with_format else (x, rate)
+
+
+def quantize_pcm16(samples):
+    """Samples on the int16 scale -> the PCM16 values ``sf.write`` stores for them (AA/infer.py:501): clamp(rint(32767 * x),
+    -32768, 32767) of x = samples / 32768, in float64, as float32 (the quantisation resample_batch applies to every output)."""
+    x = np.asarray(samples, dtype=np.float64) / 32768.0
+    return np.clip(np.rint(x * 32767.0), -32768.0, 32767.0).astype(np.float32)
 
 
 def read_cmvn_stats(path):
@@ -122,7 +173,7 @@ def load_mat(spec):
         return np.frombuffer(f.read(4 * rows * cols), dtype="<f4").reshape(rows, cols).copy()
 
 
-def fbank_batch(wavs, cmvn=None, right_ctx=2, n_skip_frame=2, n_downsample=2, out=None):
+def fbank_batch(wavs, cmvn=None, right_ctx=2, n_skip_frame=2, n_downsample=2, out=None, offsets=None):
     """B utterances -> the padded model input the reference's infer.py batches from them, in one kernel launch (mdd_fbank_batch):
     fbank + CMVN per utterance, make_context(., 0, right_ctx) + skip_feat(., n_skip_frame) + zero rows up to a multiple of
     n_downsample (AA/utils/data_loader.py:138-142), zero-padded to the longest (create_input, :151-181).
@@ -130,12 +181,23 @@ def fbank_batch(wavs, cmvn=None, right_ctx=2, n_skip_frame=2, n_downsample=2, ou
     ``wavs``: list of 1-D sample arrays / tensors at 16 kHz on the int16 scale; ``cmvn``: None or the (scale, offset) pair of
     ``cmvn_scale_offset``.  Returns (inputs [B, T_out, (right_ctx+1)*81] float32 CUDA, input_sizes [B] float32 CPU), where
     input_sizes[b] is create_input's float32 ``feature_length / inputs_max_length``.  Each stored frame is bit-identical to
-    ``compute_fbank_feats`` of that utterance.  ``out`` (optional) is written whole, padding included."""
-    if len(wavs) == 0:
-        raise ValueError("fbank_batch: empty batch")
-    host = [np.asarray(w.detach().cpu().numpy() if torch.is_tensor(w) else w, dtype=np.float32).reshape(-1) for w in wavs]
-    B = len(host)
-    n = np.array([h.size for h in host], dtype=np.int64)
+    ``compute_fbank_feats`` of that utterance.  ``out`` (optional) is written whole, padding included.
+
+    With ``offsets`` ([B+1] int64, host), ``wavs`` is instead one 1-D float32 CUDA tensor holding the B utterances back to back,
+    utterance b at [offsets[b], offsets[b+1]) -- what ``resample_batch`` returns; the samples stay on the device."""
+    if offsets is not None:
+        offsets = np.asarray(offsets.cpu().numpy() if torch.is_tensor(offsets) else offsets, dtype=np.int64).reshape(-1)
+        if not (torch.is_tensor(wavs) and wavs.is_cuda and wavs.dtype == torch.float32 and wavs.dim() == 1):
+            raise ValueError("fbank_batch: with offsets, wavs must be one 1-D float32 CUDA tensor")
+        if offsets.size < 2 or offsets[0] != 0 or np.any(np.diff(offsets) < 0) or offsets[-1] > wavs.numel():
+            raise ValueError("fbank_batch: offsets must rise from 0 to at most %d" % wavs.numel())
+        n = np.diff(offsets)
+    else:
+        if len(wavs) == 0:
+            raise ValueError("fbank_batch: empty batch")
+        host = [np.asarray(w.detach().cpu().numpy() if torch.is_tensor(w) else w, dtype=np.float32).reshape(-1) for w in wavs]
+        n = np.array([h.size for h in host], dtype=np.int64)
+    B = len(n)
     L = _lib.lib()
     t_out = L.mdd_fbank_batch_len(n.ctypes.data_as(C.POINTER(C.c_int64)), B, n_skip_frame, n_downsample)
     if t_out < 0:
@@ -144,9 +206,15 @@ def fbank_batch(wavs, cmvn=None, right_ctx=2, n_skip_frame=2, n_downsample=2, ou
                          % (short[0] if short else "?", L.mdd_last_error().decode()))
     _lib.require_gpu()
     dev = torch.device("cuda", torch.cuda.current_device())
-    offsets = np.concatenate([[0], np.cumsum(n)]).astype(np.int64)
-    wav = torch.from_numpy(np.concatenate(host)).to(dev)
-    off = torch.from_numpy(offsets).to(dev)
+    if offsets is not None:
+        wav = wavs.contiguous()
+        if wav.device != dev:
+            raise ValueError("fbank_batch: the samples are on %s, the current device is %s" % (wav.device, dev))
+        off = torch.from_numpy(offsets).to(dev)
+    else:
+        offsets = np.concatenate([[0], np.cumsum(n)]).astype(np.int64)
+        wav = torch.from_numpy(np.concatenate(host)).to(dev)
+        off = torch.from_numpy(offsets).to(dev)
     W = (right_ctx + 1) * NUM_COLS
     if out is None:
         out = torch.empty((B, t_out, W), dtype=torch.float32, device=dev)
@@ -166,3 +234,50 @@ def fbank_batch(wavs, cmvn=None, right_ctx=2, n_skip_frame=2, n_downsample=2, ou
     for b in range(B):
         sizes[b] = lens[b] / t_out          # a Python true division stored into float32, as create_input does (:177)
     return out, sizes
+
+
+RESAMPLE_MIN_RATE, RESAMPLE_MAX_RATE = 1000, 384000
+RESAMPLE_TABLE = 32769        # entries of the kaiser_best half window (64 zero crossings x 512 + 1)
+
+
+def resample_len(n, rate):
+    """Samples ``n`` samples at ``rate`` Hz become at 16 kHz (librosa's int(ceil(n * 16000 / rate)); n itself at 16 kHz)."""
+    m = _lib.lib().mdd_resample_len(int(n), int(rate))
+    if m < 0:
+        raise ValueError("resample: %d Hz is outside [%d, %d] (or n = %d < 0)" % (rate, RESAMPLE_MIN_RATE, RESAMPLE_MAX_RATE, n))
+    return int(m)
+
+
+def resample_filter(rate):
+    """The library's kaiser_best table for ``rate`` (mdd_resample_filter): (win, delta), float64 [32769] each."""
+    win, delta = np.zeros(RESAMPLE_TABLE), np.zeros(RESAMPLE_TABLE)
+    _lib.check(_lib.lib().mdd_resample_filter(int(rate), C.c_void_p(win.ctypes.data), C.c_void_p(delta.ctypes.data),
+                                              RESAMPLE_TABLE))
+    return win, delta
+
+
+def resample_batch(wavs, rates):
+    """B utterances at their own rates -> 16 kHz PCM16 samples on the device, in one kernel launch (mdd_resample_batch): what
+    the reference's ``librosa.resample(data, orig_sr=fs, target_sr=16000)`` + ``sf.write`` give it (AA/infer.py:498-501).
+
+    ``wavs``: list of 1-D sample arrays / tensors on the int16 scale; ``rates``: their sample rates in Hz (1000..384000).
+    Returns (samples, offsets): a 1-D float32 CUDA tensor with the utterances back to back, utterance b at
+    [offsets[b], offsets[b+1]), and offsets, an int64 CPU tensor [B+1] -- the input ``fbank_batch(samples, offsets=offsets)``
+    takes.  Resampled rows hold integers in [-32768, 32767]; 16 kHz rows are the input's float32 values unchanged."""
+    if len(wavs) == 0 or len(wavs) != len(rates):
+        raise ValueError("resample_batch: %d utterances and %d rates" % (len(wavs), len(rates)))
+    host = [np.asarray(w.detach().cpu().numpy() if torch.is_tensor(w) else w, dtype=np.float32).reshape(-1) for w in wavs]
+    r = np.array([int(v) for v in rates], dtype=np.int32)
+    n_in = np.array([h.size for h in host], dtype=np.int64)
+    n_out = np.array([resample_len(k, v) for k, v in zip(n_in, r)], dtype=np.int64)
+    in_off = np.concatenate([[0], np.cumsum(n_in)]).astype(np.int64)
+    out_off = np.concatenate([[0], np.cumsum(n_out)]).astype(np.int64)
+    _lib.require_gpu()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    wav = torch.from_numpy(np.concatenate(host)).to(dev)
+    d_in, d_out, d_rates = (torch.from_numpy(a).to(dev) for a in (in_off, out_off, r))
+    out = torch.empty(int(out_off[-1]), dtype=torch.float32, device=dev)
+    _lib.check(_lib.lib().mdd_resample_batch(C.c_void_p(wav.data_ptr()), C.c_void_p(d_in.data_ptr()),
+                                             C.c_void_p(d_rates.data_ptr()), len(host), C.c_void_p(d_out.data_ptr()),
+                                             C.c_void_p(out.data_ptr()), _lib.current_stream_ptr()))
+    return out, torch.from_numpy(out_off)

@@ -199,6 +199,24 @@ int mdd_fbank_batch(const float *wav_dev, const int64_t *offsets_dev, int32_t B,
                     const float *cmvn_scale_dev, const float *cmvn_offset_dev,
                     int32_t right, int32_t skip, int32_t n_down, float *out_dev, void *stream);
 
+/* ---- Any-rate input -> 16 kHz PCM16 in front of the fbank: the reference resamples every WAV that is not 16 kHz and writes it
+ * back as a 16-bit WAV (`librosa.resample(data, orig_sr=fs, target_sr=16000)` = resampy kaiser_best, then `sf.write`,
+ * AA/infer.py:498-501), restated in float64 without contraction (csrc/resample.hip).  Rates 1000..384000 Hz.
+ * mdd_resample_len (host, AA/infer.py:498-501): librosa's output length int(ceil(n * (16000.0 / rate))) (n itself at 16 kHz),
+ *   -1 for a rate outside the range or n < 0. */
+int64_t mdd_resample_len(int64_t n, int32_t rate);
+/* mdd_resample_filter (host, AA/infer.py:498-501): the library's own kaiser_best table for `rate`, 32769 entries each of win (the
+ *   half window, times 16000/rate when that is below 1) and delta (win[j+1] - win[j], delta[32768] = 0); cap >= 32769. */
+int mdd_resample_filter(int32_t rate, double *win, double *delta, int64_t cap);
+/* mdd_resample_batch (AA/infer.py:498-501): B utterances back to back in wav_dev (int16 scale, as float), utterance b at
+ *   [in_off_dev[b], in_off_dev[b+1]) sampled at rates_dev[b]; writes mdd_resample_len(n_b, rate_b) samples at
+ *   [out_off_dev[b], out_off_dev[b+1]) of out_dev, in one launch (one per 16 distinct rates beyond that): the quantised 16 kHz
+ *   PCM16 values clamp(rint(32767 * y), -32768, 32767) as float, y the filtered x / 32768; 16 kHz rows are copied bit for bit.
+ *   All arrays are device memory; the call reads the offsets and rates back (a sync of `stream`) for the launch geometry, the
+ *   per-rate tables (built once per device and rate) and its checks: every row's output span must be mdd_resample_len's. */
+int mdd_resample_batch(const float *wav_dev, const int64_t *in_off_dev, const int32_t *rates_dev, int32_t B,
+                       const int64_t *out_off_dev, float *out_dev, void *stream);
+
 /* ---- evaluation counts of a batch (AA/steps/test_ctc_nosil.py:33-60,218-298), host.
  * Row x of dec / lab / can (row pitch `stride` ids) holds the decoded, annotated and canonical phoneme ids of utterance x
  * with 'sil' already removed (:196-209).  counts[8] = { phonemes in canonical, TA, FR, FA, TR correctly diagnosed,
