@@ -44,7 +44,7 @@ struct GraphKey {
 
 // The weights of one BiLSTM layer on the device; the text encoder's sit at index cfg.layers.
 struct LstmWeights {
-    float *wih = nullptr, *whh = nullptr;          // fp32, gate rows permuted (whh in the packed layout where use_packed)
+    float *wih = nullptr, *whh = nullptr;          // fp32, gate rows permuted (whh in the packed layout where packed_whh)
     SplitPtr wih_s{nullptr, nullptr}, whh_s{nullptr, nullptr};   // split-bf16 copies (whh row-major)
     unsigned short *wih_3 = nullptr;               // three-plane (f32x6) copy of W_ih, K-tile-major
     unsigned short *whh_3 = nullptr;               // Whh' [3][2][4H][H]: three row-major planes (f32x6 layer kernel)
@@ -76,9 +76,11 @@ struct DecodeWeights {
 struct mdd_model {
     mdd_config cfg;
     int device = 0;
-    bool finalized = false, taps = false, use_graph = true;
+    bool finalized = false, taps = false;
     int precision = 2;   // 2 (default): fp32-grade, the large contractions as f32x6 on the bf16 matrix cores (falls back to 0 when the geometry does not allow);
                          // 0: exact fp32 MFMA everywhere; 1: split-bf16 x3 for every contraction (narrower than fp32: flagged variant)
+    mdd::Switches sw;    // the environment at create (plan.h)
+    mdd::DeviceFit fit;
     std::map<std::string, std::vector<float>> host;  // state_dict entries as loaded
     std::unique_ptr<mdd::DecodeWeights> weights;   // the set of the last successful mdd_finalize_weights
     // workspace
@@ -89,40 +91,17 @@ struct mdd_model {
     mdd::DeviceArray<int> err_flag;
     hipStream_t cap_stream = nullptr;  // graphs are captured here (the legacy default stream cannot capture)
     int lastB = 0, lastT = 0, lastL = 0;
+    mdd::ForwardPlan plan{};    // the kernels of the last prepared forward (shape lastB / lastT / lastL)
     int raw_T = 0;              // > 0 while mdd_forward_raw runs the fused front-end straight on unstacked frames
     const int *tlen = nullptr, *llen = nullptr;   // set while mdd_forward_fused runs: per-row posterior frames / canonical length of the row's own batch
     mdd::DeviceBuf xstack;      // mdd_forward_raw without the fused front-end: stacked copy
     std::map<mdd::GraphKey, hipGraphExec_t> graphs;
     void drop_graphs() { for (auto &kv : graphs) (void)hipGraphExecDestroy(kv.second); graphs.clear(); }
     ~mdd_model() { drop_graphs(); if (cap_stream) (void)hipStreamDestroy(cap_stream); }
-    int W1() const { return (cfg.feat + 2 - 3) / 2 + 1; }
-    int W2() const { return (W1() + 2 - 3) / 2 + 1; }
-    int rnn_in() const { return cfg.channels * W2(); }
-    int granule_max_b = 1024;   // batch rows the persistent kernel's teams cover (4 row tiles x 16 rows x 16 groups)
-    bool lstm_persist = true;   // one persistent team-synchronised launch per BiLSTM layer (split-bf16 mode, >= 256 CUs, B <= 1024)
-    int n_cu = 0;
+    int W1() const { return mdd::conv_out(cfg.feat); }
+    int W2() const { return mdd::conv_out(W1()); }
+    int rnn_in() const { return mdd::rnn_in(cfg); }
     mdd::DeviceArray<unsigned int> sync_words;
-    bool lstm_x3 = false;   // MDD_LSTM=x3: LDS-tiled split-bf16 step kernel (measured slower than the packed fp32 step; kept for study)
-    bool conv_fused() const { return (x3() || x6()) && cfg.feat == 243 && cfg.channels == 32; }
-    bool packed_h() const { return cfg.hidden == 384 || cfg.hidden == 256; }
-    // one persistent launch per BiLSTM layer: the split-bf16 teams (lstm.hip) in mode 1, the exact-fp32 teams (lstm_f32.hip) in mode 0
-    bool persist(int B) const { return lstm_persist && !lstm_x3 && packed_h() && B <= granule_max_b && (x3() || lstm_persist_f32); }
-    bool lstm_persist_f32 = true;
-    bool lstm_persist_x6 = true;     // MDD_LSTM_X6=0: mode 2 runs the exact-fp32 layer kernel instead (diagnostic); =force: lstm_x6.hip wherever it can run
-    bool lstm_x6_force = false;
-    bool conv_rowwise = false;       // MDD_CONV=rowwise: mode 2's front end runs the row-at-a-time conv kernel (diagnostic; bit-identical)
-    // the f32x6 recurrence (lstm_x6.hip) where it is the faster of the two reference-width layer kernels (tools/lstm_kernel_choice.py,
-    // profiles/round3_lstm_x6_notes.txt): at H = 384 for every batch size (0.60 - 0.93 of the exact-fp32 kernel's time), at H = 256 up to
-    // 128 rows (0.83; beyond, the fp32 kernel's shorter products win: 1.07 - 1.5)
-    bool lx6(int B) const {
-        return x6() && lstm_persist_x6 && persist(B) && B <= mdd::lstm_x6_max_b(cfg.hidden) && (lstm_x6_force || cfg.hidden == 384 || B <= 128);
-    }
-    bool x6() const {   // f32x6: the time-batched input projections on the bf16 matrix cores with three planes per operand; all else as mode 0
-        return precision == 2 && rnn_in() % 32 == 0 && (2 * cfg.hidden) % 32 == 0 && cfg.emb_dim % 32 == 0;
-    }
-    bool x3() const {   // the bf16x3 GEMM needs K % 32 == 0 for every contraction and the packed LSTM layouts
-        return precision == 1 && (cfg.hidden == 384 || cfg.hidden == 256) && rnn_in() % 32 == 0 && cfg.emb_dim % 32 == 0;
-    }
 };
 
 namespace mdd {
@@ -216,8 +195,6 @@ static bool pack_gate_rows(mdd_model *m, const std::string &base, const char *wh
     return true;
 }
 
-static bool use_packed(const mdd_model *m) { return m->cfg.hidden == 384 || m->cfg.hidden == 256; }
-
 // Whh' [2][4H][H] (gate-permuted rows) -> Wp[d][ut][j][lane][m] (see lstm.hip)
 static void pack_whh(const std::vector<float> &w, int H, std::vector<float> &out) {
     const int NUT = H / 4, J = H / 16;
@@ -287,8 +264,8 @@ static int build_weights(mdd_model *m, DecodeWeights &w) {
         if (K % 32 == 0 && ((rc = w.alloc(&lw.wih_3, (size_t)3 * 8 * H * K)) || (rc = launch_split3(lw.wih, 8 * H, K, K, lw.wih_3, nullptr)))) return rc;
         if (!pack_gate_rows(m, base, "weight_hh_l0", H, H, tmp)) return MDD_ERR_STATE;
         if ((rc = upload_split(w, tmp, &lw.whh_s))) return rc;
-        if (use_packed(m) && (rc = upload_split3(w, tmp, &lw.whh_3))) return rc;
-        if (use_packed(m)) { std::vector<float> pk; pack_whh(tmp, H, pk); tmp.swap(pk); }
+        if (packed_whh(c) && (rc = upload_split3(w, tmp, &lw.whh_3))) return rc;
+        if (packed_whh(c)) { std::vector<float> pk; pack_whh(tmp, H, pk); tmp.swap(pk); }
         if ((rc = upload(w, tmp, &lw.whh))) return rc;
         if (n > 0 && n < c.layers) {
             snprintf(base, sizeof(base), "rnns.%d.batch_norm", n);
@@ -336,18 +313,23 @@ struct Stage { const char *name; int launches; double flops; };
 
 static int n_stages(const mdd_model *m) { return 2 + 2 * m->cfg.layers + 6; }
 
+// The kernels a forward of B rows runs on this handle as it stands now (plan.h)
+static ForwardPlan plan_of(const mdd_model *m, int B) { return plan_forward(m->cfg, m->precision, m->sw, m->fit, B); }
+
 // One BiLSTM layer: the caller sets a.T, a.B, a.seqlen and the outputs, the rest is filled here.  The persistent layer kernel where
-// it runs (f32x6, split-bf16 or exact-fp32 teams), else one launch per step.
+// the plan has one (f32x6, split-bf16 or exact-fp32 teams), else one launch per step (launch_lstm_layer: hsplit selects the x3 step).
 static int run_lstm(mdd_model *m, const LstmWeights &lw, LstmStepArgs &a, hipStream_t st, Stage *info) {
-    const bool x3 = m->x3();
+    const ForwardPlan &p = m->plan;
     a.gx = m->gx.p; a.whh = lw.whh; a.hbuf = m->hbuf.p; a.cbuf = m->cbuf.p;
-    a.H = m->cfg.hidden; a.packed = use_packed(m);
-    a.whh_split = lw.whh_s; a.hsplit = (x3 && m->lstm_x3) ? reinterpret_cast<unsigned short *>(m->hsplit.p) : nullptr;
-    if (!m->persist(a.B)) return launch_lstm_layer(a, st);
+    a.H = m->cfg.hidden; a.packed = packed_whh(m->cfg);
+    a.whh_split = lw.whh_s; a.hsplit = p.lstm == Lstm::StepX3 ? reinterpret_cast<unsigned short *>(m->hsplit.p) : nullptr;
+    if (!p.gated) return launch_lstm_layer(a, st);
     info->launches = 1;
     unsigned short *hx = reinterpret_cast<unsigned short *>(m->hx.p);
-    if (m->lx6(a.B)) return launch_lstm_layer_x6(a, lw.whh_3, hx, m->sync_words.p, m->err_flag.p, st);
-    return x3 ? launch_lstm_layer_granule(a, hx, m->sync_words.p, m->err_flag.p, st) : launch_lstm_layer_f32(a, hx, m->sync_words.p, m->err_flag.p, st);
+    long long *stamps = m->sw.lstm_dbg && a.T > 100 ? reinterpret_cast<long long *>(m->hx.p + p.stamps_at) : nullptr;
+    if (p.lstm == Lstm::X6) return launch_lstm_layer_x6(a, lw.whh_3, hx, m->sync_words.p, m->err_flag.p, st, stamps, m->sw.x6_redo_mask);
+    if (p.lstm == Lstm::Granule) return launch_lstm_layer_granule(a, hx, m->sync_words.p, m->err_flag.p, st, stamps, m->sw.lstm_early);
+    return launch_lstm_layer_f32(a, hx, m->sync_words.p, m->err_flag.p, st, stamps);
 }
 
 static int run_stage(mdd_model *m, int si, const float *x, int B, int T, const int64_t *x1, int L, float *logp,
@@ -355,21 +337,23 @@ static int run_stage(mdd_model *m, int si, const float *x, int B, int T, const i
     const mdd_config &c = m->cfg;
     const DecodeWeights &w = *m->weights;
     const int H = c.hidden, H2 = 2 * H, G2 = 8 * H, Tp = T / 2, Lp = L, nl = c.layers;
-    const bool x3 = m->x3();
+    const ForwardPlan &p = m->plan;
+    const bool x3 = p.precision == 1, fused = p.conv != Conv::Separate;   // x3: the activations travel as split-bf16 planes
     const size_t rows = (size_t)Tp * B, trows = (size_t)L * B;
     static thread_local char namebuf[32];
     Stage dummy; if (!info) info = &dummy;
     info->launches = 1; info->flops = 0.0;
-    if (si == 0 && m->conv_fused()) {   // conv0 recomputed per output row (x1.5) + conv1 as implicit GEMM, one kernel
+    if (si == 0 && fused) {   // conv0 recomputed per output row (x1.5) + conv1 as implicit GEMM, one kernel
         info->name = "conv_fused";
         info->flops = 2.0 * 9 * c.channels * (double)B * Tp * m->W2() * (c.channels + 6.0);
-        if (m->x6())   // fp32-grade form: three K-tile-major planes straight into the projection GEMM's operand buffer
-            return launch_conv_fused3(x, w.w_conv0, w.sc0, w.sh0, w.w_conv1_3, w.sc1, w.sh1, reinterpret_cast<unsigned short *>(m->p3.p),
-                                      m->taps ? m->seq0.p : nullptr, B, T, m->raw_T, st, m->conv_rowwise);
-        return launch_conv_fused(x, w.w_conv0, w.sc0, w.sh0, w.w_conv1_s, w.sc1, w.sh1, split_view(m->seq0_s, rows * m->rnn_in()),
-                                 nullptr, B, T, m->raw_T, st);
+        if (p.conv == Conv::FusedX3)
+            return launch_conv_fused(x, w.w_conv0, w.sc0, w.sh0, w.w_conv1_s, w.sc1, w.sh1, split_view(m->seq0_s, rows * m->rnn_in()),
+                                     nullptr, B, T, m->raw_T, st);
+        // fp32-grade form: three K-tile-major planes straight into the projection GEMM's operand buffer
+        return launch_conv_fused3(x, w.w_conv0, w.sc0, w.sh0, w.w_conv1_3, w.sc1, w.sh1, reinterpret_cast<unsigned short *>(m->p3.p),
+                                  m->taps ? m->seq0.p : nullptr, B, T, m->raw_T, st, p.conv == Conv::FusedX6Rowwise);
     }
-    if (si == 1 && m->conv_fused()) { info->name = "conv1_in_fused"; info->launches = 0; return MDD_OK; }
+    if (si == 1 && fused) { info->name = "conv1_in_fused"; info->launches = 0; return MDD_OK; }
     if (si == 0) { info->name = "conv0"; info->flops = 2.0 * 9 * c.channels * (double)B * T * m->W1();
         return launch_conv0(x, w.w_conv0, w.sc0, w.sh0, m->y0.p, B, T, c.feat, c.channels, st); }
     if (si == 1) { info->name = "conv1"; info->flops = 2.0 * 9 * c.channels * c.channels * (double)B * Tp * m->W2();
@@ -382,14 +366,14 @@ static int run_stage(mdd_model *m, int si, const float *x, int B, int T, const i
         if (si % 2 == 0) {
             snprintf(namebuf, sizeof(namebuf), "gemm_ih%d", n); info->name = namebuf;
             info->flops = 2.0 * (double)Tp * B * G2 * K;
-            if (x3) {
+            if (p.proj == Gemm::Bf16x3) {
                 const SplitPtr in = n == 0 ? split_view(m->seq0_s, rows * K) : split_view(m->act_s[(n - 1) & 1], rows * K);
                 return launch_gemm_bf16x3(in, w.rnn[n].wih_s, nullptr, m->gx.p, nullptr, Tp * B, G2, K, K, K, G2, 1, 0, 0, 0, st);
             }
             const float *in = n == 0 ? m->seq0.p : m->act[(n - 1) & 1].p;
-            if (m->x6()) {   // fp32-grade arithmetic at 6/16 of the fp32 MFMA's cost (gemm_bf16x6.hip)
+            if (p.proj == Gemm::F32x6) {   // fp32-grade arithmetic at 6/16 of the fp32 MFMA's cost (gemm_bf16x6.hip)
                 unsigned short *p3 = reinterpret_cast<unsigned short *>(m->p3.p);
-                if (!(n == 0 && m->conv_fused()))      // (layer 0: the fused front-end has written the planes already)
+                if (!(n == 0 && fused))      // (layer 0: the fused front-end has written the planes already)
                     if (int rc = launch_split3(in, Tp * B, K, K, p3, st)) return rc;
                 return launch_gemm_f32x6(p3, (size_t)Tp * B * K, w.rnn[n].wih_3, (size_t)G2 * K, nullptr, m->gx.p, Tp * B, G2, K, G2, st);
             }
@@ -418,9 +402,9 @@ static int run_stage(mdd_model *m, int si, const float *x, int B, int T, const i
                             x3 ? split_view(m->embo_s, trows * c.emb_dim) : kNoSplit, m->err_flag.p, st);
     case 1:
         info->name = "gemm_text"; info->flops = 2.0 * (double)L * B * G2 * c.emb_dim;
-        if (x3) return launch_gemm_bf16x3(split_view(m->embo_s, trows * c.emb_dim), tw.wih_s, w.t_bias, m->gx.p, nullptr, L * B, G2,
-                                          c.emb_dim, c.emb_dim, c.emb_dim, G2, 1, 0, 0, 0, st);
-        if (m->x6()) {
+        if (p.proj == Gemm::Bf16x3) return launch_gemm_bf16x3(split_view(m->embo_s, trows * c.emb_dim), tw.wih_s, w.t_bias, m->gx.p, nullptr, L * B, G2,
+                                                              c.emb_dim, c.emb_dim, c.emb_dim, G2, 1, 0, 0, 0, st);
+        if (p.proj == Gemm::F32x6) {
             unsigned short *p3 = reinterpret_cast<unsigned short *>(m->p3.p);
             if (int rc = launch_split3(m->embo.p, L * B, c.emb_dim, c.emb_dim, p3, st)) return rc;
             return launch_gemm_f32x6(p3, (size_t)L * B * c.emb_dim, tw.wih_3, (size_t)G2 * c.emb_dim, w.t_bias, m->gx.p, L * B, G2, c.emb_dim, G2, st);
@@ -515,15 +499,8 @@ extern "C" int mdd_create(const mdd_config *cfg, int device, mdd_model **out) {
     std::unique_ptr<mdd_model> m(new mdd_model());
     m->cfg = *cfg;
     m->device = device;
-    const char *pr = getenv("MDD_PRECISION");
-    if (pr && (!strcmp(pr, "f32") || !strcmp(pr, "0"))) m->precision = 0;
-    if (pr && (!strcmp(pr, "bf16x3") || !strcmp(pr, "1"))) m->precision = 1;
-    if (pr && (!strcmp(pr, "f32x6") || !strcmp(pr, "2"))) m->precision = 2;
-    const char *lx = getenv("MDD_LSTM");
-    m->lstm_x3 = lx && !strcmp(lx, "x3");
-    if (lx && !strcmp(lx, "step")) m->lstm_persist = false;
-    const char *g = getenv("MDD_GRAPH");
-    m->use_graph = !(g && g[0] == '0');
+    m->sw = read_switches();
+    m->precision = m->sw.precision;
     if (int rc = init_kernel_attributes()) return rc;
     if (int rc = init_lstm_attributes()) return rc;
     if (int rc = init_granule_attributes()) return rc;
@@ -532,12 +509,8 @@ extern "C" int mdd_create(const mdd_config *cfg, int device, mdd_model **out) {
     if (int rc = init_conv_attributes()) return rc;
     if (int rc = init_gemm_attributes()) return rc;
     if (int rc = init_gemm_x6_attributes()) return rc;
-    m->n_cu = prop.multiProcessorCount;
-    if (!persistent_grid_fits(m->n_cu)) m->lstm_persist = false;   // per-step kernels instead (smaller partitions, other gfx950 SKUs)
-    if (!persistent_f32_grid_fits(m->n_cu)) m->lstm_persist_f32 = false;
-    if (!persistent_x6_grid_fits(m->n_cu)) m->lstm_persist_x6 = false;
-    { const char *cv = getenv("MDD_CONV"); m->conv_rowwise = cv && !strcmp(cv, "rowwise"); }
-    { const char *e6 = getenv("MDD_LSTM_X6"); if (e6 && e6[0] == '0') m->lstm_persist_x6 = false; if (e6 && e6[0] == 'f') m->lstm_x6_force = true; }
+    const int n_cu = prop.multiProcessorCount;   // (where a grid does not fit: per-step kernels, e.g. smaller partitions, other gfx950 SKUs)
+    m->fit = {persistent_grid_fits(n_cu) != 0, persistent_f32_grid_fits(n_cu) != 0, persistent_x6_grid_fits(n_cu) != 0};
     if (int rc = m->err_flag.need(1)) return rc;
     if (int rc = m->sync_words.need(32)) return rc;
     hipError_t e = hipMemset(m->err_flag.p, 0, sizeof(int));
@@ -594,7 +567,7 @@ extern "C" int mdd_set_precision(mdd_model *m, int32_t mode) {
     }
     return MDD_OK;
 }
-extern "C" int32_t mdd_get_precision(mdd_model *m) { return m ? (m->x3() ? 1 : (m->x6() ? 2 : 0)) : -1; }
+extern "C" int32_t mdd_get_precision(mdd_model *m) { return m ? plan_of(m, 1).precision : -1; }   // (the same for every batch size)
 
 extern "C" int mdd_stack_skip(const float *raw_dev, int32_t B, int32_t T_raw, int32_t D, int32_t right, int32_t skip,
                               int32_t n_down, float *out_dev, void *stream) {
@@ -612,34 +585,32 @@ static int forward_prepare(mdd_model *m, const float *x_dev, int32_t B, int32_t 
     hipStream_t zs = m->cap_stream;
     const mdd_config &c = m->cfg;
     const int H = c.hidden, Tp = T / 2;
+    const ForwardPlan p = plan_of(m, B);
     int rc;
     const size_t rows = (size_t)Tp * B, trows = (size_t)L * B, mrows = rows > trows ? rows : trows;
-    if ((!m->conv_fused() && (rc = ensure(m->y0, (size_t)B * c.channels * T * m->W1(), zs))) || (rc = ensure(m->seq0, rows * m->rnn_in(), zs)) ||
+    if ((p.conv == Conv::Separate && (rc = ensure(m->y0, (size_t)B * c.channels * T * m->W1(), zs))) || (rc = ensure(m->seq0, rows * m->rnn_in(), zs)) ||
         (rc = ensure(m->gx, mrows * 8 * H, zs)) || (rc = ensure(m->act[0], rows * 2 * H, zs)) || (rc = ensure(m->act[1], rows * 2 * H, zs)) ||
         (rc = ensure(m->xraw, rows * 2 * H, zs)) || (rc = ensure(m->hbuf, (size_t)4 * ((B + 15) / 16 * 16) * H, zs)) || (rc = ensure(m->cbuf, (size_t)2 * ((B + 15) / 16 * 16) * H, zs)) ||
         (rc = ensure(m->embo, trows * c.emb_dim, zs)) || (rc = ensure(m->text, trows * 2 * H, zs)) || (rc = ensure(m->key, trows * 2 * H, zs)) ||
         (rc = ensure(m->S, (size_t)B * Tp * L, zs)))
         return rc;
-    if (m->x3() && ((rc = ensure(m->seq0_s, rows * m->rnn_in(), zs)) || (rc = ensure(m->act_s[0], rows * 2 * H, zs)) ||
-                    (rc = ensure(m->act_s[1], rows * 2 * H, zs)) || (rc = ensure(m->x_s, rows * 2 * H, zs)) ||
-                    (rc = ensure(m->embo_s, trows * c.emb_dim, zs)) || (rc = ensure(m->text_s, trows * 2 * H, zs)) ||
-                    (rc = ensure(m->key_s, trows * 2 * H, zs)) || (rc = ensure(m->hsplit, (size_t)4 * B * H, zs))))
+    if (p.precision == 1 && ((rc = ensure(m->seq0_s, rows * m->rnn_in(), zs)) || (rc = ensure(m->act_s[0], rows * 2 * H, zs)) ||
+                             (rc = ensure(m->act_s[1], rows * 2 * H, zs)) || (rc = ensure(m->x_s, rows * 2 * H, zs)) ||
+                             (rc = ensure(m->embo_s, trows * c.emb_dim, zs)) || (rc = ensure(m->text_s, trows * 2 * H, zs)) ||
+                             (rc = ensure(m->key_s, trows * 2 * H, zs)) || (rc = ensure(m->hsplit, (size_t)4 * B * H, zs))))
         return rc;
     {   // f32x6: three bf16 planes of the largest projection operand = 1.5 x its fp32 size (in floats: 3/2)
         const size_t kmax = (size_t)(m->rnn_in() > 2 * H ? m->rnn_in() : 2 * H), k2 = (size_t)c.emb_dim;
         const size_t need = (rows * kmax > trows * k2 ? rows * kmax : trows * k2) * 3 / 2 + 64;
-        if (m->x6() && (rc = ensure(m->p3, need, zs))) return rc;
+        if (p.proj == Gemm::F32x6 && (rc = ensure(m->p3, need, zs))) return rc;
     }
-    if (m->persist(B)) {   // the exchange buffer of the persistent layers (u64 granules; three bf16 planes per (parity, team, tile) in lstm_x6.hip) + stamps
-        size_t need = (size_t)2 * 32 * granule_bg(B) * H * 2;
-        if (m->lx6(B) && lstm_x6_hx_bytes(H, B) / 4 > need) need = lstm_x6_hx_bytes(H, B) / 4;
-        if ((rc = ensure(m->hx, need + 64 + 256 * 6 * 2, zs))) return rc;
-    }
+    if (p.hx_floats && (rc = ensure(m->hx, p.hx_floats, zs))) return rc;   // the exchange buffer of the persistent layers + stamps
     if (m->taps) {
         m->tap_rnn.resize(c.layers);
         for (int n = 0; n + 1 < c.layers; n++) if ((rc = ensure(m->tap_rnn[n], rows * 2 * H, zs))) return rc;
     }
     m->lastB = B; m->lastT = T; m->lastL = L;
+    m->plan = p;
     if (g_ws_moved) {   // hipFree above synchronised the device, so no replay of an old graph is still running
         m->drop_graphs();
         g_ws_moved = false;
@@ -652,9 +623,9 @@ extern "C" int mdd_forward(mdd_model *m, const float *x_dev, int32_t B, int32_t 
     int rc = forward_prepare(m, x_dev, B, T, x1_dev, L, logp_dev);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const bool gated = m->persist(B);
+    const bool gated = m->plan.gated;
     bool held = false;
-    if (!m->use_graph) {
+    if (!m->sw.graph) {
         if (gated && (rc = gate_enter(m, st, &held))) return rc;
         rc = forward_enqueue(m, x_dev, B, T, x1_dev, L, logp_dev, st);
         return gate_leave(m, st, held, rc);
@@ -707,7 +678,7 @@ extern "C" int mdd_forward_raw(mdd_model *m, const float *raw_dev, int32_t B, in
     if (!m || !raw_dev || B <= 0 || T_raw < 1) { set_error("mdd_forward_raw: bad argument"); return MDD_ERR_ARG; }
     const int D = m->cfg.feat / 3, T = mdd_stack_len(T_raw, 2, 2);
     if (m->cfg.feat != 3 * D) { set_error("mdd_forward_raw: feat=%d is not 3 stacked frames", m->cfg.feat); return MDD_ERR_ARG; }
-    if (m->finalized && m->conv_fused()) {
+    if (m->finalized && plan_of(m, B).conv != Conv::Separate) {
         m->raw_T = T_raw;
         const int rc = mdd_forward(m, raw_dev, B, T, x1_dev, L, logp_dev, stream);
         m->raw_T = 0;
@@ -733,7 +704,7 @@ extern "C" int mdd_forward_profile(mdd_model *m, const float *x_dev, int32_t B, 
     const int ns = n_stages(m);
     if (cap < ns || !ms || !launches || !flops || !names) { set_error("mdd_forward_profile: need room for %d stages", ns); return MDD_ERR_ARG; }
     hipStream_t st = (hipStream_t)stream;
-    if (m->persist(B)) {   // keep other handles' forwards off the device while the stages replay: wait for the last gated forward
+    if (m->plan.gated) {   // keep other handles' forwards off the device while the stages replay: wait for the last gated forward
         bool held = false;
         if ((rc = gate_enter(m, st, &held))) return rc;
         if ((rc = gate_leave(m, st, held, MDD_OK))) return rc;
@@ -786,7 +757,7 @@ extern "C" const float *mdd_tap(mdd_model *m, const char *name, int64_t *numel) 
     std::string n(name);
     const float *p = nullptr;
     int64_t ne = 0;
-    if (m->x3() && (n == "conv1" || n == "key")) {   // these stages exist only as split-bf16 planes: rebuild fp32 = hi + lo
+    if (m->plan.precision == 1 && (n == "conv1" || n == "key")) {   // these stages exist only as split-bf16 planes: rebuild fp32 = hi + lo
         const bool cv = n == "conv1";
         ne = cv ? (int64_t)Tp * B * m->rnn_in() : (int64_t)L * B * H2;
         DeviceBuf &dst = cv ? m->seq0 : m->key;
@@ -794,8 +765,8 @@ extern "C" const float *mdd_tap(mdd_model *m, const char *name, int64_t *numel) 
         if (hipStreamSynchronize(nullptr) != hipSuccess) return nullptr;
         p = dst.p;
     }
-    else if (n == "lstm_dbg" && m->hx.p) {   // diagnostic stamps of the last persistent layer launch (MDD_LSTM_DBG=1)
-        p = m->hx.p + (m->lx6(B) ? lstm_x6_hx_bytes(m->cfg.hidden, B) / 4 : (size_t)2 * 32 * granule_bg(B) * m->cfg.hidden * 2);
+    else if (n == "lstm_dbg" && m->plan.gated) {   // diagnostic stamps of the last persistent layer launch (MDD_LSTM_DBG=1)
+        p = m->hx.p + m->plan.stamps_at;
         ne = 256 * 6 * 2;
     }
     else if (n == "conv1") { p = m->seq0.p; ne = (int64_t)Tp * B * m->rnn_in(); }

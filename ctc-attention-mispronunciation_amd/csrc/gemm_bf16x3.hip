@@ -470,12 +470,9 @@ int launch_gemm_bf16x3(const SplitPtr &A, const SplitPtr &W, const float *bias, 
         const int tn = (N + 255) / 256;
         const dim3 grid(((M + 255) / 256) * tn), block(512);
         const size_t smem = 2 * 4 * 256 * XROW;
-        // MDD_GEMM=glds256: the single-barrier kernel; MDD_GEMM_DMA=M: the 8-phase kernel with the LDS-DMA issued from inside the MFMA
-        // phases (measured 5-8 % slower than from the load phases: profiles/round2_gemm_phase_stamps.txt)
-        static const int form = (getenv("MDD_GEMM") && !strcmp(getenv("MDD_GEMM"), "glds256")) ? 0 : ((getenv("MDD_GEMM_DMA") && !strcmp(getenv("MDD_GEMM_DMA"), "M")) ? 2 : 1);
-        if (form == 2) hipLaunchKernelGGL(gemm_bf16x3_ph8_kernel<true>, grid, block, smem, st, A.hi, A.lo, W.hi, W.lo, bias, C, M, N, K, lda, ldw, ldc, tn);
-        else if (form == 1) hipLaunchKernelGGL(gemm_bf16x3_ph8_kernel<false>, grid, block, smem, st, A.hi, A.lo, W.hi, W.lo, bias, C, M, N, K, lda, ldw, ldc, tn);
-        else hipLaunchKernelGGL(gemm_bf16x3_glds256_kernel, grid, block, smem, st, A.hi, A.lo, W.hi, W.lo, bias, C, M, N, K, lda, ldw, ldc, tn);
+        // the 8-phase kernel with the LDS-DMA issued from the load phases (5-8 % faster than from inside the MFMA phases:
+        // profiles/round2_gemm_phase_stamps.txt; that form and the single-barrier kernel run in mdd_diag_gemm_ph8's race screen)
+        hipLaunchKernelGGL(gemm_bf16x3_ph8_kernel<false>, grid, block, smem, st, A.hi, A.lo, W.hi, W.lo, bias, C, M, N, K, lda, ldw, ldc, tn);
         MDD_LAUNCH_CHECK();
         return MDD_OK;
     }

@@ -298,8 +298,7 @@ int launch_gemm_f32x6(const unsigned short *A3, size_t a_plane, const unsigned s
         return MDD_ERR_ARG;
     }
     const int tn = (N + X6_BN - 1) / X6_BN, ntiles = ((M + X6_BM - 1) / X6_BM) * tn;
-    static const int grid_cap = [] { const char *e = getenv("MDD_GEMM_X6_GRID"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 256; }();   // one persistent workgroup per CU
-    const dim3 grid(ntiles < grid_cap ? ntiles : grid_cap);
+    const dim3 grid(ntiles < 256 ? ntiles : 256);   // one persistent workgroup per CU
     if (stamps) hipLaunchKernelGGL(gemm_f32x6_kernel<true>, grid, dim3(256), X6_NS * X6_STAGE, st, A3, W3, a_plane, w_plane, bias, C, M, N, K, ldc, tn, ntiles, stamps);
     else hipLaunchKernelGGL(gemm_f32x6_kernel<false>, grid, dim3(256), X6_NS * X6_STAGE, st, A3, W3, a_plane, w_plane, bias, C, M, N, K, ldc, tn, ntiles, (long long *)nullptr);
     MDD_LAUNCH_CHECK();

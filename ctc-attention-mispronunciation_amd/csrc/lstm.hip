@@ -747,20 +747,19 @@ __global__ __launch_bounds__(256, 1) void lstm_layer_granule_kernel(PersistArgs 
     if (a.dbg && tid == 0) for (int i = 0; i < 6; i++) a.dbg[blockIdx.x * 6 + i] = ph[i];
 }
 
-int granule_bg(int B) { const int r = (B + 15) / 16; return (r + 15) / 16 * 16; }   // rows per batch group (16 groups), padded to whole tiles
-
-
 __global__ void zero_fill_kernel(u32x4 *p, size_t n16) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += (size_t)gridDim.x * blockDim.x) p[i] = (u32x4){0u, 0u, 0u, 0u};
 }
 // The persistent layer kernels need their exchange buffer's tags and their abort word zeroed before every launch.  Inside a captured graph a
 // hipMemsetAsync becomes a memset NODE, and replays of such graphs were measured to let a layer kernel start on the previous launch's
 // contents (tools/fused_repro3.py, exact-fp32 mode, small batches: the second and later mdd_forward_fused calls gave wrong layer-0 outputs,
-// up to 2e-2, in 7 of 12 and 4 of 14 processes; in none of 12 with MDD_GRAPH=0; in none of 14 with this kernel in the memset's place;
-// MDD_ZERO_BY_MEMSET=1 brings the memset nodes back for study).  A kernel node orders like every other kernel of the chain.
+// up to 2e-2, in 7 of 12 and 4 of 14 processes; in none of 12 with MDD_GRAPH=0; in none of 14 with this kernel in the memset's place).
+// A kernel node orders like every other kernel of the chain.
 int launch_zero_fill(void *p, size_t n, hipStream_t st) {
-    static const bool by_memset = [] { const char *e = getenv("MDD_ZERO_BY_MEMSET"); return e && e[0] == '1'; }();
-    if (by_memset) { MDD_HIP_CHECK(hipMemsetAsync(p, 0, n, st)); return MDD_OK; }
+    if (n % 16 || reinterpret_cast<uintptr_t>(p) % 16) {
+        set_error("zero fill: %zu bytes at %p (a multiple of 16 bytes at a 16-byte aligned address)", n, p);
+        return MDD_ERR_ARG;
+    }
     const size_t n16 = n / 16;
     const int blocks = (int)std::min<size_t>((n16 + 255) / 256, 2048);
     hipLaunchKernelGGL(zero_fill_kernel, dim3(blocks > 0 ? blocks : 1), dim3(256), 0, st, reinterpret_cast<u32x4 *>(p), n16);
@@ -778,13 +777,14 @@ static int launch_granule_t(PersistArgs a, hipStream_t st) {
     return MDD_OK;
 }
 
-int launch_lstm_layer_granule(const LstmStepArgs &s, unsigned short *hx, unsigned int *sync, int *err_flag, hipStream_t st) {
+int launch_lstm_layer_granule(const LstmStepArgs &s, unsigned short *hx, unsigned int *sync, int *err_flag, hipStream_t st,
+                              long long *stamps, bool early) {
     PersistArgs a;
     a.gx = s.gx; a.whh = s.whh_split; a.whh_f32 = nullptr; a.hx = hx; a.sync = sync; a.err_flag = err_flag;
     a.out = s.out; a.out_raw = s.out_raw; a.out_split = s.out_split; a.oscale = s.oscale; a.oshift = s.oshift;
     a.T = s.T; a.B = s.B; a.BGr = (s.B + 15) / 16; a.BG = granule_bg(s.B); a.seqlen = s.seqlen;
-    a.dbg = (getenv("MDD_LSTM_DBG") && s.T > 100) ? reinterpret_cast<long long *>(reinterpret_cast<u64 *>(hx) + (size_t)2 * 32 * a.BG * s.H) : nullptr;
-    a.early = getenv("MDD_LSTM_EARLY") != nullptr;
+    a.dbg = stamps;
+    a.early = early;
     if (a.oscale == nullptr) a.oshift = nullptr;
     if (a.out && a.out != a.out_raw) { set_error("granule lstm: a separate scaled fp32 output is not supported (split planes carry it)"); return MDD_ERR_ARG; }
     a.gates_save = s.gates_save; a.c_save = s.c_save;

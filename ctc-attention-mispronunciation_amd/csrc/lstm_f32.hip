@@ -314,12 +314,12 @@ static int launch_f32_t(PersistArgs a, hipStream_t st) {
     return MDD_OK;
 }
 
-int launch_lstm_layer_f32(const LstmStepArgs &s, unsigned short *hx, unsigned int *sync, int *err_flag, hipStream_t st) {
+int launch_lstm_layer_f32(const LstmStepArgs &s, unsigned short *hx, unsigned int *sync, int *err_flag, hipStream_t st, long long *stamps) {
     PersistArgs a;
     a.gx = s.gx; a.whh = {nullptr, nullptr}; a.whh_f32 = s.whh; a.hx = hx; a.sync = sync; a.err_flag = err_flag;
     a.out = s.out; a.out_raw = s.out_raw; a.out_split = {nullptr, nullptr}; a.oscale = s.oscale; a.oshift = s.oscale ? s.oshift : nullptr;
     a.T = s.T; a.B = s.B; a.BGr = (s.B + 15) / 16; a.BG = granule_bg(s.B); a.seqlen = s.seqlen;
-    a.dbg = (getenv("MDD_LSTM_DBG") && s.T > 100) ? reinterpret_cast<long long *>(reinterpret_cast<u64 *>(hx) + (size_t)2 * 32 * a.BG * s.H) : nullptr;
+    a.dbg = stamps;
     a.early = 0; a.gates_save = nullptr; a.c_save = nullptr;
     if (!s.packed || s.out_split.hi || s.gates_save) { set_error("persistent fp32 lstm: packed W_hh layout, fp32 outputs, inference only"); return MDD_ERR_ARG; }
     if (!a.out && !a.out_raw) { set_error("persistent fp32 lstm: no output"); return MDD_ERR_ARG; }

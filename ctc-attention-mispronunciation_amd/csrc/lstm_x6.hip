@@ -497,11 +497,6 @@ static size_t x6_smem(int H, int NBT) {
     return (size_t)16 * UW * 4 * 2 + (size_t)3 * 3 * 16 * 8 * 2 + (size_t)NBT * (NBT == 1 ? 2 : 1) * 16 * UW * 16 + (size_t)2 * 3 * (H / 8) * 256 + (size_t)2 * 6 * 2 * 1024;
 }
 
-size_t lstm_x6_hx_bytes(int H, int B) {
-    const int bgr = (B + 7) / 8, nbt = (bgr + 15) / 16;
-    return (size_t)2 * 16 * nbt * 3 * (H / 8) * 256;
-}
-
 template <int H, int NBT, bool DBG = false>
 static int launch_x6_t(const X6Args &a, hipStream_t st) {
     if (int rc = launch_zero_fill(a.sync, 32 * sizeof(unsigned int), st)) return rc;
@@ -529,16 +524,15 @@ static int launch_x6_pick(const X6Args &a, hipStream_t st) {
     }
 }
 
-int lstm_x6_max_b(int H) { return 8 * 16 * 8; }   // 8 groups x 8 tiles x 16 rows
-
-int launch_lstm_layer_x6(const LstmStepArgs &s, const unsigned short *whh3, unsigned short *hx, unsigned int *sync, int *err_flag, hipStream_t st) {
+int launch_lstm_layer_x6(const LstmStepArgs &s, const unsigned short *whh3, unsigned short *hx, unsigned int *sync, int *err_flag, hipStream_t st,
+                         long long *stamps, int force_mask) {
     X6Args a;
     a.gx = s.gx; a.whh3 = whh3; a.hx = hx; a.sync = sync; a.err_flag = err_flag;
     a.out = s.out; a.out_raw = s.out_raw; a.oscale = s.oscale; a.oshift = s.oscale ? s.oshift : nullptr;
     a.T = s.T; a.B = s.B; a.BGr = (s.B + 7) / 8; a.seqlen = s.seqlen;
-    { const char *fr = getenv("MDD_X6_FORCE_REDO"); const int n = fr ? atoi(fr) : 0; a.force_mask = (n > 0 && (n & (n - 1)) == 0) ? n - 1 : -1; }
+    a.force_mask = force_mask;
     const int nbt = (a.BGr + 15) / 16;
-    a.dbg = (getenv("MDD_LSTM_DBG") && s.T > 100) ? reinterpret_cast<long long *>(reinterpret_cast<unsigned char *>(hx) + lstm_x6_hx_bytes(s.H, s.B)) : nullptr;
+    a.dbg = stamps;
     if (s.out_split.hi || s.gates_save || (!a.out && !a.out_raw) || !whh3) { set_error("persistent x6 lstm: fp32 outputs, inference only"); return MDD_ERR_ARG; }
     if (nbt < 1 || nbt > 8) { set_error("persistent x6 lstm: B=%d needs %d row tiles per team (max 8)", s.B, nbt); return MDD_ERR_ARG; }
 #define X6_CASE(H_, N_) case N_: return launch_x6_pick<H_, N_>(a, st)

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/mdd_hip.h"
+#include "plan.h"
 
 namespace mdd {
 
@@ -126,23 +127,24 @@ int init_kernel_attributes();
 int init_ctc_attributes();
 int init_lstm_attributes();
 // One launch for the whole layer (256 co-resident workgroups in 8-workgroup teams, data-tagged hand-off; see lstm.hip).
-int granule_bg(int B);
 int init_granule_attributes();
 int persistent_grid_fits(int n_cu);   // 1 when all 256 workgroups of a persistent layer launch can be resident at once
-// data-tagged variant (8-workgroup teams, no counter): hx = 2*32*granule_bg(B)*H u64 granules (+ stamps), sync: 32 uints
-int launch_lstm_layer_granule(const LstmStepArgs &s, unsigned short *hx, unsigned int *sync, int *err_flag, hipStream_t st);
+// data-tagged variant (8-workgroup teams, no counter): hx = 2*32*granule_bg(B)*H u64 granules (+ stamps), sync: 32 uints.
+// Diagnostics: stamps (nullable) receive per-workgroup phase cycle sums; early requests the next panel too early (redo path).
+int launch_lstm_layer_granule(const LstmStepArgs &s, unsigned short *hx, unsigned int *sync, int *err_flag, hipStream_t st,
+                              long long *stamps = nullptr, bool early = false);
 // Exact-fp32 persistent layer (lstm_f32.hip): same teams / exchange buffer; W_hh in the packed layout (LstmStepArgs::packed), fp32 outputs
-// zero fill by a kernel (n a multiple of 16; see its definition in lstm.hip for why not hipMemsetAsync)
+// zero fill by a kernel (n a multiple of 16, p 16-byte aligned; see its definition in lstm.hip for why not hipMemsetAsync)
 int launch_zero_fill(void *p, size_t n, hipStream_t st);
-int launch_lstm_layer_f32(const LstmStepArgs &s, unsigned short *hx, unsigned int *sync, int *err_flag, hipStream_t st);
+int launch_lstm_layer_f32(const LstmStepArgs &s, unsigned short *hx, unsigned int *sync, int *err_flag, hipStream_t st, long long *stamps);
 int init_lstm_f32_attributes();
 int persistent_f32_grid_fits(int n_cu);
-// f32x6 persistent layer (lstm_x6.hip): teams of 16, W_hh' as three row-major bf16 planes [3][2][4H][H], h exchanged as three bf16 planes; fp32 outputs
-int launch_lstm_layer_x6(const LstmStepArgs &s, const unsigned short *whh3, unsigned short *hx, unsigned int *sync, int *err_flag, hipStream_t st);
+// f32x6 persistent layer (lstm_x6.hip): teams of 16, W_hh' as three row-major bf16 planes [3][2][4H][H], h exchanged as three bf16 planes
+// (lstm_x6_hx_bytes); fp32 outputs.  force_mask >= 0: every (force_mask + 1)-th phase is declared stale (refetch branch).
+int launch_lstm_layer_x6(const LstmStepArgs &s, const unsigned short *whh3, unsigned short *hx, unsigned int *sync, int *err_flag, hipStream_t st,
+                         long long *stamps, int force_mask);
 int init_lstm_x6_attributes();
 int persistent_x6_grid_fits(int n_cu);
-size_t lstm_x6_hx_bytes(int H, int B);
-int lstm_x6_max_b(int H);
 // The backward recurrence of a layer in one launch (split-bf16 training variant, B <= 256, H in {256, 384}); hx: lstm_bwd_granule_hx_bytes(H)
 size_t lstm_bwd_granule_hx_bytes(int H);
 int launch_lstm_bwd_granule(const float *dout, const float *gates, const float *cst, SplitPtr whhT, float *dg, int T, int B, int H, unsigned short *hx,

@@ -1,0 +1,139 @@
+// Kernel selection of the decode forward (api.hip) in one place: which kernel each stage runs, as a pure function of the
+// geometry, the arithmetic mode, the environment switches, what the device can hold and the batch size.  Host only: no HIP,
+// no device code (tests/test_host.py builds it with the host compiler and checks the selection table).
+//
+// Environment switches of the decode handle.  read_switches() parses them once, in mdd_create; a handle keeps what it read for its
+// whole life, so a switch is set before the model is created.  Any other value of a switch is its default.
+//
+//   switch               selects                                                      read at   relied on by
+//   MDD_PRECISION=m      the arithmetic mode a handle starts in: f32x6|2 (default),   create    infer.py --precision
+//                        f32|0 or bf16x3|1 (mdd_set_precision changes it later)
+//   MDD_GRAPH=0          every forward enqueued stage by stage, no captured graph     create    (diagnostic)
+//   MDD_LSTM=step        the per-step recurrence in every mode: no persistent layer   create    test_persistent_f32_lstm_batch_sizes_match_step_kernels,
+//                        launch, no device gate (a second process on the device)                test_persistent_f32_lstm_full_length_and_poisoned_input,
+//                                                                                               test_bench_two_ranks_rehearsal, test_bench_exchange_runs_beside_the_next_forward,
+//                                                                                               tools/lstm_bcheck.py
+//   MDD_LSTM=x3          mode 1: lstm_step_x3_kernel, the LDS-tiled split-bf16 step;  create    test_persistent_lstm_equals_step_kernels_bitwise,
+//                        modes 0 and 2: the packed step kernel                                  test_persistent_lstm_batch_sizes_match_step_kernels,
+//                                                                                               test_fused_batches_of_different_lengths_equal_their_own_runs[*-bf16x3-x3]
+//   MDD_LSTM_X6=0        mode 2: the exact-fp32 layer kernel instead of the f32x6 one create    test_persistent_x6_lstm_tracks_exact_fp32_recurrence,
+//                                                                                               test_persistent_x6_lstm_full_length_and_poisoned_input, tools/lstm_kernel_choice.py
+//   MDD_LSTM_X6=force    mode 2: the f32x6 layer kernel wherever it can run           create    test_persistent_x6_lstm_tracks_exact_fp32_recurrence
+//   MDD_CONV=rowwise     mode 2: the row-at-a-time conv_fused_kernel<3>               create    tests/test_conv_multirow.py
+//   MDD_LSTM_DBG         persistent layer launches with T' > 100 write phase stamps   create    test_persistent_lstm_stale_panel_redo_path, tools/lstm_stamps.py,
+//                        behind their exchange buffer (mdd_tap "lstm_dbg")                      tools/lstm_f32_stamps.py
+//   MDD_LSTM_EARLY       split-bf16 layer kernel: the next panel requested a whole    create    test_persistent_lstm_stale_panel_redo_path
+//                        MFMA section early, so that the redo path runs
+//   MDD_X6_FORCE_REDO=n  f32x6 layer kernel: every n-th phase declared stale (n a     create    test_persistent_x6_lstm_redo_branch
+//                        power of two), so that the refetch branch runs
+//
+// The last three were read at each launch (that is, at graph capture) before they joined this table; every test and tool above sets them
+// before it creates the model.  The training handle's persistent layer launches take none of them.
+#pragma once
+#include <stddef.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "../../include/mdd_hip.h"
+
+namespace mdd {
+
+struct Switches {
+    int precision = 2;          // MDD_PRECISION
+    bool graph = true;          // MDD_GRAPH
+    bool lstm_step = false;     // MDD_LSTM=step
+    bool lstm_x3 = false;       // MDD_LSTM=x3
+    bool x6_off = false;        // MDD_LSTM_X6=0
+    bool x6_force = false;      // MDD_LSTM_X6=force
+    bool conv_rowwise = false;  // MDD_CONV=rowwise
+    bool lstm_dbg = false;      // MDD_LSTM_DBG
+    bool lstm_early = false;    // MDD_LSTM_EARLY
+    int x6_redo_mask = -1;      // MDD_X6_FORCE_REDO=n: n - 1, or -1 (off)
+};
+
+inline Switches read_switches() {
+    Switches s;
+    auto is = [](const char *e, const char *v) { return e && !strcmp(e, v); };
+    const char *e = getenv("MDD_PRECISION");
+    if (is(e, "f32") || is(e, "0")) s.precision = 0;
+    if (is(e, "bf16x3") || is(e, "1")) s.precision = 1;
+    e = getenv("MDD_GRAPH");
+    s.graph = !(e && e[0] == '0');
+    e = getenv("MDD_LSTM");
+    s.lstm_step = is(e, "step");
+    s.lstm_x3 = is(e, "x3");
+    e = getenv("MDD_LSTM_X6");
+    s.x6_off = e && e[0] == '0';
+    s.x6_force = e && e[0] == 'f';
+    s.conv_rowwise = is(getenv("MDD_CONV"), "rowwise");
+    s.lstm_dbg = getenv("MDD_LSTM_DBG") != nullptr;
+    s.lstm_early = getenv("MDD_LSTM_EARLY") != nullptr;
+    e = getenv("MDD_X6_FORCE_REDO");
+    const int n = e ? atoi(e) : 0;
+    if (n > 0 && (n & (n - 1)) == 0) s.x6_redo_mask = n - 1;
+    return s;
+}
+
+// Whether a device holds the whole grid of each persistent layer kernel (persistent_grid_fits, persistent_f32_grid_fits,
+// persistent_x6_grid_fits), asked once at create.
+struct DeviceFit { bool granule, f32, x6; };
+
+// Width after a 3x3 convolution with stride 2 and padding 1, and the first BiLSTM layer's input width.
+inline int conv_out(int w) { return (w + 2 - 3) / 2 + 1; }
+inline int rnn_in(const mdd_config &c) { return c.channels * conv_out(conv_out(c.feat)); }
+
+// W_hh' in the packed consumer layout (lstm_step_packed_kernel, lstm_layer_f32_kernel); every persistent layer kernel and the
+// split-bf16 step kernel are built for these hidden sizes only.
+inline bool packed_whh(const mdd_config &c) { return c.hidden == 384 || c.hidden == 256; }
+
+// Exchange buffers of the persistent layer kernels: batch rows per group of the 8-workgroup teams (lstm.hip, lstm_f32.hip; 16 groups,
+// padded to whole 16-row tiles), and the bytes of the 16-workgroup teams' buffer (lstm_x6.hip).  Both cover at most 1024 rows.
+inline int granule_bg(int B) { const int r = (B + 15) / 16; return (r + 15) / 16 * 16; }
+inline size_t lstm_x6_hx_bytes(int H, int B) { const int bgr = (B + 7) / 8, nbt = (bgr + 15) / 16; return (size_t)2 * 16 * nbt * 3 * (H / 8) * 256; }
+static constexpr int kPersistMaxB = 1024;
+
+enum class Conv { Separate, FusedX3, FusedX6, FusedX6Rowwise };   // conv0 + conv1 | conv_fused_kernel<2> | <3, 2> | <3>
+enum class Gemm { Nt, Bf16x3, F32x6 };                             // gemm_nt_f32_kernel | the bf16x3 kernels | gemm_f32x6_kernel
+enum class Lstm { X6, F32, Granule, StepX3, StepPacked, Step };    // persistent layer kernels | per-step kernels (lstm_step_kernel<0>)
+
+struct ForwardPlan {
+    int precision;      // the mode in effect; in mode 1 the activations travel as split-bf16 planes and the key and score GEMMs are bf16x3
+    Conv conv;
+    Gemm proj;          // the input projections: gemm_ih<n>, gemm_text
+    Lstm lstm;
+    bool gated;         // a persistent layer kernel runs: the forward is ordered behind the device's previous one
+    size_t hx_floats;   // the persistent kernels' exchange buffer with the stamp area (0 when none runs)
+    size_t stamps_at;   // where the stamps start in it
+};
+
+inline ForwardPlan plan_forward(const mdd_config &c, int precision, const Switches &sw, const DeviceFit &fit, int B) {
+    const int H = c.hidden, K0 = rnn_in(c);
+    const bool packed = packed_whh(c);
+    // bf16x3 and f32x6 need every contraction length a multiple of 32 (bf16x3 also the packed LSTM layouts); mode 0 otherwise
+    const bool x3 = precision == 1 && packed && K0 % 32 == 0 && c.emb_dim % 32 == 0;
+    const bool x6 = precision == 2 && K0 % 32 == 0 && (2 * H) % 32 == 0 && c.emb_dim % 32 == 0;
+    ForwardPlan p{};
+    p.precision = x3 ? 1 : x6 ? 2 : 0;
+    if ((x3 || x6) && c.feat == 243 && c.channels == 32) p.conv = x3 ? Conv::FusedX3 : sw.conv_rowwise ? Conv::FusedX6Rowwise : Conv::FusedX6;
+    else p.conv = Conv::Separate;
+    p.proj = x3 ? Gemm::Bf16x3 : x6 ? Gemm::F32x6 : Gemm::Nt;
+    // one persistent launch per BiLSTM layer: the split-bf16 teams in mode 1, the exact-fp32 teams in modes 0 and 2 ...
+    const bool persist = fit.granule && !sw.lstm_step && !sw.lstm_x3 && packed && B <= kPersistMaxB && (x3 || fit.f32);
+    // ... and in mode 2 the f32x6 teams where they are the faster of the two reference-width layer kernels (tools/lstm_kernel_choice.py,
+    // profiles/round3_lstm_x6_notes.txt): at H = 384 for every batch size (0.60 - 0.93 of the exact-fp32 kernel's time), at H = 256 up to
+    // 128 rows (0.83; beyond, the fp32 kernel's shorter products win: 1.07 - 1.5)
+    const bool lx6 = x6 && persist && fit.x6 && !sw.x6_off && (sw.x6_force || H == 384 || B <= 128);
+    if (lx6) p.lstm = Lstm::X6;
+    else if (persist) p.lstm = x3 ? Lstm::Granule : Lstm::F32;
+    else if (x3 && sw.lstm_x3) p.lstm = Lstm::StepX3;
+    else p.lstm = packed ? Lstm::StepPacked : Lstm::Step;
+    p.gated = persist;
+    if (persist) {   // u64 granules of the 8-workgroup teams or the three bf16 planes of the 16-workgroup ones, in floats; 256 x 6 stamps behind
+        const size_t granules = (size_t)2 * 32 * granule_bg(B) * H * 2, planes = lstm_x6_hx_bytes(H, B) / 4;
+        p.stamps_at = lx6 ? planes : granules;
+        p.hx_floats = (lx6 && planes > granules ? planes : granules) + 64 + 256 * 6 * 2;
+    }
+    return p;
+}
+
+}  // namespace mdd

@@ -333,6 +333,108 @@ def test_asm_mfma_hazards(tmp_path):
         assert not r.stdout.startswith("0 kernel(s)"), unit
 
 
+_PLAN_DRIVER = r'''
+#include <iostream>
+#include <sstream>
+#include <string>
+#include "plan.h"
+using namespace mdd;
+// stdin, one case per line: hidden channels mode|env B fit_granule fit_f32 fit_x6 [SWITCH=value ...]  (other geometry: the reference's)
+int main() {
+    const char *env[] = {"MDD_PRECISION", "MDD_GRAPH", "MDD_LSTM", "MDD_LSTM_X6", "MDD_CONV", "MDD_LSTM_DBG", "MDD_LSTM_EARLY", "MDD_X6_FORCE_REDO"};
+    const char *conv[] = {"conv0+conv1", "conv_fused_kernel<2>", "conv_fused_kernel<3,2>", "conv_fused_kernel<3>"};
+    const char *gemm[] = {"gemm_nt", "bf16x3", "f32x6"};
+    const char *lstm[] = {"x6", "f32", "granule", "lstm_step_x3_kernel", "lstm_step_packed_kernel", "lstm_step_kernel<0>"};
+    for (std::string line; std::getline(std::cin, line);) {
+        std::istringstream in(line);
+        mdd_config c{243, 384, 4, 45, 32, 44, 512, 1e-5f};
+        std::string mode;
+        int B;
+        DeviceFit fit;
+        in >> c.hidden >> c.channels >> mode >> B >> fit.granule >> fit.f32 >> fit.x6;
+        for (const char *e : env) unsetenv(e);
+        for (std::string kv; in >> kv;) setenv(kv.substr(0, kv.find('=')).c_str(), kv.substr(kv.find('=') + 1).c_str(), 1);
+        const Switches sw = read_switches();
+        const ForwardPlan p = plan_forward(c, mode == "env" ? sw.precision : std::stoi(mode), sw, fit, B);
+        std::cout << p.precision << ' ' << conv[(int)p.conv] << ' ' << gemm[(int)p.proj] << ' '
+                  << (p.precision == 1 ? "bf16x3" : "gemm_nt") << ' '   // key and score GEMMs: run_stage's split-bf16 activations
+                  << lstm[(int)p.lstm] << ' ' << p.gated << ' ' << p.hx_floats << ' ' << p.stamps_at << ' '
+                  << sw.graph << ' ' << sw.lstm_dbg << ' ' << sw.lstm_early << ' ' << sw.x6_redo_mask << '\n';
+    }
+}
+'''
+
+
+def test_decode_kernel_selection_table(tmp_path):
+    """csrc/plan.h, built with the host compiler and driven case by case: the kernels each stage of the decode forward runs for a
+    geometry, mode, set of switches, device fit and batch size; the exchange buffer of the persistent layers; the switch parser.
+    Every kernel agrees with the others within the tests' tolerances, so only this table notices a slip in the policy."""
+    import subprocess
+    drv = tmp_path / "plan_driver.cpp"
+    drv.write_text(_PLAN_DRIVER)
+    exe = str(tmp_path / "plan_driver")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "ctc-attention-mispronunciation_amd", "csrc"),
+                           str(drv), "-o", exe])
+    R, FIT = "384 32", "1 1 1"
+    mode = {0: "0 conv0+conv1 gemm_nt gemm_nt", 1: "1 conv_fused_kernel<2> bf16x3 bf16x3", 2: "2 conv_fused_kernel<3,2> f32x6 gemm_nt"}
+    cases = []   # (geometry, mode, B, fit, switches) -> "precision conv ih/text-GEMM key/score-GEMM recurrence gated"
+
+    def row(geom, m, Bs, want, fit=FIT, sw=""):
+        cases.extend(("%s %s %d %s %s" % (geom, m, B, fit, sw), want) for B in Bs)
+    row(R, 2, [1, 512, 1024], mode[2] + " x6 1")
+    row(R, 2, [1025], mode[2] + " lstm_step_packed_kernel 0")
+    row("256 32", 2, [128], mode[2] + " x6 1")
+    row("256 32", 2, [129, 1024], mode[2] + " f32 1")
+    row("256 32", 2, [1025], mode[2] + " lstm_step_packed_kernel 0")
+    row(R, 2, [1, 512, 1024], mode[2] + " f32 1", sw="MDD_LSTM_X6=0")
+    row("256 32", 2, [1024], mode[2] + " x6 1", sw="MDD_LSTM_X6=force")
+    row(R, 2, [512], "2 conv_fused_kernel<3> f32x6 gemm_nt x6 1", sw="MDD_CONV=rowwise")
+    row(R, 2, [1025], "2 conv_fused_kernel<3> f32x6 gemm_nt lstm_step_packed_kernel 0", sw="MDD_CONV=rowwise")
+    row(R, 0, [1, 1024], mode[0] + " f32 1")
+    row(R, 0, [1025], mode[0] + " lstm_step_packed_kernel 0")
+    row(R, 1, [1, 700, 1024], mode[1] + " granule 1")
+    row(R, 1, [1025], mode[1] + " lstm_step_packed_kernel 0")     # (split-plane outputs)
+    row(R, 1, [1, 512, 1025], mode[1] + " lstm_step_x3_kernel 0", sw="MDD_LSTM=x3")
+    for m in (0, 1, 2):
+        row(R, m, [512], mode[m] + " lstm_step_packed_kernel 0", sw="MDD_LSTM=step")
+        row(R, m, [512], mode[m] + " lstm_step_packed_kernel 0", fit="0 1 1")    # the granule grid does not fit
+    for m in (0, 2):
+        row(R, m, [512], mode[m] + " lstm_step_packed_kernel 0", sw="MDD_LSTM=x3")   # (x3 is a mode-1 kernel; the others take the packed step)
+        row(R, m, [512], mode[m] + " lstm_step_packed_kernel 0", fit="1 0 1")    # only the f32 grid does not fit
+    row(R, 1, [512], mode[1] + " granule 1", fit="1 0 1")
+    row(R, 2, [512], mode[2] + " f32 1", fit="1 1 0")                            # only the x6 grid does not fit
+    row("128 32", 2, [512], mode[2] + " lstm_step_kernel<0> 0")
+    row("128 32", 1, [512], mode[0] + " lstm_step_kernel<0> 0")
+    for m in (1, 2):                                                            # 4 channels: rnn_in 244, not a multiple of 32
+        row("384 4", m, [1, 1024], mode[0] + " f32 1")
+    # the exchange buffer (floats) and where the stamps start: u64 granules 2*32*granule_bg(B)*H, or the x6 planes' bytes / 4; + 64 + 256*6*2
+    row(R, 2, [1024], mode[2] + " x6 1 %d %d" % (2 * 32 * 64 * 384 * 2 + 64 + 3072, 2 * 16 * 8 * 3 * 48 * 256 // 4))
+    row(R, 1, [700], mode[1] + " granule 1 %d %d" % (2 * 32 * 48 * 384 * 2 + 64 + 3072, 2 * 32 * 48 * 384 * 2))
+    row(R, 0, [1025], mode[0] + " lstm_step_packed_kernel 0 0 0")
+    # the switch parser: mode from MDD_PRECISION ("env"); graph, stamps, early panel requests, forced redo mask
+    row(R, "env", [512], mode[2] + " x6 1")
+    row(R, "env", [512], mode[2] + " x6 1", sw="MDD_PRECISION=f32x6")
+    row(R, "env", [512], mode[2] + " x6 1", sw="MDD_PRECISION=fp64")
+    row(R, "env", [512], mode[0] + " f32 1", sw="MDD_PRECISION=f32")
+    row(R, "env", [512], mode[0] + " f32 1", sw="MDD_PRECISION=0")
+    row(R, "env", [512], mode[1] + " granule 1", sw="MDD_PRECISION=bf16x3")
+    row(R, "env", [512], mode[1] + " granule 1", sw="MDD_PRECISION=1")
+    row(R, 2, [512], mode[2] + " lstm_step_packed_kernel 0", sw="MDD_LSTM=step MDD_LSTM_X6=force")
+    row(R, 2, [512], mode[2] + " x6 1", sw="MDD_LSTM=steps MDD_CONV=row")
+    switches = [("", "1 0 0 -1"), ("MDD_GRAPH=0", "0 0 0 -1"), ("MDD_GRAPH=1", "1 0 0 -1"), ("MDD_LSTM_DBG=1 MDD_LSTM_EARLY=1", "1 1 1 -1"),
+                ("MDD_X6_FORCE_REDO=4", "1 0 0 3"), ("MDD_X6_FORCE_REDO=1", "1 0 0 0"), ("MDD_X6_FORCE_REDO=6", "1 0 0 -1"),
+                ("MDD_X6_FORCE_REDO=0", "1 0 0 -1")]
+    lines = [c for c, _ in cases] + ["%s 2 512 %s %s" % (R, FIT, sw) for sw, _ in switches]
+    r = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0, r.stderr
+    out = r.stdout.splitlines()
+    assert len(out) == len(lines)
+    for (case, want), got in zip(cases, out):
+        assert got.split()[:len(want.split())] == want.split(), (case, got)
+    for (sw, want), got in zip(switches, out[len(cases):]):
+        assert got.split()[-4:] == want.split(), (sw, got)
+
+
 def test_bench_dump_outputs_types_budget_and_sample(tmp_path, monkeypatch):
     """bench.py --dump-outputs' writer: integers and float32 as float32, float64 kept; within the byte budget every utterance,
     beyond it the same fixed seeded sample of utterances from every array (each along its own utterance axis), files within budget."""

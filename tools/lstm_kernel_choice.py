@@ -1,5 +1,5 @@
 """Diagnostic: time of one BiLSTM layer (stage replay) with the f32x6 recurrence (lstm_layer_x6_kernel) beside the exact-fp32 layer kernel,
-over batch sizes and both hidden sizes -- the table behind mdd_model::lx6()'s choice.  Each configuration runs in a child process
+over batch sizes and both hidden sizes -- the table behind plan_forward's choice (csrc/plan.h).  Each configuration runs in a child process
 (MDD_LSTM_X6 is read when the handle is created)."""
 import os, sys, subprocess, json
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
