@@ -15,7 +15,8 @@
 //                                                                                               tools/lstm_bcheck.py
 //   MDD_LSTM=x3          mode 1: lstm_step_x3_kernel, the LDS-tiled split-bf16 step;  create    test_persistent_lstm_equals_step_kernels_bitwise,
 //                        modes 0 and 2: the packed step kernel                                  test_persistent_lstm_batch_sizes_match_step_kernels,
-//                                                                                               test_fused_batches_of_different_lengths_equal_their_own_runs[*-bf16x3-x3]
+//                                                                                               test_fused_batches_of_different_lengths_equal_their_own_runs[*-bf16x3-x3],
+//                                                                                               test_fused_batches_straddling_64_equal_their_own_runs[*-bf16x3-x3]
 //   MDD_LSTM_X6=0        mode 2: the exact-fp32 layer kernel instead of the f32x6 one create    test_persistent_x6_lstm_tracks_exact_fp32_recurrence,
 //                                                                                               test_persistent_x6_lstm_full_length_and_poisoned_input, tools/lstm_kernel_choice.py
 //   MDD_LSTM_X6=force    mode 2: the f32x6 layer kernel wherever it can run           create    test_persistent_x6_lstm_tracks_exact_fp32_recurrence

@@ -2,8 +2,8 @@
 decoded phoneme string and the canonical phoneme string into the printed diagnosis and score.
 
 Reference: AA/infer.py:155-209 (print_aligned_string, align_canonical_decoded), :405-433 (stastics),
-:304-342 (sil removal, 'err' stripping, score).  Pure Python on <= ~50 tokens per utterance; function
-names are the reference's so callers can switch by changing the import.
+:304-342 (sil removal, 'err' stripping, score).  Pure Python per utterance (a sentence of 15-20 words is
+past 64 phonemes; the forward accepts up to 1596 at H = 384, include/mdd_hip.h); function names are the reference's so callers can switch by changing the import.
 
 ``infer`` is the batch loop around them (AA/infer.py:282-372): model, decoder, diagnosis and the printed block per
 utterance, over any loader that yields the reference's 7-tuple (``SpeechDataLoader`` or ``WavBatchLoader``).

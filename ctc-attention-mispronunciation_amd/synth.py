@@ -66,7 +66,7 @@ def _bn(rng, sd, prefix, n):
     sd[prefix + ".num_batches_tracked"] = np.array(7, dtype=np.int64)
 
 
-def synth_state_dict(geom, seed=1234, fc_gain=6.0):
+def synth_state_dict(geom, seed=1234, fc_gain=6.0, score_gain=1.0):
     """Ordered dict key -> numpy array, keys/shapes as the reference state_dict."""
     rng = np.random.Generator(np.random.PCG64(seed))
     sd = OrderedDict()
@@ -93,6 +93,10 @@ def synth_state_dict(geom, seed=1234, fc_gain=6.0):
         sd["lstm_embeds.bias_ih_l0" + sfx] = _uni(rng, (4 * H,), k)
         sd["lstm_embeds.bias_hh_l0" + sfx] = _uni(rng, (4 * H,), k)
     sd["score.weight"] = _uni(rng, (2 * H, 2 * H), 1.0 / np.sqrt(2.0 * H))
+    # score_gain > 1 scales the attention scores (std ~0.25 at gain 1: a nearly uniform attention) so that the softmax is peaked,
+    # as a trained model's unscaled dot-product attention is.  Applied in float32 after the draw: the random stream is unchanged.
+    if score_gain != 1.0:
+        sd["score.weight"] *= np.float32(score_gain)
     _bn(rng, sd, "fc.0", 4 * H)
     # fc_gain > 1 makes the posteriors of a random-weight model less flat so that
     # argmax / beam decisions have a margin (SURVEY.md §7 "hard parts").

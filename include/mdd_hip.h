@@ -81,8 +81,13 @@ int mdd_finalize_weights(mdd_model *m);
  *     W_hh.h products, the attention tail and the convolutions).
  * 1 = split-bf16 "x3" on v_mfma_f32_16x16x32_bf16: each fp32 operand = bf16 hi + bf16 lo (~16 significand bits), products hi.lo +
  *     lo.hi + hi.hi, for EVERY contraction of the forward including the recurrent W_hh.h products (h is re-split every step); cell state,
- *     gates, softmax and the classifier tail stay fp32.  Measured effect on the log-probs <= 1e-5 (tolerance 1e-4).  NARROWER than the
- *     reference's arithmetic: a flagged variant.  Falls back to 0 when a contraction length is not a multiple of 32 or H is not 256 / 384.
+ *     gates, softmax and the classifier tail stay fp32.  NARROWER than the reference's arithmetic: a flagged variant.  Its effect on the
+ *     log-probs grows with the magnitude of the attention scores, because a score carries an error of ~2^-17 of its size into exp():
+ *     measured against float64 (tests/test_canonical_length.py, profiles/canonical_length_margins.json) <= 1.1e-5 with the synthetic
+ *     weights as they are (|score| ~ 1, near-uniform attention, L up to 1852), <= 5.2e-5 with score.weight x 16 (|score| ~ 13),
+ *     <= 2.0e-4 at x 64 (|score| ~ 50) and <= 6.1e-4 at x 256 (|score| ~ 200, rows dominated by one key) -- i.e. past the 1e-4
+ *     tolerance once scores reach a few tens, where modes 0 and 2 stay <= 2.2e-5.  Use mode 2 or 0 for a model with peaked attention.
+ *     Falls back to 0 when a contraction length is not a multiple of 32 or H is not 256 / 384.
  * Env MDD_PRECISION=f32x6 / f32 / bf16x3 selects the mode at mdd_create.  mdd_get_precision returns the mode actually in use. */
 int mdd_set_precision(mdd_model *m, int32_t mode);
 int32_t mdd_get_precision(mdd_model *m);
@@ -99,7 +104,13 @@ int32_t mdd_len_frames(int32_t len, int32_t maxlen, int32_t t_out);
 /* ---- A2-A7: CTC_Model.forward(x, x1) in eval mode (AA/models/model_ctc.py:160-223)
  * x_dev [B,T,F] fp32 (T even), x1_dev [B,L] int64 canonical ids (0-padded) ->
  * logp_dev [T/2,B,C] fp32 log-probabilities.  ids outside [0,emb_rows) are an error
- * (the reference raises IndexError) and are reported by the next mdd_sync(). */
+ * (the reference raises IndexError) and are reported by the next mdd_sync().
+ * Canonical length: the attention tail keeps 16 rows of attention weights in LDS next to its classifier operands (160 KB in all),
+ * which bounds L.  With the matrix-core tail (4H a multiple of 256, C <= 48: the reference geometries) L <= 2364 - 2H, i.e. 1596 at
+ * H = 384 and 1852 at H = 256; with the scalar tail (any other geometry) L <= 2560 - 4H - C.  A longer L returns MDD_ERR_ARG
+ * (mdd_last_error() names L) from mdd_forward, mdd_forward_fused (whose bound applies to the common L) and mdd_forward_raw.  It is a
+ * host check: logp_dev is untouched and the handle stays usable; in the default graph mode it fires while the library's own capture
+ * is open, so nothing of that forward has been enqueued (with MDD_GRAPH=0 the stages before the tail have run into the workspace). */
 int mdd_forward(mdd_model *m, const float *x_dev, int32_t B, int32_t T, const int64_t *x1_dev, int32_t L,
                 float *logp_dev, void *stream);
 /* ---- A2-A7 for several reference batches of different padded lengths in ONE launch sequence.  The reference pads each

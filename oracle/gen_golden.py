@@ -20,6 +20,7 @@ What is imported:
   the same chain for each of the 20 words of egs/vocabulary/single, canonicals from AA/dict/phonetic_dict.py's CMU lookup -> G12
   torch.nn.CTCLoss(reduction='sum') as called at AA/steps/train_ctc.py:72,186 -> G5
   G2's and G11's cases again with the model in float64 (module.double()) -> g2_ref64.npz, g11_train64.npz
+  CTC_Model in float64 at canonical lengths 67, 130 and 200 (the last with peaked attention) -> G14 (g14_longL.*)
 
 Usage:  python oracle/gen_golden.py            (writes tests/golden/*)
 """
@@ -783,6 +784,35 @@ def gen_float64_goldens():
     np.savez_compressed(os.path.join(OUT, "g11_train64.npz"), **arrays)
 
 
+# ----------------------------------------------------------------------------- G14: canonical lengths past 64
+LONG_CASES = (("h384L67", dict(synth.REFERENCE), 3, 40, 67, 1.0), ("h256L130", dict(synth.REFERENCE_256), 2, 40, 130, 1.0),
+              ("h384L200g64", dict(synth.REFERENCE), 2, 40, 200, 64.0))
+
+
+def gen_long_canonical_goldens():
+    """The REFERENCE model in float64 at canonical lengths past 64 phonemes (the attention tail's strided branches, the second
+    column tile of the score GEMM) and, in the third case, with score.weight x 64 (peaked attention: largest weight ~0.9 per row).
+    Log-probs only, stored uncompressed with fixed zip timestamps so that a regeneration gives the same bytes."""
+    import zipfile
+    meta = []
+    with zipfile.ZipFile(os.path.join(OUT, "g14_longL.npz"), "w", zipfile.ZIP_STORED) as zf:
+        for tag, g, B, T, L, gain in LONG_CASES:
+            geom = synth.Geometry(**g)
+            sd = synth.synth_state_dict(geom, seed=1234, score_gain=gain)
+            x, x1, _, _ = synth.synth_batch(geom, B=B, T=T, L=L, seed=L)
+            m = build_reference_model(geom, sd).double()
+            with torch.no_grad():
+                logp = m(torch.from_numpy(x).double(), torch.from_numpy(x1)).numpy()
+            assert logp.dtype == np.float64 and logp.shape == (T // 2, B, geom.num_class)
+            with zf.open(zipfile.ZipInfo(tag + "_logp.npy", date_time=(1980, 1, 1, 0, 0, 0)), "w") as f:
+                np.lib.format.write_array(f, np.ascontiguousarray(logp), allow_pickle=False)
+            meta.append(dict(tag=tag, geom=g, B=B, T=T, L=L, seed=1234, batch_seed=L, score_gain=gain))
+            print("G14", tag, logp.shape, "%d bytes" % logp.nbytes)
+    with open(os.path.join(OUT, "g14_longL.json"), "w") as f:
+        json.dump(meta, f, indent=1)
+        f.write("\n")
+
+
 # ----------------------------------------------------------------------------- G11 (SURVEY 8(f) #3: one training step)
 class GivenDropout(nn.Module):
     """nn.Dropout with the mask handed in: y = x * (mask / (1-p)), the arithmetic of ATen's dropout with a fixed noise tensor."""
@@ -839,7 +869,7 @@ def gen_train_goldens():
 
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
-    which = sys.argv[1:] or ["model", "decode", "align", "eval", "ctc", "input", "chain", "aug", "train", "words", "float64"]
+    which = sys.argv[1:] or ["model", "decode", "align", "eval", "ctc", "input", "chain", "aug", "train", "words", "float64", "longL"]
     with torch.no_grad():
         if "model" in which:
             gen_model_goldens()
@@ -861,5 +891,7 @@ if __name__ == "__main__":
         gen_train_goldens()
     if "words" in which:
         gen_words_goldens()
+    if "longL" in which:
+        gen_long_canonical_goldens()
     if "float64" in which:                   # after "model" and "train": reads their case lists and G11's sampled indices
         gen_float64_goldens()

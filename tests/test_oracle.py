@@ -303,3 +303,30 @@ def test_g11_train_step_restatement(idx):
     for k, v in run.items():
         np.testing.assert_allclose(v, g64["%s_run_%s" % (tag, k)], rtol=0, atol=1e-12, err_msg=k)
     _within_fp32_envelope(ref_port.train_step(sd, x, x1, masks, tg, il, tl, 0.2)[0], g[tag + "_logp"], g64[tag + "_logp"], tag)
+
+
+@pytest.mark.parametrize("idx", [0, 1, 2])
+def test_g14_long_canonical_lengths(idx):
+    """G14: the reference model in float64 at canonical lengths 67, 130 and 200 (the last with score.weight x 64: peaked
+    attention).  The port's float64 graph equals it to 1e-10 (measured 2e-14), which is what lets tests/test_canonical_length.py
+    use ref_port float64 as its yardstick past 64 phonemes; and on the gain-1 cases the port in fp32 and the scalar C oracle are
+    within 1e-4 of it."""
+    import torch
+    from oracle import ref_port
+    meta = jload("g14_longL.json")[idx]
+    ref64 = npz("g14_longL.npz")[meta["tag"] + "_logp"]
+    assert ref64.dtype == np.float64
+    geom = synth.Geometry(**meta["geom"])
+    sd = synth.synth_state_dict(geom, seed=meta["seed"], score_gain=meta["score_gain"])
+    x, x1, _, _ = synth.synth_batch(geom, B=meta["B"], T=meta["T"], L=meta["L"], seed=meta["batch_seed"])
+    assert x1.shape[1] == meta["L"] > 64
+    p64 = ref_port.forward(sd, x, x1, dtype=torch.float64).numpy()
+    print("G14 %s: |port64 - reference64| = %.2e" % (meta["tag"], np.abs(p64 - ref64).max()))
+    np.testing.assert_allclose(p64, ref64, rtol=0, atol=1e-10)
+    if meta["score_gain"] != 1.0:
+        return
+    p32 = ref_port.forward(sd, x, x1).numpy()
+    c32 = oracle.forward(sd, x, x1)
+    print("G14 %s: |port32 - reference64| = %.2e, |C oracle - reference64| = %.2e" % (meta["tag"], np.abs(p32 - ref64).max(), np.abs(c32 - ref64).max()))
+    np.testing.assert_allclose(p32, ref64, rtol=0, atol=1e-4)
+    np.testing.assert_allclose(c32, ref64, rtol=0, atol=1e-4)
