@@ -373,7 +373,7 @@ static int run_stage(mdd_model *m, int si, const float *x, int B, int T, const i
             const float *in = n == 0 ? m->seq0.p : m->act[(n - 1) & 1].p;
             if (p.proj == Gemm::F32x6) {   // fp32-grade arithmetic at 6/16 of the fp32 MFMA's cost (gemm_bf16x6.hip)
                 unsigned short *p3 = reinterpret_cast<unsigned short *>(m->p3.p);
-                if (!(n == 0 && fused))      // (layer 0: the fused front-end has written the planes already)
+                if (!(n == 0 && fused) && !(n >= 1 && p.planes_out))   // (the fused front-end / the layer kernel before has written the planes already)
                     if (int rc = launch_split3(in, Tp * B, K, K, p3, st)) return rc;
                 return launch_gemm_f32x6(p3, (size_t)Tp * B * K, w.rnn[n].wih_3, (size_t)G2 * K, nullptr, m->gx.p, Tp * B, G2, K, G2, st);
             }
@@ -387,7 +387,10 @@ static int run_stage(mdd_model *m, int si, const float *x, int B, int T, const i
             a.out = m->xraw.p; a.out_raw = m->xraw.p; a.oscale = nullptr; a.oshift = nullptr;
             a.out_split = x3 ? split_view(m->x_s, rows * H2) : kNoSplit;
         } else {             // next layer's BatchNorm folded into the store
-            a.out = x3 ? nullptr : m->act[n & 1].p; a.out_raw = m->taps ? m->tap_rnn[n].p : nullptr;
+            a.out = x3 || p.planes_out ? nullptr : m->act[n & 1].p; a.out_raw = m->taps ? m->tap_rnn[n].p : nullptr;
+            if (p.planes_out) {   // straight into the next projection's operand buffer (gemm_ih<n> has read it: same stream, stages in order)
+                a.out_planes = reinterpret_cast<unsigned short *>(m->p3.p); a.out_planes_stride = rows * H2;
+            }
             a.out_split = x3 ? split_view(m->act_s[n & 1], rows * H2) : kNoSplit;
             a.oscale = w.rnn[n + 1].scale; a.oshift = w.rnn[n + 1].shift;
         }

@@ -12,7 +12,11 @@
 // the product 2 x 2: three row tiles x half of K each (216 registers of weight fragments, half of the panel to read); the two partial
 // sums of a row tile meet at the wave that owns its cell update (see the kernel).  A team's batch rows are NBT tiles of 16 (B = 512:
 // four), independent recurrences advanced in turn, so that one tile's h travels while the others' products run; from three tiles up
-// the schedule is SKEWED: the cell update, publish and output stores of a tile run inside the next tile's product loop.
+// the schedule is SKEWED: the cell update and publish of a tile run inside the next tile's product loop.
+// The layer outputs leave through the wave that owns no cell update (wave (1, 1), which would otherwise wait at the phase's barrier for the
+// three owners): the owners leave the output tile in LDS (double-buffered by phase), and a barrier later that wave stores it -- as fp32
+// (`out`, `out_raw`) and / or as the next projection's A operand: three K-tile-major bf16 planes (split3_kernel's layout and arithmetic,
+// gemm_bf16x6.hip), so that no fp32 copy of the layer output and no split pass over it exist (X6Args::planes).
 // Hand-off as in lstm_f32.hip (data-tagged, no counter, no drain): h travels as 16-byte granules = eight consecutive units of one batch
 // row of ONE plane; |h| <= 1 leaves bit 14 of every bf16 element (the top exponent bit) free in all three planes, the epoch tag
 // (step % 3 + 1) rides there in the granule's first two elements and is cleared on the MFMA operand registers (one v_and per fragment).
@@ -20,7 +24,7 @@
 // k-slice q) at k-step ks is chunk column 4 ks + q of each plane, as it lies.  A NaN state travels as 1.5.
 // One wave per SIMD issues one instruction every four cycles at best and stalls on every dependency, so the kernel is written for
 // few instructions per phase: one assembly block per sweep (an immediate offset moves the global and the LDS address together), one
-// 16-byte publish store per owner, one barrier per phase, counted waits that skip the write-through stores' acknowledgements.
+// 16-byte publish store per owner, one barrier per phase, counted waits that skip the stores' acknowledgements.
 #include "lstm_persist.h"
 #include <type_traits>
 #include <utility>
@@ -48,6 +52,9 @@ struct X6Args {
     int force_mask;                  // diagnostic (MDD_X6_FORCE_REDO=n, a power of two): every n-th phase is declared stale, so that the refetch-and-multiply-again branch runs; -1: off
     long long *dbg;
     const int *seqlen;
+    unsigned short *planes;          // the layer output (the value `out` would hold) as the next projection's A operand: three K-tile-major bf16 planes
+    size_t plane_stride;             // (launch_split3's layout and arithmetic), plane_stride elements apart, of `rows` = T * B rows each; null: off
+    int rows;
 };
 
 template <int H, int NBT, bool DBG = false>
@@ -65,9 +72,9 @@ __global__ __launch_bounds__(256, 1) void lstm_layer_x6_kernel(X6Args a) {
     static_assert(PANB % (NTH * 16) == 0 && (NLD == 9 || NLD == 6), "a panel is whole passes of the workgroup");
     constexpr int NGB = NBT == 1 ? 2 : 1;                            // gx slab buffers per tile (one tile: the next step's slab is needed right away)
     constexpr int GXT = 16 * UW * 4;                                 // floats per gx slab
-    float *Os = reinterpret_cast<float *>(smem);                     // [16 rows][UW] layer output
-    float *Or = Os + 16 * UW;                                       // [16 rows][UW] raw h, when both leave
-    unsigned short *Og = reinterpret_cast<unsigned short *>(Or + 16 * UW);   // [3 owner waves][3 planes][16 rows][8] tagged bf16: the publish order
+    float *Os = reinterpret_cast<float *>(smem);                     // [2][16 rows][UW] layer output: written by the owners, read a barrier later by wave (1, 1)
+    float *Or = Os + 2 * 16 * UW;                                   // [2][16 rows][UW] raw h, when it leaves as well
+    unsigned short *Og = reinterpret_cast<unsigned short *>(Or + 2 * 16 * UW);   // [3 owner waves][3 planes][16 rows][8] tagged bf16: the publish order
     float *Gx = reinterpret_cast<float *>(Og + 3 * 3 * 16 * 8);      // [NBT][NGB][GXT]
     unsigned char *Rw = reinterpret_cast<unsigned char *>(Gx + NBT * NGB * GXT);   // [2][PANB]
     float *Px = reinterpret_cast<float *>(Rw + 2 * PANB);              // [2 phases][6 tiles][2 K halves][64 lanes][4]: partial sums on their way to the tile's owner
@@ -83,8 +90,8 @@ __global__ __launch_bounds__(256, 1) void lstm_layer_x6_kernel(X6Args a) {
     // (H = 256: {2 rh, 2 rh + 1}) over the k-steps of K half kh: three tiles x half of K each, and only half of the panel to read.
     // Cell updates: a row tile's two partial sums meet at its OWNER -- wave (rh, 0) owns tiles 2 rh and 2 rh + 1 (its own partial stays in
     // registers, the other arrives through LDS), wave (0, 1) owns tiles 4 and 5 (H = 384).  Owners hold two ADJACENT tiles = eight
-    // consecutive units, one 16-byte chunk of each plane per batch row: the granule h travels in.  Wave (1, 1) owns nothing and is the
-    // one that compares the panels' tags.
+    // consecutive units, one 16-byte chunk of each plane per batch row: the granule h travels in.  Wave (1, 1) owns nothing: it compares
+    // the panels' tags and, while the owners update cells, stores the layer outputs of the tile they updated a barrier earlier.
     const int rh = wave >> 1, kh = wave & 1;
 
     // ---- resident weights: A fragments W'[row = member * RM + tile * 16 + li][k = (kh * KH + j) * 32 + kq * 8 .. +8], three planes
@@ -221,8 +228,9 @@ __global__ __launch_bounds__(256, 1) void lstm_layer_x6_kernel(X6Args a) {
         return ok;
     };
     const size_t slab = (size_t)B * 2 * H;
-    const bool two_out = a.out_raw && a.out && a.out_raw != a.out;
-    float *const out_main = a.out ? a.out : a.out_raw;
+    // what leaves: the output tile Os as planes and / or fp32 (`out`; `out_raw` where it is the only target), the raw tile Or as a second fp32 target
+    float *const out_main = a.out ? a.out : (a.planes ? nullptr : a.out_raw);
+    float *const out_raw2 = (a.out_raw && a.out_raw != out_main) ? a.out_raw : nullptr;
     auto tile_rows = [&](int bt) { const int nv = min(a.BGr, B - g * a.BGr) - bt * 16; return nv < 0 ? 0 : (nv > 16 ? 16 : nv); };
 
     // Products of this wave's NT row tiles against its half of the panel in Rw[pb].  The tag bits (first dword of every chunk) are
@@ -292,11 +300,11 @@ __global__ __launch_bounds__(256, 1) void lstm_layer_x6_kernel(X6Args a) {
     };
 
     // Cell update of (tile bt, step sc) for the two row tiles this wave owns: lstm_f32.hip's arithmetic.  Part 1: the partial sums
-    // meet, gates, c, h into the LDS tiles (the layer output, and h as three tagged bf16 planes in publish order).  Part 2: the request
-    // for the tile's next gx slab, then publish (one 16-byte granule = eight units of one row of one plane per lane, write-through) and
-    // the layer outputs.  `on` false (the skewed schedule's first phase has no previous tile; a product loop run again): every store
-    // lands out of bounds = is dropped.
-    auto cell1 = [&](auto role_, const f32x4 *gsum, int buf, auto bt_, int sc, bool on) {
+    // meet, gates, c, h into the LDS tiles (the layer output tiles [ob], which emit() stores a barrier later, and h as three tagged bf16
+    // planes in publish order).  Part 2: the request for the tile's next gx slab, then publish (one 16-byte granule = eight units of one
+    // row of one plane per lane, write-through).  `on` false (the skewed schedule's first phase has no previous tile; a product loop run
+    // again): the store lands out of bounds = is dropped.
+    auto cell1 = [&](auto role_, const f32x4 *gsum, int buf, auto bt_, int sc, bool on, int ob) {
         constexpr int ROLE = decltype(role_)::value;
         constexpr int bt = decltype(bt_)::value;
         const int t = d ? (T - 1 - sc) : sc;
@@ -320,8 +328,8 @@ __global__ __launch_bounds__(256, 1) void lstm_layer_x6_kernel(X6Args a) {
             const float hn = (valid && live) ? hr_ : 0.f;
             cst[r][bt] = on ? (live ? cn : 0.f) : cst[r][bt];
             const int ul = rt * 4 + kq;                              // unit inside the workgroup's share
-            Os[li * UW + ul] = scaled ? hn * osc[r] + osh[r] : hn;
-            Or[li * UW + ul] = hn;
+            Os[ob * (16 * UW) + li * UW + ul] = scaled ? hn * osc[r] + osh[r] : hn;   // (both always: a wave-uniform branch here costs the owners more than the write)
+            Or[ob * (16 * UW) + li * UW + ul] = hn;
             // h -> hi + mid + lo (exact); elements 0, 1 of each plane's granule (the first tile's units 0, 1) carry the tag in bit 14;
             // a NaN state travels as 1.5 + 0 + 0
             const unsigned tagw = r == 0 ? ((kq == 0 ? (tg & 1u) : kq == 1 ? (tg >> 1) : 0u) << 14) : 0u;
@@ -337,10 +345,10 @@ __global__ __launch_bounds__(256, 1) void lstm_layer_x6_kernel(X6Args a) {
     };
     // (the step's addresses come in as pointers worked out once per step: gxn = the gx slab of the tile's next step, hxpub = the team's
     // panels of the step's parity, outp / rawp = the layer outputs' slabs of the step's time index)
-    auto cell2 = [&](auto bt_, const float *gxn, unsigned char *hxpub, float *outp, float *rawp, bool on) {
+    auto cell2 = [&](auto bt_, const float *gxn, unsigned char *hxpub, bool on) {
         constexpr int bt = decltype(bt_)::value;
         if (NBT >= 2) load_gx(bt, 0, gxn);   // this tile's next slab, into the buffer part 1 has read (needed a round from now)
-        // the stores come last in the phase: the wait at its end, s_waitcnt vmcnt(3), then covers every transfer into LDS (vector memory
+        // the store comes last in the phase: the wait at its end, s_waitcnt vmcnt(1), then covers every transfer into LDS (vector memory
         // operations return in order) without waiting for the write-through store's acknowledgement (~1 us)
         {
             const int prow = lane & 15, pp = lane >> 4;              // lane -> (plane, batch row): 48 lanes
@@ -349,24 +357,67 @@ __global__ __launch_bounds__(256, 1) void lstm_layer_x6_kernel(X6Args a) {
             const unsigned off = (pp < 3 && on) ? (unsigned)(pp * PLB + ((member * CPM + (ot0 >> 1)) * 16 + prow) * 16) : 0xffffffffu;
             __builtin_amdgcn_raw_buffer_store_b128(pv, drs, off, 0, 16 /* sc1 */);
         }
-        {   // layer outputs: lane -> (row, which of the two tiles): 32 pieces of 16 B read back from the LDS tiles
-            const int nr = tile_rows(bt);
-            const int rr = min(lane & 15, max(nr - 1, 0)), piece = lane >> 4;
-            const bool mine = piece < 2 && nr > 0 && on;
-            const int rt = ot0 + (piece & 1);
-            const unsigned el = (unsigned)((g * a.BGr + bt * 16 + rr) * 2 * H + d * H + member * UW + rt * 4);
-            const int lo = rr * UW + rt * 4;
-            const u32x4 v = *reinterpret_cast<const u32x4 *>(Os + lo);
-            const __amdgpu_buffer_rsrc_t rs_ = __builtin_amdgcn_make_buffer_rsrc(outp, 0, (int)(slab * 4), 0x00020000);
-            __builtin_amdgcn_raw_buffer_store_b128(v, rs_, mine ? el * 4u : 0xffffffffu, 0, 0);
-            const u32x4 v2 = *reinterpret_cast<const u32x4 *>(Or + lo);
-            const __amdgpu_buffer_rsrc_t rs2 = __builtin_amdgcn_make_buffer_rsrc(rawp, 0, (int)(slab * 4), 0x00020000);
-            __builtin_amdgcn_raw_buffer_store_b128(v2, rs2, (mine && two_out) ? el * 4u : 0xffffffffu, 0, 0);
+    };
+    // The layer outputs of (tile bt, step st), by wave (1, 1), from the LDS tiles [ob] the owners' part 1 filled before the last barrier:
+    // the planes (lane -> (row, chunk column): eight consecutive units of one row, split by split3_kernel's arithmetic, one 16-byte store
+    // per plane at element ((k / 32) * rows + row) * 32 + k % 32 -- UW and H are multiples of 8, a granule never straddles a K-tile) and
+    // the fp32 forms (lane -> (row, 16-byte piece)).  Rows past tile_rows(bt), and everything when `on` is false, land out of bounds =
+    // are dropped; the number of store instructions is always n_out: the wave's wait at the end of a phase counts them.
+    constexpr int NFS = (16 * (UW / 4) + 63) / 64;                   // fp32 store instructions per target: 96 (64) pieces of 16 bytes
+    const int n_out = (a.planes ? 3 : 0) + (out_main ? NFS : 0) + (out_raw2 ? NFS : 0);
+    auto emit = [&](auto bt_, int st, int ob, bool on) {
+        constexpr int bt = decltype(bt_)::value;
+        const int t = d ? (T - 1 - max(st, 0)) : max(st, 0);
+        const int nr = on ? tile_rows(bt) : 0;
+        const float *os = Os + ob * (16 * UW), *orw = Or + ob * (16 * UW);
+        if (a.planes) {
+            const int cc = min(kq, CPM - 1);
+            const bool mine = kq < CPM && li < nr;
+            const f32x4 v0 = *reinterpret_cast<const f32x4 *>(os + li * UW + cc * 8), v1 = *reinterpret_cast<const f32x4 *>(os + li * UW + cc * 8 + 4);
+            // two values at a time: one packed conversion per plane (round to nearest even, as split3_kernel's scalar ones), a bf16 back to
+            // fp32 is a shift (low half) or a mask (high half) of the packed word
+            typedef float f32x2 __attribute__((ext_vector_type(2)));
+            typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+            u32x4 p0, p1, p2;
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                const f32x2 x = i < 2 ? (f32x2){v0[(i & 1) * 2], v0[(i & 1) * 2 + 1]} : (f32x2){v1[(i & 1) * 2], v1[(i & 1) * 2 + 1]};
+                const unsigned w0 = __builtin_bit_cast(unsigned, __builtin_convertvector(x, bf16x2));
+                const f32x2 r1 = x - (f32x2){__builtin_bit_cast(float, w0 << 16), __builtin_bit_cast(float, w0 & 0xffff0000u)};
+                const unsigned w1 = __builtin_bit_cast(unsigned, __builtin_convertvector(r1, bf16x2));
+                const f32x2 r2 = r1 - (f32x2){__builtin_bit_cast(float, w1 << 16), __builtin_bit_cast(float, w1 & 0xffff0000u)};
+                p0[i] = w0; p1[i] = w1; p2[i] = __builtin_bit_cast(unsigned, __builtin_convertvector(r2, bf16x2));
+            }
+            const int k = d * H + member * UW + cc * 8;
+            const unsigned row = (unsigned)(t * B + g * a.BGr + bt * 16 + li);
+            const unsigned off = mine ? (((unsigned)(k >> 5) * (unsigned)a.rows + row) * 32u + (unsigned)(k & 31)) * 2u : 0xffffffffu;
+            const int pbytes_ = (int)((unsigned)a.rows * (unsigned)(2 * H) * 2u);   // (under 4 GB: launch_lstm_layer_x6)
+            __builtin_amdgcn_raw_buffer_store_b128(p0, __builtin_amdgcn_make_buffer_rsrc(a.planes, 0, pbytes_, 0x00020000), off, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b128(p1, __builtin_amdgcn_make_buffer_rsrc(a.planes + a.plane_stride, 0, pbytes_, 0x00020000), off, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b128(p2, __builtin_amdgcn_make_buffer_rsrc(a.planes + 2 * a.plane_stride, 0, pbytes_, 0x00020000), off, 0, 0);
+        }
+#pragma unroll
+        for (int i = 0; i < NFS; i++) {
+            const int piece = i * 4 + kq;
+            const bool mine = piece < UW / 4 && li < nr;
+            const int lo = li * UW + min(piece, UW / 4 - 1) * 4;
+            const unsigned off = mine ? (unsigned)((g * a.BGr + bt * 16 + li) * 2 * H + d * H + member * UW + piece * 4) * 4u : 0xffffffffu;
+            if (out_main) {
+                const u32x4 v = *reinterpret_cast<const u32x4 *>(os + lo);
+                __builtin_amdgcn_raw_buffer_store_b128(v, __builtin_amdgcn_make_buffer_rsrc(out_main + (size_t)t * slab, 0, (int)(slab * 4), 0x00020000), off, 0, 0);
+            }
+            if (out_raw2) {
+                const u32x4 v = *reinterpret_cast<const u32x4 *>(orw + lo);
+                __builtin_amdgcn_raw_buffer_store_b128(v, __builtin_amdgcn_make_buffer_rsrc(out_raw2 + (size_t)t * slab, 0, (int)(slab * 4), 0x00020000), off, 0, 0);
+            }
         }
     };
 
     // One wave's program over all phases.  ROLE 0: waves (0, 0), (1, 0) -- K half 0, owner of its first two tiles; 1: wave (0, 1) -- K half 1,
-    // owner of tiles 4, 5 at H = 384 (of nothing at H = 256); 2: wave (1, 1) -- K half 1, owner of nothing, compares the tags.
+    // owner of tiles 4, 5 at H = 384 (of nothing at H = 256); 2: wave (1, 1) -- K half 1, owner of nothing, compares the tags and stores
+    // the layer outputs.  The owners fill the output tiles [ob] in part 1; wave (1, 1) reads them after the next barrier, while the owners
+    // fill the other pair: one tile per team -- after the phase's barrier, beside the next cell update; two -- after the next phase's first
+    // barrier, beside its part 1; skewed -- at the end of the next phase's product loop, where it used to wait for the owners.
     auto run = [&](auto role_) {
         constexpr int ROLE = decltype(role_)::value;
         constexpr bool OWNER = ROLE == 0 || (ROLE == 1 && NRT == 6);
@@ -390,14 +441,11 @@ __global__ __launch_bounds__(256, 1) void lstm_layer_x6_kernel(X6Args a) {
             lds_barrier();                                              // the partial sums are in place
             if (DBG) ph[5] += 1000;
         };
-        float *const raw_main = two_out ? a.out_raw : out_main;
         auto t_of = [&](int st) { return d ? (T - 1 - st) : st; };
         for (int s = 0; s < T && !dead; s++) {
             // the step's addresses (and the previous step's, which the skewed schedule's first tile still works on)
-            const int sp_ = max(s - 1, 0), sn_ = min(s + 1, T - 1);
+            const int sn_ = min(s + 1, T - 1);
             const float *const gx_s = gx_at(t_of(s)), *const gx_n = gx_at(t_of(sn_));
-            float *const out_s = out_main + (size_t)t_of(s) * slab, *const out_p = out_main + (size_t)t_of(sp_) * slab;
-            float *const raw_s = raw_main + (size_t)t_of(s) * slab, *const raw_p = raw_main + (size_t)t_of(sp_) * slab;
             unsigned char *const hx_s = const_cast<unsigned char *>(hx_parity(s)), *const hx_p = const_cast<unsigned char *>(hx_parity(s - 1));
             auto phase = [&](auto bt_) {
                 constexpr int bt = decltype(bt_)::value;
@@ -419,19 +467,20 @@ __global__ __launch_bounds__(256, 1) void lstm_layer_x6_kernel(X6Args a) {
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the gx slab
                     lds_barrier();                                      // the partial sums
                     XSTAMP(2);
-                    if constexpr (OWNER) { cell1(role_, gs, 0, bt_, s, true); XSTAMP(3); cell2(bt_, gx_n, hx_s, out_s, raw_s, true); }
+                    if constexpr (OWNER) { cell1(role_, gs, 0, bt_, s, true, s & 1); XSTAMP(3); cell2(bt_, gx_n, hx_s, true); }
+                    if constexpr (ROLE == 2) emit(bt_, s - 1, (s & 1) ^ 1, s >= 1);   // (acknowledged by the next phase's wait for the owners' publish)
                     XSTAMP(4);
                     return;
                 }
                 // Two or more tiles per team.  SKEW (three or more): the next phase's panel is requested as this phase's product loop begins, and
-                // the previous phase's cell update, publish and output stores run inside the loop.  Two tiles: the next panel's state was published
+                // the previous phase's cell update and publish run inside the loop (its output stores: wave (1, 1), a phase later).  Two tiles: the next panel's state was published
                 // at the end of the phase before -- requested when the product loop ends, it travels during the cell update.
                 constexpr int RQJ = SKEW ? 0 : KH - 1;
                 const bool stale = products(chk_, pb, tag_word(s + 2), gs, [&](int j) {   // (s - 1) % 3 == (s + 2) % 3, s >= 0
                     if (j == RQJ) request_sweep(hx_parity(ns - 1), nbt, pb ^ 1);   // (step -1 = parity 1 before anything was published there: zeros, as step 0 wants them)
                     if constexpr (SKEW && OWNER) {
-                        if (j == 0) cell1(role_, gP, (pc & 1), std::integral_constant<int, pbt>{}, max(psv, 0), psv >= 0);
-                        if (j == 1) { if (bt > 0) cell2(std::integral_constant<int, pbt>{}, gx_n, hx_s, out_s, raw_s, true); else cell2(std::integral_constant<int, pbt>{}, gx_s, hx_p, out_p, raw_p, psv >= 0); }
+                        if (j == 0) cell1(role_, gP, (pc & 1), std::integral_constant<int, pbt>{}, max(psv, 0), psv >= 0, pc & 1);
+                        if (j == 1) { if (bt > 0) cell2(std::integral_constant<int, pbt>{}, gx_n, hx_s, true); else cell2(std::integral_constant<int, pbt>{}, gx_s, hx_p, psv >= 0); }
                     }
                 }, [&] {
                     // SKEW: was the previous phase's panel whole?  (rare: no -- a granule had not arrived: the panel is fetched until it is, that
@@ -443,7 +492,14 @@ __global__ __launch_bounds__(256, 1) void lstm_layer_x6_kernel(X6Args a) {
                 send_partials(role_, gs, (pc & 1) ^ 1);
                 if constexpr (SKEW) {
                     post(stale || forced);
-                    if constexpr (OWNER) wait_vmcnt(3); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the next panel's pieces and the next gx slab: all but cell2()'s three stores
+                    if constexpr (ROLE == 2) {   // the outputs of the tile whose cell update ran in the phase before (two tiles back)
+                        constexpr int ebt = (bt + NBT - 2) % NBT;
+                        const int es = bt >= 2 ? s : s - 1;
+                        emit(std::integral_constant<int, ebt>{}, es, (pc & 1) ^ 1, es >= 0);
+                        XSTAMP(3);
+                    }
+                    // the next panel's pieces and the next gx slab: all but the stores behind them (cell2()'s publish, emit()'s outputs)
+                    if constexpr (OWNER) wait_vmcnt(1); else if constexpr (ROLE == 2) { if (n_out == 3) wait_vmcnt(3); else wait_vmcnt(n_out); } else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                     lds_barrier();                                      // the next panel is whole; this phase's panel buffer is free again; the partial sums are in place
                     posted();
                     have_v = true;
@@ -464,11 +520,13 @@ __global__ __launch_bounds__(256, 1) void lstm_layer_x6_kernel(X6Args a) {
 #pragma unroll
                     for (int t = 0; t < NT; t++) gP[t] = gs[t];
                 } else {
-                    if constexpr (OWNER) cell1(role_, gs, (pc & 1) ^ 1, bt_, s, true);
+                    if constexpr (OWNER) cell1(role_, gs, (pc & 1) ^ 1, bt_, s, true, pc & 1);
+                    if constexpr (ROLE == 2) emit(std::integral_constant<int, pbt>{}, psv, (pc & 1) ^ 1, psv >= 0);   // the previous phase's tile, beside this one's cell update
                     XSTAMP(3);
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the next panel's pieces (travelling since the product loop ended) -- before the publish, whose acknowledgement takes longer
+                    // the next panel's pieces (travelling since the product loop ended) -- before the publish, whose acknowledgement takes longer, and not emit()'s stores
+                    if constexpr (ROLE == 2) wait_vmcnt(n_out); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                     lds_barrier();
-                    if constexpr (OWNER) cell2(bt_, gx_n, hx_s, out_s, raw_s, true);
+                    if constexpr (OWNER) cell2(bt_, gx_n, hx_s, true);
                     XSTAMP(4);
                 }
                 XSTAMP(0);
@@ -477,11 +535,23 @@ __global__ __launch_bounds__(256, 1) void lstm_layer_x6_kernel(X6Args a) {
         }
         if constexpr (SKEW) {   // the last phase's verdict and cell update (its partial sums were sent before the last barrier)
             if (!dead && have_v && s_flag[vslot] != 0) redo(NBT - 1, T - 1, (pc & 1) ^ 1, (pc & 1) ^ 1);
-            if constexpr (OWNER) {
-                if (!dead) {
-                    cell1(role_, gP, (pc & 1) ^ 1, std::integral_constant<int, NBT - 1>{}, T - 1, true);
-                    cell2(std::integral_constant<int, NBT - 1>{}, gx_at(t_of(T - 1)), const_cast<unsigned char *>(hx_parity(T - 1)), out_main + (size_t)t_of(T - 1) * slab, raw_main + (size_t)t_of(T - 1) * slab, true);
+            if (!dead) {   // (the outputs of the last two tiles: one more barrier for the last one's)
+                if constexpr (OWNER) {
+                    cell1(role_, gP, (pc & 1) ^ 1, std::integral_constant<int, NBT - 1>{}, T - 1, true, (pc & 1) ^ 1);
+                    cell2(std::integral_constant<int, NBT - 1>{}, gx_at(t_of(T - 1)), const_cast<unsigned char *>(hx_parity(T - 1)), true);
                 }
+                if constexpr (ROLE == 2) emit(std::integral_constant<int, NBT - 2>{}, T - 1, pc & 1, true);
+                lds_barrier();
+                if constexpr (ROLE == 2) emit(std::integral_constant<int, NBT - 1>{}, T - 1, (pc & 1) ^ 1, true);
+            }
+        }
+        if constexpr (NBT == 2) {   // (the last phase's second barrier is behind its cell update)
+            if constexpr (ROLE == 2) { if (!dead) emit(std::integral_constant<int, 1>{}, T - 1, pc & 1, true); }
+        }
+        if constexpr (NBT == 1) {
+            if (!dead) {   // the last step's outputs
+                lds_barrier();
+                if constexpr (ROLE == 2) emit(std::integral_constant<int, 0>{}, T - 1, (T - 1) & 1, true);
             }
         }
     };
@@ -494,7 +564,7 @@ __global__ __launch_bounds__(256, 1) void lstm_layer_x6_kernel(X6Args a) {
 
 static size_t x6_smem(int H, int NBT) {
     const int UW = H / 16;
-    return (size_t)16 * UW * 4 * 2 + (size_t)3 * 3 * 16 * 8 * 2 + (size_t)NBT * (NBT == 1 ? 2 : 1) * 16 * UW * 16 + (size_t)2 * 3 * (H / 8) * 256 + (size_t)2 * 6 * 2 * 1024;
+    return (size_t)2 * 16 * UW * 4 * 2 + (size_t)3 * 3 * 16 * 8 * 2 + (size_t)NBT * (NBT == 1 ? 2 : 1) * 16 * UW * 16 + (size_t)2 * 3 * (H / 8) * 256 + (size_t)2 * 6 * 2 * 1024;
 }
 
 template <int H, int NBT, bool DBG = false>
@@ -533,7 +603,9 @@ int launch_lstm_layer_x6(const LstmStepArgs &s, const unsigned short *whh3, unsi
     a.force_mask = force_mask;
     const int nbt = (a.BGr + 15) / 16;
     a.dbg = stamps;
-    if (s.out_split.hi || s.gates_save || (!a.out && !a.out_raw) || !whh3) { set_error("persistent x6 lstm: fp32 outputs, inference only"); return MDD_ERR_ARG; }
+    a.planes = s.out_planes; a.plane_stride = s.out_planes_stride; a.rows = s.T * s.B;
+    if (a.planes && (double)a.rows * (2 * s.H) * 2 >= 4294967296.0) { set_error("persistent x6 lstm: a plane of %d x %d elements is beyond the 32-bit store offsets", a.rows, 2 * s.H); return MDD_ERR_ARG; }
+    if (s.out_split.hi || s.gates_save || (!a.out && !a.out_raw && !a.planes) || !whh3) { set_error("persistent x6 lstm: fp32 outputs, inference only"); return MDD_ERR_ARG; }
     if (nbt < 1 || nbt > 8) { set_error("persistent x6 lstm: B=%d needs %d row tiles per team (max 8)", s.B, nbt); return MDD_ERR_ARG; }
 #define X6_CASE(H_, N_) case N_: return launch_x6_pick<H_, N_>(a, st)
     if (s.H == 384) switch (nbt) { X6_CASE(384, 1); X6_CASE(384, 2); X6_CASE(384, 3); X6_CASE(384, 4); X6_CASE(384, 5); X6_CASE(384, 6); X6_CASE(384, 7); X6_CASE(384, 8); }

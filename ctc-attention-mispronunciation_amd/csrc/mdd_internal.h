@@ -112,6 +112,8 @@ struct LstmStepArgs {
     float *c_save = nullptr;       //                                          [T][B][2][H]    cell state
     const int *seqlen = nullptr;   // fused batches of different lengths: steps valid per batch row; the REVERSE direction holds h = c = 0 while t >= seqlen[b]
                                    // (it starts at seqlen[b]-1 with a zero state, as it would in the row's own batch); null = all T steps
+    unsigned short *out_planes = nullptr;   // f32x6 layer kernel only (the others ignore it): the values of `out` as the next projection's A operand, three
+    size_t out_planes_stride = 0;           // K-tile-major bf16 planes (launch_split3's layout, rows = T * B, K = 2H) out_planes_stride elements apart
 };
 // Enqueue all T steps of one bidirectional layer.
 int launch_lstm_layer(const LstmStepArgs &a, hipStream_t st);

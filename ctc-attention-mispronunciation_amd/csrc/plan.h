@@ -27,6 +27,9 @@
 //                        MFMA section early, so that the redo path runs
 //   MDD_X6_FORCE_REDO=n  f32x6 layer kernel: every n-th phase declared stale (n a     create    test_persistent_x6_lstm_redo_branch
 //                        power of two), so that the refetch branch runs
+//   MDD_X6_OUT=fp32      f32x6 layer kernel: fp32 layer outputs and a split3_kernel   create    tests/test_x6_plane_output.py
+//                        pass in front of the next projection, instead of the layer
+//                        kernel writing that projection's bf16 planes itself
 //
 // The last three were read at each launch (that is, at graph capture) before they joined this table; every test and tool above sets them
 // before it creates the model.  The training handle's persistent layer launches take none of them.
@@ -50,6 +53,7 @@ struct Switches {
     bool lstm_dbg = false;      // MDD_LSTM_DBG
     bool lstm_early = false;    // MDD_LSTM_EARLY
     int x6_redo_mask = -1;      // MDD_X6_FORCE_REDO=n: n - 1, or -1 (off)
+    bool x6_out_fp32 = false;   // MDD_X6_OUT=fp32
 };
 
 inline Switches read_switches() {
@@ -72,6 +76,7 @@ inline Switches read_switches() {
     e = getenv("MDD_X6_FORCE_REDO");
     const int n = e ? atoi(e) : 0;
     if (n > 0 && (n & (n - 1)) == 0) s.x6_redo_mask = n - 1;
+    s.x6_out_fp32 = is(getenv("MDD_X6_OUT"), "fp32");
     return s;
 }
 
@@ -105,6 +110,7 @@ struct ForwardPlan {
     bool gated;         // a persistent layer kernel runs: the forward is ordered behind the device's previous one
     size_t hx_floats;   // the persistent kernels' exchange buffer with the stamp area (0 when none runs)
     size_t stamps_at;   // where the stamps start in it
+    bool planes_out;    // BiLSTM layers 0 .. layers - 2 write the next projection's three bf16 planes themselves: no fp32 copy, no split3_kernel pass
 };
 
 inline ForwardPlan plan_forward(const mdd_config &c, int precision, const Switches &sw, const DeviceFit &fit, int B) {
@@ -129,6 +135,7 @@ inline ForwardPlan plan_forward(const mdd_config &c, int precision, const Switch
     else if (x3 && sw.lstm_x3) p.lstm = Lstm::StepX3;
     else p.lstm = packed ? Lstm::StepPacked : Lstm::Step;
     p.gated = persist;
+    p.planes_out = p.proj == Gemm::F32x6 && lx6 && !sw.x6_out_fp32;
     if (persist) {   // u64 granules of the 8-workgroup teams or the three bf16 planes of the 16-workgroup ones, in floats; 256 x 6 stamps behind
         const size_t granules = (size_t)2 * 32 * granule_bg(B) * H * 2, planes = lstm_x6_hx_bytes(H, B) / 4;
         p.stamps_at = lx6 ? planes : granules;

@@ -22,7 +22,7 @@ for B in [int(v) for v in (sys.argv[1:] or ['512'])]:
     print('B=%d (%d tiles per team): cycles per (tile, step), mean over workgroups / max workgroup' % (B, nbt))
     for i in [1, 2, 3, 4, 0]:
         print('  %-26s %8.0f  (%4.1f%%)   max %8.0f   min %8.0f' % (names[i], ph[:, i].mean() / 250 / nbt, 100 * ph[:, i].mean() / tot.mean(), ph[:, i].max() / 250 / nbt, ph[:, i].min() / 250 / nbt))
-    if PREC != 'f32':   # lstm_layer_x6_kernel: the reporting wave is (blockIdx / 8) % 4 -- wave (0,0) owner | (0,1) owner of the halved pair | (1,0) owner | (1,1) tag checker
+    if PREC != 'f32':   # lstm_layer_x6_kernel: the reporting wave is (blockIdx / 8) % 4 -- wave (0,0) owner | (0,1) owner of the halved pair | (1,0) owner | (1,1) tag checker, whose 'cell' column in the skewed schedule is its layer-output stores (emit)
         for wv in range(4):
             sel = ph[((np.arange(256) >> 3) & 3) == wv]
             print('    wave %d: ' % wv + '  '.join('%s %6.0f' % (names[i].split()[0], sel[:, i].mean() / 250 / nbt) for i in [1, 2, 3, 4, 0]))
