@@ -91,7 +91,8 @@ int launch_conv_fused(const float *x, const float *w0, const float *sc0, const f
                       const float *sh1, SplitPtr out, float *out_f32, int B, int T, int Traw, hipStream_t st);
 int launch_conv_fused3(const float *x, const float *w0, const float *sc0, const float *sh0, const unsigned short *w1_3, const float *sc1,
                        const float *sh1, unsigned short *out3, float *out_f32, int B, int T, int Traw, hipStream_t st,
-                       bool rowwise = false);   // f32x6 form: three K-tile-major planes out (rowwise: the row-at-a-time kernel, MDD_CONV=rowwise)
+                       bool rowwise = false,    // f32x6 form: three K-tile-major planes out (rowwise: the row-at-a-time kernel, MDD_CONV=rowwise)
+                       long long *stamps = nullptr);   // stamps (diagnostic, default kernel only): the stamped instantiation's phase cycle sums
 int init_conv_attributes();
 
 struct LstmStepArgs {

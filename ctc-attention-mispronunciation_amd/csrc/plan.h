@@ -20,7 +20,7 @@
 //   MDD_LSTM_X6=0        mode 2: the exact-fp32 layer kernel instead of the f32x6 one create    test_persistent_x6_lstm_tracks_exact_fp32_recurrence,
 //                                                                                               test_persistent_x6_lstm_full_length_and_poisoned_input, tools/lstm_kernel_choice.py
 //   MDD_LSTM_X6=force    mode 2: the f32x6 layer kernel wherever it can run           create    test_persistent_x6_lstm_tracks_exact_fp32_recurrence
-//   MDD_CONV=rowwise     mode 2: the row-at-a-time conv_fused_kernel<3>               create    tests/test_conv_multirow.py
+//   MDD_CONV=rowwise     mode 2: the row-at-a-time conv_fused_kernel<3>               create    tests/test_conv_multirow.py, tests/test_conv_pipeline.py
 //   MDD_LSTM_DBG         persistent layer launches with T' > 100 write phase stamps   create    test_persistent_lstm_stale_panel_redo_path, tools/lstm_stamps.py,
 //                        behind their exchange buffer (mdd_tap "lstm_dbg")                      tools/lstm_f32_stamps.py
 //   MDD_LSTM_EARLY       split-bf16 layer kernel: the next panel requested a whole    create    test_persistent_lstm_stale_panel_redo_path

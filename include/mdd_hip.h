@@ -281,6 +281,11 @@ int mdd_diag_gemm_ph8(int M, int N, int K, int reps, unsigned seed, unsigned *mi
 int mdd_diag_gemm(int mode, const float *A_dev, const float *W_dev, float *C_dev, int M, int N, int K, void *stream);
 /* mdd_diag_gemm_time: mean milliseconds of `reps` launches of one GEMM kernel on resident, pre-split pseudo-random operands. */
 int mdd_diag_gemm_time(int mode, int M, int N, int K, int reps, float *ms_out);
+/* mdd_diag_conv_time: mean milliseconds of `reps` launches of the f32x6 conv front end on pseudo-random features [B, T, 243] and weights.
+   which: 0 the default kernel, 1 the row-at-a-time kernel.  phases (nullable; 8 waves x 10 phases): mean cycles per workgroup of each
+   wave in each phase, from one launch of the stamped instantiation of the default kernel.  mismatch (nullable): the number of output
+   words in which the two kernels differ. */
+int mdd_diag_conv_time(int B, int T, int reps, int which, float *ms_out, double *phases, long long *mismatch);
 int mdd_diag_gates(const float *x_dev, float *sig_dev, float *tanh_dev, int64_t n, void *stream);
 
 #ifdef __cplusplus
