@@ -1,6 +1,7 @@
 """Thin object over the C ABI for callers that hold a state_dict of numpy arrays / tensors and want
 ``forward`` without constructing torch modules (bench.py, tests, the sharded driver).  The
 reference-shaped drop-in class is ``models.model_ctc.CTC_Model``; both call the same entry points."""
+import collections
 import ctypes as C
 
 import numpy as np
@@ -142,3 +143,41 @@ def ctc_loss(logp, targets, in_len, tgt_len, blank=0, want_grad=True):
                                            C.c_void_p(nll.data_ptr()), C.c_void_p(grad.data_ptr()) if want_grad else None,
                                            C.c_void_p(ws.data_ptr()), ws.numel() * 8, _lib.current_stream_ptr()))
     return nll, grad
+
+
+AlignResult = collections.namedtuple("AlignResult", "score status path seg seg_logp")
+ALIGN_OK, ALIGN_INFEASIBLE, ALIGN_BAD_TARGET = 0, 1, 2      # include/mdd_hip.h: mdd_align_status
+
+
+def ctc_align(logp, lens, ids, nids, blank=0, max_len=None, want_path=True, want_segments=True):
+    """CTC forced alignment on the GPU (mdd_ctc_align): the best path of ``ids`` through ``logp``.
+
+    logp [T,B,C] fp32 CUDA, lens [B], ids [B,stride] / nids [B] as ``decode_ids`` returns them (int32 CUDA tensors pass through with
+    no copy).  ``max_len`` bounds nids (default: ids.shape[1], so the call needs no sync).  Returns
+    ``AlignResult(score [B] f32, status [B] i32, path [B,T] i32 | None, seg [B,stride,2] i32 | None, seg_logp [B,stride] f32 | None)``:
+    path[b,t] is the position of the label frame t emits or -1, seg[b,i] the first and one-past-last frame of label i, seg_logp[b,i]
+    the sum of its frames' log-posteriors.  Nothing synchronises."""
+    assert logp.is_cuda and logp.dtype == torch.float32
+    logp = logp.contiguous()
+    T, B, Cn = logp.shape
+    dev = logp.device
+    lens = torch.as_tensor(lens).to(dev, torch.int32).contiguous()
+    ids = torch.as_tensor(ids).to(dev, torch.int32).contiguous()
+    nids = torch.as_tensor(nids).to(dev, torch.int32).contiguous()
+    if ids.dim() != 2 or ids.shape[0] != B or lens.shape != (B,) or nids.shape != (B,):
+        raise ValueError("ctc_align: lens [B], ids [B, stride], nids [B]")
+    stride = ids.shape[1]
+    Lmax = stride if max_len is None else int(max_len)
+    score = torch.empty((B,), dtype=torch.float32, device=dev)
+    status = torch.empty((B,), dtype=torch.int32, device=dev)
+    path = torch.empty((B, T), dtype=torch.int32, device=dev) if want_path else None
+    seg = torch.empty((B, stride, 2), dtype=torch.int32, device=dev) if want_segments else None
+    seg_logp = torch.empty((B, stride), dtype=torch.float32, device=dev) if want_segments else None
+    nws = _lib.lib().mdd_ctc_align_workspace_bytes(T, B, Cn, max(Lmax, 0))
+    ws = torch.empty((max(nws, 16) + 7) // 8, dtype=torch.float64, device=dev)      # torch's caching allocator, as ctc_loss
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().mdd_ctc_align(ptr(logp), T, B, Cn, ptr(lens), C.c_void_p(ids.data_ptr() if stride else ws.data_ptr()), stride,
+                                            ptr(nids), Lmax, blank, ptr(score), ptr(status), ptr(path), ptr(seg), ptr(seg_logp),
+                                            ptr(ws), ws.numel() * 8, _lib.current_stream_ptr()))
+    return AlignResult(score, status, path, seg, seg_logp)

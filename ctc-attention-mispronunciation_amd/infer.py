@@ -2,7 +2,7 @@
 (AA/infer.py:435-598, ``main``), run as
 
     python -m ctc_attention_mispronunciation_amd.infer --conf CONF --wav_transcript_path DIR [-p cmudict] [-f cmu]
-        [--cmvn PATH] [--cmudict PATH] [--precision f32x6|f32|bf16x3] [--decode_seq PATH]
+        [--cmvn PATH] [--cmudict PATH] [--precision f32x6|f32|bf16x3] [--decode_seq PATH] [--timestamps]
 
 The conf YAML is read as ``infer_init`` reads it (AA/infer.py:211-261): the checkpoint
 ``checkpoint_dir/exp_name/ctc_best_model.pkl``, ``vocab_file``, ``decode_type``, ``beam_width``, ``lm_path``, ``lm_alpha``,
@@ -49,6 +49,9 @@ def parse_args(argv=None):
     ap.add_argument("--cmudict", default=None, help="CMU pronouncing dictionary (default: dict/cmudict.dict or $MDD_CMUDICT)")
     ap.add_argument("--precision", default=None, choices=("f32x6", "f32", "bf16x3"), help="arithmetic mode of the forward")
     ap.add_argument("--decode_seq", default=None, help="write '<utt> <decoded phones>' lines here")
+    ap.add_argument("--timestamps", action="store_true",
+                    help="add a 'time   :' line (start-end seconds and confidence per decoded phoneme) and a 'gop    :' line (mean "
+                         "log-posterior per canonical phoneme) to each block; times are nominal frame starts")
     return ap.parse_args(argv)
 
 
@@ -160,7 +163,7 @@ def main(argv=None):
                             n_downsample=getattr(opts, "n_downsample", 2))
     device = torch.device("cuda", torch.cuda.current_device())
     c1, c2, c3 = infer(phonetic, word_dict, loader, device, model, decoder, vocab, transcripts, False,
-                       decode_seq_path=args.decode_seq)
+                       decode_seq_path=args.decode_seq, timestamps=args.timestamps)
     print(c1, c2, c3)
     end = time.time()
     total = max(total_wav_time, 1e-9)

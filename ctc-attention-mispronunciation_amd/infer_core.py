@@ -86,8 +86,79 @@ def diagnose(decoded, canonical, decoder, to_display=None):
                 correct=ok, del_sub=ds, score=score, printed=print_aligned_string(ph_dec, ph_can, path))
 
 
+def _tokens(phones):
+    return phones.split() if isinstance(phones, str) else [p for p in phones if p]
+
+
+def diagnose_timed(decoded_phones, spans, canonical_phones, canon_spans, decoder, seconds_per_frame, to_display=None):
+    """``diagnose`` plus timing and goodness of pronunciation.  decoded_phones / canonical_phones: the phoneme strings ``diagnose``
+    takes (or token lists); spans / canon_spans: one ``(start_frame, end_frame, mean_logp)`` per token of each, from the forced
+    alignment of the decoded and of the canonical ids to the posteriors (``decode_timed`` / ``ctcDecoder.timed_spans``), or ``None``
+    when that alignment is infeasible.  Returns ``diagnose``'s dict (computed by ``diagnose`` itself) with two more keys, both
+    index-aligned with ``path``:
+      times  (start_s, end_s, confidence = exp(mean_logp)) of the decoded phoneme on '-', 'S' and 'I' rows, None on 'D' rows (and on
+             every row when ``spans`` is None).  Times are nominal frame starts, frame index x seconds_per_frame: the offset of the
+             analysis window's centre is ignored.
+      gop    the mean log-posterior of the canonical phoneme over its segment of the canonical alignment on '-', 'S' and 'D' rows,
+             None on 'I' rows (and on every row when ``canon_spans`` is None).
+    The spans follow their tokens through the 'sil' strip, the 'err' removal and the leading-insertion drops of ``diagnose`` /
+    ``align_canonical_decoded``; a count that does not fit raises ValueError rather than mis-assigning a span."""
+    dec, can = _tokens(decoded_phones), _tokens(canonical_phones)
+    if spans is not None and len(spans) != len(dec):
+        raise ValueError("diagnose_timed: %d spans for %d decoded phonemes" % (len(spans), len(dec)))
+    if canon_spans is not None and len(canon_spans) != len(can):
+        raise ValueError("diagnose_timed: %d spans for %d canonical phonemes" % (len(canon_spans), len(can)))
+    d = diagnose(" ".join(dec), " ".join(can), decoder, to_display)
+    # the same strip as diagnose, with each token's index carried along ('err' is removed as a substring, as diagnose removes it)
+    dec_kept = [i for i, p in enumerate(dec) if p != "sil" and p.replace("err", "")]
+    can_kept = [i for i, p in enumerate(can) if p != "sil"]
+    hyp = " ".join(dec[i].replace("err", "") for i in dec_kept)
+    _, full = decoder.wer(hyp, " ".join(can[i] for i in can_kept))
+    dropped = len(full) - len(d["path"])
+    if dropped < 0 or list(full[dropped:]) != list(d["path"]) or any(op != "I" for op in full[:dropped]) \
+            or sum(op != "D" for op in full) != len(dec_kept) or sum(op != "I" for op in full) != len(can_kept):
+        raise ValueError("diagnose_timed: the alignment path does not fit the phoneme counts")
+    times, gop = [], []
+    di, ci = dropped, 0                      # the dropped leading rows are insertions: decoded tokens only
+    for op in d["path"]:
+        t = g = None
+        if op != "D":
+            if spans is not None:
+                s, e, m = spans[dec_kept[di]]
+                t = (s * seconds_per_frame, e * seconds_per_frame, math.exp(m))
+            di += 1
+        if op != "I":
+            if canon_spans is not None:
+                g = canon_spans[can_kept[ci]][2]
+            ci += 1
+        times.append(t); gop.append(g)
+    if di != len(dec_kept) or ci != len(can_kept):
+        raise ValueError("diagnose_timed: the alignment path does not fit the phoneme counts")
+    return dict(d, times=times, gop=gop)
+
+
+def timed_lines(d):
+    """The two extra lines of a printed block: ``time   : ph[start-end confidence] ...`` over the decoded row without its 'D'
+    placeholders, ``gop    : ph[mean log-posterior] ...`` over the canonical row without its 'I' placeholders ('-' where unknown)."""
+    tl = ["%s[%s]" % (p, "-" if t is None else "%.2f-%.2f %.2f" % t) for p, t, op in zip(d["decoded"], d["times"], d["path"]) if op != "D"]
+    gl = ["%s[%s]" % (p, "-" if g is None else "%.2f" % g) for p, g, op in zip(d["canonical"], d["gop"], d["path"]) if op != "I"]
+    return "time   : " + " ".join(tl), "gop    : " + " ".join(gl)
+
+
+def seconds_per_frame(test_loader, cnn_time_stride):
+    """Seconds between posterior frames: the fbank's frame shift x the loader's ``n_skip_frame`` x the CNN's time stride (0.04 s in
+    the reference configuration)."""
+    from .utils.fbank import FRAME_SHIFT_SAMPLES, SAMPLE_RATE
+    skip = getattr(test_loader, "n_skip_frame", None)
+    if skip is None:
+        skip = getattr(getattr(test_loader, "dataset", None), "n_skip_frame", None)
+    if skip is None:
+        raise ValueError("timestamps need the loader's n_skip_frame (WavBatchLoader / SpeechDataLoader have it)")
+    return FRAME_SHIFT_SAMPLES / float(SAMPLE_RATE) * int(skip) * int(cnn_time_stride)
+
+
 def infer(phonetic, word_dict, test_loader, device, model, decoder, vocab, test_transcipt_dict, use_ipa, out=None,
-          decode_seq_path=None):
+          decode_seq_path=None, timestamps=False):
     """AA/infer.py:282-372.  Per batch ``(inputs, input_sizes, _, _, trans, trans_sizes, utt_list)``: ``model(inputs, trans)``,
     frame counts ``(input_sizes * T').long()``, ``decoder.decode``, then per utterance the 'sil' strip, 'err' removal, ``wer``,
     alignment, fault lists and score (``diagnose``), printed as the reference's 13-line block to ``out`` (stdout by default).
@@ -96,7 +167,11 @@ def infer(phonetic, word_dict, test_loader, device, model, decoder, vocab, test_
     Offline substitutions: line 3 prints ``word_dict[utt]['ipa']`` as given; line 4 is ``phonetic.api_word_translation(word)``
     when ``phonetic`` has it (the reference asks ECDICT), else empty.  ``use_ipa`` needs ``phonetic.cmu_to_ipa_wiki``.  The
     reference always writes '<utt> <decoded phones>' lines to decode_seq.txt in the input folder and main() deletes the file;
-    here they are written only when ``decode_seq_path`` is given."""
+    here they are written only when ``decode_seq_path`` is given.
+
+    ``timestamps=True`` (no reference counterpart) adds two lines to each block between ``score  :`` and the closing empty line --
+    ``time   :`` and ``gop    :`` (``diagnose_timed`` / ``timed_lines``) -- from two forced alignments per batch on the GPU: of the
+    decoder's own ids and of the canonical ids.  Times are nominal frame starts (``seconds_per_frame``); nothing else changes."""
     out = sys.stdout if out is None else out
     to_display = phonetic.cmu_to_ipa_wiki if use_ipa else None
     translate = getattr(phonetic, "api_word_translation", None)
@@ -110,12 +185,22 @@ def infer(phonetic, word_dict, test_loader, device, model, decoder, vocab, test_
                 trans = trans.to(device)
                 probs = model(inputs, trans)
                 lens = frames_from_fraction(input_sizes, probs.size(0))
-                decoded = decoder.decode(probs, lens.numpy().tolist())
+                if timestamps:
+                    from .utils.ctcDecoder import timed_spans
+                    frame_lens = lens.numpy().tolist()
+                    decoded, spans = decoder.decode_timed(probs, frame_lens)
+                    canon_spans = timed_spans(probs, frame_lens, trans, trans_sizes, decoder.blank_index)
+                    spf = seconds_per_frame(test_loader, inputs.size(1) // probs.size(0))
+                else:
+                    decoded = decoder.decode(probs, lens.numpy().tolist())
                 trans, trans_sizes = trans.cpu().numpy(), trans_sizes.numpy()
                 for x in range(len(decoded)):
                     canonical = " ".join(vocab.index2word[num] for num in trans[x][:trans_sizes[x]])
                     utterance = test_transcipt_dict[utt_list[x]]
-                    d = diagnose(decoded[x], canonical, decoder, to_display)
+                    if timestamps:
+                        d = diagnose_timed(decoded[x], spans[x], canonical, canon_spans[x], decoder, spf, to_display)
+                    else:
+                        d = diagnose(decoded[x], canonical, decoder, to_display)
                     tmp1, tmp2, tmp3 = d["printed"]
                     block = ["id     : " + utt_list[x], utt_list[x] + ": " + utterance, str(word_dict[utt_list[x]]["ipa"]),
                              str(translate(utterance)) if translate is not None else "", tmp2, tmp3, tmp1,
@@ -123,6 +208,8 @@ def infer(phonetic, word_dict, test_loader, device, model, decoder, vocab, test_
                              "del err: " + " ".join(d["deletions"]),
                              "Comp.  : " + str(d["correct"]) + "/" + str(d["correct"] + d["del_sub"]),
                              "score  : " + str(d["score"]), ""]
+                    if timestamps:
+                        block[-1:-1] = timed_lines(d)
                     out.write("\n".join(block) + "\n")
                     total_correct_cnt += d["correct"]
                     total_cnt += d["correct"] + d["del_sub"]

@@ -146,6 +146,25 @@ def _lens_tensor(frame_seq_len, B, T, dev):
     return torch.tensor([int(v) for v in frame_seq_len], dtype=torch.int32, device=dev)
 
 
+def timed_spans(prob_tensor, frame_seq_len, ids, nids, blank=0):
+    """Forced alignment of ``ids`` / ``nids`` ([B, stride] / [B], as ``decode_ids`` returns them) to the posteriors (mdd_ctc_align):
+    per utterance a list of ``(start_frame, end_frame, mean_logp)``, one per id -- the first frame, one past the last frame and the mean
+    log-posterior of the id over its frames -- or ``None`` when the ids have no feasible alignment (or are no valid targets)."""
+    from ..hip_model import ctc_align
+    lp = _device_posteriors(prob_tensor)
+    T, B, _ = lp.shape
+    lens = _lens_tensor(frame_seq_len, B, T, lp.device)
+    r = ctc_align(lp, lens, ids, nids, blank=blank, want_path=False)
+    status, seg, seg_logp, n = r.status.cpu().numpy(), r.seg.cpu().numpy(), r.seg_logp.cpu().numpy(), torch.as_tensor(nids).cpu().numpy()
+    out = []
+    for b in range(B):
+        if status[b] != 0:
+            out.append(None)
+            continue
+        out.append([(int(seg[b, i, 0]), int(seg[b, i, 1]), float(seg_logp[b, i]) / int(seg[b, i, 1] - seg[b, i, 0])) for i in range(int(n[b]))])
+    return out
+
+
 class GreedyDecoder(Decoder):
     """argmax per frame, collapse repeats, drop blanks (ctcDecoder.py:186-200)."""
 
@@ -162,7 +181,16 @@ class GreedyDecoder(Decoder):
         return ids, nids
 
     def decode(self, prob_tensor, frame_seq_len):
-        ids, nids = self.decode_ids(prob_tensor, frame_seq_len)
+        return self._strings(*self.decode_ids(prob_tensor, frame_seq_len))
+
+    def decode_timed(self, prob_tensor, frame_seq_len):
+        """``decode`` plus, per utterance, the ``(start_frame, end_frame, mean_logp)`` of every decoded id (``timed_spans`` on the
+        decoder's own ids: the alignment of the greedy ids is the per-frame argmax path)."""
+        lp = _device_posteriors(prob_tensor)
+        ids, nids = self.decode_ids(lp, frame_seq_len)
+        return self._strings(ids, nids), timed_spans(lp, frame_seq_len, ids, nids, self.blank_index)
+
+    def _strings(self, ids, nids):
         ids, nids = ids.cpu().numpy(), nids.cpu().numpy()
         out = []
         for b in range(ids.shape[0]):
@@ -210,6 +238,18 @@ class BeamDecoder(Decoder):
 
     def decode(self, prob_tensor, frame_seq_len=None):
         ids, nids, status, _ = self.decode_ids(prob_tensor, frame_seq_len)
+        return self._strings(ids, nids, status)
+
+    def decode_timed(self, prob_tensor, frame_seq_len=None):
+        """``decode`` (same strings, same exceptions first) plus, per utterance, the ``(start_frame, end_frame, mean_logp)`` of every
+        decoded id, or ``None`` for an utterance whose winner has no feasible alignment: the beam skips near-certain blank frames and
+        merges repeats by its own rule, so its winner need not be a CTC path of the posteriors."""
+        lp = _device_posteriors(prob_tensor)
+        ids, nids, status, _ = self.decode_ids(lp, frame_seq_len)
+        strings = self._strings(ids, nids, status)
+        return strings, timed_spans(lp, frame_seq_len, ids, nids, self.blank_index)
+
+    def _strings(self, ids, nids, status):
         ids, nids, status = ids.cpu().numpy(), nids.cpu().numpy(), status.cpu().numpy()
         bad = np.nonzero(status)[0]
         if len(bad):   # the reference stops at the first utterance that raises

@@ -18,6 +18,7 @@ import torch
 from .. import _lib
 
 SAMPLE_RATE = 16000
+FRAME_SHIFT_SAMPLES = 160        # Kaldi's 10 ms frame shift at 16 kHz (AA/conf/fbank.conf leaves the default)
 NUM_COLS = 81
 
 

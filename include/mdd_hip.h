@@ -174,6 +174,34 @@ int mdd_ctc_loss(const float *logp_dev, int32_t T, int32_t B, int32_t C, const i
                  const int64_t *in_len_dev, const int64_t *tgt_len_dev, int32_t blank, float *nll_dev,
                  float *grad_dev, void *workspace_dev, int64_t workspace_bytes, void *stream);
 
+/* ---- CTC forced alignment (no reference counterpart): the best (max-product) path of ids through the posteriors, for phoneme
+ * timestamps (align the decoded ids) and goodness-of-pronunciation scores (align the canonical ids).
+ * logp_dev [T,B,C], len_dev [B] (clamped to [0,T]), ids_dev [B,ids_stride] / nids_dev [B] int32: exactly what mdd_greedy / mdd_beam
+ * write, so a decode chains into an alignment with no conversion; Lmax (0 <= Lmax <= ids_stride) is the host's bound on nids that
+ * sizes the launch.  Outputs:
+ *   score_dev [B]   fp32 log-probability of the best path;  status_dev [B]  mdd_align_status
+ *   path_dev [B,T]  (nullable) written whole: the label position i in [0,nids[b]) a frame emits, -1 for a blank frame and for t >= len
+ *   seg_dev [B,ids_stride,2] + seg_logp_dev [B,ids_stride]  (nullable, only together) every position i < Lmax written: first frame and
+ *                   one past the last frame of label i (its frames are contiguous) and the fp32 sum of logp[t,b,ids[i]] over them in
+ *                   ascending frame order; -1, -1, 0 for nids[b] <= i < Lmax
+ * MDD_ALIGN_INFEASIBLE: no path (len < nids + number of adjacent equal labels, or every path scores -inf; len = 0 with nids > 0):
+ *   score -inf, path -1, seg -1,-1, seg_logp 0.  MDD_ALIGN_BAD_TARGET: a label outside [0,C) or equal to blank, or nids[b] outside
+ *   [0,Lmax]: score NaN, the rest as for infeasible; other utterances are unaffected.  nids = 0 is the all-blank path (score 0 at len 0).
+ * Arithmetic: fp32, one addition per state and step; on equal values staying wins over the move from s-1, which wins over the skip
+ *   from s-2; the path ends in the closing blank only if that is strictly better than the last label (csrc/ctc_align.hip):
+ *   a float32 loop with those rules gives the same bits.  NaN inputs are unspecified.
+ * workspace_dev: caller-owned scratch of at least mdd_ctc_align_workspace_bytes(T,B,C,Lmax) bytes (16-byte aligned; 0 when the shapes
+ *   fit the wave form: Lmax <= 255, C <= 256, LDS budget), NULL = the library allocates stream-ordered for the call.  Nothing
+ *   synchronises.  Env MDD_CTC_ALIGN=generic (read per call) forces the general kernel; both forms give the same bits.
+ * Bad host arguments (a required pointer NULL, T/B/C <= 0, blank outside [0,C), Lmax < 0 or > ids_stride, one of seg_dev /
+ *   seg_logp_dev without the other, a caller workspace that is too small) return MDD_ERR_ARG before any device work. */
+enum mdd_align_status { MDD_ALIGN_OK = 0, MDD_ALIGN_INFEASIBLE = 1, MDD_ALIGN_BAD_TARGET = 2 };
+int64_t mdd_ctc_align_workspace_bytes(int32_t T, int32_t B, int32_t C, int32_t Lmax);
+int mdd_ctc_align(const float *logp_dev, int32_t T, int32_t B, int32_t C, const int32_t *len_dev,
+                  const int32_t *ids_dev, int32_t ids_stride, const int32_t *nids_dev, int32_t Lmax, int32_t blank,
+                  float *score_dev, int32_t *status_dev, int32_t *path_dev, int32_t *seg_dev, float *seg_logp_dev,
+                  void *workspace_dev, int64_t workspace_bytes, void *stream);
+
 /* ---- A10: Decoder.wer core = _edit_distance + printChanges (AA/utils/ctcDecoder.py:118-184), host.
  * a = hypothesis tokens, b = canonical tokens; ops (capacity >= na+nb): 0 '-', 1 'S', 2 'I', 3 'D'.
  * Either side empty -> MDD_ERR_EMPTY (reference: TypeError). */
