@@ -146,7 +146,9 @@ int mdd_enable_taps(mdd_model *m, int32_t on);
 int mdd_sync(mdd_model *m, void *stream);
 
 /* ---- A8: GreedyDecoder.decode (AA/utils/ctcDecoder.py:188-200, 80-92)
- * logp_dev [T,B,C], len_dev [B] -> ids_dev [B,T] (collapsed, blanks removed), nids_dev [B]. */
+ * logp_dev [T,B,C], len_dev [B] (clamped to [0,T]) -> ids_dev [B,T] (collapsed, blanks removed; only the first nids[b] entries of a
+ * row are written), nids_dev [B].  Any C >= 1, 0 <= blank < C; ties go to the lowest class, an all -inf row to class 0.
+ * Limit: T <= 38400 (one int of LDS per frame, 150 KB); a longer T returns MDD_ERR_ARG. */
 int mdd_greedy(const float *logp_dev, int32_t T, int32_t B, int32_t C, const int32_t *len_dev, int32_t blank,
                int32_t *ids_dev, int32_t *nids_dev, void *stream);
 
@@ -154,9 +156,21 @@ int mdd_greedy(const float *logp_dev, int32_t T, int32_t B, int32_t C, const int
  * AA/utils/BeamSearch.py:73-153): CTC prefix beam search, float64 scores.
  * lm_dev: dense (C+1)x(C+1) table of natural-log bigram scores T[prev][next] as
  * LanguageModel.get_bi_prob returns them (prev == C: sentence start, next == C: sentence end),
- * NaN where the reference would raise KeyError.  beam <= 64, C <= 256.
- * Outputs: ids_dev [B,T], nids_dev [B], status_dev [B] (mdd_beam_status), score_dev [B] or NULL
- * (length-normalised score of the winner). */
+ * NaN where the reference would raise KeyError.  1 <= beam <= 64, 2 <= C <= 256, 0 <= blank < C; len_dev is clamped to [0,T].
+ * Outputs: ids_dev [B,T] (only the first nids[b] entries of a row are written), nids_dev [B], status_dev [B] (mdd_beam_status),
+ * score_dev [B] or NULL (length-normalised score of the winner; NaN for an utterance whose status is an error).
+ * Kernels and limits.  With Tcap = (T + 4) & ~3 (a prefix row: one byte per id, whole words):
+ *   - beam <= 16, C <= 64 and beam*C <= 1024: the single-wave kernel (beam_fast_kernel), up to four utterances per workgroup once
+ *     B > 64.  Needs  lm + wave <= 160 KB  of LDS, each term rounded up to 16 bytes, with lm = 8 (C+1)^2 and
+ *     wave = 24 S + 33 Tcap + 2688, S = 512 slots if beam*C <= 512, else 1024:  33 Tcap <= 161152 - 24 S - 8 (C+1)^2.
+ *   - every other shape: the generic kernel (beam_kernel), one utterance per workgroup.  Needs
+ *     base = 20 beam C + (2 beam + 1) Tcap <= 140 KB;  the LM table is held in LDS while base + 8 (C+1)^2 <= 96 KB and read from
+ *     global memory beyond that.
+ *   The generic bound is checked for every shape, so the single-wave kernel obeys both.  For C = 45: T <= 3995 at beam 10,
+ *   T <= 663 at beam 64.  A shape over a limit returns MDD_ERR_ARG (mdd_last_error names the LDS need) and writes nothing.
+ * Environment, read at every call (diagnostics and tests): MDD_BEAM_GENERIC (any value) sends every shape to the generic kernel;
+ * MDD_BEAM_W = w sets the utterances per workgroup of the single-wave kernel when B > 64 and 1 <= w <= W, W = min(4, what the LDS
+ * holds); any other value is ignored, and so is the variable when B <= 64 (one utterance per workgroup). */
 int mdd_beam(const float *logp_dev, int32_t T, int32_t B, int32_t C, const int32_t *len_dev, int32_t beam,
              int32_t blank, const double *lm_dev, double lm_alpha, int32_t *ids_dev, int32_t *nids_dev,
              int32_t *status_dev, double *score_dev, void *stream);
