@@ -769,10 +769,9 @@ int launch_zero_fill(void *p, size_t n, hipStream_t st) {
 
 template <int H, int NBT, int RTW, bool TRAIN = false>
 static int launch_granule_t(PersistArgs a, hipStream_t st) {
-    const size_t smem = (size_t)16 * (H / 8) * 12 + (size_t)NBT * 2 * 16 * (H / 8) * 16 + (size_t)2 * 16 * H * 4;   // tiles (2 bf16 planes, fp32, tagged words) + gx slabs (2 parities) + two panel buffers
     if (int rc = launch_zero_fill(a.sync, 32 * sizeof(unsigned int), st)) return rc;
-    if (int rc = launch_zero_fill(a.hx, (size_t)2 * 32 * NBT * 16 * H * 4, st)) return rc;   // tags must start at 0 on every launch
-    hipLaunchKernelGGL((lstm_layer_granule_kernel<H, NBT, RTW, TRAIN>), dim3(kPersistGrid), dim3(256), smem, st, a);
+    if (int rc = launch_zero_fill(a.hx, team8_hx_live_bytes(H, NBT * 16), st)) return rc;   // tags must start at 0 on every launch
+    hipLaunchKernelGGL((lstm_layer_granule_kernel<H, NBT, RTW, TRAIN>), dim3(kPersistGrid), dim3(256), team8_lds_bytes(H, NBT), st, a);
     MDD_LAUNCH_CHECK();
     return MDD_OK;
 }
@@ -1064,14 +1063,8 @@ int init_granule_attributes() {
 // with n_cu compute units can hold that grid (>= 1 workgroup of the largest configuration per CU, and enough CUs); when it
 // cannot, the library uses the per-step kernels instead of risking a grid that waits for workgroups that never start.
 int persistent_grid_fits(int n_cu) {
-    if (n_cu < kPersistGrid) return 0;
-    int per_cu = 0;
-    const size_t smem384 = (size_t)16 * (384 / 8) * 12 + (size_t)4 * 2 * 16 * (384 / 8) * 16 + (size_t)2 * 16 * 384 * 4;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)lstm_layer_granule_kernel<384, 4, 3>, 256, smem384) != hipSuccess) return 0;
-    if (per_cu < 1) return 0;
-    const size_t smem256 = (size_t)16 * (256 / 8) * 12 + (size_t)4 * 2 * 16 * (256 / 8) * 16 + (size_t)2 * 16 * 256 * 4;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)lstm_layer_granule_kernel<256, 4, 2>, 256, smem256) != hipSuccess) return 0;
-    return per_cu >= 1 ? 1 : 0;
+    return persist_grid_fits(n_cu, (const void *)lstm_layer_granule_kernel<384, 4, 3>, team8_lds_bytes(384, 4)) &&
+           persist_grid_fits(n_cu, (const void *)lstm_layer_granule_kernel<256, 4, 2>, team8_lds_bytes(256, 4));
 }
 
 int launch_lstm_layer_train(const LstmStepArgs &a, hipStream_t st) {

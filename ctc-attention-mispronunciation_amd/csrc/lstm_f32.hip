@@ -306,10 +306,9 @@ __global__ __launch_bounds__(256, 1) void lstm_layer_f32_kernel(PersistArgs a) {
 
 template <int H, int NBT, bool DBG = false>
 static int launch_f32_t(PersistArgs a, hipStream_t st) {
-    const size_t smem = (size_t)16 * (H / 8) * 12 + (size_t)NBT * 2 * 16 * (H / 8) * 16 + (size_t)2 * 16 * H * 4;   // tiles + gx slabs (2 parities) + two panel buffers
     if (int rc = launch_zero_fill(a.sync, 32 * sizeof(unsigned int), st)) return rc;
-    if (int rc = launch_zero_fill(a.hx, (size_t)2 * 32 * NBT * 16 * H * 4, st)) return rc;   // tags must start at 0 on every launch (by a kernel: lstm.hip)
-    hipLaunchKernelGGL((lstm_layer_f32_kernel<H, NBT, DBG>), dim3(kPersistGrid), dim3(256), smem, st, a);
+    if (int rc = launch_zero_fill(a.hx, team8_hx_live_bytes(H, NBT * 16), st)) return rc;   // tags must start at 0 on every launch (by a kernel: lstm.hip)
+    hipLaunchKernelGGL((lstm_layer_f32_kernel<H, NBT, DBG>), dim3(kPersistGrid), dim3(256), team8_lds_bytes(H, NBT), st, a);
     MDD_LAUNCH_CHECK();
     return MDD_OK;
 }
@@ -344,11 +343,7 @@ int init_lstm_f32_attributes() {
 }
 
 int persistent_f32_grid_fits(int n_cu) {
-    if (n_cu < kPersistGrid) return 0;
-    int per_cu = 0;
-    const size_t smem384 = (size_t)16 * (384 / 8) * 12 + (size_t)4 * 2 * 16 * (384 / 8) * 16 + (size_t)2 * 16 * 384 * 4;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)lstm_layer_f32_kernel<384, 4>, 256, smem384) != hipSuccess) return 0;
-    return per_cu >= 1 ? 1 : 0;
+    return persist_grid_fits(n_cu, (const void *)lstm_layer_f32_kernel<384, 4>, team8_lds_bytes(384, 4));
 }
 
 __global__ void diag_gates_kernel(const float *x, float *sg, float *th, long long n) {

@@ -107,4 +107,13 @@ __device__ __forceinline__ void lds_dma16(const void *g, void *l) {
 
 static constexpr int kPersistGrid = 256;   // see persistent_grid_fits()
 
+// Dynamic LDS of a workgroup of the 8-workgroup teams (lstm_layer_granule_kernel, lstm_layer_f32_kernel) at NBT row tiles per team:
+// the h tiles (2 bf16 planes, fp32, tagged words) + the gx slabs of NBT tiles (2 parities) + two panel buffers.
+constexpr size_t team8_lds_bytes(int H, int NBT) { return (size_t)16 * (H / 8) * 12 + (size_t)NBT * 2 * 16 * (H / 8) * 16 + (size_t)2 * 16 * H * 4; }
+// Whether a device of n_cu compute units holds the whole grid of a persistent layer kernel: a 256-thread workgroup with `lds` bytes on every CU
+inline bool persist_grid_fits(int n_cu, const void *kernel, size_t lds) {
+    int per_cu = 0;
+    return n_cu >= kPersistGrid && hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, lds) == hipSuccess && per_cu >= 1;
+}
+
 }  // namespace mdd

@@ -570,7 +570,7 @@ static size_t x6_smem(int H, int NBT) {
 template <int H, int NBT, bool DBG = false>
 static int launch_x6_t(const X6Args &a, hipStream_t st) {
     if (int rc = launch_zero_fill(a.sync, 32 * sizeof(unsigned int), st)) return rc;
-    if (int rc = launch_zero_fill(a.hx, (size_t)2 * 16 * NBT * 3 * (H / 8) * 256, st)) return rc;   // tags must start at 0 on every launch (by a kernel: lstm.hip)
+    if (int rc = launch_zero_fill(a.hx, lstm_x6_hx_bytes(H, a.B), st)) return rc;   // tags must start at 0 on every launch (by a kernel: lstm.hip)
     hipLaunchKernelGGL((lstm_layer_x6_kernel<H, NBT, DBG>), dim3(kPersistGrid), dim3(256), x6_smem(H, NBT), st, a);
     MDD_LAUNCH_CHECK();
     return MDD_OK;
@@ -633,11 +633,8 @@ int init_lstm_x6_attributes() {
 }
 
 int persistent_x6_grid_fits(int n_cu) {
-    if (n_cu < kPersistGrid) return 0;
-    int per_cu = 0;
     constexpr int N = x6_built<384, 8>() ? 8 : 4;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)lstm_layer_x6_kernel<384, N>, 256, x6_smem(384, N)) != hipSuccess) return 0;
-    return per_cu >= 1 ? 1 : 0;
+    return persist_grid_fits(n_cu, (const void *)lstm_layer_x6_kernel<384, N>, x6_smem(384, N));
 }
 
 }  // namespace mdd

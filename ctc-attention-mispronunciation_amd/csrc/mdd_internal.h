@@ -100,11 +100,11 @@ struct LstmStepArgs {
     const float *whh;    // [2][4H][H], rows permuted the same way
     float *hbuf;         // [2 parity][2 dir][B][H]
     float *cbuf;         // [2 dir][B][H]
-    float *out;          // [T][B][2H] layer output with oscale/oshift applied (may equal out_raw; nullable)
-    SplitPtr out_split;  // same values as split-bf16 planes (nullable): the next GEMM's A operand
-    float *out_raw;      // [T][B][2H] raw h (nullable)
-    const float *oscale; // [2H] (nullable -> identity)
-    const float *oshift;
+    float *out = nullptr;          // [T][B][2H] layer output with oscale/oshift applied (may equal out_raw; nullable)
+    SplitPtr out_split = {nullptr, nullptr};   // same values as split-bf16 planes (nullable): the next GEMM's A operand
+    float *out_raw = nullptr;      // [T][B][2H] raw h (nullable)
+    const float *oscale = nullptr; // [2H] (nullable -> identity)
+    const float *oshift = nullptr;
     int T, B, H;
     SplitPtr whh_split;  // row-major Whh' [2][4H][H] as hi/lo planes (split-bf16 step only)
     unsigned short *hsplit;  // h exchange of the split-bf16 step: [2 parity][hi|lo][2 dir][B][H]; null selects the fp32 steps
@@ -132,7 +132,7 @@ int init_lstm_attributes();
 // One launch for the whole layer (256 co-resident workgroups in 8-workgroup teams, data-tagged hand-off; see lstm.hip).
 int init_granule_attributes();
 int persistent_grid_fits(int n_cu);   // 1 when all 256 workgroups of a persistent layer launch can be resident at once
-// data-tagged variant (8-workgroup teams, no counter): hx = 2*32*granule_bg(B)*H u64 granules (+ stamps), sync: 32 uints.
+// data-tagged variant (8-workgroup teams, no counter): hx = team8_hx_alloc_floats(H, B) floats (+ stamps; plan.h), sync: 32 uints.
 // Diagnostics: stamps (nullable) receive per-workgroup phase cycle sums; early requests the next panel too early (redo path).
 int launch_lstm_layer_granule(const LstmStepArgs &s, unsigned short *hx, unsigned int *sync, int *err_flag, hipStream_t st,
                               long long *stamps = nullptr, bool early = false);

@@ -1,9 +1,9 @@
-// Kernel selection of the decode forward (api.hip) in one place: which kernel each stage runs, as a pure function of the
-// geometry, the arithmetic mode, the environment switches, what the device can hold and the batch size.  Host only: no HIP,
-// no device code (tests/test_host.py builds it with the host compiler and checks the selection table).
+// Kernel selection of the decode forward in one place: which kernel each stage of api.hip's forward_stages() runs, as a pure function of the
+// geometry, the arithmetic mode, the environment switches, what the device can hold and the batch size; and the sizes of the persistent layers'
+// exchange buffers.  Host only: no HIP, no device code (tests/test_host.py builds it with the host compiler and checks the selection table).
 //
-// Environment switches of the decode handle.  read_switches() parses them once, in mdd_create; a handle keeps what it read for its
-// whole life, so a switch is set before the model is created.  Any other value of a switch is its default.
+// Environment switches.  read_switches() parses them once, in mdd_create and in mdd_train_create; a handle keeps what it read for its
+// whole life, so a switch is set before the handle is created.  Any other value of a switch is its default.
 //
 //   switch               selects                                                      read at   relied on by
 //   MDD_PRECISION=m      the arithmetic mode a handle starts in: f32x6|2 (default),   create    infer.py --precision
@@ -30,9 +30,13 @@
 //   MDD_X6_OUT=fp32      f32x6 layer kernel: fp32 layer outputs and a split3_kernel   create    tests/test_x6_plane_output.py
 //                        pass in front of the next projection, instead of the layer
 //                        kernel writing that projection's bf16 planes itself
+//   MDD_TRAIN_PRECISION  training handle: bf16x3|1 starts it in the split-bf16        create    train.py
+//                        variant (mdd_train_set_precision changes it later)
+//   MDD_TRAIN_CONV1_IM2COL  training handle: conv1 as im2col + GEMM in the forward    create    tests/test_forward_call.py
+//                        and the backward, instead of the direct kernels
 //
-// The last three were read at each launch (that is, at graph capture) before they joined this table; every test and tool above sets them
-// before it creates the model.  The training handle's persistent layer launches take none of them.
+// The training handle takes MDD_LSTM=step (per-step recurrence in its split-bf16 variant too), its own two switches and nothing else
+// of this table: its persistent layer launches carry no diagnostics.
 #pragma once
 #include <stddef.h>
 #include <stdlib.h>
@@ -54,6 +58,8 @@ struct Switches {
     bool lstm_early = false;    // MDD_LSTM_EARLY
     int x6_redo_mask = -1;      // MDD_X6_FORCE_REDO=n: n - 1, or -1 (off)
     bool x6_out_fp32 = false;   // MDD_X6_OUT=fp32
+    int train_precision = 0;    // MDD_TRAIN_PRECISION
+    bool train_conv1_im2col = false;   // MDD_TRAIN_CONV1_IM2COL
 };
 
 inline Switches read_switches() {
@@ -77,6 +83,9 @@ inline Switches read_switches() {
     const int n = e ? atoi(e) : 0;
     if (n > 0 && (n & (n - 1)) == 0) s.x6_redo_mask = n - 1;
     s.x6_out_fp32 = is(getenv("MDD_X6_OUT"), "fp32");
+    e = getenv("MDD_TRAIN_PRECISION");
+    if (is(e, "bf16x3") || is(e, "1")) s.train_precision = 1;
+    s.train_conv1_im2col = getenv("MDD_TRAIN_CONV1_IM2COL") != nullptr;
     return s;
 }
 
@@ -96,6 +105,12 @@ inline bool packed_whh(const mdd_config &c) { return c.hidden == 384 || c.hidden
 // padded to whole 16-row tiles), and the bytes of the 16-workgroup teams' buffer (lstm_x6.hip).  Both cover at most 1024 rows.
 inline int granule_bg(int B) { const int r = (B + 15) / 16; return (r + 15) / 16 * 16; }
 inline size_t lstm_x6_hx_bytes(int H, int B) { const int bgr = (B + 7) / 8, nbt = (bgr + 15) / 16; return (size_t)2 * 16 * nbt * 3 * (H / 8) * 256; }
+// The 8-workgroup teams' buffer, two sizes on purpose.  What the owners ALLOCATE, in floats: 2 parities x 32 teams x granule_bg(B) rows x H
+// u64 granules.  What the launchers zero before every launch and the kernels use, in bytes: 2 x 32 x BG rows x H tagged 4-byte words, half of
+// the allocation (the 2x slack is kept: the allocation's value is pinned by tests/test_host.py and the stamps sit behind it).
+inline size_t team8_hx_alloc_floats(int H, int B) { return (size_t)2 * 32 * granule_bg(B) * H * 2; }
+inline size_t team8_hx_live_bytes(int H, int BG) { return (size_t)2 * 32 * BG * H * 4; }
+static constexpr size_t kHxTailFloats = 64 + 256 * 6 * 2;   // behind either buffer: a gap and the 256 x 6 diagnostic stamps (MDD_LSTM_DBG)
 static constexpr int kPersistMaxB = 1024;
 
 enum class Conv { Separate, FusedX3, FusedX6, FusedX6Rowwise };   // conv0 + conv1 | conv_fused_kernel<2> | <3, 2> | <3>
@@ -137,9 +152,9 @@ inline ForwardPlan plan_forward(const mdd_config &c, int precision, const Switch
     p.gated = persist;
     p.planes_out = p.proj == Gemm::F32x6 && lx6 && !sw.x6_out_fp32;
     if (persist) {   // u64 granules of the 8-workgroup teams or the three bf16 planes of the 16-workgroup ones, in floats; 256 x 6 stamps behind
-        const size_t granules = (size_t)2 * 32 * granule_bg(B) * H * 2, planes = lstm_x6_hx_bytes(H, B) / 4;
+        const size_t granules = team8_hx_alloc_floats(H, B), planes = lstm_x6_hx_bytes(H, B) / 4;
         p.stamps_at = lx6 ? planes : granules;
-        p.hx_floats = (lx6 && planes > granules ? planes : granules) + 64 + 256 * 6 * 2;
+        p.hx_floats = (lx6 && planes > granules ? planes : granules) + kHxTailFloats;
     }
     return p;
 }

@@ -41,6 +41,7 @@ struct mdd_train_ws {
     bool persist_ok = false;           // the device can hold the persistent layer kernel's grid
     mdd::DeviceBuf xs_a, xs_b;         // split-bf16 operand planes of the flagged variant's GEMMs (hi plane, then lo plane)
     int precision = 0;                 // 0: exact fp32 MFMA everywhere (the reference trains in fp32); 1: the large contractions as split-bf16 x3
+    bool conv1_im2col = false;         // MDD_TRAIN_CONV1_IM2COL at create
     mdd::DeviceArray<int> err_flag;    // set by the embedding gather on an id outside the table
     mdd::DeviceBuf masks;              // generated dropout masks (bytes)
     std::vector<const unsigned char *> mask_ptr;
@@ -53,8 +54,11 @@ struct mdd_train_ws {
 
 namespace mdd {
 
-static int W1_of(const mdd_config &c) { return (c.feat + 2 - 3) / 2 + 1; }
-static int W2_of(const mdd_config &c) { return (W1_of(c) + 2 - 3) / 2 + 1; }
+static int W1_of(const mdd_config &c) { return conv_out(c.feat); }
+static int W2_of(const mdd_config &c) { return conv_out(W1_of(c)); }
+
+// conv1 of a step, forward and backward alike: the direct kernels (train_conv1.hip), else im2col + GEMM
+static bool conv1_direct(const mdd_train_ws *w) { return w->cfg.channels == 32 && W1_of(w->cfg) <= 128 && !w->conv1_im2col; }
 
 static void build_info(mdd_train_ws *w) {
     const mdd_config &c = w->cfg;
@@ -144,7 +148,7 @@ static int lstm_forward_layer(mdd_train_ws *w, LstmStepArgs &a, hipStream_t st) 
         if (int rc = launch_split_rows(a.whh, H, (size_t)8 * H, H, H, hi, lo, st)) return rc;
         a.whh_split = SplitPtr{hi, lo};
         a.out = nullptr;
-        if (int rc = w->hx.need((size_t)2 * 32 * granule_bg(a.B) * H * 2 + 64 + 256 * 6 * 2)) return rc;
+        if (int rc = w->hx.need(team8_hx_alloc_floats(H, a.B) + kHxTailFloats)) return rc;
         return launch_lstm_layer_granule(a, reinterpret_cast<unsigned short *>(w->hx.p), w->sync_words.p, w->err_flag.p + 1, st);
     }
     return launch_lstm_layer_train(a, st);
@@ -168,7 +172,9 @@ extern "C" int mdd_train_create(const mdd_config *cfg, int device, mdd_train_ws 
     MDD_HIP_CHECK(hipSetDevice(device));
     std::unique_ptr<mdd_train_ws> w(new mdd_train_ws());
     w->cfg = *cfg; w->device = device;
-    { const char *pr = getenv("MDD_TRAIN_PRECISION"); if (pr && (!strcmp(pr, "bf16x3") || !strcmp(pr, "1"))) w->precision = 1; }
+    const Switches sw = read_switches();   // the environment at create (plan.h): forward and backward of a step then always agree
+    w->precision = sw.train_precision;
+    w->conv1_im2col = sw.train_conv1_im2col;
     build_info(w.get());
     const int nl = cfg->layers + 1;
     w->xin.resize(nl); w->hraw.resize(nl); w->pd.resize(nl); w->gates.resize(nl); w->cst.resize(nl); w->wihp.resize(nl); w->whhp.resize(nl); w->whht.resize(nl);
@@ -178,8 +184,7 @@ extern "C" int mdd_train_create(const mdd_config *cfg, int device, mdd_train_ws 
     if (int rc = init_gemm_attributes()) return rc;
     if (int rc = init_granule_attributes()) return rc;
     if (int rc = init_conv1_attributes()) return rc;
-    { int n_cu = 0; w->persist_ok = hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && persistent_grid_fits(n_cu) &&
-                                     !(getenv("MDD_LSTM") && !strcmp(getenv("MDD_LSTM"), "step")); }
+    { int n_cu = 0; w->persist_ok = hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && persistent_grid_fits(n_cu) && !sw.lstm_step; }
     if (8 * cfg->hidden > 8192) { set_error("mdd_train_create: hidden too large for the statistics scratch"); return MDD_ERR_ARG; }
     *out = w.release();
     return MDD_OK;
@@ -231,7 +236,7 @@ static int train_forward_enqueue(mdd_train_ws *w, float *const *tensors, const f
     w->B = B; w->T = T; w->L = L; w->p_drop = p_drop; w->ids = x1_dev; w->x = x_dev;
     // ---- buffers
     TRY(w->z0.need(R0 * ch)); TRY(w->a0.need(R0 * ch)); TRY(w->w1r.need((size_t)ch * 9 * ch));
-    const bool direct1 = ch == 32 && W1 <= 128 && !getenv("MDD_TRAIN_CONV1_IM2COL");   // conv1 as direct kernels (train_conv1.hip); else im2col + GEMM
+    const bool direct1 = conv1_direct(w);
     if (!direct1) TRY(w->col1.need(R1 * 9 * ch));
     TRY(w->z1.need(R1 * ch)); TRY(w->a1.need(R1 * ch)); TRY(w->seq0.need(R * Kin0));
     TRY(w->gx.need(std::max(R, Rt) * G2)); TRY(w->hb.need((size_t)4 * B * H)); TRY(w->cb.need((size_t)2 * B * H));
@@ -468,7 +473,7 @@ static int train_backward_enqueue(mdd_train_ws *w, float *const *tensors, const 
     TRY(launch_col_sum(dz1, R1, ch, w->dacc.p, GR("conv.1.conv.bias"), st));
     TRY(w->d_b.need((size_t)ch * 9 * ch));
     float *da0 = w->d_c.p;
-    const bool direct1 = ch == 32 && W1 <= 128 && !getenv("MDD_TRAIN_CONV1_IM2COL");
+    const bool direct1 = conv1_direct(w);
     if (direct1) {
         const int parts = conv1_wgrad_parts(B, T, W2);
         TRY(w->part.need((size_t)parts * ch * 9 * ch));

@@ -40,20 +40,24 @@ class HipModel(object):
             _lib.check(L.mdd_load_weight(self.handle, key.encode(), a.ctypes.data_as(C.c_void_p), shape, a.ndim))
         _lib.check(L.mdd_finalize_weights(self.handle))
 
+    def _run(self, entry, like, B, T, out, sync_errors, args):
+        """Allocate logp [T/2,B,C] unless given, enqueue ``entry(handle, *args, out, stream)`` and, on request, wait and raise device-side errors."""
+        if out is None:
+            out = torch.empty((T // 2, B, self.geom.num_class), dtype=torch.float32, device=like.device)
+        st = _lib.current_stream_ptr()
+        _lib.check(entry(self.handle, *args, C.c_void_p(out.data_ptr()), st))
+        if sync_errors:
+            if _lib.lib().mdd_sync(self.handle, st) != 0:
+                raise IndexError(_lib.lib().mdd_last_error().decode())
+        return out
+
     def forward(self, x, x1, out=None, sync_errors=False):
         """x [B,T,F] f32 cuda, x1 [B,L] i64 cuda -> logp [T/2,B,C] (enqueued on the current stream)."""
         assert x.is_cuda and x1.is_cuda and x.dtype == torch.float32 and x1.dtype == torch.int64
         x, x1 = x.contiguous(), x1.contiguous()
         B, T, _ = x.shape
-        if out is None:
-            out = torch.empty((T // 2, B, self.geom.num_class), dtype=torch.float32, device=x.device)
-        st = _lib.current_stream_ptr()
-        _lib.check(_lib.lib().mdd_forward(self.handle, C.c_void_p(x.data_ptr()), B, T, C.c_void_p(x1.data_ptr()),
-                                          x1.shape[1], C.c_void_p(out.data_ptr()), st))
-        if sync_errors:
-            if _lib.lib().mdd_sync(self.handle, st) != 0:
-                raise IndexError(_lib.lib().mdd_last_error().decode())
-        return out
+        return self._run(_lib.lib().mdd_forward, x, B, T, out, sync_errors,
+                         (C.c_void_p(x.data_ptr()), B, T, C.c_void_p(x1.data_ptr()), x1.shape[1]))
 
     def forward_fused(self, x, x1, frames, canon, out=None, sync_errors=False):
         """Several reference batches of different padded lengths in one launch sequence (mdd_forward_fused): x [B,T,F] with every
@@ -63,15 +67,9 @@ class HipModel(object):
         assert frames.is_cuda and canon.is_cuda and frames.dtype == torch.int32 and canon.dtype == torch.int32
         x, x1, frames, canon = x.contiguous(), x1.contiguous(), frames.contiguous(), canon.contiguous()
         B, T, _ = x.shape
-        if out is None:
-            out = torch.empty((T // 2, B, self.geom.num_class), dtype=torch.float32, device=x.device)
-        st = _lib.current_stream_ptr()
-        _lib.check(_lib.lib().mdd_forward_fused(self.handle, C.c_void_p(x.data_ptr()), B, T, C.c_void_p(x1.data_ptr()), x1.shape[1],
-                                                C.c_void_p(frames.data_ptr()), C.c_void_p(canon.data_ptr()), C.c_void_p(out.data_ptr()), st))
-        if sync_errors:
-            if _lib.lib().mdd_sync(self.handle, st) != 0:
-                raise IndexError(_lib.lib().mdd_last_error().decode())
-        return out
+        return self._run(_lib.lib().mdd_forward_fused, x, B, T, out, sync_errors,
+                         (C.c_void_p(x.data_ptr()), B, T, C.c_void_p(x1.data_ptr()), x1.shape[1],
+                          C.c_void_p(frames.data_ptr()), C.c_void_p(canon.data_ptr())))
 
     def forward_raw(self, raw, x1, out=None, sync_errors=False):
         """raw [B,T_raw,F/3] f32 cuda (unstacked frames), x1 [B,L] i64 cuda -> logp, exactly as
@@ -80,16 +78,8 @@ class HipModel(object):
         raw, x1 = raw.contiguous(), x1.contiguous()
         B, T_raw, D = raw.shape
         assert 3 * D == self.geom.feat
-        T = _lib.lib().mdd_stack_len(T_raw, 2, 2)
-        if out is None:
-            out = torch.empty((T // 2, B, self.geom.num_class), dtype=torch.float32, device=raw.device)
-        st = _lib.current_stream_ptr()
-        _lib.check(_lib.lib().mdd_forward_raw(self.handle, C.c_void_p(raw.data_ptr()), B, T_raw, C.c_void_p(x1.data_ptr()),
-                                              x1.shape[1], C.c_void_p(out.data_ptr()), st))
-        if sync_errors:
-            if _lib.lib().mdd_sync(self.handle, st) != 0:
-                raise IndexError(_lib.lib().mdd_last_error().decode())
-        return out
+        return self._run(_lib.lib().mdd_forward_raw, raw, B, _lib.lib().mdd_stack_len(T_raw, 2, 2), out, sync_errors,
+                         (C.c_void_p(raw.data_ptr()), B, T_raw, C.c_void_p(x1.data_ptr()), x1.shape[1]))
 
     def profile(self, x, x1):
         """Per-stage (name, ms, launches, flops) of one forward replayed stage by stage between HIP events."""

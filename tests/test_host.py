@@ -345,6 +345,9 @@ int main() {
     const char *conv[] = {"conv0+conv1", "conv_fused_kernel<2>", "conv_fused_kernel<3,2>", "conv_fused_kernel<3>"};
     const char *gemm[] = {"gemm_nt", "bf16x3", "f32x6"};
     const char *lstm[] = {"x6", "f32", "granule", "lstm_step_x3_kernel", "lstm_step_packed_kernel", "lstm_step_kernel<0>"};
+    // the 8-workgroup teams' exchange buffer at B = 700 (48 rows per group): allocated floats, the live half in bytes, the tail behind it
+    if (team8_hx_alloc_floats(384, 700) != (size_t)2 * 32 * 48 * 384 * 2 || team8_hx_live_bytes(384, granule_bg(700)) != (size_t)2 * 32 * 48 * 384 * 4 ||
+        team8_hx_live_bytes(384, granule_bg(700)) * 2 != team8_hx_alloc_floats(384, 700) * sizeof(float) || kHxTailFloats != 64 + 3072) return 2;
     for (std::string line; std::getline(std::cin, line);) {
         std::istringstream in(line);
         mdd_config c{243, 384, 4, 45, 32, 44, 512, 1e-5f};
