@@ -19,7 +19,7 @@ EXPORTS = (
     "mdd_resample_len", "mdd_resample_filter", "mdd_resample_batch",
     "mdd_train_create", "mdd_train_destroy", "mdd_train_num_tensors", "mdd_train_tensor_info", "mdd_train_num_masks", "mdd_train_mask_bytes",
     "mdd_train_forward", "mdd_train_backward", "mdd_train_sync", "mdd_train_set_precision", "mdd_adam_step",
-    "mdd_diag_gemm_ph8", "mdd_diag_gates", "mdd_diag_gemm", "mdd_diag_gemm_time", "mdd_diag_conv_time",
+    "mdd_diag_gemm_ph8", "mdd_diag_gates", "mdd_diag_gemm", "mdd_diag_gemm_ops", "mdd_diag_gemm_time", "mdd_diag_conv_time",
 )
 
 
@@ -104,6 +104,7 @@ def lib():
     L.mdd_train_backward.argtypes = [vp, vp, vp, vp, vp]
     L.mdd_train_sync.argtypes = [vp, vp]
     L.mdd_train_set_precision.argtypes = [vp, C.c_int32]
+    L.mdd_diag_gemm_ops.argtypes = [C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     L.mdd_adam_step.argtypes = [vp, vp, vp, vp, vp, i32, i32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, vp]
     _lib = L
     return L

@@ -14,7 +14,7 @@
 
 #include <vector>
 
-#include "mdd_internal.h"
+#include "train.h"
 
 namespace mdd {
 
@@ -59,6 +59,102 @@ int launch_split3(const float *x, int rows, int K, int ld, unsigned short *plane
     const size_t waves = (size_t)((rows + 15) / 16) * (K / 32);
     int grid = (int)((waves + 3) / 4); if (grid > 16384) grid = 16384; if (grid < 1) grid = 1;
     hipLaunchKernelGGL(split3_kernel, dim3(grid), dim3(256), 0, st, x, rows, K, ld, planes, (size_t)rows * K);
+    MDD_LAUNCH_CHECK();
+    return MDD_OK;
+}
+
+// ---- operand planes of the training step's contractions (gemm_f32x6_ops below).  Both kernels write planes of `rows` x Kp elements,
+// plane_elems apart, in split3_kernel's K-tile-major order, with the contraction axis zero-padded from K to Kp (a multiple of 32): a padded
+// position is zero in all three planes, so a padded K-tile adds exact zeros to every accumulator.
+__device__ __forceinline__ void split3_store8(const float (&f)[8], unsigned short *planes, size_t plane_elems, size_t off) {
+    typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
+    u16x8 h, m, l;
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        h[k] = bf16_rn(f[k]);
+        const float r1 = f[k] - bf16_f32(h[k]);
+        m[k] = bf16_rn(r1);
+        l[k] = bf16_rn(r1 - bf16_f32(m[k]));
+    }
+    *reinterpret_cast<u16x8 *>(planes + off) = h;
+    *reinterpret_cast<u16x8 *>(planes + plane_elems + off) = m;
+    *reinterpret_cast<u16x8 *>(planes + 2 * plane_elems + off) = l;
+}
+
+// The row operand, x [rows][ld] with K leading columns used (any K): split3_kernel's wave shape; a lane whose eight columns reach past K
+// reads what is there one float at a time and zeros for the rest.
+__global__ void split3_pad_kernel(const float *__restrict__ x, int rows, int K, int ld, int Kp, unsigned short *__restrict__ planes, size_t plane_elems) {
+    const int lane = threadIdx.x & 63;
+    const int nkt = Kp / 32, ngr = (rows + 15) / 16;
+    const size_t total = (size_t)ngr * nkt;
+    for (size_t w = (size_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); w < total; w += (size_t)gridDim.x * (blockDim.x >> 6)) {
+        const int g = (int)(w / nkt), kt = (int)(w - (size_t)g * nkt);
+        const int row = g * 16 + (lane >> 2), c = lane & 3, k0 = kt * 32 + c * 8;
+        if (row >= rows) continue;
+        const float *src = x + (size_t)row * ld + k0;
+        float f[8];
+        if (k0 + 8 <= K) {
+            const float4 v0 = reinterpret_cast<const float4 *>(src)[0], v1 = reinterpret_cast<const float4 *>(src)[1];
+            f[0] = v0.x; f[1] = v0.y; f[2] = v0.z; f[3] = v0.w; f[4] = v1.x; f[5] = v1.y; f[6] = v1.z; f[7] = v1.w;
+        } else {
+#pragma unroll
+            for (int k = 0; k < 8; k++) f[k] = k0 + k < K ? src[k] : 0.f;
+        }
+        split3_store8(f, planes, plane_elems, ((size_t)kt * rows + row) * 32 + c * 8);
+    }
+}
+
+// The transposed operand: x is stored [K][ld] with `rows` leading columns used, and the operand's row r is x's COLUMN r (the contraction runs
+// down x's rows).  One workgroup per (K-tile, 64 operand rows): the 32 x 64 block is read along x's rows (16 lanes x 16 bytes = 256 contiguous
+// bytes per x row), turned in LDS, and leaves as 64 rows x 64 bytes per plane = 4 KB of contiguous memory, 16 bytes per lane.
+// LDS row pitch 33 words: the turn's writes (bank 4 m4 + k) and its reads (bank r + 8 c + j) both spread over the banks.
+constexpr int TS3_R = 64;
+__global__ __launch_bounds__(256) void transpose_split3_kernel(const float *__restrict__ x, int K, int rows, int ld, unsigned short *__restrict__ planes,
+                                                               size_t plane_elems) {
+    __shared__ float tile[TS3_R][33];
+    const int kt = blockIdx.x, r0 = blockIdx.y * TS3_R, tid = threadIdx.x;
+    {
+        const int m4 = tid & 15, rr = r0 + m4 * 4;
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+            const int kl = (tid >> 4) + h * 16, k = kt * 32 + kl;
+            float4 v = {0.f, 0.f, 0.f, 0.f};
+            if (k < K) {
+                const float *src = x + (size_t)k * ld + rr;
+                if (rr + 3 < rows) v = *reinterpret_cast<const float4 *>(src);
+                else { if (rr < rows) v.x = src[0]; if (rr + 1 < rows) v.y = src[1]; if (rr + 2 < rows) v.z = src[2]; }
+            }
+            tile[m4 * 4 + 0][kl] = v.x; tile[m4 * 4 + 1][kl] = v.y; tile[m4 * 4 + 2][kl] = v.z; tile[m4 * 4 + 3][kl] = v.w;
+        }
+    }
+    __syncthreads();
+    const int rl = tid >> 2, c = tid & 3, row = r0 + rl;
+    if (row >= rows) return;
+    float f[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) f[k] = tile[rl][c * 8 + k];
+    split3_store8(f, planes, plane_elems, ((size_t)kt * rows + row) * 32 + c * 8);
+}
+
+static bool split3_args_ok(const float *x, int rows, int K, int ld, int Kp, const unsigned short *planes, size_t plane_elems) {
+    return x && planes && rows > 0 && K > 0 && Kp >= K && Kp % 32 == 0 && ld % 4 == 0 && (uintptr_t)x % 16 == 0 && (uintptr_t)planes % 16 == 0 &&
+           plane_elems % 8 == 0 && plane_elems >= (size_t)rows * Kp;
+}
+int launch_split3_pad(const float *x, int rows, int K, int ld, int Kp, unsigned short *planes, size_t plane_elems, hipStream_t st) {
+    if (!split3_args_ok(x, rows, K, ld, Kp, planes, plane_elems) || ld < K) {
+        set_error("split3_pad: rows=%d K=%d ld=%d Kp=%d (Kp a multiple of 32 >= K, ld a multiple of 4 >= K, 16-byte aligned)", rows, K, ld, Kp); return MDD_ERR_ARG;
+    }
+    const size_t waves = (size_t)((rows + 15) / 16) * (Kp / 32);
+    int grid = (int)((waves + 3) / 4); if (grid > 16384) grid = 16384;
+    hipLaunchKernelGGL(split3_pad_kernel, dim3(grid), dim3(256), 0, st, x, rows, K, ld, Kp, planes, plane_elems);
+    MDD_LAUNCH_CHECK();
+    return MDD_OK;
+}
+int launch_transpose_split3(const float *x, int K, int rows, int ld, int Kp, unsigned short *planes, size_t plane_elems, hipStream_t st) {
+    if (!split3_args_ok(x, rows, K, ld, Kp, planes, plane_elems) || ld < rows || (rows + TS3_R - 1) / TS3_R > 65535) {
+        set_error("transpose_split3: K=%d rows=%d ld=%d Kp=%d (Kp a multiple of 32 >= K, ld a multiple of 4 >= rows, 16-byte aligned)", K, rows, ld, Kp); return MDD_ERR_ARG;
+    }
+    hipLaunchKernelGGL(transpose_split3_kernel, dim3(Kp / 32, (rows + TS3_R - 1) / TS3_R), dim3(256), 0, st, x, K, rows, ld, planes, plane_elems);
     MDD_LAUNCH_CHECK();
     return MDD_OK;
 }
@@ -115,7 +211,14 @@ __device__ __forceinline__ bf16x8 x6_frag(const unsigned char *plane, int row, i
     return *reinterpret_cast<const bf16x8 *>(plane + row * X6_ROW + ((((kbyte >> 4) ^ ((row >> 2) & 3))) << 4));
 }
 
-template <bool STAMP>
+// SPLITK (the weight gradients of the training step: few output tiles, a long contraction): the contraction is cut into chunks of K
+// elements each and the workgroups walk chunks x tiles VIRTUAL tiles.  In K-tile-major planes chunk s is a contiguous slab of every plane,
+// (s * K / 32) * rows * 32 elements in, so a virtual tile is an ordinary tile on shifted plane pointers; it writes its M x N partial
+// product (ldc == N) behind the s - 1 before it, and a reduction pass sums them (no atomics: the sum has one fixed order).  tiles_c: output
+// tiles per chunk, which arrives in the `ldc` argument (the row stride of a partial product is N); ntiles counts the virtual tiles; K is
+// the chunk's length.  The instantiation with SPLITK false is the decode path's kernel, instruction for instruction what it was without
+// this parameter: every SPLITK expression below folds to the kernel argument it replaces.
+template <bool STAMP, bool SPLITK = false>
 __global__ __launch_bounds__(256, 1) void gemm_f32x6_kernel(const unsigned short *__restrict__ Ap, const unsigned short *__restrict__ Wp, size_t a_plane, size_t w_plane,
                                                             const float *__restrict__ bias, float *__restrict__ C, int M, int N, int K, int ldc, int tiles_n,
                                                             int ntiles, long long *stamps) {
@@ -129,9 +232,19 @@ __global__ __launch_bounds__(256, 1) void gemm_f32x6_kernel(const unsigned short
     // tile's first operands are requested before this tile's epilogue).  Tile of a virtual block index: an XCD (vb % 8) walks consecutive
     // tiles, so that the A panel stays in its L2.
     const int tq = ntiles >> 3, trem = ntiles & 7;
+    const unsigned short *Ab_ = Ap, *Wb_ = Wp;   // SPLITK: this tile's chunk of the planes and its partial product
+    float *Cb_ = C;
+#define X6_AB (SPLITK ? Ab_ : Ap)
+#define X6_WB (SPLITK ? Wb_ : Wp)
+#define X6_LDC (SPLITK ? N : ldc)
     auto tile_of = [&](int vb, int &m0_, int &n0_) {
         const int xcd = vb & 7;
-        const int swz = (xcd < trem ? xcd * (tq + 1) : trem * (tq + 1) + (xcd - trem) * tq) + (vb >> 3);
+        const int vt = (xcd < trem ? xcd * (tq + 1) : trem * (tq + 1) + (xcd - trem) * tq) + (vb >> 3);
+        const int tiles_c = ldc, s = SPLITK ? vt / tiles_c : 0;
+        const int swz = SPLITK ? vt - s * tiles_c : vt;
+        if (SPLITK) {
+            Ab_ = Ap + (size_t)s * (K / X6_BK) * M * 32; Wb_ = Wp + (size_t)s * (K / X6_BK) * N * 32; Cb_ = C + (size_t)s * M * N;
+        }
         const int tm = swz / tiles_n, tn = swz % tiles_n;
         m0_ = tm * X6_BM + wave * (16 * X6_RT); n0_ = tn * X6_BN;  // this wave's first row; the workgroup's first column
     };
@@ -145,7 +258,7 @@ __global__ __launch_bounds__(256, 1) void gemm_f32x6_kernel(const unsigned short
     auto load_a = [&](bf16x8 (&fa)[X6_RT][3], int kt) {
 #pragma unroll
         for (int p = 0; p < 3; p++) {
-            const unsigned char *base = reinterpret_cast<const unsigned char *>(Ap + (size_t)p * a_plane + (size_t)kt * M * 32);
+            const unsigned char *base = reinterpret_cast<const unsigned char *>(X6_AB + (size_t)p * a_plane + (size_t)kt * M * 32);
 #pragma unroll
             for (int i = 0; i < X6_RT; i++) fa[i][p] = *reinterpret_cast<const bf16x8 *>(base + aoff[i]);
         }
@@ -165,7 +278,7 @@ __global__ __launch_bounds__(256, 1) void gemm_f32x6_kernel(const unsigned short
     set_tile();
     auto piece = [&](int idx, int kt_, unsigned stage_off) {   // idx 0..5: plane idx / 2, row group idx % 2
         const int p = idx >> 1, g = idx & 1;
-        const unsigned short *base = Wp + (size_t)p * w_plane + (size_t)kt_ * N * 32;
+        const unsigned short *base = X6_WB + (size_t)p * w_plane + (size_t)kt_ * N * 32;
         const unsigned la = lds0 + stage_off + (unsigned)(p * X6_PW + (wave * 2 + g) * 1024);
         asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" :: "v"(voffW[g]), "s"(base), "s"(la) : "memory", "m0");
     };
@@ -201,7 +314,7 @@ __global__ __launch_bounds__(256, 1) void gemm_f32x6_kernel(const unsigned short
             // memory instructions of the next K-tile, one per product group: 9 A fragment loads (pairs 0, 1), 6 W pieces (pairs 1, 2)
 #define X6_MEM(g_) do { const int s_ = jp * 6 + (g_); \
                 if (s_ < 9) { const int p_ = s_ / X6_RT, i_ = s_ % X6_RT; \
-                    asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(fan[i_][p_]) : "v"(aoff[i_]), "s"(Ap + (size_t)p_ * a_plane + (size_t)ktn * M * 32) : "memory"); } \
+                    asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(fan[i_][p_]) : "v"(aoff[i_]), "s"(X6_AB + (size_t)p_ * a_plane + (size_t)ktn * M * 32) : "memory"); } \
                 else if (s_ < 9 + X6_NPW) piece(s_ - 9, ktn, nst); } while (0)
 #define X6_GROUP(acc_, wp_, ap_) _Pragma("unroll") for (int i = 0; i < X6_RT; i++) { _Pragma("unroll") for (int jj = 0; jj < 2; jj++) X6_MFMA(acc_[i][jp * 2 + jj], fw[jp & 1][wp_][jj], fac[i][ap_]); }
             X6_MEM(0); X6_GROUP(sm, 1, 1)      // mid . mid
@@ -251,6 +364,7 @@ __global__ __launch_bounds__(256, 1) void gemm_f32x6_kernel(const unsigned short
     // the next tile's first W stage and A fragments are requested before this tile's epilogue (stage 0 and faA are free: every wave has passed
     // the last K-tile's barrier)
     const int m0c = m0, n0c = n0, vbn = vb + (int)gridDim.x;
+    float *const Cc = SPLITK ? Cb_ : C;
     const bool more = vbn < ntiles;
     if (more) {
         tile_of(vbn, m0, n0);
@@ -270,7 +384,7 @@ __global__ __launch_bounds__(256, 1) void gemm_f32x6_kernel(const unsigned short
             if (row >= M || col >= N) continue;
             f32x4 v = tot[i][j] + sm[i][j];
             if (bias) { v[0] += bias[col]; if (col + 1 < N) v[1] += bias[col + 1]; if (col + 2 < N) v[2] += bias[col + 2]; if (col + 3 < N) v[3] += bias[col + 3]; }
-            float *dst = C + (size_t)row * ldc + col;
+            float *dst = Cc + (size_t)row * X6_LDC + col;
             if (col + 3 < N) *reinterpret_cast<f32x4 *>(dst) = v;
             else for (int r = 0; r < 4 && col + r < N; r++) dst[r] = v[r];
         }
@@ -282,11 +396,15 @@ __global__ __launch_bounds__(256, 1) void gemm_f32x6_kernel(const unsigned short
     if (STAMP && stamps && lane == 0 && blockIdx.x < 1024)
         for (int i = 0; i < 4; i++) stamps[((size_t)blockIdx.x * 4 + wave) * 4 + i] = sacc[i];
 #undef X6_T
+#undef X6_AB
+#undef X6_WB
+#undef X6_LDC
 }
 
 int init_gemm_x6_attributes() {
     MDD_HIP_CHECK(hipFuncSetAttribute((const void *)gemm_f32x6_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, X6_NS * X6_STAGE));
     MDD_HIP_CHECK(hipFuncSetAttribute((const void *)gemm_f32x6_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, X6_NS * X6_STAGE));
+    MDD_HIP_CHECK(hipFuncSetAttribute((const void *)gemm_f32x6_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, X6_NS * X6_STAGE));
     return MDD_OK;
 }
 
@@ -305,9 +423,77 @@ int launch_gemm_f32x6(const unsigned short *A3, size_t a_plane, const unsigned s
     return MDD_OK;
 }
 
+// Split-K form: part[s][M][N] = A[:, s*Kc .. (s+1)*Kc) . W[:, same]^T for s < S, one launch over S x tiles virtual tiles.  A3 / W3: three
+// K-tile-major planes each, a_plane / w_plane elements apart, of M (N) rows x S*Kc contraction elements.
+int launch_gemm_f32x6_splitk(const unsigned short *A3, size_t a_plane, const unsigned short *W3, size_t w_plane, float *part, int M, int N, int Kc, int S,
+                             hipStream_t st) {
+    if (!A3 || !W3 || !part || M <= 0 || N <= 0 || Kc <= 0 || Kc % X6_BK || S < 1 || N % 4 || (uintptr_t)part % 16 || (uintptr_t)A3 % 16 || (uintptr_t)W3 % 16 ||
+        a_plane % 8 || w_plane % 8 || a_plane < (size_t)M * Kc * S || w_plane < (size_t)N * Kc * S) {
+        set_error("gemm_f32x6_splitk: bad shape M=%d N=%d Kc=%d S=%d", M, N, Kc, S);
+        return MDD_ERR_ARG;
+    }
+    const int tn = (N + X6_BN - 1) / X6_BN, tiles_c = ((M + X6_BM - 1) / X6_BM) * tn;
+    if ((long long)tiles_c * S > (1 << 24)) { set_error("gemm_f32x6_splitk: %d x %d tiles", S, tiles_c); return MDD_ERR_ARG; }
+    const int nvt = tiles_c * S;
+    hipLaunchKernelGGL((gemm_f32x6_kernel<false, true>), dim3(nvt < 256 ? nvt : 256), dim3(256), X6_NS * X6_STAGE, st, A3, W3, a_plane, w_plane, (const float *)nullptr, part, M, N, Kc,
+                       /* ldc carries */ tiles_c, tn, nvt, (long long *)nullptr);
+    MDD_LAUNCH_CHECK();
+    return MDD_OK;
+}
+
+// C[M,N] (row stride ldc) = opA . opB^T (+ bias[N]) as f32x6, for the training step: opA[m,k] = ta ? A[k*lda + m] : A[m*lda + k], opB[n,k]
+// likewise.  Both operands are written as three K-tile-major planes into xs_a / xs_b (transposed on the way when stored [K, *]) with the
+// contraction zero-padded to S chunks of whole K-tiles.  S == 1: one launch of the decode path's kernel.  S > 1 (no bias): the split-K
+// launch into `part` and launch_reduce_parts (into C itself when ldc == N, as the step calls it; else into one more slot of `part`, copied
+// out row by row).  The caller has checked x6_ops_ok.
+bool x6_ops_ok(const float *A, int lda, const float *B, int ldb, const float *C, int ldc) {
+    return lda % 4 == 0 && ldb % 4 == 0 && ldc % 4 == 0 && (uintptr_t)A % 16 == 0 && (uintptr_t)B % 16 == 0 && (uintptr_t)C % 16 == 0;
+}
+int gemm_f32x6_ops(bool ta, bool tb, const float *A, int lda, const float *B, int ldb, const float *bias, float *C, int ldc, int M, int N, int K, int S,
+                   DeviceBuf &xs_a, DeviceBuf &xs_b, DeviceBuf &part, hipStream_t st) {
+    if (M <= 0 || N <= 0 || K <= 0 || S < 1 || ldc < N || !x6_ops_ok(A, lda, B, ldb, C, ldc) || (S > 1 && bias)) {
+        set_error("gemm_f32x6_ops: M=%d N=%d K=%d S=%d lda=%d ldb=%d ldc=%d", M, N, K, S, lda, ldb, ldc); return MDD_ERR_ARG;
+    }
+    const int nkt = (K + X6_BK - 1) / X6_BK;
+    if (S > nkt) S = nkt;
+    const int Kc = (nkt + S - 1) / S * X6_BK, Kp = S * Kc;
+    const size_t pa = (size_t)M * Kp, pw = (size_t)N * Kp;   // elements per plane (multiples of 32)
+    if (int rc = xs_a.need((3 * pa + 1) / 2)) return rc;
+    if (int rc = xs_b.need((3 * pw + 1) / 2)) return rc;
+    unsigned short *a3 = reinterpret_cast<unsigned short *>(xs_a.p), *w3 = reinterpret_cast<unsigned short *>(xs_b.p);
+    if (int rc = ta ? launch_transpose_split3(A, K, M, lda, Kp, a3, pa, st) : launch_split3_pad(A, M, K, lda, Kp, a3, pa, st)) return rc;
+    if (int rc = tb ? launch_transpose_split3(B, K, N, ldb, Kp, w3, pw, st) : launch_split3_pad(B, N, K, ldb, Kp, w3, pw, st)) return rc;
+    if (S == 1) return launch_gemm_f32x6(a3, pa, w3, pw, bias, C, M, N, Kp, ldc, st, nullptr);
+    const size_t mn = (size_t)M * N;
+    if (int rc = part.need((S + (ldc != N ? 1 : 0)) * mn)) return rc;
+    if (int rc = launch_gemm_f32x6_splitk(a3, pa, w3, pw, part.p, M, N, Kc, S, st)) return rc;
+    if (ldc == N) return launch_reduce_parts(part.p, S, mn, C, st);
+    if (int rc = launch_reduce_parts(part.p, S, mn, part.p + S * mn, st)) return rc;
+    return launch_copy_cols(part.p + S * mn, N, 0, C, ldc, 0, (size_t)M, N, false, st);
+}
+
 }  // namespace mdd
 
 using namespace mdd;
+
+extern "C" int mdd_diag_gemm_ops(int mode, int ta, int tb, const float *A_dev, int lda, const float *B_dev, int ldb, float *C_dev, int ldc, int M, int N, int K,
+                                 int splits, void *stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (!A_dev || !B_dev || !C_dev || M <= 0 || N <= 0 || K <= 0 || splits < 1 || lda < (ta ? M : K) || ldb < (tb ? N : K) || ldc < N) {
+        set_error("mdd_diag_gemm_ops: bad arguments"); return MDD_ERR_ARG;
+    }
+    int rc;
+    if (mode == 0) rc = launch_gemm_f32(ta != 0, tb != 0, A_dev, B_dev, nullptr, C_dev, M, N, K, lda, ldb, ldc, 1, 0, 0, 0, false, st);
+    else if (mode == 3) {
+        DeviceBuf xa, xb, part;     // freed on return, behind the synchronisation
+        rc = init_gemm_x6_attributes();
+        if (!rc) rc = gemm_f32x6_ops(ta != 0, tb != 0, A_dev, lda, B_dev, ldb, nullptr, C_dev, ldc, M, N, K, splits, xa, xb, part, st);
+        if (hipStreamSynchronize(st) != hipSuccess && !rc) { set_error("mdd_diag_gemm_ops: the stream failed"); rc = MDD_ERR_HIP; }
+        return rc;
+    } else { set_error("mdd_diag_gemm_ops: mode %d (0 exact fp32, 3 f32x6)", mode); return MDD_ERR_ARG; }
+    if (hipStreamSynchronize(st) != hipSuccess && !rc) { set_error("mdd_diag_gemm_ops: the stream failed"); rc = MDD_ERR_HIP; }
+    return rc;
+}
 
 // Diagnostic / test entry: one GEMM through a chosen arithmetic, fp32 operands and result on the device.
 //   mode 0: exact fp32 MFMA (gemm_nt_f32_kernel)      1: split-bf16 x3 (operands split here)

@@ -76,6 +76,13 @@ int launch_split3(const float *x, int rows, int K, int ld, unsigned short *plane
 int launch_gemm_f32x6(const unsigned short *A3, size_t a_plane, const unsigned short *W3, size_t w_plane, const float *bias, float *C, int M, int N, int K,
                       int ldc, hipStream_t st, long long *stamps = nullptr);
 int init_gemm_x6_attributes();
+// The same planes for the training step's operands: the contraction zero-padded from K to Kp (a multiple of 32), planes plane_elems apart.
+// launch_split3_pad: x [rows][ld], K leading columns; launch_transpose_split3: x stored [K][ld], operand row r = column r of x.
+int launch_split3_pad(const float *x, int rows, int K, int ld, int Kp, unsigned short *planes, size_t plane_elems, hipStream_t st);
+int launch_transpose_split3(const float *x, int K, int rows, int ld, int Kp, unsigned short *planes, size_t plane_elems, hipStream_t st);
+// split-K form of the f32x6 GEMM: S partial products [S][M][N] of Kc contraction elements each, in one launch (gemm_bf16x6.hip)
+int launch_gemm_f32x6_splitk(const unsigned short *A3, size_t a_plane, const unsigned short *W3, size_t w_plane, float *part, int M, int N, int Kc, int S,
+                             hipStream_t st);
 
 int launch_stack_skip(const float *raw, int B, int T_raw, int D, int right, int skip, int n_down, float *out,
                       hipStream_t st);
@@ -94,6 +101,12 @@ int launch_conv_fused3(const float *x, const float *w0, const float *sc0, const 
                        bool rowwise = false,    // f32x6 form: three K-tile-major planes out (rowwise: the row-at-a-time kernel, MDD_CONV=rowwise)
                        long long *stamps = nullptr);   // stamps (diagnostic, default kernel only): the stamped instantiation's phase cycle sums
 int init_conv_attributes();
+
+// C = opA . opB^T (+ bias) as f32x6 in the training step's operand forms (ta / tb: stored [K, rows]); S > 1: split-K into `part` and a sum.
+// x6_ops_ok: the alignment half of the rule (leading dimensions multiples of 4, 16-byte aligned pointers).
+bool x6_ops_ok(const float *A, int lda, const float *B, int ldb, const float *C, int ldc);
+int gemm_f32x6_ops(bool ta, bool tb, const float *A, int lda, const float *B, int ldb, const float *bias, float *C, int ldc, int M, int N, int K, int S,
+                   DeviceBuf &xs_a, DeviceBuf &xs_b, DeviceBuf &part, hipStream_t st);
 
 struct LstmStepArgs {
     const float *gx;     // [T][B][2][4H], gate columns permuted to u*4+g

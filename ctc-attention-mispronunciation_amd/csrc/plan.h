@@ -32,6 +32,8 @@
 //                        kernel writing that projection's bf16 planes itself
 //   MDD_TRAIN_PRECISION  training handle: bf16x3|1 starts it in the split-bf16        create    train.py
 //                        variant (mdd_train_set_precision changes it later)
+//   MDD_TRAIN_PRECISION  training handle: f32x6|2 starts it with the large            create    train.py, tests/test_train_f32x6.py
+//                        contractions as f32x6 on the bf16 matrix cores
 //   MDD_TRAIN_CONV1_IM2COL  training handle: conv1 as im2col + GEMM in the forward    create    tests/test_forward_call.py
 //                        and the backward, instead of the direct kernels
 //
@@ -85,6 +87,7 @@ inline Switches read_switches() {
     s.x6_out_fp32 = is(getenv("MDD_X6_OUT"), "fp32");
     e = getenv("MDD_TRAIN_PRECISION");
     if (is(e, "bf16x3") || is(e, "1")) s.train_precision = 1;
+    if (is(e, "f32x6") || is(e, "2")) s.train_precision = 2;
     s.train_conv1_im2col = getenv("MDD_TRAIN_CONV1_IM2COL") != nullptr;
     return s;
 }

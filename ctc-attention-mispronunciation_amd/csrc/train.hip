@@ -39,8 +39,9 @@ struct mdd_train_ws {
     mdd::DeviceBuf whhs, hx;           // flagged variant: W_hh' as hi/lo planes and the h exchange buffer of the persistent layer kernel
     mdd::DeviceArray<unsigned int> sync_words;
     bool persist_ok = false;           // the device can hold the persistent layer kernel's grid
-    mdd::DeviceBuf xs_a, xs_b;         // split-bf16 operand planes of the flagged variant's GEMMs (hi plane, then lo plane)
-    int precision = 0;                 // 0: exact fp32 MFMA everywhere (the reference trains in fp32); 1: the large contractions as split-bf16 x3
+    mdd::DeviceBuf xs_a, xs_b;         // operand planes of the GEMMs of modes 1 (hi plane, then lo plane) and 2 (hi | mid | lo); written afresh by every GEMM
+    int precision = 0;                 // 0: exact fp32 MFMA everywhere (the reference trains in fp32); 1: the large contractions as split-bf16 x3;
+                                       // 2: the large contractions as f32x6 (reference width), everything else as 0
     bool conv1_im2col = false;         // MDD_TRAIN_CONV1_IM2COL at create
     mdd::DeviceArray<int> err_flag;    // set by the embedding gather on an id outside the table
     mdd::DeviceBuf masks;              // generated dropout masks (bytes)
@@ -110,9 +111,24 @@ static int gemm_tn(mdd_train_ws *w, const float *A, int lda, const float *Bm, in
 // precision 0: exact fp32 (gemm_f32 / split-K for the weight gradients).  precision 1 and a problem large enough to fill 256 x 256
 // tiles: both operands are written as bf16 hi/lo planes with the contraction along their rows' contiguous axis (transposed on the way
 // when the operand is stored [K, *]) and the product runs on the bf16 matrix cores (3 MFMA flops per flop, fp32 accumulate).
+// precision 2 (f32x6, reference width: gemm_bf16x6.hip) takes a problem when
+//     M >= 128 and N >= 128 (most of one 192 x 128 tile), K >= 64, M * N * K >= 2^27,
+//     lda, ldb and ldc are multiples of 4 and A, B and C are 16-byte aligned (the split kernels' 16-byte reads, the GEMM's 16-byte stores).
+// The product threshold is a quarter of the x3 path's 2^30 on purpose: below ~2^27 multiply-adds the exact kernel finishes in the time
+// of the x6 path's three or four launches; above it the six bf16 products win (tools/time_train_step.py has the kernel times at the
+// step's shapes).  Both operands go into xs_a / xs_b as three K-tile-major planes with the contraction zero-padded to whole K-tiles.
+// One launch when the output has enough tiles; the weight gradients' shape (fewer than 256 tiles of 192 x 128, K >= 512, no bias, ldc == N)
+// is cut into S chunks of at least 8 K-tiles, S x tiles as close to 256 workgroups as it gets, which run as ONE launch into `part` and are
+// summed by launch_reduce_parts in a fixed order.  Anything outside the rule runs as in precision 0, bit for bit.
 static int gemm_big(mdd_train_ws *w, bool ta, bool tb, const float *A, int lda, const float *Bm, int ldb, const float *bias, float *C, int ldc, int M, int N,
                     int K, hipStream_t st) {
     const bool x3 = w->precision == 1 && M >= 256 && N >= 256 && K >= 256 && ldc % 4 == 0 && (size_t)M * N * K >= ((size_t)1 << 30);
+    if (w->precision == 2 && M >= 128 && N >= 128 && K >= 64 && (size_t)M * N * K >= ((size_t)1 << 27) && x6_ops_ok(A, lda, Bm, ldb, C, ldc)) {
+        const int tiles = ((M + 191) / 192) * ((N + 127) / 128), nkt = (K + 31) / 32;
+        int S = 1;
+        if (tiles < 256 && K >= 512 && !bias && ldc == N) S = std::min(16, std::max(1, std::min(nkt / 8, 256 / tiles)));
+        return gemm_f32x6_ops(ta, tb, A, lda, Bm, ldb, bias, C, ldc, M, N, K, S, w->xs_a, w->xs_b, w->part, st);
+    }
     if (!x3) {
         if (ta && tb && !bias && ldc == N) return gemm_tn(w, A, lda, Bm, ldb, C, M, N, K, st);
         return launch_gemm_f32(ta, tb, A, Bm, bias, C, M, N, K, lda, ldb, ldc, 1, 0, 0, 0, false, st);
@@ -159,7 +175,9 @@ static int lstm_forward_layer(mdd_train_ws *w, LstmStepArgs &a, hipStream_t st) 
 using namespace mdd;
 
 extern "C" int mdd_train_set_precision(mdd_train_ws *w, int32_t mode) {
-    if (!w || (mode != 0 && mode != 1)) { set_error("mdd_train_set_precision: mode must be 0 (exact fp32) or 1 (split-bf16 x3 contractions)"); return MDD_ERR_ARG; }
+    if (!w || mode < 0 || mode > 2) {
+        set_error("mdd_train_set_precision: mode must be 0 (exact fp32), 1 (split-bf16 x3 contractions) or 2 (f32x6 contractions)"); return MDD_ERR_ARG;
+    }
     w->precision = mode;
     return MDD_OK;
 }
@@ -182,6 +200,7 @@ extern "C" int mdd_train_create(const mdd_config *cfg, int device, mdd_train_ws 
         set_error("mdd_train_create: out of memory"); return MDD_ERR_NOMEM;
     }
     if (int rc = init_gemm_attributes()) return rc;
+    if (int rc = init_gemm_x6_attributes()) return rc;
     if (int rc = init_granule_attributes()) return rc;
     if (int rc = init_conv1_attributes()) return rc;
     { int n_cu = 0; w->persist_ok = hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && persistent_grid_fits(n_cu) && !sw.lstm_step; }
@@ -216,7 +235,7 @@ static int train_forward_enqueue(mdd_train_ws *w, float *const *tensors, const f
 extern "C" int mdd_train_forward(mdd_train_ws *w, float *const *tensors, const float *x_dev, int32_t B, int32_t T, const int64_t *x1_dev, int32_t L,
                                  const uint8_t *const *masks, uint64_t seed, float p_drop, float *logp_dev, void *stream) {
     if (!w) { set_error("mdd_train_forward: null handle"); return MDD_ERR_ARG; }
-    const bool gated = w->precision == 1 && w->persist_ok;      // the forward then contains persistent launches: one at a time per device
+    const bool gated = w->precision == 1 && w->persist_ok;      // the forward then contains persistent launches: one at a time per device (mode 2 has none)
     bool held = false;
     if (gated) { MDD_HIP_CHECK(hipSetDevice(w->device)); if (int rc = device_gate_enter(w->device, (hipStream_t)stream, &held)) return rc; }
     const int rc = train_forward_enqueue(w, tensors, x_dev, B, T, x1_dev, L, masks, seed, p_drop, logp_dev, stream);

@@ -77,6 +77,10 @@ class TrainHandle(object):
             pass
 
 
+# model.train_precision -> mdd_train_set_precision: exact fp32 | flagged split-bf16 x3 | the large contractions as f32x6 (reference width)
+TRAIN_PRECISIONS = {"f32": 0, "bf16x3": 1, "f32x6": 2}
+
+
 class _TrainForward(torch.autograd.Function):
     """logp = CTC_Model.forward(x, x1) in train mode; backward hands every parameter its gradient."""
 
@@ -111,7 +115,9 @@ def model_forward_train(model, x, x1, masks=None, seed=None):
         model._train_handle = h
     want = getattr(model, "train_precision", None)          # None: the library default (exact fp32, or MDD_TRAIN_PRECISION)
     if want is not None and want != getattr(h, "precision", None):
-        _lib.check(_lib.lib().mdd_train_set_precision(h.handle, {"f32": 0, "bf16x3": 1}[want]))
+        if want not in TRAIN_PRECISIONS:
+            raise ValueError("train_precision %r: expected one of %s" % (want, ", ".join(repr(k) for k in TRAIN_PRECISIONS)))
+        _lib.check(_lib.lib().mdd_train_set_precision(h.handle, TRAIN_PRECISIONS[want]))
         h.precision = want
     sd = dict(model.named_parameters())
     sd.update(dict(model.named_buffers()))

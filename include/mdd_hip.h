@@ -293,12 +293,21 @@ int mdd_eval_batch(const int32_t *dec, const int32_t *dec_len, const int32_t *la
  *                               by 1/B as train_ctc.py:73-74 divides the loss) -> one gradient per parameter into grads[i]
  *                               (entries of running-statistics buffers are ignored and may be NULL)
  *   mdd_adam_step               torch.optim.Adam over n tensors (train_ctc.py:187: lr 1e-3, weight_decay 5e-4 added to the gradient)
- * Arithmetic is exact fp32 (v_mfma_f32_*), as the reference trains; mdd_train_set_precision(w, 1) (or MDD_TRAIN_PRECISION=bf16x3 at create)
- * sends the large projections and their two backward products through the split-bf16 x3 matrix-core GEMM of the decode path instead
- * (operands to 16 mantissa bits, fp32 accumulate); everything else stays fp32 in both modes. */
+ * Arithmetic: three modes, chosen per handle by mdd_train_set_precision (or MDD_TRAIN_PRECISION at create); they differ only in how the
+ * LARGE CONTRACTIONS of the step run -- the BiLSTM and text-encoder input projections, dW_ih, the dW_hh products and dX:
+ *   0 "f32"     exact fp32 MFMA (v_mfma_f32_*) everywhere, as the reference trains.  The default.
+ *   1 "bf16x3"  flagged variant: those contractions through the split-bf16 x3 matrix-core GEMM of the decode path (operands to 16
+ *               significand bits, fp32 accumulate) and the recurrences in the persistent split-bf16 layer kernels.  Narrower than the
+ *               reference: log-probs within 5e-4.
+ *   2 "f32x6"   reference width on the bf16 matrix cores: those contractions as f32x6 (every fp32 operand as three bf16 planes, six
+ *               products, fp32 accumulate: csrc/gemm_bf16x6.hip), the weight gradients with the contraction cut into chunks that run as
+ *               one launch and are summed afterwards (no atomics: run-to-run deterministic).  The recurrences -- forward and backward,
+ *               about half of the exact step -- and everything else are mode 0's kernels and bits; mode 2 meets mode 0's bounds.
+ * Fallback: in modes 1 and 2 a contraction outside the mode's size / alignment rule (the header comment of gemm_big, csrc/train.hip;
+ * mode 2: M, N >= 128, K >= 64, M.N.K >= 2^27, leading dimensions multiples of 4, 16-byte aligned operands) runs as in mode 0. */
 typedef struct mdd_train_ws mdd_train_ws;
 int mdd_train_create(const mdd_config *cfg, int device, mdd_train_ws **out);
-int mdd_train_set_precision(mdd_train_ws *w, int32_t mode);   /* 0 exact fp32 (default), 1 split-bf16 x3 contractions */
+int mdd_train_set_precision(mdd_train_ws *w, int32_t mode);   /* 0 exact fp32 (default), 1 split-bf16 x3, 2 f32x6 contractions */
 void mdd_train_destroy(mdd_train_ws *w);
 int32_t mdd_train_num_tensors(mdd_train_ws *w);
 int mdd_train_tensor_info(mdd_train_ws *w, int32_t i, char *key, int32_t cap, int64_t *numel, int32_t *is_buffer);
@@ -321,6 +330,13 @@ int mdd_diag_gemm_ph8(int M, int N, int K, int reps, unsigned seed, unsigned *mi
 /* mdd_diag_gemm: C_dev[M,N] = A_dev[M,K] . W_dev[N,K]^T through one arithmetic (0 exact fp32 MFMA, 1 split-bf16 x3, 2 the f32x6
  * prototype, 3 the f32x6 kernel), fp32 operands and result on the device; synchronises (tests/test_gpu_parity.py::test_gemm_f32x6_accuracy). */
 int mdd_diag_gemm(int mode, const float *A_dev, const float *W_dev, float *C_dev, int M, int N, int K, void *stream);
+/* mdd_diag_gemm_ops: C_dev[M,N] (row stride ldc) = opA . opB^T in the operand forms of the training step's large contractions:
+ * opA[m,k] = ta ? A_dev[k*lda + m] : A_dev[m*lda + k], opB[n,k] likewise with tb / ldb.  mode 0: the exact-fp32 kernels; mode 3: the f32x6
+ * path (operands split -- transposed on the way for ta / tb -- into K-tile-major planes with the contraction zero-padded to whole K-tiles);
+ * splits = 1 the one-launch form, splits > 1 the split-K form with that many chunks.  Any size: the training step's
+ * dispatch thresholds do not apply.  Synchronises (tests/test_train_f32x6.py). */
+int mdd_diag_gemm_ops(int mode, int ta, int tb, const float *A_dev, int lda, const float *B_dev, int ldb, float *C_dev, int ldc, int M, int N, int K,
+                      int splits, void *stream);
 /* mdd_diag_gemm_time: mean milliseconds of `reps` launches of one GEMM kernel on resident, pre-split pseudo-random operands. */
 int mdd_diag_gemm_time(int mode, int M, int N, int K, int reps, float *ms_out);
 /* mdd_diag_conv_time: mean milliseconds of `reps` launches of the f32x6 conv front end on pseudo-random features [B, T, 243] and weights.
