@@ -262,14 +262,13 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const float *__restrict__
         }
 }
 
-int launch_gemm_f32(bool ta, bool tb, const float *A, const float *B, const float *bias, float *C, int M, int N, int K, int lda, int ldb,
-                    int ldc, int batch, long sA, long sB, long sC, bool accumulate, hipStream_t st, int ksplit) {
-    if (M <= 0 || N <= 0 || K <= 0 || batch <= 0) { set_error("gemm_f32: bad shape %d %d %d x%d", M, N, K, batch); return MDD_ERR_ARG; }
+int launch_gemm_f32(const GemmOperand &A, const GemmOperand &B, float *C, int ldc, int M, int N, int K, hipStream_t st, const GemmOpts &o) {
+    if (M <= 0 || N <= 0 || K <= 0 || o.batch <= 0) { set_error("gemm_f32: bad shape %d %d %d x%d", M, N, K, o.batch); return MDD_ERR_ARG; }
     const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
-    if (ksplit > 0) batch = (K + ksplit - 1) / ksplit;     // split-K: `batch` partial products, C + z*sC each
+    const int batch = o.ksplit > 0 ? (K + o.ksplit - 1) / o.ksplit : o.batch;     // split-K: that many partial products, C + z*sC each
     dim3 grid(tiles_m * tiles_n, 1, batch), block(256);
-#define GO(TA_, TB_) hipLaunchKernelGGL((gemm_f32_kernel<TA_, TB_>), grid, block, 0, st, A, B, bias, C, M, N, K, lda, ldb, ldc, sA, sB, sC, tiles_n, accumulate ? 1 : 0, ksplit)
-    if (!ta && !tb) GO(false, false); else if (!ta && tb) GO(false, true); else if (ta && !tb) GO(true, false); else GO(true, true);
+#define GO(TA_, TB_) hipLaunchKernelGGL((gemm_f32_kernel<TA_, TB_>), grid, block, 0, st, A.p, B.p, o.bias, C, M, N, K, A.ld, B.ld, ldc, A.stride, B.stride, o.sC, tiles_n, o.accumulate ? 1 : 0, o.ksplit)
+    if (!A.k_major && !B.k_major) GO(false, false); else if (!A.k_major && B.k_major) GO(false, true); else if (A.k_major && !B.k_major) GO(true, false); else GO(true, true);
 #undef GO
     MDD_LAUNCH_CHECK();
     return MDD_OK;

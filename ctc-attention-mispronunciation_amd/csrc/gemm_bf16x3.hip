@@ -24,7 +24,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "mdd_internal.h"
+#include "train.h"
 
 namespace mdd {
 
@@ -486,6 +486,25 @@ int launch_gemm_bf16x3(const SplitPtr &A, const SplitPtr &W, const float *bias, 
                            (unsigned short *)nullptr, M, N, K, lda, ldw, ldc, sA, sW, sC, tn);
     MDD_LAUNCH_CHECK();
     return MDD_OK;
+}
+
+// C[M,N] (row stride ldc) = opA . opB^T (+ bias[N]) as split-bf16 x3, for the training step (the sibling of gemm_f32x6_ops): both operands
+// are written into xs_a / xs_b as bf16 hi/lo planes with the contraction along their rows' contiguous axis (transposed on the way when the
+// operand is stored [K, *]).  S > 1: the K axis is cut into S chunks that run as a batch of partial products (the planes' K axis is
+// contiguous, so chunk s starts s*Kc elements into every row), summed afterwards.
+int gemm_bf16x3_ops(const GemmOperand &A, const GemmOperand &B, const float *bias, float *C, int ldc, int M, int N, int K, int S, DeviceBuf &xs_a,
+                    DeviceBuf &xs_b, DeviceBuf &part, hipStream_t st) {
+    if (S < 1 || (S > 1 && (bias || ldc != N))) { set_error("gemm_bf16x3_ops: %d chunks need ldc == N and no bias", S); return MDD_ERR_ARG; }
+    const int Kc = ((K + S - 1) / S + 31) / 32 * 32, Kp = S * Kc;
+    if (int rc = xs_a.need((size_t)M * Kp)) return rc;
+    if (int rc = xs_b.need((size_t)N * Kp)) return rc;
+    SplitPtr sa{reinterpret_cast<unsigned short *>(xs_a.p), reinterpret_cast<unsigned short *>(xs_a.p) + (size_t)M * Kp};
+    SplitPtr sb{reinterpret_cast<unsigned short *>(xs_b.p), reinterpret_cast<unsigned short *>(xs_b.p) + (size_t)N * Kp};
+    if (int rc = A.k_major ? launch_transpose_split(A.p, A.ld, K, M, Kp, sa.hi, sa.lo, st) : launch_split_rows(A.p, A.ld, (size_t)M, K, Kp, sa.hi, sa.lo, st)) return rc;
+    if (int rc = B.k_major ? launch_transpose_split(B.p, B.ld, K, N, Kp, sb.hi, sb.lo, st) : launch_split_rows(B.p, B.ld, (size_t)N, K, Kp, sb.hi, sb.lo, st)) return rc;
+    if (S == 1) return launch_gemm_bf16x3(sa, sb, bias, C, nullptr, M, N, Kp, Kp, Kp, ldc, 1, 0, 0, 0, st);
+    return sum_parts(part, S, (size_t)M * N, C, st,
+                     [&](float *p) { return launch_gemm_bf16x3(sa, sb, nullptr, p, nullptr, M, N, Kc, Kp, Kp, N, S, Kc, Kc, (long)M * N, st); });
 }
 
 }  // namespace mdd

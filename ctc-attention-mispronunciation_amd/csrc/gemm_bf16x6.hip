@@ -446,13 +446,13 @@ int launch_gemm_f32x6_splitk(const unsigned short *A3, size_t a_plane, const uns
 // contraction zero-padded to S chunks of whole K-tiles.  S == 1: one launch of the decode path's kernel.  S > 1 (no bias): the split-K
 // launch into `part` and launch_reduce_parts (into C itself when ldc == N, as the step calls it; else into one more slot of `part`, copied
 // out row by row).  The caller has checked x6_ops_ok.
-bool x6_ops_ok(const float *A, int lda, const float *B, int ldb, const float *C, int ldc) {
-    return lda % 4 == 0 && ldb % 4 == 0 && ldc % 4 == 0 && (uintptr_t)A % 16 == 0 && (uintptr_t)B % 16 == 0 && (uintptr_t)C % 16 == 0;
+bool x6_ops_ok(const GemmOperand &A, const GemmOperand &B, const float *C, int ldc) {
+    return A.ld % 4 == 0 && B.ld % 4 == 0 && ldc % 4 == 0 && (uintptr_t)A.p % 16 == 0 && (uintptr_t)B.p % 16 == 0 && (uintptr_t)C % 16 == 0;
 }
-int gemm_f32x6_ops(bool ta, bool tb, const float *A, int lda, const float *B, int ldb, const float *bias, float *C, int ldc, int M, int N, int K, int S,
-                   DeviceBuf &xs_a, DeviceBuf &xs_b, DeviceBuf &part, hipStream_t st) {
-    if (M <= 0 || N <= 0 || K <= 0 || S < 1 || ldc < N || !x6_ops_ok(A, lda, B, ldb, C, ldc) || (S > 1 && bias)) {
-        set_error("gemm_f32x6_ops: M=%d N=%d K=%d S=%d lda=%d ldb=%d ldc=%d", M, N, K, S, lda, ldb, ldc); return MDD_ERR_ARG;
+int gemm_f32x6_ops(const GemmOperand &A, const GemmOperand &B, const float *bias, float *C, int ldc, int M, int N, int K, int S, DeviceBuf &xs_a,
+                   DeviceBuf &xs_b, DeviceBuf &part, hipStream_t st) {
+    if (M <= 0 || N <= 0 || K <= 0 || S < 1 || ldc < N || !x6_ops_ok(A, B, C, ldc) || (S > 1 && bias)) {
+        set_error("gemm_f32x6_ops: M=%d N=%d K=%d S=%d lda=%d ldb=%d ldc=%d", M, N, K, S, A.ld, B.ld, ldc); return MDD_ERR_ARG;
     }
     const int nkt = (K + X6_BK - 1) / X6_BK;
     if (S > nkt) S = nkt;
@@ -461,14 +461,14 @@ int gemm_f32x6_ops(bool ta, bool tb, const float *A, int lda, const float *B, in
     if (int rc = xs_a.need((3 * pa + 1) / 2)) return rc;
     if (int rc = xs_b.need((3 * pw + 1) / 2)) return rc;
     unsigned short *a3 = reinterpret_cast<unsigned short *>(xs_a.p), *w3 = reinterpret_cast<unsigned short *>(xs_b.p);
-    if (int rc = ta ? launch_transpose_split3(A, K, M, lda, Kp, a3, pa, st) : launch_split3_pad(A, M, K, lda, Kp, a3, pa, st)) return rc;
-    if (int rc = tb ? launch_transpose_split3(B, K, N, ldb, Kp, w3, pw, st) : launch_split3_pad(B, N, K, ldb, Kp, w3, pw, st)) return rc;
+    if (int rc = A.k_major ? launch_transpose_split3(A.p, K, M, A.ld, Kp, a3, pa, st) : launch_split3_pad(A.p, M, K, A.ld, Kp, a3, pa, st)) return rc;
+    if (int rc = B.k_major ? launch_transpose_split3(B.p, K, N, B.ld, Kp, w3, pw, st) : launch_split3_pad(B.p, N, K, B.ld, Kp, w3, pw, st)) return rc;
     if (S == 1) return launch_gemm_f32x6(a3, pa, w3, pw, bias, C, M, N, Kp, ldc, st, nullptr);
     const size_t mn = (size_t)M * N;
-    if (int rc = part.need((S + (ldc != N ? 1 : 0)) * mn)) return rc;
-    if (int rc = launch_gemm_f32x6_splitk(a3, pa, w3, pw, part.p, M, N, Kc, S, st)) return rc;
-    if (ldc == N) return launch_reduce_parts(part.p, S, mn, C, st);
-    if (int rc = launch_reduce_parts(part.p, S, mn, part.p + S * mn, st)) return rc;
+    auto partials = [&](float *p) { return launch_gemm_f32x6_splitk(a3, pa, w3, pw, p, M, N, Kc, S, st); };
+    if (ldc == N) return sum_parts(part, S, mn, C, st, partials);
+    if (int rc = part.need((S + 1) * mn)) return rc;          // one more slot for the sum, copied out row by row
+    if (int rc = sum_parts(part, S, mn, part.p + S * mn, st, partials)) return rc;
     return launch_copy_cols(part.p + S * mn, N, 0, C, ldc, 0, (size_t)M, N, false, st);
 }
 
@@ -483,11 +483,12 @@ extern "C" int mdd_diag_gemm_ops(int mode, int ta, int tb, const float *A_dev, i
         set_error("mdd_diag_gemm_ops: bad arguments"); return MDD_ERR_ARG;
     }
     int rc;
-    if (mode == 0) rc = launch_gemm_f32(ta != 0, tb != 0, A_dev, B_dev, nullptr, C_dev, M, N, K, lda, ldb, ldc, 1, 0, 0, 0, false, st);
+    const GemmOperand A{A_dev, lda, ta != 0}, B{B_dev, ldb, tb != 0};
+    if (mode == 0) rc = launch_gemm_f32(A, B, C_dev, ldc, M, N, K, st);
     else if (mode == 3) {
         DeviceBuf xa, xb, part;     // freed on return, behind the synchronisation
         rc = init_gemm_x6_attributes();
-        if (!rc) rc = gemm_f32x6_ops(ta != 0, tb != 0, A_dev, lda, B_dev, ldb, nullptr, C_dev, ldc, M, N, K, splits, xa, xb, part, st);
+        if (!rc) rc = gemm_f32x6_ops(A, B, nullptr, C_dev, ldc, M, N, K, splits, xa, xb, part, st);
         if (hipStreamSynchronize(st) != hipSuccess && !rc) { set_error("mdd_diag_gemm_ops: the stream failed"); rc = MDD_ERR_HIP; }
         return rc;
     } else { set_error("mdd_diag_gemm_ops: mode %d (0 exact fp32, 3 f32x6)", mode); return MDD_ERR_ARG; }

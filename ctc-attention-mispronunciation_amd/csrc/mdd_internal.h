@@ -58,9 +58,21 @@ struct SplitPtr { unsigned short *hi, *lo; };
 int launch_gemm_nt(const float *A, const float *W, const float *bias, float *C, int M, int N, int K, int lda, int ldw,
                    int ldc, int batch, long sA, long sW, long sC, hipStream_t st);
 
-// General fp32 GEMM (training step): C[m,n] (+)= sum_k opA[m,k] opB[n,k]; ta / tb: the operand is stored [K, rows] (see gemm.hip)
-int launch_gemm_f32(bool ta, bool tb, const float *A, const float *B, const float *bias, float *C, int M, int N, int K, int lda, int ldb,
-                    int ldc, int batch, long sA, long sB, long sC, bool accumulate, hipStream_t st, int ksplit = 0);
+// General fp32 GEMM (training step): C[m,n] (+)= sum_k opA[m,k] opB[n,k] (see gemm.hip).  Written at the call site with the field names:
+//   launch_gemm_f32({.p = dS, .ld = L, .stride = (long)Tp * L}, {.p = key, .ld = B * H2, .k_major = true, .stride = H2}, dX, B * H2, Tp, H2, L, st,
+//                   {.batch = B, .sC = H2, .accumulate = true});
+struct GemmOperand {
+    const float *p; int ld;    // op[r,k] = k_major ? p[k * ld + r] : p[r * ld + k]
+    bool k_major = false;      // the operand is stored [K, rows]
+    long stride = 0;           // elements from one matrix of a batch to the next
+};
+struct GemmOpts {
+    const float *bias = nullptr;   // [N], added to every row
+    int batch = 1; long sC = 0;    // `batch` products, C + z * sC each
+    bool accumulate = false;       // C += the product
+    int ksplit = 0;                // > 0: split-K instead of a batch -- partial product z contracts k in [z * ksplit, (z + 1) * ksplit) into C + z * sC
+};
+int launch_gemm_f32(const GemmOperand &A, const GemmOperand &B, float *C, int ldc, int M, int N, int K, hipStream_t st, const GemmOpts &o = GemmOpts());
 
 // C = A . W^T on the bf16 matrix cores with split-bf16 operands (see gemm_bf16x3.hip).  Output fp32 C, or a
 // split-bf16 tensor when Csplit != nullptr.  K % 32 == 0, ld* % 8 == 0.
@@ -104,9 +116,13 @@ int init_conv_attributes();
 
 // C = opA . opB^T (+ bias) as f32x6 in the training step's operand forms (ta / tb: stored [K, rows]); S > 1: split-K into `part` and a sum.
 // x6_ops_ok: the alignment half of the rule (leading dimensions multiples of 4, 16-byte aligned pointers).
-bool x6_ops_ok(const float *A, int lda, const float *B, int ldb, const float *C, int ldc);
-int gemm_f32x6_ops(bool ta, bool tb, const float *A, int lda, const float *B, int ldb, const float *bias, float *C, int ldc, int M, int N, int K, int S,
-                   DeviceBuf &xs_a, DeviceBuf &xs_b, DeviceBuf &part, hipStream_t st);
+bool x6_ops_ok(const GemmOperand &A, const GemmOperand &B, const float *C, int ldc);
+int gemm_f32x6_ops(const GemmOperand &A, const GemmOperand &B, const float *bias, float *C, int ldc, int M, int N, int K, int S, DeviceBuf &xs_a,
+                   DeviceBuf &xs_b, DeviceBuf &part, hipStream_t st);
+// The same for the split-bf16 x3 GEMM (gemm_bf16x3.hip): operands as hi/lo planes with the contraction along their rows, zero-padded to S chunks
+// of whole K-tiles; S > 1 (no bias, ldc == N): the chunks as a batch of partial products into `part` and a sum.
+int gemm_bf16x3_ops(const GemmOperand &A, const GemmOperand &B, const float *bias, float *C, int ldc, int M, int N, int K, int S, DeviceBuf &xs_a,
+                    DeviceBuf &xs_b, DeviceBuf &part, hipStream_t st);
 
 struct LstmStepArgs {
     const float *gx;     // [T][B][2][4H], gate columns permuted to u*4+g

@@ -45,6 +45,13 @@ int launch_softmax_rows(const float *x, size_t R, int n, float *y, bool log, hip
 int launch_softmax_bwd_rows(const float *y, const float *g, size_t R, int n, float *dx, bool log, hipStream_t st);
 int launch_embed_bwd(const float *g, const int64_t *ids, int B, int L, int E, int rows, float *dE, hipStream_t st);
 int launch_reduce_parts(const float *part, int parts, size_t n, float *out, hipStream_t st);
+// The tail of every "few output tiles, long contraction" product: `partials(p)` writes `parts` partial results of n floats each into p,
+// which are then summed into out in a fixed order (no atomics: the same bits on every run).
+template <class F> int sum_parts(DeviceBuf &part, int parts, size_t n, float *out, hipStream_t st, F partials) {
+    if (int rc = part.need((size_t)parts * n)) return rc;
+    if (int rc = partials(part.p)) return rc;
+    return launch_reduce_parts(part.p, parts, n, out, st);
+}
 int launch_pack_gates(const float *w_fwd, const float *w_rev, float *packed, int H, int K, hipStream_t st);
 int launch_unpack_gates(const float *packed, float *out_fwd, float *out_rev, int H, int K, hipStream_t st);
 int launch_transpose_whh(const float *w, float *wt, int H, hipStream_t st);

@@ -16,10 +16,39 @@
 
 #include "train.h"
 
-struct mdd_train_ws;
 namespace mdd {
 
 struct TInfo { std::string key; int64_t numel; int is_buffer; };
+
+// Where each tensor of the state_dict sits in tensors[] / grads[]: filled beside `info` at create, the only place that spells the keys.
+struct BnIdx { int weight, bias, running_mean, running_var; };
+struct LstmIdx { int w_ih[2], w_hh[2]; };                  // [forward, reverse]
+struct ParamTable {
+    struct Conv { int weight, bias; BnIdx bn; } conv[2];
+    std::vector<BnIdx> rnn_bn;                             // BatchNorm in front of acoustic layer n (n >= 1; entry 0 unused)
+    std::vector<LstmIdx> lstm;                             // acoustic layers 0..layers-1, then the text encoder
+    int embeds, text_b_ih[2], text_b_hh[2], score, fc_weight;
+    BnIdx fc_bn;
+};
+
+// Every size of one step, from (cfg, B, T, L).  BiLSTM n: 0..nl-1 the acoustic layers, nl the text encoder.
+struct StepDims {
+    int B, T, L, ch, H, H2, G2, Tp, W1, W2, Kin0, nl, E, C;
+    size_t R0, R1, R, Rt;                                  // rows of conv0's / conv1's output, of the acoustic and of the text sequence
+    StepDims(const mdd_config &c, int B_, int T_, int L_)
+        : B(B_), T(T_), L(L_), ch(c.channels), H(c.hidden), H2(2 * H), G2(8 * H), Tp(T / 2), W1(conv_out(c.feat)), W2(conv_out(W1)), Kin0(ch * W2),
+          nl(c.layers), E(c.emb_dim), C(c.num_class), R0((size_t)B * T * W1), R1((size_t)B * Tp * W2), R((size_t)Tp * B), Rt((size_t)L * B) {}
+    int K(int n) const { return n == nl ? E : n == 0 ? Kin0 : H2; }      // input width of BiLSTM n
+    int steps(int n) const { return n == nl ? L : Tp; }
+    size_t rows(int n) const { return n == nl ? Rt : R; }
+    // slots of the BatchNorm sites in the saved mean / invstd planes (stats_plane floats each)
+    int conv_slot(int i) const { return i * ch; }
+    int rnn_slot(int n) const { return 2 * ch + (n - 1) * H2; }
+    int fc_slot() const { return 2 * ch + nl * H2; }
+    int stats_plane() const { return fc_slot() + 2 * H2; }
+    // bytes of dropout mask `site` (conv0, conv1, rnn 0..nl-1)
+    int64_t mask_bytes(int site) const { return site == 0 ? (int64_t)R0 * ch : site == 1 ? (int64_t)R1 * ch : (int64_t)R * H2; }
+};
 
 }  // namespace mdd
 
@@ -28,146 +57,146 @@ struct mdd_train_ws {
     mdd_config cfg;
     int device = 0;
     std::vector<mdd::TInfo> info;
-    int B = 0, T = 0, L = 0;          // shapes of the saved forward
-    float p_drop = 0.f;
+    mdd::ParamTable params;
+    // The forward whose activations the buffers below hold.  valid: it was enqueued completely and no backward has used it yet (the backward
+    // overwrites saved activations, so it runs once per forward).  precision / conv1_direct: the kernels that forward chose; its backward
+    // follows them, whatever the handle's mode is by then.
+    struct Saved {
+        bool valid = false, conv1_direct = false;
+        int B = 0, T = 0, L = 0, precision = 0;
+        float p_drop = 0.f;
+        const int64_t *ids = nullptr; const float *x = nullptr;   // canonical ids and features (caller memory, must stay valid until backward)
+    } saved;
     // saved activations / scratch
-    mdd::DeviceBuf z0, a0, col1, w1r, z1, a1, seq0, gx, dgx, hb, cb, emb, text, key, att, cat, ycat, logits, logp;
+    mdd::DeviceBuf z0, a0, col1, w1r, z1, a1, seq0, gx, dgx, hb, cb, emb, text, key, att, cat, ycat, logits, logp, tbias;
     mdd::DeviceBuf stats;              // per-site mean / invstd
-    std::vector<mdd::DeviceBuf> xin, hraw, pd, gates, cst, wihp, whhp, whht;    // per rnn layer (index layers = the text encoder)
-    mdd::DeviceBuf tbias;
+    std::vector<mdd::DeviceBuf> xin, hraw, pd, gates, cst, wihp, whhp, whht;    // per BiLSTM (index layers = the text encoder)
     mdd::DeviceBuf d_a, d_b, d_c, part, dtext, dkey;      // backward temporaries
     mdd::DeviceBuf whhs, hx;           // flagged variant: W_hh' as hi/lo planes and the h exchange buffer of the persistent layer kernel
     mdd::DeviceArray<unsigned int> sync_words;
     bool persist_ok = false;           // the device can hold the persistent layer kernel's grid
     mdd::DeviceBuf xs_a, xs_b;         // operand planes of the GEMMs of modes 1 (hi plane, then lo plane) and 2 (hi | mid | lo); written afresh by every GEMM
-    int precision = 0;                 // 0: exact fp32 MFMA everywhere (the reference trains in fp32); 1: the large contractions as split-bf16 x3;
-                                       // 2: the large contractions as f32x6 (reference width), everything else as 0
+    int precision = 0;                 // mode of the NEXT forward.  0: exact fp32 MFMA everywhere (the reference trains in fp32); 1: the large contractions
+                                       // as split-bf16 x3; 2: the large contractions as f32x6 (reference width), everything else as 0
     bool conv1_im2col = false;         // MDD_TRAIN_CONV1_IM2COL at create
     mdd::DeviceArray<int> err_flag;    // set by the embedding gather on an id outside the table
-    mdd::DeviceBuf masks;              // generated dropout masks (bytes)
+    mdd::DeviceBuf masks, maskt;       // generated dropout masks (bytes); the conv sites' in channels-last order
     std::vector<const unsigned char *> mask_ptr;
     const unsigned char *mask_rows[2] = {nullptr, nullptr};   // the two conv sites' masks in channels-last order
-    mdd::DeviceBuf maskt;
     mdd::DeviceArray<double> dacc;     // fp64 column sums
-    const int64_t *ids = nullptr;      // canonical ids of the saved forward (caller memory, must stay valid until backward)
-    const float *x = nullptr;
 };
+
+#define TRY(expr) do { if (int rc_ = (expr)) return rc_; } while (0)
 
 namespace mdd {
 
-static int W1_of(const mdd_config &c) { return conv_out(c.feat); }
-static int W2_of(const mdd_config &c) { return conv_out(W1_of(c)); }
-
-// conv1 of a step, forward and backward alike: the direct kernels (train_conv1.hip), else im2col + GEMM
-static bool conv1_direct(const mdd_train_ws *w) { return w->cfg.channels == 32 && W1_of(w->cfg) <= 128 && !w->conv1_im2col; }
-
 static void build_info(mdd_train_ws *w) {
     const mdd_config &c = w->cfg;
-    const int ch = c.channels, H = c.hidden, Kin0 = ch * W2_of(c);
-    auto add = [&](const std::string &k, int64_t n, int buf = 0) { w->info.push_back(TInfo{k, n, buf}); };
-    auto bn = [&](const std::string &p, int n) { add(p + ".weight", n); add(p + ".bias", n); add(p + ".running_mean", n, 1); add(p + ".running_var", n, 1); };
-    add("conv.0.conv.weight", (int64_t)ch * 9); add("conv.0.conv.bias", ch); bn("conv.0.batch_norm", ch);
-    add("conv.1.conv.weight", (int64_t)ch * ch * 9); add("conv.1.conv.bias", ch); bn("conv.1.batch_norm", ch);
-    for (int n = 0; n < c.layers; n++) {
-        const std::string r = "rnns." + std::to_string(n);
-        const int K = n == 0 ? Kin0 : 2 * H;
-        if (n > 0) bn(r + ".batch_norm", 2 * H);
-        for (const char *sfx : {"", "_reverse"}) {
-            add(r + ".rnn.weight_ih_l0" + sfx, (int64_t)4 * H * K);
-            add(r + ".rnn.weight_hh_l0" + sfx, (int64_t)4 * H * H);
+    const StepDims d(c, 1, 2, 1);
+    const int H = d.H, ch = d.ch;
+    ParamTable &p = w->params;
+    auto add = [&](const std::string &k, int64_t n, int buf = 0) { w->info.push_back(TInfo{k, n, buf}); return (int)w->info.size() - 1; };
+    auto bn = [&](const std::string &k, int n) { return BnIdx{add(k + ".weight", n), add(k + ".bias", n), add(k + ".running_mean", n, 1), add(k + ".running_var", n, 1)}; };
+    p.conv[0] = {add("conv.0.conv.weight", (int64_t)ch * 9), add("conv.0.conv.bias", ch), bn("conv.0.batch_norm", ch)};
+    p.conv[1] = {add("conv.1.conv.weight", (int64_t)ch * ch * 9), add("conv.1.conv.bias", ch), bn("conv.1.batch_norm", ch)};
+    p.rnn_bn.assign(d.nl, BnIdx{-1, -1, -1, -1});
+    p.lstm.resize(d.nl + 1);
+    auto lstm = [&](const std::string &k, int n, bool bias) {          // one nn.LSTM: per direction weight_ih, weight_hh (, bias_ih, bias_hh)
+        for (int dir = 0; dir < 2; dir++) {
+            const char *sfx = dir ? "_l0_reverse" : "_l0";
+            p.lstm[n].w_ih[dir] = add(k + "weight_ih" + sfx, (int64_t)4 * H * d.K(n)); p.lstm[n].w_hh[dir] = add(k + "weight_hh" + sfx, (int64_t)4 * H * H);
+            if (bias) { p.text_b_ih[dir] = add(k + "bias_ih" + sfx, 4 * H); p.text_b_hh[dir] = add(k + "bias_hh" + sfx, 4 * H); }
         }
+    };
+    for (int n = 0; n < d.nl; n++) {
+        if (n > 0) p.rnn_bn[n] = bn("rnns." + std::to_string(n) + ".batch_norm", 2 * H);
+        lstm("rnns." + std::to_string(n) + ".rnn.", n, false);
     }
-    add("embeds.weight", (int64_t)c.emb_rows * c.emb_dim);
-    for (const char *sfx : {"", "_reverse"}) {
-        add(std::string("lstm_embeds.weight_ih_l0") + sfx, (int64_t)4 * H * c.emb_dim);
-        add(std::string("lstm_embeds.weight_hh_l0") + sfx, (int64_t)4 * H * H);
-        add(std::string("lstm_embeds.bias_ih_l0") + sfx, 4 * H);
-        add(std::string("lstm_embeds.bias_hh_l0") + sfx, 4 * H);
-    }
-    add("score.weight", (int64_t)4 * H * H);
-    bn("fc.0", 4 * H);
-    add("fc.1.weight", (int64_t)c.num_class * 4 * H);
+    p.embeds = add("embeds.weight", (int64_t)c.emb_rows * c.emb_dim);
+    lstm("lstm_embeds.", d.nl, true);
+    p.score = add("score.weight", (int64_t)4 * H * H);
+    p.fc_bn = bn("fc.0", 4 * H);
+    p.fc_weight = add("fc.1.weight", (int64_t)c.num_class * 4 * H);
 }
 
-static int idx(const mdd_train_ws *w, const std::string &key) {
-    for (size_t i = 0; i < w->info.size(); i++) if (w->info[i].key == key) return (int)i;
-    return -1;
+// "Few output tiles, long contraction" (the weight gradients, the classifier): the contraction is cut into chunks that run as partial products and
+// are summed afterwards (sum_parts), so the whole chip works on it.  One rule per arithmetic: fewer than max_tiles output tiles of tile_m x 128 and
+// K >= min_k -> min(max_chunks, max(1, min(K' / k_unit, wg_budget / tiles))) chunks, K' = K rounded up to k_round.  The exact kernels cut K into
+// chunks of ceil(K / chunks), or of k_unit itself (fixed_len).  The values decide the order of summation, i.e. the bits.
+enum class Arith { Exact, X3, X6, Classifier };
+struct SplitRule { int tile_m, max_tiles, min_k, k_round, k_unit, wg_budget, max_chunks; bool fixed_len; };
+static const SplitRule kSplitRules[] = {
+    /* Exact      */ {128, 256, 1025, 1, 512, 512, 64, false},
+    /* X3         */ {128, 256, 2049, 1, 1024, 512, 16, false},
+    /* X6         */ {192, 256, 512, 32, 256, 256, 16, false},       // K' / 256 = K-tiles of 32 / 8: chunks of at least 8 K-tiles
+    /* Classifier */ {128, 128, 1024, 256, 256, 1 << 30, 1 << 30, true},   // [R, 4H] x [C, 4H]^T: one column tile, 63 row tiles at R = 8000; chunks of 256
+};
+static int split_chunks(Arith a, int M, int N, int K) {
+    const SplitRule &r = kSplitRules[(int)a];
+    const int tiles = ((M + r.tile_m - 1) / r.tile_m) * ((N + 127) / 128);
+    if (tiles >= r.max_tiles || K < r.min_k) return 1;
+    return std::min(r.max_chunks, std::max(1, std::min((K + r.k_round - 1) / r.k_round * r.k_round / r.k_unit, r.wg_budget / tiles)));
 }
 
-// C[M,N] = A^T . B over K rows (A stored [K, M...] with lda, B stored [K, N...] with ldb): weight gradients.  Few output tiles and a
-// long contraction -> split-K into `part` + a reduction, so the whole chip works on it.
-static int gemm_tn(mdd_train_ws *w, const float *A, int lda, const float *Bm, int ldb, float *C, int M, int N, int K, hipStream_t st) {
-    const int tiles = ((M + 127) / 128) * ((N + 127) / 128);
-    int nsplit = 1;
-    if (tiles < 256 && K > 1024) nsplit = std::min(64, std::max(1, std::min(K / 512, 512 / tiles)));
-    if (nsplit <= 1) return launch_gemm_f32(true, true, A, Bm, nullptr, C, M, N, K, lda, ldb, N, 1, 0, 0, 0, false, st);
-    const int kc = (K + nsplit - 1) / nsplit, parts = (K + kc - 1) / kc;
-    if (int rc = w->part.need((size_t)parts * M * N)) return rc;
-    if (int rc = launch_gemm_f32(true, true, A, Bm, nullptr, w->part.p, M, N, K, lda, ldb, N, 1, 0, 0, (long)M * N, false, st, kc)) return rc;
-    return launch_reduce_parts(w->part.p, parts, (size_t)M * N, C, st);
+// C[M,N] (ldc == N, no bias) = opA . opB^T in exact fp32, split by `rule` (Exact or Classifier)
+static int gemm_f32_split(mdd_train_ws *w, Arith rule, const GemmOperand &A, const GemmOperand &B, float *C, int M, int N, int K, hipStream_t st) {
+    const int chunks = split_chunks(rule, M, N, K);
+    if (chunks <= 1) return launch_gemm_f32(A, B, C, N, M, N, K, st);
+    const int kc = kSplitRules[(int)rule].fixed_len ? kSplitRules[(int)rule].k_unit : (K + chunks - 1) / chunks;
+    return sum_parts(w->part, (K + kc - 1) / kc, (size_t)M * N, C, st,
+                     [&](float *part) { return launch_gemm_f32(A, B, part, N, M, N, K, st, {.sC = (long)M * N, .ksplit = kc}); });
 }
 
-// C[M,N] = opA . opB^T for the large contractions of the step; opA[m,k] = ta ? A[k*lda + m] : A[m*lda + k], opB[n,k] likewise.
-// precision 0: exact fp32 (gemm_f32 / split-K for the weight gradients).  precision 1 and a problem large enough to fill 256 x 256
-// tiles: both operands are written as bf16 hi/lo planes with the contraction along their rows' contiguous axis (transposed on the way
-// when the operand is stored [K, *]) and the product runs on the bf16 matrix cores (3 MFMA flops per flop, fp32 accumulate).
-// precision 2 (f32x6, reference width: gemm_bf16x6.hip) takes a problem when
-//     M >= 128 and N >= 128 (most of one 192 x 128 tile), K >= 64, M * N * K >= 2^27,
-//     lda, ldb and ldc are multiples of 4 and A, B and C are 16-byte aligned (the split kernels' 16-byte reads, the GEMM's 16-byte stores).
-// The product threshold is a quarter of the x3 path's 2^30 on purpose: below ~2^27 multiply-adds the exact kernel finishes in the time
-// of the x6 path's three or four launches; above it the six bf16 products win (tools/time_train_step.py has the kernel times at the
-// step's shapes).  Both operands go into xs_a / xs_b as three K-tile-major planes with the contraction zero-padded to whole K-tiles.
-// One launch when the output has enough tiles; the weight gradients' shape (fewer than 256 tiles of 192 x 128, K >= 512, no bias, ldc == N)
-// is cut into S chunks of at least 8 K-tiles, S x tiles as close to 256 workgroups as it gets, which run as ONE launch into `part` and are
-// summed by launch_reduce_parts in a fixed order.  Anything outside the rule runs as in precision 0, bit for bit.
-static int gemm_big(mdd_train_ws *w, bool ta, bool tb, const float *A, int lda, const float *Bm, int ldb, const float *bias, float *C, int ldc, int M, int N,
-                    int K, hipStream_t st) {
-    const bool x3 = w->precision == 1 && M >= 256 && N >= 256 && K >= 256 && ldc % 4 == 0 && (size_t)M * N * K >= ((size_t)1 << 30);
-    if (w->precision == 2 && M >= 128 && N >= 128 && K >= 64 && (size_t)M * N * K >= ((size_t)1 << 27) && x6_ops_ok(A, lda, Bm, ldb, C, ldc)) {
-        const int tiles = ((M + 191) / 192) * ((N + 127) / 128), nkt = (K + 31) / 32;
-        int S = 1;
-        if (tiles < 256 && K >= 512 && !bias && ldc == N) S = std::min(16, std::max(1, std::min(nkt / 8, 256 / tiles)));
-        return gemm_f32x6_ops(ta, tb, A, lda, Bm, ldb, bias, C, ldc, M, N, K, S, w->xs_a, w->xs_b, w->part, st);
-    }
-    if (!x3) {
-        if (ta && tb && !bias && ldc == N) return gemm_tn(w, A, lda, Bm, ldb, C, M, N, K, st);
-        return launch_gemm_f32(ta, tb, A, Bm, bias, C, M, N, K, lda, ldb, ldc, 1, 0, 0, 0, false, st);
-    }
-    // few output tiles and a long contraction (the weight gradients): the K axis is cut into S chunks that run as a batch of partial
-    // products (the planes' K axis is contiguous, so chunk s starts s*Kc elements into every row), summed afterwards.
-    const int tiles = ((M + 127) / 128) * ((N + 127) / 128);
-    int S = 1;
-    if (tiles < 256 && K > 2048 && !bias && ldc == N) S = std::min(16, std::max(1, std::min(K / 1024, 512 / tiles)));
-    const int Kc = ((K + S - 1) / S + 31) / 32 * 32, Kp = S * Kc;
-    if (int rc = w->xs_a.need((size_t)M * Kp)) return rc;
-    if (int rc = w->xs_b.need((size_t)N * Kp)) return rc;
-    SplitPtr sa{reinterpret_cast<unsigned short *>(w->xs_a.p), reinterpret_cast<unsigned short *>(w->xs_a.p) + (size_t)M * Kp};
-    SplitPtr sb{reinterpret_cast<unsigned short *>(w->xs_b.p), reinterpret_cast<unsigned short *>(w->xs_b.p) + (size_t)N * Kp};
-    if (int rc = ta ? launch_transpose_split(A, lda, K, M, Kp, sa.hi, sa.lo, st) : launch_split_rows(A, lda, (size_t)M, K, Kp, sa.hi, sa.lo, st)) return rc;
-    if (int rc = tb ? launch_transpose_split(Bm, ldb, K, N, Kp, sb.hi, sb.lo, st) : launch_split_rows(Bm, ldb, (size_t)N, K, Kp, sb.hi, sb.lo, st)) return rc;
-    if (S == 1) return launch_gemm_bf16x3(sa, sb, bias, C, nullptr, M, N, Kp, Kp, Kp, ldc, 1, 0, 0, 0, st);
-    if (int rc = w->part.need((size_t)S * M * N)) return rc;
-    if (int rc = launch_gemm_bf16x3(sa, sb, nullptr, w->part.p, nullptr, M, N, Kc, Kp, Kp, N, S, Kc, Kc, (long)M * N, st)) return rc;
-    return launch_reduce_parts(w->part.p, S, (size_t)M * N, C, st);
+// C[M,N] = opA . opB^T (+ bias) for the large contractions of the step, in the arithmetic of the saved forward's mode.  A dispatcher:
+//   mode 2 (f32x6, reference width: gemm_f32x6_ops)  M, N >= 128 (most of one 192 x 128 tile), K >= 64, M * N * K >= 2^27, lda, ldb and ldc multiples
+//          of 4 and A, B and C 16-byte aligned (the split kernels' 16-byte reads, the GEMM's 16-byte stores).  The threshold is a quarter of mode 1's
+//          on purpose: below ~2^27 multiply-adds the exact kernel finishes in the time of the x6 path's three or four launches (tools/time_train_step.py).
+//   mode 1 (split-bf16 x3: gemm_bf16x3_ops)  a problem large enough to fill 256 x 256 tiles: M, N, K >= 256, ldc a multiple of 4, M * N * K >= 2^30.
+//   otherwise, and in mode 0: exact fp32, bit for bit the same in every mode.
+// A product without bias and with ldc == N may be cut along K (split_chunks); in exact fp32 only the weight gradients' form (both stored [K, *]) is.
+static int gemm_big(mdd_train_ws *w, const GemmOperand &A, const GemmOperand &B, const float *bias, float *C, int ldc, int M, int N, int K, hipStream_t st) {
+    const int mode = w->saved.precision;
+    const size_t macs = (size_t)M * N * K;
+    const bool may_split = !bias && ldc == N;
+    if (mode == 2 && M >= 128 && N >= 128 && K >= 64 && macs >= ((size_t)1 << 27) && x6_ops_ok(A, B, C, ldc))
+        return gemm_f32x6_ops(A, B, bias, C, ldc, M, N, K, may_split ? split_chunks(Arith::X6, M, N, K) : 1, w->xs_a, w->xs_b, w->part, st);
+    if (mode == 1 && M >= 256 && N >= 256 && K >= 256 && ldc % 4 == 0 && macs >= ((size_t)1 << 30))
+        return gemm_bf16x3_ops(A, B, bias, C, ldc, M, N, K, may_split ? split_chunks(Arith::X3, M, N, K) : 1, w->xs_a, w->xs_b, w->part, st);
+    if (may_split && A.k_major && B.k_major) return gemm_f32_split(w, Arith::Exact, A, B, C, M, N, K, st);
+    return launch_gemm_f32(A, B, C, ldc, M, N, K, st, {.bias = bias});
 }
 
+// BiLSTM n of the forward (0..nl-1 the acoustic layers, nl the text encoder, which alone has a bias): gate-packed weights, input projection into gx,
+// the recurrence into hraw[n] with gates and cell states saved for the backward pass.  Exact mode: one launch per step, fp32 MFMA.  Flagged
+// split-bf16 variant on a device that holds the persistent grid: the decode path's layer kernel (one launch, W_hh' resident in registers as
+// bf16 hi/lo fragments, h exchanged inside 8-workgroup teams) with the saves added.
+static int bilstm_forward(mdd_train_ws *w, const StepDims &d, float *const *tensors, int n, const float *xin, const float *bias, hipStream_t st) {
+    const LstmIdx &p = w->params.lstm[n];
+    const int H = d.H, K = d.K(n);
+    TRY(launch_pack_gates(tensors[p.w_ih[0]], tensors[p.w_ih[1]], w->wihp[n].p, H, K, st));
+    TRY(launch_pack_gates(tensors[p.w_hh[0]], tensors[p.w_hh[1]], w->whhp[n].p, H, H, st));
+    TRY(gemm_big(w, {.p = xin, .ld = K}, {.p = w->wihp[n].p, .ld = K}, bias, w->gx.p, d.G2, (int)d.rows(n), d.G2, K, st));
+    LstmStepArgs a;
+    a.gx = w->gx.p; a.whh = w->whhp[n].p; a.hbuf = w->hb.p; a.cbuf = w->cb.p; a.out = a.out_raw = w->hraw[n].p; a.T = d.steps(n); a.B = d.B; a.H = H;
+    a.whh_split = SplitPtr{nullptr, nullptr}; a.hsplit = nullptr; a.packed = 0; a.gates_save = w->gates[n].p; a.c_save = w->cst[n].p;
+    if (w->saved.precision != 1 || !w->persist_ok || (H != 384 && H != 256) || d.B > 512) return launch_lstm_layer_train(a, st);
+    const size_t nW = (size_t)8 * H * H;
+    TRY(w->whhs.need(nW));
+    unsigned short *hi = reinterpret_cast<unsigned short *>(w->whhs.p), *lo = hi + nW;
+    TRY(launch_split_rows(a.whh, H, (size_t)8 * H, H, H, hi, lo, st));
+    a.whh_split = SplitPtr{hi, lo};
+    a.out = nullptr;
+    TRY(w->hx.need(team8_hx_alloc_floats(H, d.B) + kHxTailFloats));
+    return launch_lstm_layer_granule(a, reinterpret_cast<unsigned short *>(w->hx.p), w->sync_words.p, w->err_flag.p + 1, st);
+}
 
-// One bidirectional layer of the training forward (gates and cell states saved for the backward pass).  Exact mode: one launch per
-// step, fp32 MFMA.  Flagged split-bf16 variant on a device that holds the persistent grid: the decode path's layer kernel (one
-// launch, W_hh' resident in registers as bf16 hi/lo fragments, h exchanged inside 8-workgroup teams) with the saves added.
-static int lstm_forward_layer(mdd_train_ws *w, LstmStepArgs &a, hipStream_t st) {
-    const int H = a.H;
-    if (w->precision == 1 && w->persist_ok && (H == 384 || H == 256) && a.B <= 512) {
-        const size_t nW = (size_t)8 * H * H;
-        if (int rc = w->whhs.need(nW)) return rc;
-        unsigned short *hi = reinterpret_cast<unsigned short *>(w->whhs.p), *lo = hi + nW;
-        if (int rc = launch_split_rows(a.whh, H, (size_t)8 * H, H, H, hi, lo, st)) return rc;
-        a.whh_split = SplitPtr{hi, lo};
-        a.out = nullptr;
-        if (int rc = w->hx.need(team8_hx_alloc_floats(H, a.B) + kHxTailFloats)) return rc;
-        return launch_lstm_layer_granule(a, reinterpret_cast<unsigned short *>(w->hx.p), w->sync_words.p, w->err_flag.p + 1, st);
-    }
-    return launch_lstm_layer_train(a, st);
+// Work that may contain persistent launches (mode 1 on a device that holds their grid): one at a time per device.  Mode 2 has none.
+template <class F> static int with_device_gate(mdd_train_ws *w, int precision, void *stream, F body) {
+    const bool gated = precision == 1 && w->persist_ok;
+    bool held = false;
+    if (gated) { MDD_HIP_CHECK(hipSetDevice(w->device)); if (int rc = device_gate_enter(w->device, (hipStream_t)stream, &held)) return rc; }
+    const int rc = body();
+    return gated ? device_gate_leave(w->device, (hipStream_t)stream, held, rc) : rc;
 }
 
 }  // namespace mdd
@@ -190,7 +219,7 @@ extern "C" int mdd_train_create(const mdd_config *cfg, int device, mdd_train_ws 
     MDD_HIP_CHECK(hipSetDevice(device));
     std::unique_ptr<mdd_train_ws> w(new mdd_train_ws());
     w->cfg = *cfg; w->device = device;
-    const Switches sw = read_switches();   // the environment at create (plan.h): forward and backward of a step then always agree
+    const Switches sw = read_switches();   // the environment at create (plan.h); the mode can change later, a backward follows its own forward (Saved)
     w->precision = sw.train_precision;
     w->conv1_im2col = sw.train_conv1_im2col;
     build_info(w.get());
@@ -199,10 +228,7 @@ extern "C" int mdd_train_create(const mdd_config *cfg, int device, mdd_train_ws 
     if (w->dacc.need(2 * 8192) || w->err_flag.need(2) || hipMemset(w->err_flag.p, 0, 2 * sizeof(int)) != hipSuccess || w->sync_words.need(32)) {
         set_error("mdd_train_create: out of memory"); return MDD_ERR_NOMEM;
     }
-    if (int rc = init_gemm_attributes()) return rc;
-    if (int rc = init_gemm_x6_attributes()) return rc;
-    if (int rc = init_granule_attributes()) return rc;
-    if (int rc = init_conv1_attributes()) return rc;
+    TRY(init_gemm_attributes()); TRY(init_gemm_x6_attributes()); TRY(init_granule_attributes()); TRY(init_conv1_attributes());
     { int n_cu = 0; w->persist_ok = hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && persistent_grid_fits(n_cu) && !sw.lstm_step; }
     if (8 * cfg->hidden > 8192) { set_error("mdd_train_create: hidden too large for the statistics scratch"); return MDD_ERR_ARG; }
     *out = w.release();
@@ -221,172 +247,128 @@ extern "C" int mdd_train_tensor_info(mdd_train_ws *w, int32_t i, char *key, int3
 extern "C" int32_t mdd_train_num_masks(mdd_train_ws *w) { return w ? 2 + w->cfg.layers : 0; }
 extern "C" int64_t mdd_train_mask_bytes(mdd_train_ws *w, int32_t site, int32_t B, int32_t T) {
     if (!w || site < 0 || site >= 2 + w->cfg.layers) return -1;
-    const mdd_config &c = w->cfg;
-    if (site == 0) return (int64_t)B * c.channels * T * W1_of(c);
-    if (site == 1) return (int64_t)B * c.channels * (T / 2) * W2_of(c);
-    return (int64_t)(T / 2) * B * 2 * c.hidden;
+    return StepDims(w->cfg, B, T, 1).mask_bytes(site);
 }
 
-#define P(key) (tensors[idx(w, key)])
-#define TRY(expr) do { if (int rc_ = (expr)) return rc_; } while (0)
-
 static int train_forward_enqueue(mdd_train_ws *w, float *const *tensors, const float *x_dev, int32_t B, int32_t T, const int64_t *x1_dev, int32_t L,
-                                 const uint8_t *const *masks, uint64_t seed, float p_drop, float *logp_dev, void *stream);
-extern "C" int mdd_train_forward(mdd_train_ws *w, float *const *tensors, const float *x_dev, int32_t B, int32_t T, const int64_t *x1_dev, int32_t L,
-                                 const uint8_t *const *masks, uint64_t seed, float p_drop, float *logp_dev, void *stream) {
-    if (!w) { set_error("mdd_train_forward: null handle"); return MDD_ERR_ARG; }
-    const bool gated = w->precision == 1 && w->persist_ok;      // the forward then contains persistent launches: one at a time per device (mode 2 has none)
-    bool held = false;
-    if (gated) { MDD_HIP_CHECK(hipSetDevice(w->device)); if (int rc = device_gate_enter(w->device, (hipStream_t)stream, &held)) return rc; }
-    const int rc = train_forward_enqueue(w, tensors, x_dev, B, T, x1_dev, L, masks, seed, p_drop, logp_dev, stream);
-    return gated ? device_gate_leave(w->device, (hipStream_t)stream, held, rc) : rc;
-}
-static int train_forward_enqueue(mdd_train_ws *w, float *const *tensors, const float *x_dev, int32_t B, int32_t T, const int64_t *x1_dev, int32_t L,
-                                 const uint8_t *const *masks, uint64_t seed, float p_drop, float *logp_dev, void *stream) {
-    if (!w || !tensors || !x_dev || !x1_dev || !logp_dev || B <= 0 || T < 2 || (T & 1) || L <= 0 || p_drop < 0.f || p_drop >= 1.f) {
+                                 const uint8_t *const *masks, uint64_t seed, float p_drop, float *logp_dev, hipStream_t st) {
+    if (!tensors || !x_dev || !x1_dev || !logp_dev || B <= 0 || T < 2 || (T & 1) || L <= 0 || p_drop < 0.f || p_drop >= 1.f) {
         set_error("mdd_train_forward: bad argument"); return MDD_ERR_ARG;
     }
     MDD_HIP_CHECK(hipSetDevice(w->device));
-    hipStream_t st = (hipStream_t)stream;
     const mdd_config &c = w->cfg;
-    const int ch = c.channels, H = c.hidden, H2 = 2 * H, G2 = 8 * H, Tp = T / 2, W1 = W1_of(c), W2 = W2_of(c), Kin0 = ch * W2, nl = c.layers, E = c.emb_dim, C = c.num_class;
-    const size_t R0 = (size_t)B * T * W1, R1 = (size_t)B * Tp * W2, R = (size_t)Tp * B, Rt = (size_t)L * B;
-    const float scale = 1.f / (1.f - p_drop), eps = c.bn_eps, mom = 0.1f;
-    w->B = B; w->T = T; w->L = L; w->p_drop = p_drop; w->ids = x1_dev; w->x = x_dev;
+    const ParamTable &p = w->params;
+    const StepDims d(c, B, T, L);
+    const int ch = d.ch, H = d.H, H2 = d.H2, G2 = d.G2, Tp = d.Tp, W1 = d.W1, W2 = d.W2, nl = d.nl, E = d.E, C = d.C;
+    const size_t R0 = d.R0, R1 = d.R1, R = d.R, Rt = d.Rt;
+    const float scale = 1.f / (1.f - p_drop);
+    w->saved.B = B; w->saved.T = T; w->saved.L = L; w->saved.p_drop = p_drop; w->saved.ids = x1_dev; w->saved.x = x_dev; w->saved.precision = w->precision;
+    const bool direct1 = w->saved.conv1_direct = ch == 32 && W1 <= 128 && !w->conv1_im2col;    // conv1: the direct kernels (train_conv1.hip), else im2col + GEMM
     // ---- buffers
     TRY(w->z0.need(R0 * ch)); TRY(w->a0.need(R0 * ch)); TRY(w->w1r.need((size_t)ch * 9 * ch));
-    const bool direct1 = conv1_direct(w);
     if (!direct1) TRY(w->col1.need(R1 * 9 * ch));
-    TRY(w->z1.need(R1 * ch)); TRY(w->a1.need(R1 * ch)); TRY(w->seq0.need(R * Kin0));
+    TRY(w->z1.need(R1 * ch)); TRY(w->a1.need(R1 * ch)); TRY(w->seq0.need(R * d.Kin0));
     TRY(w->gx.need(std::max(R, Rt) * G2)); TRY(w->hb.need((size_t)4 * B * H)); TRY(w->cb.need((size_t)2 * B * H));
     TRY(w->emb.need(Rt * E)); TRY(w->key.need(Rt * H2)); TRY(w->att.need((size_t)B * Tp * L));
     TRY(w->cat.need(R * 2 * H2)); TRY(w->ycat.need(R * 2 * H2)); TRY(w->logits.need(R * C)); TRY(w->logp.need(R * C));
-    TRY(w->stats.need((size_t)2 * (2 * ch + nl * H2 + 2 * H2) + 64)); TRY(w->tbias.need(G2));
+    TRY(w->stats.need((size_t)2 * d.stats_plane() + 64)); TRY(w->tbias.need(G2)); TRY(w->d_a.need(G2));
     for (int n = 0; n <= nl; n++) {
-        const size_t rows = n < nl ? R : Rt;
-        const int K = n == nl ? E : (n == 0 ? Kin0 : H2);
+        const size_t rows = d.rows(n), K = d.K(n);
         if (n > 0 && n < nl) TRY(w->xin[n].need(rows * K));
         TRY(w->hraw[n].need(rows * H2)); if (n < nl) TRY(w->pd[n].need(rows * H2));
         TRY(w->gates[n].need(rows * 2 * H * 4)); TRY(w->cst[n].need(rows * 2 * H));
-        TRY(w->wihp[n].need((size_t)G2 * K)); TRY(w->whhp[n].need((size_t)G2 * H)); TRY(w->whht[n].need((size_t)G2 * H));
+        TRY(w->wihp[n].need(G2 * K)); TRY(w->whhp[n].need((size_t)G2 * H)); TRY(w->whht[n].need((size_t)G2 * H));
     }
-    // ---- dropout masks: the caller's, or drawn here
+    // ---- dropout masks: the caller's, or drawn here; the conv sites' kernels walk channels-last rows: their masks once more in that order
     const int nm = 2 + nl;
+    auto pad16 = [](size_t n) { return (n + 15) & ~(size_t)15; };
     w->mask_ptr.assign(nm, nullptr);
+    w->mask_rows[0] = w->mask_rows[1] = nullptr;
     if (p_drop > 0.f) {
-        size_t tot = 0;
-        std::vector<size_t> off(nm);
-        for (int s = 0; s < nm; s++) { off[s] = tot; tot += ((size_t)mdd_train_mask_bytes(w, s, B, T) + 15) & ~(size_t)15; }
-        if (!masks) TRY(w->masks.need((tot + 3) / 4));
-        for (int s = 0; s < nm; s++) {
-            if (masks && masks[s]) w->mask_ptr[s] = masks[s];
-            else {
-                if (masks) { set_error("mdd_train_forward: mask %d missing", s); return MDD_ERR_ARG; }
-                unsigned char *m = reinterpret_cast<unsigned char *>(w->masks.p) + off[s];
-                TRY(launch_dropout_mask(m, (size_t)mdd_train_mask_bytes(w, s, B, T), seed, (unsigned)s, p_drop, st));
+        if (masks) {
+            for (int s = 0; s < nm; s++) { if (!masks[s]) { set_error("mdd_train_forward: mask %d missing", s); return MDD_ERR_ARG; } w->mask_ptr[s] = masks[s]; }
+        } else {
+            size_t tot = 0;
+            for (int s = 0; s < nm; s++) tot += pad16((size_t)d.mask_bytes(s));
+            TRY(w->masks.need((tot + 3) / 4));
+            unsigned char *m = reinterpret_cast<unsigned char *>(w->masks.p);
+            for (int s = 0; s < nm; m += pad16((size_t)d.mask_bytes(s)), s++) {
+                TRY(launch_dropout_mask(m, (size_t)d.mask_bytes(s), seed, (unsigned)s, p_drop, st));
                 w->mask_ptr[s] = m;
             }
         }
-    }
-    w->mask_rows[0] = w->mask_rows[1] = nullptr;
-    if (p_drop > 0.f) {   // the conv sites' kernels walk channels-last rows: their masks once in that order
-        const size_t n0 = (R0 * ch + 15) & ~(size_t)15, n1 = R1 * ch;
+        const size_t n0 = pad16(R0 * ch), n1 = R1 * ch;
         TRY(w->maskt.need((n0 + n1 + 3) / 4));
         unsigned char *m0 = reinterpret_cast<unsigned char *>(w->maskt.p), *m1 = m0 + n0;
         TRY(launch_mask_rows(w->mask_ptr[0], m0, B, ch, T * W1, st));
         TRY(launch_mask_rows(w->mask_ptr[1], m1, B, ch, Tp * W2, st));
         w->mask_rows[0] = m0; w->mask_rows[1] = m1;
     }
-    float *mean = w->stats.p, *invstd = w->stats.p + (2 * ch + nl * H2 + 2 * H2);
+    // BatchNorm on batch statistics at one site: its parameters by table entry, its saved mean / invstd by slot
+    float *mean = w->stats.p, *invstd = w->stats.p + d.stats_plane();
+    auto bn = [&](const BnIdx &i, int slot, const float *x, size_t rows, int F, const BnSite *drop, float *y) {
+        return launch_bn_train_fwd(x, rows, F, tensors[i.weight], tensors[i.bias], c.bn_eps, 0.1f, tensors[i.running_mean], tensors[i.running_var], w->dacc.p,
+                                   mean + slot, invstd + slot, drop, y, st);
+    };
+    const BnSite drop0{w->mask_rows[0], scale}, drop1{w->mask_rows[1], scale};
     // ---- conv0 -> BN -> ReLU -> Dropout
-    TRY(launch_conv0_train_fwd(x_dev, P("conv.0.conv.weight"), P("conv.0.conv.bias"), w->z0.p, B, T, c.feat, ch, st));
-    BnSite s0{w->mask_rows[0], scale};
-    TRY(launch_bn_train_fwd(w->z0.p, R0, ch, P("conv.0.batch_norm.weight"), P("conv.0.batch_norm.bias"), eps, mom, P("conv.0.batch_norm.running_mean"),
-                            P("conv.0.batch_norm.running_var"), w->dacc.p, mean, invstd, &s0, w->a0.p, st));
-    // ---- conv1 (im2col + GEMM) -> BN -> ReLU -> Dropout -> [T',B,ch*W2]
-    TRY(launch_pack_w1(P("conv.1.conv.weight"), w->w1r.p, ch, true, st));
+    TRY(launch_conv0_train_fwd(x_dev, tensors[p.conv[0].weight], tensors[p.conv[0].bias], w->z0.p, B, T, c.feat, ch, st));
+    TRY(bn(p.conv[0].bn, d.conv_slot(0), w->z0.p, R0, ch, &drop0, w->a0.p));
+    // ---- conv1 (direct, or im2col + GEMM) -> BN -> ReLU -> Dropout -> [T',B,ch*W2]
+    TRY(launch_pack_w1(tensors[p.conv[1].weight], w->w1r.p, ch, true, st));
     if (direct1) {
-        TRY(launch_conv1_fwd_direct(w->a0.p, w->w1r.p, P("conv.1.conv.bias"), w->z1.p, B, T, W1, W2, ch, st));
+        TRY(launch_conv1_fwd_direct(w->a0.p, w->w1r.p, tensors[p.conv[1].bias], w->z1.p, B, T, W1, W2, ch, st));
     } else {
         TRY(launch_im2col1(w->a0.p, w->col1.p, B, T, W1, W2, ch, st));
-        TRY(launch_gemm_f32(false, false, w->col1.p, w->w1r.p, P("conv.1.conv.bias"), w->z1.p, (int)R1, ch, 9 * ch, 9 * ch, 9 * ch, ch, 1, 0, 0, 0, false, st));
+        TRY(launch_gemm_f32({.p = w->col1.p, .ld = 9 * ch}, {.p = w->w1r.p, .ld = 9 * ch}, w->z1.p, ch, (int)R1, ch, 9 * ch, st, {.bias = tensors[p.conv[1].bias]}));
     }
-    BnSite s1{w->mask_rows[1], scale};
-    TRY(launch_bn_train_fwd(w->z1.p, R1, ch, P("conv.1.batch_norm.weight"), P("conv.1.batch_norm.bias"), eps, mom, P("conv.1.batch_norm.running_mean"),
-                            P("conv.1.batch_norm.running_var"), w->dacc.p, mean + ch, invstd + ch, &s1, w->a1.p, st));
+    TRY(bn(p.conv[1].bn, d.conv_slot(1), w->z1.p, R1, ch, &drop1, w->a1.p));
     TRY(launch_cnn_seq(w->a1.p, w->seq0.p, B, Tp, W2, ch, true, st));
-    // ---- BatchRNN x layers
+    // ---- BatchRNN x layers: (BN ->) BiLSTM -> Dropout
     for (int n = 0; n < nl; n++) {
-        const std::string r = "rnns." + std::to_string(n);
-        const int K = n == 0 ? Kin0 : H2;
-        const float *xin = w->seq0.p;
-        if (n > 0) {
-            TRY(launch_bn_train_fwd(w->pd[n - 1].p, R, H2, P(r + ".batch_norm.weight"), P(r + ".batch_norm.bias"), eps, mom, P(r + ".batch_norm.running_mean"),
-                                    P(r + ".batch_norm.running_var"), w->dacc.p, mean + 2 * ch + (n - 1) * H2, invstd + 2 * ch + (n - 1) * H2, nullptr, w->xin[n].p, st));
-            xin = w->xin[n].p;
-        }
-        TRY(launch_pack_gates(P(r + ".rnn.weight_ih_l0"), P(r + ".rnn.weight_ih_l0_reverse"), w->wihp[n].p, H, K, st));
-        TRY(launch_pack_gates(P(r + ".rnn.weight_hh_l0"), P(r + ".rnn.weight_hh_l0_reverse"), w->whhp[n].p, H, H, st));
-        TRY(gemm_big(w, false, false, xin, K, w->wihp[n].p, K, nullptr, w->gx.p, G2, (int)R, G2, K, st));
-        LstmStepArgs a;
-        a.gx = w->gx.p; a.whh = w->whhp[n].p; a.hbuf = w->hb.p; a.cbuf = w->cb.p; a.out = w->hraw[n].p; a.out_raw = w->hraw[n].p;
-        a.out_split = SplitPtr{nullptr, nullptr}; a.oscale = nullptr; a.oshift = nullptr; a.T = Tp; a.B = B; a.H = H;
-        a.whh_split = SplitPtr{nullptr, nullptr}; a.hsplit = nullptr; a.packed = 0; a.gates_save = w->gates[n].p; a.c_save = w->cst[n].p;
-        TRY(lstm_forward_layer(w, a, st));
+        if (n > 0) TRY(bn(p.rnn_bn[n], d.rnn_slot(n), w->pd[n - 1].p, R, H2, nullptr, w->xin[n].p));
+        TRY(bilstm_forward(w, d, tensors, n, n > 0 ? w->xin[n].p : w->seq0.p, nullptr, st));
         TRY(launch_dropout_rows(w->hraw[n].p, w->mask_ptr[2 + n], scale, R * H2, w->pd[n].p, st));
     }
-    const float *X = w->pd[nl - 1].p;
-    // ---- text encoder: Embedding -> BiLSTM (bias) ; key = score(text)
-    TRY(launch_embed(P("embeds.weight"), c.emb_rows, E, x1_dev, B, L, w->emb.p, SplitPtr{nullptr, nullptr}, w->err_flag.p, st));
-    TRY(launch_pack_gates(P("lstm_embeds.weight_ih_l0"), P("lstm_embeds.weight_ih_l0_reverse"), w->wihp[nl].p, H, E, st));
-    TRY(launch_pack_gates(P("lstm_embeds.weight_hh_l0"), P("lstm_embeds.weight_hh_l0_reverse"), w->whhp[nl].p, H, H, st));
-    TRY(launch_pack_gates(P("lstm_embeds.bias_ih_l0"), P("lstm_embeds.bias_ih_l0_reverse"), w->tbias.p, H, 1, st));
-    TRY(w->d_a.need(G2));
-    TRY(launch_pack_gates(P("lstm_embeds.bias_hh_l0"), P("lstm_embeds.bias_hh_l0_reverse"), w->d_a.p, H, 1, st));
+    const float *X = w->pd[nl - 1].p, *text = w->hraw[nl].p;
+    // ---- text encoder: Embedding -> BiLSTM with bias b_ih + b_hh (packed into tbias; d_a holds b_hh on the way) ; key = score(text)
+    TRY(launch_embed(tensors[p.embeds], c.emb_rows, E, x1_dev, B, L, w->emb.p, SplitPtr{nullptr, nullptr}, w->err_flag.p, st));
+    TRY(launch_pack_gates(tensors[p.text_b_ih[0]], tensors[p.text_b_ih[1]], w->tbias.p, H, 1, st));
+    TRY(launch_pack_gates(tensors[p.text_b_hh[0]], tensors[p.text_b_hh[1]], w->d_a.p, H, 1, st));
     TRY(launch_copy_cols(w->d_a.p, G2, 0, w->tbias.p, G2, 0, 1, G2, true, st));
-    TRY(gemm_big(w, false, false, w->emb.p, E, w->wihp[nl].p, E, w->tbias.p, w->gx.p, G2, (int)Rt, G2, E, st));
-    {
-        LstmStepArgs a;
-        a.gx = w->gx.p; a.whh = w->whhp[nl].p; a.hbuf = w->hb.p; a.cbuf = w->cb.p; a.out = w->hraw[nl].p; a.out_raw = w->hraw[nl].p;
-        a.out_split = SplitPtr{nullptr, nullptr}; a.oscale = nullptr; a.oshift = nullptr; a.T = L; a.B = B; a.H = H;
-        a.whh_split = SplitPtr{nullptr, nullptr}; a.hsplit = nullptr; a.packed = 0; a.gates_save = w->gates[nl].p; a.c_save = w->cst[nl].p;
-        TRY(lstm_forward_layer(w, a, st));
-    }
-    TRY(launch_gemm_f32(false, false, w->hraw[nl].p, P("score.weight"), nullptr, w->key.p, (int)Rt, H2, H2, H2, H2, H2, 1, 0, 0, 0, false, st));
-    // ---- attention: S = X.key^T, softmax over L (no scale, no mask), ctx = A.text, cat(X, ctx)
-    TRY(launch_gemm_f32(false, false, X, w->key.p, nullptr, w->att.p, Tp, L, H2, B * H2, B * H2, L, B, H2, H2, (long)Tp * L, false, st));
+    TRY(bilstm_forward(w, d, tensors, nl, w->emb.p, w->tbias.p, st));
+    TRY(launch_gemm_f32({.p = text, .ld = H2}, {.p = tensors[p.score], .ld = H2}, w->key.p, H2, (int)Rt, H2, H2, st));
+    // ---- attention per batch entry b: S = X.key^T, softmax over L (no scale, no mask), ctx = A.text, cat(X, ctx)
+    const long sS = (long)Tp * L;      // att is [B][T'][L]; X, key, text and cat are time-major rows, entry b at column offset b * width
+    TRY(launch_gemm_f32({.p = X, .ld = B * H2, .stride = H2}, {.p = w->key.p, .ld = B * H2, .stride = H2}, w->att.p, L, Tp, L, H2, st, {.batch = B, .sC = sS}));
     TRY(launch_softmax_rows(w->att.p, (size_t)B * Tp, L, w->att.p, false, st));
     TRY(launch_copy_cols(X, H2, 0, w->cat.p, 2 * H2, 0, R, H2, false, st));
-    TRY(launch_gemm_f32(false, true, w->att.p, w->hraw[nl].p, nullptr, w->cat.p + H2, Tp, H2, L, L, B * H2, B * 2 * H2, B, (long)Tp * L, H2, 2 * H2, false, st));
+    TRY(launch_gemm_f32({.p = w->att.p, .ld = L, .stride = sS}, {.p = text, .ld = B * H2, .k_major = true, .stride = H2}, w->cat.p + H2, B * 2 * H2, Tp, H2, L, st,
+                        {.batch = B, .sC = 2 * H2}));
     // ---- fc: BatchNorm1d(4H) -> Linear(4H -> C, no bias) -> log-softmax
-    TRY(launch_bn_train_fwd(w->cat.p, R, 2 * H2, P("fc.0.weight"), P("fc.0.bias"), eps, mom, P("fc.0.running_mean"), P("fc.0.running_var"), w->dacc.p,
-                            mean + 2 * ch + nl * H2, invstd + 2 * ch + nl * H2, nullptr, w->ycat.p, st));
-    {   // [R, 1536] x [45, 1536]^T: one column tile, 63 row tiles at R = 8000 -> the contraction is cut into partial products so the chip is busy
-        const int Kfc = 2 * H2, tiles = (int)((R + 127) / 128) * ((C + 127) / 128);
-        const int ks = (tiles < 128 && Kfc >= 1024) ? 256 : 0;
-        if (ks) {
-            const int parts = (Kfc + ks - 1) / ks;
-            TRY(w->part.need((size_t)parts * R * C));
-            TRY(launch_gemm_f32(false, false, w->ycat.p, P("fc.1.weight"), nullptr, w->part.p, (int)R, C, Kfc, Kfc, Kfc, C, 1, 0, 0, (long)R * C, false, st, ks));
-            TRY(launch_reduce_parts(w->part.p, parts, R * C, w->logits.p, st));
-        } else {
-            TRY(launch_gemm_f32(false, false, w->ycat.p, P("fc.1.weight"), nullptr, w->logits.p, (int)R, C, Kfc, Kfc, Kfc, C, 1, 0, 0, 0, false, st));
-        }
-    }
+    TRY(bn(p.fc_bn, d.fc_slot(), w->cat.p, R, 2 * H2, nullptr, w->ycat.p));
+    TRY(gemm_f32_split(w, Arith::Classifier, {.p = w->ycat.p, .ld = 2 * H2}, {.p = tensors[p.fc_weight], .ld = 2 * H2}, w->logits.p, (int)R, C, 2 * H2, st));
     TRY(launch_softmax_rows(w->logits.p, R, C, w->logp.p, true, st));
     MDD_HIP_CHECK(hipMemcpyAsync(logp_dev, w->logp.p, R * C * sizeof(float), hipMemcpyDeviceToDevice, st));
     return MDD_OK;
 }
+extern "C" int mdd_train_forward(mdd_train_ws *w, float *const *tensors, const float *x_dev, int32_t B, int32_t T, const int64_t *x1_dev, int32_t L,
+                                 const uint8_t *const *masks, uint64_t seed, float p_drop, float *logp_dev, void *stream) {
+    if (!w) { set_error("mdd_train_forward: null handle"); return MDD_ERR_ARG; }
+    w->saved.valid = false;            // whatever this call does to the buffers, the previous forward is gone
+    const int rc = with_device_gate(w, w->precision, stream, [&] { return train_forward_enqueue(w, tensors, x_dev, B, T, x1_dev, L, masks, seed, p_drop, logp_dev, (hipStream_t)stream); });
+    w->saved.valid = rc == MDD_OK;     // enqueued completely
+    return rc;
+}
 
-// one BiLSTM's backward: dout [rows,2H] -> DG (in w->dgx), weight gradients into the reference-layout tensors, dxin (optional)
-static int lstm_backward(mdd_train_ws *w, int n, int Tn, int B, int K, const float *dout, const float *xin, float *g_ih_f, float *g_ih_r, float *g_hh_f,
-                         float *g_hh_r, float *dxin, hipStream_t st) {
-    const int H = w->cfg.hidden, H2 = 2 * H, G2 = 8 * H, G = 4 * H;
-    const size_t rows = (size_t)Tn * B;
+// one BiLSTM's backward: dout [rows,2H] -> DG (in w->dgx), weight gradients into the reference-layout tensors (packed in d_b on the way), dxin [rows,K]
+static int lstm_backward(mdd_train_ws *w, const StepDims &d, int n, const float *dout, const float *xin, float *const *grads, float *dxin, hipStream_t st) {
+    const LstmIdx &p = w->params.lstm[n];
+    const int H = d.H, H2 = d.H2, G2 = d.G2, G = 4 * H, Tn = d.steps(n), B = d.B, K = d.K(n), rows = (int)d.rows(n), rows1 = rows - B;
     TRY(launch_transpose_whh(w->whhp[n].p, w->whht[n].p, H, st));
     LstmBwdArgs a;
     a.dout = dout; a.gates = w->gates[n].p; a.cst = w->cst[n].p; a.whhT = w->whht[n].p; a.dg = w->dgx.p; a.dc = w->cb.p; a.T = Tn; a.B = B; a.H = H;
-    if (w->precision == 1 && w->persist_ok && (H == 384 || H == 256) && B <= 256) {   // flagged variant: the whole recurrence in one persistent launch
+    if (w->saved.precision == 1 && w->persist_ok && (H == 384 || H == 256) && B <= 256) {   // flagged variant: the whole recurrence in one persistent launch
         const size_t nW = (size_t)8 * H * H;
         TRY(w->whhs.need(nW));
         unsigned short *hi = reinterpret_cast<unsigned short *>(w->whhs.p), *lo = hi + nW;
@@ -396,123 +378,114 @@ static int lstm_backward(mdd_train_ws *w, int n, int Tn, int B, int K, const flo
     } else {
         TRY(launch_lstm_bwd(a, st));
     }
-    // dWih' [2*4H, K] = DG^T . xin ;  dWhh'[d] [4H, H] = DG_d^T . h_prev_d  (h_prev = the layer's raw output one step earlier in that direction)
-    TRY(w->d_b.need((size_t)G2 * std::max(K, H)));
-    TRY(gemm_big(w, true, true, w->dgx.p, G2, xin, K, nullptr, w->d_b.p, K, G2, K, (int)rows, st));
-    TRY(launch_unpack_gates(w->d_b.p, g_ih_f, g_ih_r, H, K, st));
+    // dWih' [2*4H, K] = DG^T . xin ;  dWhh'[d] [4H, H] = DG_d^T . h_prev_d  (h_prev = the layer's raw output one step earlier in that direction:
+    // forward t = 1.., h_{t-1}; reverse t = 0..T-2, h_{t+1})
+    float *const dg = w->dgx.p, *const h = w->hraw[n].p, *const dwp = w->d_b.p;
+    TRY(gemm_big(w, {.p = dg, .ld = G2, .k_major = true}, {.p = xin, .ld = K, .k_major = true}, nullptr, dwp, K, G2, K, rows, st));
+    TRY(launch_unpack_gates(dwp, grads[p.w_ih[0]], grads[p.w_ih[1]], H, K, st));
     if (Tn > 1) {
-        const size_t rows1 = (size_t)(Tn - 1) * B;
-        TRY(gemm_big(w, true, true, w->dgx.p + (size_t)B * G2, G2, w->hraw[n].p, H2, nullptr, w->d_b.p, H, G, H, (int)rows1, st));                  // forward direction: t = 1.., h_{t-1}
-        TRY(gemm_big(w, true, true, w->dgx.p + G, G2, w->hraw[n].p + (size_t)B * H2 + H, H2, nullptr, w->d_b.p + (size_t)G * H, H, G, H, (int)rows1, st));   // reverse: t = 0..T-2, h_{t+1}
+        TRY(gemm_big(w, {.p = dg + (size_t)B * G2, .ld = G2, .k_major = true}, {.p = h, .ld = H2, .k_major = true}, nullptr, dwp, H, G, H, rows1, st));
+        TRY(gemm_big(w, {.p = dg + G, .ld = G2, .k_major = true}, {.p = h + (size_t)B * H2 + H, .ld = H2, .k_major = true}, nullptr, dwp + (size_t)G * H, H, G, H, rows1, st));
     } else {
-        MDD_HIP_CHECK(hipMemsetAsync(w->d_b.p, 0, sizeof(float) * G2 * H, st));
+        MDD_HIP_CHECK(hipMemsetAsync(dwp, 0, sizeof(float) * G2 * H, st));
     }
-    TRY(launch_unpack_gates(w->d_b.p, g_hh_f, g_hh_r, H, H, st));
-    if (dxin) TRY(gemm_big(w, false, true, w->dgx.p, G2, w->wihp[n].p, K, nullptr, dxin, K, (int)rows, K, G2, st));
-    return MDD_OK;
+    TRY(launch_unpack_gates(dwp, grads[p.w_hh[0]], grads[p.w_hh[1]], H, H, st));
+    return gemm_big(w, {.p = dg, .ld = G2}, {.p = w->wihp[n].p, .ld = K, .k_major = true}, nullptr, dxin, K, rows, K, G2, st);
 }
 
-#define GR(key) (grads[idx(w, key)])
-
-static int train_backward_enqueue(mdd_train_ws *w, float *const *tensors, const float *dlogp_dev, float *const *grads, void *stream);
-extern "C" int mdd_train_backward(mdd_train_ws *w, float *const *tensors, const float *dlogp_dev, float *const *grads, void *stream) {
-    if (!w) { set_error("mdd_train_backward: null handle"); return MDD_ERR_ARG; }
-    const bool gated = w->precision == 1 && w->persist_ok;      // persistent launches inside: one at a time per device
-    bool held = false;
-    if (gated) { MDD_HIP_CHECK(hipSetDevice(w->device)); if (int rc = device_gate_enter(w->device, (hipStream_t)stream, &held)) return rc; }
-    const int rc = train_backward_enqueue(w, tensors, dlogp_dev, grads, stream);
-    return gated ? device_gate_leave(w->device, (hipStream_t)stream, held, rc) : rc;
-}
-static int train_backward_enqueue(mdd_train_ws *w, float *const *tensors, const float *dlogp_dev, float *const *grads, void *stream) {
-    if (!w || !tensors || !dlogp_dev || !grads || w->B <= 0) { set_error("mdd_train_backward: bad argument (forward first)"); return MDD_ERR_ARG; }
+static int train_backward_enqueue(mdd_train_ws *w, float *const *tensors, const float *dlogp_dev, float *const *grads, hipStream_t st) {
     MDD_HIP_CHECK(hipSetDevice(w->device));
-    hipStream_t st = (hipStream_t)stream;
     const mdd_config &c = w->cfg;
-    const int B = w->B, T = w->T, L = w->L;
-    const int ch = c.channels, H = c.hidden, H2 = 2 * H, G2 = 8 * H, Tp = T / 2, W1 = W1_of(c), W2 = W2_of(c), Kin0 = ch * W2, nl = c.layers, E = c.emb_dim, C = c.num_class;
-    const size_t R0 = (size_t)B * T * W1, R1 = (size_t)B * Tp * W2, R = (size_t)Tp * B, Rt = (size_t)L * B;
-    const float scale = 1.f / (1.f - w->p_drop);
-    float *mean = w->stats.p, *invstd = w->stats.p + (2 * ch + nl * H2 + 2 * H2);
-    const float *X = w->pd[nl - 1].p;
-    TRY(w->dgx.need(std::max(R, Rt) * G2));
-    const size_t big = std::max(std::max(std::max(R * 2 * H2, R0 * ch), std::max(R * (size_t)Kin0, Rt * (size_t)E)), std::max((size_t)B * Tp * L, R1 * ch));
-    TRY(w->d_a.need(big)); TRY(w->d_c.need(big)); TRY(w->dtext.need(Rt * H2)); TRY(w->dkey.need(Rt * H2));
+    const ParamTable &p = w->params;
+    const StepDims d(c, w->saved.B, w->saved.T, w->saved.L);
+    const int B = d.B, T = d.T, L = d.L, ch = d.ch, H = d.H, H2 = d.H2, G2 = d.G2, Tp = d.Tp, W1 = d.W1, W2 = d.W2, nl = d.nl, E = d.E, C = d.C;
+    const size_t R0 = d.R0, R1 = d.R1, R = d.R, Rt = d.Rt;
+    const float scale = 1.f / (1.f - w->saved.p_drop);
+    const bool direct1 = w->saved.conv1_direct;
+    const size_t big = std::max(std::max(std::max(R * 2 * H2, R0 * ch), std::max(R * (size_t)d.Kin0, Rt * (size_t)E)), std::max((size_t)B * Tp * L, R1 * ch));
+    TRY(w->dgx.need(std::max(R, Rt) * G2)); TRY(w->d_a.need(big)); TRY(w->d_c.need(big)); TRY(w->dtext.need(Rt * H2)); TRY(w->dkey.need(Rt * H2));
+    TRY(w->d_b.need(std::max((size_t)G2 * std::max(std::max(d.Kin0, H2), std::max(E, H)), (size_t)ch * 9 * ch)));
+    const float *X = w->pd[nl - 1].p, *text = w->hraw[nl].p, *att = w->att.p, *key = w->key.p, *ycat = w->ycat.p;     // saved by the forward
+    // ---- scratch roles, in the order they come alive.  Three temporaries (d_a, d_c, d_b) and the forward buffers that are read for the last
+    // time on the way are reused; each line names the buffer, what it held before and why that is dead.  Reusing ycat, a1, col1 and logits is
+    // why a saved forward serves ONE backward.
+    float *dlogits = w->logits.p;   // [R,C]       logits: the forward kept logp, which is all the log-softmax backward reads
+    float *dycat = w->d_a.p;        // [R,4H]      d_a: first use (in the forward it passed b_hh to tbias)
+    float *dcat = w->d_c.p;         // [R,4H]      d_c: first use
+    float *dX = w->ycat.p;          // [R,2H]      ycat: read last by the fc.1.weight gradient
+    float *dS = w->d_a.p;           // [B][T'][L]  dycat: consumed by the classifier BatchNorm's backward
+    float *dtext = w->dtext.p, *dkey = w->dkey.p;   // [Rt,2H] each, buffers of their own
+    float *demb = w->d_c.p;         // [Rt,E]      dcat: its halves went into dX and into dS / dtext
+    float *dbias = w->tbias.p;      // [8H]        tbias: the text projection's bias, read by the forward only
+    float *dh = w->d_a.p;           // [R,2H]      dS (then the dh of the layer above): dS read last by dkey, a dh by its layer's lstm_backward
+    float *dxin = w->d_c.p;         // [R,K]       demb (then the dxin of the layer above): scattered by embed_bwd / consumed by that layer's BatchNorm backward
+    float *dpd = w->ycat.p;         // [R,2H]      dX (then the dpd of the layer above): already turned into that layer's dh
+    float *da1 = w->a1.p;           // [R1,ch]     a1: the forward relaid it into seq0
+    float *dz1 = w->d_a.p;          // [R1,ch]     dh of layer 0
+    float *dw1 = w->d_b.p;          // [ch,9ch]    lstm_backward's packed weight gradients, unpacked by then
+    float *dcol = w->col1.p;        // [R1,9ch]    im2col path only.  col1: read last by the conv1 weight gradient
+    float *da0 = w->d_c.p;          // [R0,ch]     dxin of layer 0, relaid into da1
+    float *dz0 = w->d_a.p;          // [R0,ch]     dz1: read last by conv1's input gradient
+    float *mean = w->stats.p, *invstd = w->stats.p + d.stats_plane();
+    auto bn_bwd = [&](const BnIdx &i, int slot, const float *x, const float *g, size_t rows, int F, const BnSite *drop, float *dx) {
+        return launch_bn_train_bwd(x, g, rows, F, tensors[i.weight], tensors[i.bias], mean + slot, invstd + slot, drop, w->dacc.p, dx, grads[i.weight], grads[i.bias], st);
+    };
+    const BnSite drop0{w->mask_rows[0], scale}, drop1{w->mask_rows[1], scale};
     // ---- log-softmax, Linear, BatchNorm1d of the classifier
-    float *dlogits = w->logits.p;                                   // logits are not needed again
     TRY(launch_softmax_bwd_rows(w->logp.p, dlogp_dev, R, C, dlogits, true, st));
-    TRY(gemm_tn(w, dlogits, C, w->ycat.p, 2 * H2, GR("fc.1.weight"), C, 2 * H2, (int)R, st));
-    float *dycat = w->d_a.p, *dcat = w->d_c.p;
-    TRY(launch_gemm_f32(false, true, dlogits, P("fc.1.weight"), nullptr, dycat, (int)R, 2 * H2, C, C, 2 * H2, 2 * H2, 1, 0, 0, 0, false, st));
-    TRY(launch_bn_train_bwd(w->cat.p, dycat, R, 2 * H2, P("fc.0.weight"), P("fc.0.bias"), mean + 2 * ch + nl * H2, invstd + 2 * ch + nl * H2, nullptr, w->dacc.p,
-                            dcat, GR("fc.0.weight"), GR("fc.0.bias"), st));
-    // ---- attention
-    float *dX = w->ycat.p;                                          // [R, 2H]  (ycat is free now)
+    TRY(gemm_f32_split(w, Arith::Exact, {.p = dlogits, .ld = C, .k_major = true}, {.p = ycat, .ld = 2 * H2, .k_major = true}, grads[p.fc_weight], C, 2 * H2, (int)R, st));
+    TRY(launch_gemm_f32({.p = dlogits, .ld = C}, {.p = tensors[p.fc_weight], .ld = 2 * H2, .k_major = true}, dycat, 2 * H2, (int)R, 2 * H2, C, st));
+    TRY(bn_bwd(p.fc_bn, d.fc_slot(), w->cat.p, dycat, R, 2 * H2, nullptr, dcat));
+    // ---- attention, per batch entry b (dctx = the right half of dcat)
+    const long sS = (long)Tp * L;
+    const GemmOperand dctx{.p = dcat + H2, .ld = B * 2 * H2, .stride = 2 * H2};
+    const GemmOperand dctx_t{.p = dcat + H2, .ld = B * 2 * H2, .k_major = true, .stride = 2 * H2};
     TRY(launch_copy_cols(dcat, 2 * H2, 0, dX, H2, 0, R, H2, false, st));
-    float *dS = w->d_a.p;                                           // [B][T'][L]
-    TRY(launch_gemm_f32(false, false, dcat + H2, w->hraw[nl].p, nullptr, dS, Tp, L, H2, B * 2 * H2, B * H2, L, B, 2 * H2, H2, (long)Tp * L, false, st));     // dA = dctx . text^T
-    float *dtext = w->dtext.p;                                      // [Rt, 2H]
-    TRY(launch_gemm_f32(true, true, w->att.p, dcat + H2, nullptr, dtext, L, H2, Tp, L, B * 2 * H2, B * H2, B, (long)Tp * L, 2 * H2, H2, false, st));    // dtext = A^T . dctx
-    TRY(launch_softmax_bwd_rows(w->att.p, dS, (size_t)B * Tp, L, dS, false, st));
-    TRY(launch_gemm_f32(false, true, dS, w->key.p, nullptr, dX, Tp, H2, L, L, B * H2, B * H2, B, (long)Tp * L, H2, H2, true, st));                        // dX += dS . key
-    float *dkey = w->dkey.p;                                        // [Rt, 2H]
-    TRY(launch_gemm_f32(true, true, dS, X, nullptr, dkey, L, H2, Tp, L, B * H2, B * H2, B, (long)Tp * L, H2, H2, false, st));                             // dkey = dS^T . X
-    TRY(gemm_tn(w, dkey, H2, w->hraw[nl].p, H2, GR("score.weight"), H2, H2, (int)Rt, st));
-    TRY(launch_gemm_f32(false, true, dkey, P("score.weight"), nullptr, dtext, (int)Rt, H2, H2, H2, H2, H2, 1, 0, 0, 0, true, st));                       // dtext += dkey . Ws
+    TRY(launch_gemm_f32(dctx, {.p = text, .ld = B * H2, .stride = H2}, dS, L, Tp, L, H2, st, {.batch = B, .sC = sS}));                                        // dA = dctx . text^T
+    TRY(launch_gemm_f32({.p = att, .ld = L, .k_major = true, .stride = sS}, dctx_t, dtext, B * H2, L, H2, Tp, st, {.batch = B, .sC = H2}));                  // dtext = A^T . dctx
+    TRY(launch_softmax_bwd_rows(att, dS, (size_t)B * Tp, L, dS, false, st));
+    TRY(launch_gemm_f32({.p = dS, .ld = L, .stride = sS}, {.p = key, .ld = B * H2, .k_major = true, .stride = H2}, dX, B * H2, Tp, H2, L, st,
+                        {.batch = B, .sC = H2, .accumulate = true}));                                                                                       // dX += dS . key
+    TRY(launch_gemm_f32({.p = dS, .ld = L, .k_major = true, .stride = sS}, {.p = X, .ld = B * H2, .k_major = true, .stride = H2}, dkey, B * H2, L, H2, Tp, st,
+                        {.batch = B, .sC = H2}));                                                                                                           // dkey = dS^T . X
+    TRY(gemm_f32_split(w, Arith::Exact, {.p = dkey, .ld = H2, .k_major = true}, {.p = text, .ld = H2, .k_major = true}, grads[p.score], H2, H2, (int)Rt, st));
+    TRY(launch_gemm_f32({.p = dkey, .ld = H2}, {.p = tensors[p.score], .ld = H2, .k_major = true}, dtext, H2, (int)Rt, H2, H2, st, {.accumulate = true}));    // dtext += dkey . Ws
     // ---- text encoder
-    float *demb = w->d_c.p;
-    TRY(lstm_backward(w, nl, L, B, E, dtext, w->emb.p, GR("lstm_embeds.weight_ih_l0"), GR("lstm_embeds.weight_ih_l0_reverse"), GR("lstm_embeds.weight_hh_l0"),
-                      GR("lstm_embeds.weight_hh_l0_reverse"), demb, st));
-    TRY(launch_col_sum(w->dgx.p, Rt, G2, w->dacc.p, w->tbias.p, st));            // packed bias gradient (u*4+g order)
-    TRY(launch_unpack_gates(w->tbias.p, GR("lstm_embeds.bias_ih_l0"), GR("lstm_embeds.bias_ih_l0_reverse"), H, 1, st));
-    TRY(launch_unpack_gates(w->tbias.p, GR("lstm_embeds.bias_hh_l0"), GR("lstm_embeds.bias_hh_l0_reverse"), H, 1, st));
-    TRY(launch_embed_bwd(demb, w->ids, B, L, E, c.emb_rows, GR("embeds.weight"), st));
-    // ---- BatchRNN layers, last to first
-    float *dpd = dX;                                                // gradient at the layer's (post-dropout) output
+    TRY(lstm_backward(w, d, nl, dtext, w->emb.p, grads, demb, st));
+    TRY(launch_col_sum(w->dgx.p, Rt, G2, w->dacc.p, dbias, st));            // packed bias gradient (u*4+g order)
+    TRY(launch_unpack_gates(dbias, grads[p.text_b_ih[0]], grads[p.text_b_ih[1]], H, 1, st));
+    TRY(launch_unpack_gates(dbias, grads[p.text_b_hh[0]], grads[p.text_b_hh[1]], H, 1, st));
+    TRY(launch_embed_bwd(demb, w->saved.ids, B, L, E, c.emb_rows, grads[p.embeds], st));
+    // ---- BatchRNN layers, last to first: Dropout, BiLSTM, (BN)
     for (int n = nl - 1; n >= 0; n--) {
-        const std::string r = "rnns." + std::to_string(n);
-        const int K = n == 0 ? Kin0 : H2;
-        float *dh = w->d_a.p;                                       // [R, 2H]
-        TRY(launch_dropout_rows(dpd, w->mask_ptr[2 + n], scale, R * H2, dh, st));
-        float *dxin = w->d_c.p;                                     // [R, K]
-        TRY(lstm_backward(w, n, Tp, B, K, dh, n == 0 ? w->seq0.p : w->xin[n].p, GR(r + ".rnn.weight_ih_l0"), GR(r + ".rnn.weight_ih_l0_reverse"),
-                          GR(r + ".rnn.weight_hh_l0"), GR(r + ".rnn.weight_hh_l0_reverse"), dxin, st));
-        if (n > 0) {
-            TRY(launch_bn_train_bwd(w->pd[n - 1].p, dxin, R, H2, P(r + ".batch_norm.weight"), P(r + ".batch_norm.bias"), mean + 2 * ch + (n - 1) * H2,
-                                    invstd + 2 * ch + (n - 1) * H2, nullptr, w->dacc.p, w->ycat.p, GR(r + ".batch_norm.weight"), GR(r + ".batch_norm.bias"), st));
-            dpd = w->ycat.p;
-        }
+        TRY(launch_dropout_rows(n == nl - 1 ? dX : dpd, w->mask_ptr[2 + n], scale, R * H2, dh, st));    // from the gradient at the layer's (post-dropout) output
+        TRY(lstm_backward(w, d, n, dh, n == 0 ? w->seq0.p : w->xin[n].p, grads, dxin, st));
+        if (n > 0) TRY(bn_bwd(p.rnn_bn[n], d.rnn_slot(n), w->pd[n - 1].p, dxin, R, H2, nullptr, dpd));
     }
     // ---- conv1: relayout, BN/ReLU/Dropout, weight and input gradients
-    float *da1 = w->a1.p;                                           // a1 is not needed again
-    TRY(launch_cnn_seq(da1, w->d_c.p, B, Tp, W2, ch, false, st));
-    BnSite s1{w->mask_rows[1], scale};
-    float *dz1 = w->d_a.p;
-    TRY(launch_bn_train_bwd(w->z1.p, da1, R1, ch, P("conv.1.batch_norm.weight"), P("conv.1.batch_norm.bias"), mean + ch, invstd + ch, &s1, w->dacc.p, dz1,
-                            GR("conv.1.batch_norm.weight"), GR("conv.1.batch_norm.bias"), st));
-    TRY(launch_col_sum(dz1, R1, ch, w->dacc.p, GR("conv.1.conv.bias"), st));
-    TRY(w->d_b.need((size_t)ch * 9 * ch));
-    float *da0 = w->d_c.p;
-    const bool direct1 = conv1_direct(w);
+    TRY(launch_cnn_seq(da1, dxin, B, Tp, W2, ch, false, st));
+    TRY(bn_bwd(p.conv[1].bn, d.conv_slot(1), w->z1.p, da1, R1, ch, &drop1, dz1));
+    TRY(launch_col_sum(dz1, R1, ch, w->dacc.p, grads[p.conv[1].bias], st));
     if (direct1) {
-        const int parts = conv1_wgrad_parts(B, T, W2);
-        TRY(w->part.need((size_t)parts * ch * 9 * ch));
-        TRY(launch_conv1_wgrad_direct(dz1, w->a0.p, w->part.p, B, T, W1, W2, ch, st));
-        TRY(launch_reduce_parts(w->part.p, parts, (size_t)ch * 9 * ch, w->d_b.p, st));
-        TRY(launch_pack_w1(w->d_b.p, GR("conv.1.conv.weight"), ch, false, st));
+        TRY(sum_parts(w->part, conv1_wgrad_parts(B, T, W2), (size_t)ch * 9 * ch, dw1, st,
+                      [&](float *part) { return launch_conv1_wgrad_direct(dz1, w->a0.p, part, B, T, W1, W2, ch, st); }));
+        TRY(launch_pack_w1(dw1, grads[p.conv[1].weight], ch, false, st));
         TRY(launch_conv1_dgrad_direct(dz1, w->w1r.p, da0, B, T, W1, W2, ch, st));
     } else {
-        TRY(gemm_tn(w, dz1, ch, w->col1.p, 9 * ch, w->d_b.p, ch, 9 * ch, (int)R1, st));
-        TRY(launch_pack_w1(w->d_b.p, GR("conv.1.conv.weight"), ch, false, st));
-        TRY(launch_gemm_f32(false, true, dz1, w->w1r.p, nullptr, w->col1.p, (int)R1, 9 * ch, ch, ch, 9 * ch, 9 * ch, 1, 0, 0, 0, false, st));               // dcol
-        TRY(launch_col2im1(w->col1.p, da0, B, T, W1, W2, ch, st));
+        TRY(gemm_f32_split(w, Arith::Exact, {.p = dz1, .ld = ch, .k_major = true}, {.p = w->col1.p, .ld = 9 * ch, .k_major = true}, dw1, ch, 9 * ch, (int)R1, st));
+        TRY(launch_pack_w1(dw1, grads[p.conv[1].weight], ch, false, st));
+        TRY(launch_gemm_f32({.p = dz1, .ld = ch}, {.p = w->w1r.p, .ld = 9 * ch, .k_major = true}, dcol, 9 * ch, (int)R1, 9 * ch, ch, st));
+        TRY(launch_col2im1(dcol, da0, B, T, W1, W2, ch, st));
     }
     // ---- conv0
-    BnSite s0{w->mask_rows[0], scale};
-    float *dz0 = w->d_a.p;
-    TRY(launch_bn_train_bwd(w->z0.p, da0, R0, ch, P("conv.0.batch_norm.weight"), P("conv.0.batch_norm.bias"), mean, invstd, &s0, w->dacc.p, dz0,
-                            GR("conv.0.batch_norm.weight"), GR("conv.0.batch_norm.bias"), st));
-    TRY(launch_conv0_train_bwd(w->x, dz0, w->dacc.p, GR("conv.0.conv.weight"), GR("conv.0.conv.bias"), B, T, c.feat, ch, st));
-    return MDD_OK;
+    TRY(bn_bwd(p.conv[0].bn, d.conv_slot(0), w->z0.p, da0, R0, ch, &drop0, dz0));
+    return launch_conv0_train_bwd(w->saved.x, dz0, w->dacc.p, grads[p.conv[0].weight], grads[p.conv[0].bias], B, T, c.feat, ch, st);
+}
+extern "C" int mdd_train_backward(mdd_train_ws *w, float *const *tensors, const float *dlogp_dev, float *const *grads, void *stream) {
+    if (!w) { set_error("mdd_train_backward: null handle"); return MDD_ERR_ARG; }
+    if (!tensors || !dlogp_dev || !grads || !w->saved.valid) { set_error("mdd_train_backward: bad argument (forward first)"); return MDD_ERR_ARG; }
+    w->saved.valid = false;            // consumed: from here on saved activations are overwritten
+    return with_device_gate(w, w->saved.precision, stream, [&] { return train_backward_enqueue(w, tensors, dlogp_dev, grads, (hipStream_t)stream); });
 }
 
 // wait for `stream`; reports an out-of-range canonical id seen by the last forward (the reference raises IndexError)

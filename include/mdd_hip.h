@@ -291,9 +291,14 @@ int mdd_eval_batch(const int32_t *dec, const int32_t *dec_len, const int32_t *la
  *                               of mdd_train_mask_bytes() bytes each.  x_dev / x1_dev must stay valid until the backward call.
  *   mdd_train_backward          autograd's backward of that forward: dlogp_dev [T/2,B,C] (e.g. mdd_ctc_loss's gradient scaled
  *                               by 1/B as train_ctc.py:73-74 divides the loss) -> one gradient per parameter into grads[i]
- *                               (entries of running-statistics buffers are ignored and may be NULL)
+ *                               (entries of running-statistics buffers are ignored and may be NULL).  ONE backward per forward:
+ *                               the backward overwrites activations the forward saved, so the handle holds a saved forward only
+ *                               from a forward that was enqueued completely (a refused or failed forward leaves none) until the next
+ *                               backward or forward; without one, mdd_train_backward returns MDD_ERR_ARG ("forward first") and
+ *                               writes nothing -- also for a second backward on the same forward (autograd's retain_graph).
  *   mdd_adam_step               torch.optim.Adam over n tensors (train_ctc.py:187: lr 1e-3, weight_decay 5e-4 added to the gradient)
- * Arithmetic: three modes, chosen per handle by mdd_train_set_precision (or MDD_TRAIN_PRECISION at create); they differ only in how the
+ * Arithmetic: three modes, chosen per handle by mdd_train_set_precision (or MDD_TRAIN_PRECISION at create) and read by the next FORWARD:
+ * the saved forward remembers its mode (and its conv1 path), and its backward follows that, whatever the handle's mode is by then.  They differ only in how the
  * LARGE CONTRACTIONS of the step run -- the BiLSTM and text-encoder input projections, dW_ih, the dW_hh products and dX:
  *   0 "f32"     exact fp32 MFMA (v_mfma_f32_*) everywhere, as the reference trains.  The default.
  *   1 "bf16x3"  flagged variant: those contractions through the split-bf16 x3 matrix-core GEMM of the decode path (operands to 16
