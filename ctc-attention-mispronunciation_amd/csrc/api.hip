@@ -162,10 +162,17 @@ static std::vector<Stage> forward_stages(mdd_model *m, const ForwardCall &call) 
     }
 
     const LstmWeights *tw = &w->rnn[nl];   // the text encoder (model_ctc.py:193,198) and keys (:201)
+    // Its input projection multiplies two weights: emb[id] . W_ih'^T + bias is one of emb_rows constant rows.  Where the plan says so the two
+    // stages are the id check with the row indices, and a gather from the weight set's table of those rows; gemm_text keeps the flops of the
+    // product it stands for (bench.py's roofline counts them).
+    const float *table = p.text_table ? w->text_table[p.proj == Gemm::F32x6] : nullptr;
+    int *tidx = reinterpret_cast<int *>(m->tidx.p);
     s.push_back({"embed", 1, 0.0, [=](hipStream_t st) {
+        if (table) return launch_embed_index(c.emb_rows, call.x1, B, L, tidx, m->err_flag.p, st);
         return launch_embed(w->emb, c.emb_rows, E, call.x1, B, L, x3 ? nullptr : m->embo.p, split(m->embo_s, trows * E), m->err_flag.p, st);
     }});
     s.push_back({"gemm_text", 1, 2.0 * (double)L * B * 8 * H * E, [=](hipStream_t st) {
+        if (table) return launch_gather_rows(table, tidx, m->gx.p, L * B, 8 * H, st);
         return project(m, ProjIn{m->embo.p, split(m->embo_s, trows * E), false}, L * B, E, *tw, w->t_bias, st);
     }});
     const LstmStepArgs ta = lstm_raw_out(L, B, call.llen, m->text.p, split(m->text_s, trows * H2));
@@ -180,7 +187,7 @@ static std::vector<Stage> forward_stages(mdd_model *m, const ForwardCall &call) 
     s.push_back({"gemm_score", 1, 2.0 * (double)B * Tp * L * H2, [=](hipStream_t st) {   // scores S[b][t][l] = X[t,b,:] . key[l,b,:]   (:204)
         if (x3) return launch_gemm_bf16x3(split_view(m->x_s, rows * H2), split_view(m->key_s, trows * H2), nullptr, m->S.p, nullptr, Tp, L, H2, B * H2, B * H2, Lp,
                                           B, H2, H2, (long)Tp * Lp, st);
-        return launch_gemm_nt(m->xraw.p, m->key.p, nullptr, m->S.p, Tp, L, H2, B * H2, B * H2, Lp, B, H2, H2, (long)Tp * Lp, st);
+        return launch_gemm_nt(m->xraw.p, m->key.p, nullptr, m->S.p, Tp, L, H2, B * H2, B * H2, Lp, B, H2, H2, (long)Tp * Lp, st, m->sw.score_wide);
     }});
     s.push_back({"attn_tail", 1, 2.0 * (double)B * Tp * ((double)L * H2 + 2.0 * H2 * c.num_class), [=](hipStream_t st) {
         return launch_attn_tail(m->S.p, Lp, m->xraw.p, m->text.p, w->fscale, w->fshift, w->w_fc, w->w_fcp, call.logp, Tp, B, L, H2, c.num_class, st, call.llen);
@@ -358,7 +365,7 @@ static int prepare(mdd_model *m, const ForwardCall &call) {
     bool ok = (!(call.Traw > 0 && separate) || grow(m->xstack, (size_t)B * T * c.feat)) && (!separate || grow(m->y0, (size_t)B * c.channels * T * m->W1())) &&
               grow(m->seq0, rows * K0) && grow(m->gx, mrows * 8 * H) && grow(m->act[0], rows * 2 * H) && grow(m->act[1], rows * 2 * H) &&
               grow(m->xraw, rows * 2 * H) && grow(m->hbuf, (size_t)4 * Bpad * H) && grow(m->cbuf, (size_t)2 * Bpad * H) &&
-              grow(m->embo, trows * emb) && grow(m->text, trows * 2 * H) && grow(m->key, trows * 2 * H) && grow(m->S, (size_t)B * Tp * L) &&
+              (p.text_table ? grow(m->tidx, trows) : grow(m->embo, trows * emb)) && grow(m->text, trows * 2 * H) && grow(m->key, trows * 2 * H) && grow(m->S, (size_t)B * Tp * L) &&
               (p.proj != Gemm::F32x6 || grow(m->p3, p3_floats)) &&
               (!p.hx_floats || grow(m->hx, p.hx_floats));   // the exchange buffer of the persistent layers + stamps
     if (ok && x3)
@@ -485,6 +492,7 @@ extern "C" const float *mdd_tap(mdd_model *m, const char *name, int64_t *numel) 
     if (n == "conv1") { p = m->seq0.p; ne = rows * m->rnn_in(); }
     else if (n == "text") { p = m->text.p; ne = trows * H2; }
     else if (n == "key") { p = m->key.p; ne = trows * H2; }
+    else if (n == "score") { p = m->S.p; ne = B * (m->lastT / 2) * m->lastL; }   // S[b][t][l]
     else if (n == "lstm_dbg" && m->plan.gated) {   // diagnostic stamps of the last persistent layer launch (MDD_LSTM_DBG=1)
         p = m->hx.p + m->plan.stamps_at;
         ne = 256 * 6 * 2;

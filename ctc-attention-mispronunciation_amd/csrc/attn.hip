@@ -40,6 +40,44 @@ int launch_embed(const float *table, int rows, int E, const int64_t *ids, int B,
     return MDD_OK;
 }
 
+// The text projection as a lookup (DecodeWeights::text_table): embed_index_kernel is embed_kernel's id rule with the row index as its only
+// output, gather_rows_kernel the copy out[m, :] = table[idx[m], :].  A workgroup walks rows; the row index is uniform over it, a lane moves
+// 16 bytes at a time (a row of 8H floats is 12 KB at H = 384: three float4 per thread).  The table (540 KB) stays in every L2; the
+// kernel is the write of M rows.
+__global__ void embed_index_kernel(int rows, const int64_t *__restrict__ ids, int B, int L, int *__restrict__ idx, int *err_flag) {
+    const int m = blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= B * L) return;
+    const int l = m / B, b = m - l * B;
+    long id = ids[(size_t)b * L + l];
+    if (id < 0 || id >= rows) {  // reference: IndexError from nn.Embedding
+        atomicExch(err_flag, 1);
+        id = 0;
+    }
+    idx[m] = (int)id;
+}
+
+__global__ __launch_bounds__(256) void gather_rows_kernel(const float4 *__restrict__ table, const int *__restrict__ idx, float4 *__restrict__ out, int M, int N4) {
+    for (int m = blockIdx.x; m < M; m += gridDim.x) {
+        const float4 *src = table + (size_t)idx[m] * N4;
+        float4 *dst = out + (size_t)m * N4;
+        for (int i = threadIdx.x; i < N4; i += 256) dst[i] = src[i];
+    }
+}
+
+int launch_embed_index(int rows, const int64_t *ids, int B, int L, int *idx, int *err_flag, hipStream_t st) {
+    hipLaunchKernelGGL(embed_index_kernel, dim3((B * L + 255) / 256), dim3(256), 0, st, rows, ids, B, L, idx, err_flag);
+    MDD_LAUNCH_CHECK();
+    return MDD_OK;
+}
+
+int launch_gather_rows(const float *table, const int *idx, float *out, int M, int N, hipStream_t st) {
+    if (M <= 0 || N <= 0 || N % 4 || (uintptr_t)table % 16 || (uintptr_t)out % 16) { set_error("gather_rows: M=%d N=%d (N a multiple of 4, 16-byte aligned rows)", M, N); return MDD_ERR_ARG; }
+    hipLaunchKernelGGL(gather_rows_kernel, dim3(M < 4096 ? M : 4096), dim3(256), 0, st, reinterpret_cast<const float4 *>(table), idx,
+                       reinterpret_cast<float4 *>(out), M, N / 4);
+    MDD_LAUNCH_CHECK();
+    return MDD_OK;
+}
+
 constexpr int TT = 16;  // posterior frames per workgroup
 
 // dynamic LDS: attw[TT][L] | y[TT][2*H2] | logits[TT][C]

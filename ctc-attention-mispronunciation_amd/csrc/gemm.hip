@@ -12,6 +12,10 @@
 // the next tile's loads in flight during the MFMAs (two LDS buffers, one barrier per K-tile).
 // LDS rows are padded to 17 floats: the per-lane ds_read_b32 of an MFMA operand (lane = row,
 // half-wave = k) is then conflict-free.
+//
+// N <= 64 (the attention scores: N = L, one column tile of which the wide form would fill less than half) takes a 128x64 block
+// tile: the four waves stacked 4x1, each 32 rows x 64 columns = 1x2 MFMA tiles, and W rows 64..127 of the tile never fetched.  Same
+// MFMA, same K-tile, same SEG cadence: every C element is the fmaf chain it is in the wide form, bit for bit.
 #include "mdd_internal.h"
 
 namespace mdd {
@@ -20,12 +24,12 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int BM = 128, BN = 128, BK = 16, LDS_LD = BK + 1;
 
-template <bool ALIGNED>
+template <bool ALIGNED, int NR = 2>
 __device__ __forceinline__ void load_tile_regs(const float *__restrict__ P, int ld, int rows_total, int K, int row0,
                                                int k0, int tid, float4 (&r)[2]) {
-    // thread -> (row = tid/4 [+64], 4 consecutive k at (tid%4)*4)
+    // thread -> (row = tid/4 [+64], 4 consecutive k at (tid%4)*4); NR = 1: a 64-row tile
 #pragma unroll
-    for (int i = 0; i < 2; i++) {
+    for (int i = 0; i < NR; i++) {
         int row = row0 + (tid >> 2) + i * 64;
         int k = k0 + (tid & 3) * 4;
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -44,9 +48,10 @@ __device__ __forceinline__ void load_tile_regs(const float *__restrict__ P, int 
     }
 }
 
+template <int NR = 2>
 __device__ __forceinline__ void store_tile_lds(float *s, int tid, const float4 (&r)[2]) {
 #pragma unroll
-    for (int i = 0; i < 2; i++) {
+    for (int i = 0; i < NR; i++) {
         float *d = s + ((tid >> 2) + i * 64) * LDS_LD + (tid & 3) * 4;
         d[0] = r[i].x; d[1] = r[i].y; d[2] = r[i].z; d[3] = r[i].w;
     }
@@ -58,26 +63,29 @@ __device__ __forceinline__ void store_tile_lds(float *s, int tid, const float4 (
 // K-tiles (32 roundings per segment, then one per segment): measured below ATen's blocked CPU GEMM.  The adds are vector
 // instructions an fp32 MFMA does not hide (~6 % of the kernel), so the large input projections (N > 1024), which have their own
 // fp32-grade form on the bf16 matrix cores (gemm_bf16x6.hip), keep the single chain; the choice depends on the shape only.
-template <bool ALIGNED, bool SEG>
+// BNT: the width of the block tile, 128 (waves 2x2, 64x64 each) or 64 (waves 4x1, 32x64 each)
+template <bool ALIGNED, bool SEG, int BNT = BN>
 __global__ __launch_bounds__(256) void gemm_nt_f32_kernel(const float *__restrict__ A, const float *__restrict__ W,
                                                           const float *__restrict__ bias, float *__restrict__ C, int M,
                                                           int N, int K, int lda, int ldw, int ldc, long sA, long sW,
                                                           long sC, int tiles_n) {
-    __shared__ float lds[2][2][BM * LDS_LD];  // [buffer][A|W][row][k]
+    constexpr int MT = BNT / 64, WR = 32 * MT;   // 32-row MFMA tiles per wave, rows per wave
+    constexpr int WOFF = BM * LDS_LD;
+    __shared__ float lds[2][(BM + BNT) * LDS_LD];  // [buffer][A rows | W rows][k]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1;
+    const int wm = BNT == BN ? wave >> 1 : wave, wn = BNT == BN ? wave & 1 : 0;
     // XCD-aware tile order: consecutive workgroup ids round-robin over the 8 XCDs, so give each
     // XCD a contiguous run of tiles (they share A row-panels through that XCD's L2).
     int nwg = gridDim.x, bid = blockIdx.x;
     int q = nwg >> 3, rem = nwg & 7, xcd = bid & 7;
     int swz = (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + (bid >> 3);
     const int tm = swz / tiles_n, tn = swz % tiles_n;
-    const int m0 = tm * BM, n0 = tn * BN;
+    const int m0 = tm * BM, n0 = tn * BNT;
     A += (size_t)blockIdx.z * sA; W += (size_t)blockIdx.z * sW; C += (size_t)blockIdx.z * sC;
 
-    f32x16 acc[2][2], tot[2][2];
+    f32x16 acc[MT][2], tot[MT][2];
 #pragma unroll
-    for (int i = 0; i < 2; i++)
+    for (int i = 0; i < MT; i++)
 #pragma unroll
         for (int j = 0; j < 2; j++)
 #pragma unroll
@@ -85,9 +93,9 @@ __global__ __launch_bounds__(256) void gemm_nt_f32_kernel(const float *__restric
 
     float4 ra[2], rw[2];
     load_tile_regs<ALIGNED>(A, lda, M, K, m0, 0, tid, ra);
-    load_tile_regs<ALIGNED>(W, ldw, N, K, n0, 0, tid, rw);
-    store_tile_lds(lds[0][0], tid, ra);
-    store_tile_lds(lds[0][1], tid, rw);
+    load_tile_regs<ALIGNED, MT>(W, ldw, N, K, n0, 0, tid, rw);
+    store_tile_lds(lds[0], tid, ra);
+    store_tile_lds<MT>(lds[0] + WOFF, tid, rw);
     __syncthreads();
 
     const int nk = (K + BK - 1) / BK;
@@ -96,26 +104,28 @@ __global__ __launch_bounds__(256) void gemm_nt_f32_kernel(const float *__restric
         const int cur = kt & 1;
         if (kt + 1 < nk) {
             load_tile_regs<ALIGNED>(A, lda, M, K, m0, (kt + 1) * BK, tid, ra);
-            load_tile_regs<ALIGNED>(W, ldw, N, K, n0, (kt + 1) * BK, tid, rw);
+            load_tile_regs<ALIGNED, MT>(W, ldw, N, K, n0, (kt + 1) * BK, tid, rw);
         }
-        const float *as = lds[cur][0] + (wm * 64 + li) * LDS_LD + lh;
-        const float *ws = lds[cur][1] + (wn * 64 + li) * LDS_LD + lh;
+        const float *as = lds[cur] + (wm * WR + li) * LDS_LD + lh;
+        const float *ws = lds[cur] + WOFF + (wn * 64 + li) * LDS_LD + lh;
 #pragma unroll
         for (int kk = 0; kk < BK; kk += 2) {
-            float a0 = as[kk], a1 = as[32 * LDS_LD + kk];
+            float a0 = as[kk], a1 = MT == 2 ? as[32 * LDS_LD + kk] : 0.f;
             float b0 = ws[kk], b1 = ws[32 * LDS_LD + kk];
             acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
             acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
+            if (MT == 2) {
+                acc[MT - 1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[MT - 1][0], 0, 0, 0);
+                acc[MT - 1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[MT - 1][1], 0, 0, 0);
+            }
         }
         if (kt + 1 < nk) {
-            store_tile_lds(lds[cur ^ 1][0], tid, ra);
-            store_tile_lds(lds[cur ^ 1][1], tid, rw);
+            store_tile_lds(lds[cur ^ 1], tid, ra);
+            store_tile_lds<MT>(lds[cur ^ 1] + WOFF, tid, rw);
         }
         if (SEG && (kt & 3) == 3) {
 #pragma unroll
-            for (int i = 0; i < 2; i++)
+            for (int i = 0; i < MT; i++)
 #pragma unroll
                 for (int j = 0; j < 2; j++)
 #pragma unroll
@@ -126,7 +136,7 @@ __global__ __launch_bounds__(256) void gemm_nt_f32_kernel(const float *__restric
 
     // epilogue: C/D layout of the 32x32 MFMA: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
 #pragma unroll
-    for (int i = 0; i < 2; i++)
+    for (int i = 0; i < MT; i++)
 #pragma unroll
         for (int j = 0; j < 2; j++) {
             int col = n0 + wn * 64 + j * 32 + li;
@@ -134,24 +144,30 @@ __global__ __launch_bounds__(256) void gemm_nt_f32_kernel(const float *__restric
             float bv = bias ? bias[col] : 0.f;
 #pragma unroll
             for (int r = 0; r < 16; r++) {
-                int row = m0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                int row = m0 + wm * WR + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
                 if (row < M) C[(size_t)row * ldc + col] = (SEG ? tot[i][j][r] + acc[i][j][r] : acc[i][j][r]) + bv;
             }
         }
 }
 
+// wide: the 128-column tile also where N <= 64 (MDD_SCORE_TILE=128, the comparison form of the attention scores)
 int launch_gemm_nt(const float *A, const float *W, const float *bias, float *C, int M, int N, int K, int lda, int ldw,
-                   int ldc, int batch, long sA, long sW, long sC, hipStream_t st) {
+                   int ldc, int batch, long sA, long sW, long sC, hipStream_t st, bool wide) {
     if (M <= 0 || N <= 0 || K <= 0 || batch <= 0) { set_error("gemm: bad shape %d %d %d x%d", M, N, K, batch); return MDD_ERR_ARG; }
-    int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
+    const bool narrow = N <= 64 && !wide;
+    int tiles_m = (M + BM - 1) / BM, tiles_n = narrow ? 1 : (N + BN - 1) / BN;
     dim3 grid(tiles_m * tiles_n, 1, batch), block(256);
     bool aligned = (lda % 4 == 0) && (ldw % 4 == 0) && (sA % 4 == 0) && (sW % 4 == 0) &&
                    ((uintptr_t)A % 16 == 0) && ((uintptr_t)W % 16 == 0);
     const bool seg = N <= 1024 && K > 64;
-    if (aligned && seg) hipLaunchKernelGGL((gemm_nt_f32_kernel<true, true>), grid, block, 0, st, A, W, bias, C, M, N, K, lda, ldw, ldc, sA, sW, sC, tiles_n);
-    else if (aligned) hipLaunchKernelGGL((gemm_nt_f32_kernel<true, false>), grid, block, 0, st, A, W, bias, C, M, N, K, lda, ldw, ldc, sA, sW, sC, tiles_n);
-    else if (seg) hipLaunchKernelGGL((gemm_nt_f32_kernel<false, true>), grid, block, 0, st, A, W, bias, C, M, N, K, lda, ldw, ldc, sA, sW, sC, tiles_n);
-    else hipLaunchKernelGGL((gemm_nt_f32_kernel<false, false>), grid, block, 0, st, A, W, bias, C, M, N, K, lda, ldw, ldc, sA, sW, sC, tiles_n);
+#define GO(AL_, SEG_, BNT_) hipLaunchKernelGGL((gemm_nt_f32_kernel<AL_, SEG_, BNT_>), grid, block, 0, st, A, W, bias, C, M, N, K, lda, ldw, ldc, sA, sW, sC, tiles_n)
+    if (narrow) {
+        if (aligned && seg) GO(true, true, 64); else if (aligned) GO(true, false, 64); else if (seg) GO(false, true, 64); else GO(false, false, 64);
+    } else if (aligned && seg) GO(true, true, BN);
+    else if (aligned) GO(true, false, BN);
+    else if (seg) GO(false, true, BN);
+    else GO(false, false, BN);
+#undef GO
     MDD_LAUNCH_CHECK();
     return MDD_OK;
 }

@@ -56,7 +56,7 @@ struct SplitPtr { unsigned short *hi, *lo; };
 // C[M,N] = A[M,K] . W[N,K]^T (+ bias[N]); fp32 MFMA (v_mfma_f32_32x32x2_f32).  Batched over
 // `batch` with element strides sA/sW/sC.
 int launch_gemm_nt(const float *A, const float *W, const float *bias, float *C, int M, int N, int K, int lda, int ldw,
-                   int ldc, int batch, long sA, long sW, long sC, hipStream_t st);
+                   int ldc, int batch, long sA, long sW, long sC, hipStream_t st, bool wide = false);   // N <= 64: a 128x64 tile unless `wide`
 
 // General fp32 GEMM (training step): C[m,n] (+)= sum_k opA[m,k] opB[n,k] (see gemm.hip).  Written at the call site with the field names:
 //   launch_gemm_f32({.p = dS, .ld = L, .stride = (long)Tp * L}, {.p = key, .ld = B * H2, .k_major = true, .stride = H2}, dX, B * H2, Tp, H2, L, st,
@@ -150,6 +150,11 @@ int launch_lstm_layer(const LstmStepArgs &a, hipStream_t st);
 
 int launch_embed(const float *table, int rows, int E, const int64_t *ids, int B, int L, float *out, SplitPtr out_split,
                  int *err_flag, hipStream_t st);
+// The same gather through a table of projected rows (the text encoder's input projection, DecodeWeights::text_table): launch_embed_index
+// checks the ids by launch_embed's rule and writes the time-major row indices idx[l * B + b]; launch_gather_rows copies
+// out[m, :] = table[idx[m], :] (N a multiple of 4, 16-byte aligned pointers).
+int launch_embed_index(int rows, const int64_t *ids, int B, int L, int *idx, int *err_flag, hipStream_t st);
+int launch_gather_rows(const float *table, const int *idx, float *out, int M, int N, hipStream_t st);
 // softmax over L of S[b][t][:], ctx = A.V, y = BN(cat(X, ctx)), logits = y.Wfc^T, log-softmax
 int launch_attn_tail(const float *S, int Lp, const float *X, const float *V, const float *fscale, const float *fshift,
                      const float *wfc, const float *wfcp, float *logp, int Tp, int B, int L, int H2, int C, hipStream_t st,

@@ -52,6 +52,10 @@ struct DecodeWeights {
     unsigned short *w_conv1_3 = nullptr;           // conv1 weights [co][kh][kw][ci] as three row-major planes
     std::vector<LstmWeights> rnn;                  // cfg.layers + 1
     float *emb = nullptr, *t_bias = nullptr;
+    // The text encoder's input projection of every embedding row, [emb_rows][8H]: text_table[v] = emb[v] . W_ih_text'^T + t_bias, made at finalize
+    // by the forward's own GEMM of each arithmetic on emb itself, so a row carries the bits gemm_text would produce for it.  [0]: the exact
+    // fp32 MFMA GEMM (mode 0), [1]: f32x6 (mode 2; null where the geometry has no f32x6 planes).  Mode 1 has none (plan.h, text_table).
+    float *text_table[2] = {nullptr, nullptr};
     float *w_score = nullptr, *fscale = nullptr, *fshift = nullptr, *w_fc = nullptr, *w_fcp = nullptr;
     SplitPtr w_score_s{nullptr, nullptr};
     std::vector<DeviceArray<unsigned char>> mem;   // the allocations behind every pointer above
@@ -83,6 +87,7 @@ struct mdd_model {
     mdd::DeviceBuf seq0_s, act_s[2], x_s, embo_s, text_s, key_s, hsplit, hx;   // split-bf16 activations (hi plane, then lo plane)
     mdd::DeviceBuf p3;          // f32x6 mode: the three bf16 planes of the projection GEMM's A operand (rewritten per GEMM)
     mdd::DeviceBuf xstack;      // mdd_forward_raw without the fused front-end: stacked copy
+    mdd::DeviceBuf tidx;        // the text projection as a table: int32 row index of every (l, b), time-major (embo is then not allocated)
     std::vector<mdd::DeviceBuf> tap_rnn;
     mdd::DeviceArray<int> err_flag;
     mdd::DeviceArray<unsigned int> sync_words;

@@ -30,6 +30,12 @@
 //   MDD_X6_OUT=fp32      f32x6 layer kernel: fp32 layer outputs and a split3_kernel   create    tests/test_x6_plane_output.py
 //                        pass in front of the next projection, instead of the layer
 //                        kernel writing that projection's bf16 planes itself
+//   MDD_TEXT_PROJ=gemm   modes 0 and 2: the text encoder's input projection as a GEMM  create    tests/test_text_table.py
+//                        per call (embed_kernel, gemm_text), instead of a gather from
+//                        the weight set's table of projected embedding rows
+//   MDD_SCORE_TILE=128   modes 0 and 2: the attention scores on the 128-column tile   create    tests/test_score_tile.py
+//                        of gemm_nt_f32_kernel where L <= 64, instead of the
+//                        64-column one
 //   MDD_TRAIN_PRECISION  training handle: bf16x3|1 starts it in the split-bf16        create    train.py
 //                        variant (mdd_train_set_precision changes it later)
 //   MDD_TRAIN_PRECISION  training handle: f32x6|2 starts it with the large            create    train.py, tests/test_train_f32x6.py
@@ -60,6 +66,8 @@ struct Switches {
     bool lstm_early = false;    // MDD_LSTM_EARLY
     int x6_redo_mask = -1;      // MDD_X6_FORCE_REDO=n: n - 1, or -1 (off)
     bool x6_out_fp32 = false;   // MDD_X6_OUT=fp32
+    bool text_gemm = false;     // MDD_TEXT_PROJ=gemm
+    bool score_wide = false;    // MDD_SCORE_TILE=128
     int train_precision = 0;    // MDD_TRAIN_PRECISION
     bool train_conv1_im2col = false;   // MDD_TRAIN_CONV1_IM2COL
 };
@@ -85,6 +93,8 @@ inline Switches read_switches() {
     const int n = e ? atoi(e) : 0;
     if (n > 0 && (n & (n - 1)) == 0) s.x6_redo_mask = n - 1;
     s.x6_out_fp32 = is(getenv("MDD_X6_OUT"), "fp32");
+    s.text_gemm = is(getenv("MDD_TEXT_PROJ"), "gemm");
+    s.score_wide = is(getenv("MDD_SCORE_TILE"), "128");
     e = getenv("MDD_TRAIN_PRECISION");
     if (is(e, "bf16x3") || is(e, "1")) s.train_precision = 1;
     if (is(e, "f32x6") || is(e, "2")) s.train_precision = 2;
@@ -129,6 +139,7 @@ struct ForwardPlan {
     size_t hx_floats;   // the persistent kernels' exchange buffer with the stamp area (0 when none runs)
     size_t stamps_at;   // where the stamps start in it
     bool planes_out;    // BiLSTM layers 0 .. layers - 2 write the next projection's three bf16 planes themselves: no fp32 copy, no split3_kernel pass
+    bool text_table;    // gemm_text gathers rows of the weight set's projected embedding table (DecodeWeights::text_table) instead of multiplying
 };
 
 inline ForwardPlan plan_forward(const mdd_config &c, int precision, const Switches &sw, const DeviceFit &fit, int B) {
@@ -154,6 +165,9 @@ inline ForwardPlan plan_forward(const mdd_config &c, int precision, const Switch
     else p.lstm = packed ? Lstm::StepPacked : Lstm::Step;
     p.gated = persist;
     p.planes_out = p.proj == Gemm::F32x6 && lx6 && !sw.x6_out_fp32;
+    // The table's rows carry the bits of the per-call projection where a C element depends on its own A row and W row alone, in one K order:
+    // gemm_nt_f32_kernel and gemm_f32x6_kernel.  The bf16x3 launcher picks its kernel by problem size, so mode 1 keeps the per-call GEMM.
+    p.text_table = p.proj != Gemm::Bf16x3 && !sw.text_gemm;
     if (persist) {   // u64 granules of the 8-workgroup teams or the three bf16 planes of the 16-workgroup ones, in floats; 256 x 6 stamps behind
         const size_t granules = team8_hx_alloc_floats(H, B), planes = lstm_x6_hx_bytes(H, B) / 4;
         p.stamps_at = lx6 ? planes : granules;

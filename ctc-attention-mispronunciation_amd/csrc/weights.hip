@@ -146,6 +146,17 @@ int build_weights(mdd_model *m, DecodeWeights &w) {
         if (!pack_gate_rows(m, "lstm_embeds.", "bias_ih_l0", H, 1, bi) || !pack_gate_rows(m, "lstm_embeds.", "bias_hh_l0", H, 1, bh)) return MDD_ERR_STATE;
         for (size_t i = 0; i < bi.size(); i++) bi[i] += bh[i];
         if ((rc = upload(w, bi, &w.t_bias))) return rc;
+        // the projected rows, through the launchers project() (api.hip) takes per call, with the embedding matrix as the operand
+        const LstmWeights &tw = w.rnn[c.layers];
+        const int G2 = 8 * H, E = c.emb_dim, V = c.emb_rows;
+        if ((rc = w.alloc(&w.text_table[0], (size_t)V * G2))) return rc;
+        if ((rc = launch_gemm_nt(w.emb, tw.wih, w.t_bias, w.text_table[0], V, G2, E, E, E, G2, 1, 0, 0, 0, nullptr))) return rc;
+        if (tw.wih_3) {
+            unsigned short *planes = nullptr;   // (kept with the set: the GEMM below reads it after this function has returned)
+            if ((rc = w.alloc(&planes, (size_t)3 * V * E)) || (rc = w.alloc(&w.text_table[1], (size_t)V * G2))) return rc;
+            if ((rc = launch_split3(w.emb, V, E, E, planes, nullptr))) return rc;
+            if ((rc = launch_gemm_f32x6(planes, (size_t)V * E, tw.wih_3, (size_t)G2 * E, w.t_bias, w.text_table[1], V, G2, E, G2, nullptr))) return rc;
+        }
     }
     {
         const auto *ws = get(m, "score.weight", (size_t)4 * H * H), *wf = get(m, "fc.1.weight", (size_t)c.num_class * 4 * H);

@@ -136,7 +136,8 @@ int mdd_forward_profile(mdd_model *m, const float *x_dev, int32_t B, int32_t T, 
                         double *flops, int32_t cap);
 /* Optional taps for parity tests: copies of stage outputs of the last mdd_forward (device buffers,
  * valid until the next forward).  name: "conv1" [T/2,B,ch*W2], "rnn<i>" [T/2,B,2H] (raw, before the
- * next layer's BatchNorm), "text" [L,B,2H], "key" [L,B,2H].  Returns the device pointer or NULL. */
+ * next layer's BatchNorm), "text" [L,B,2H], "key" [L,B,2H], "score" [B,T/2,L] (the attention
+ * scores before the softmax).  Returns the device pointer or NULL. */
 const float *mdd_tap(mdd_model *m, const char *name, int64_t *numel);
 /* Same, copied device-to-device into a caller buffer of `capacity` floats on `stream`. */
 int mdd_tap_copy(mdd_model *m, const char *name, float *dst_dev, int64_t capacity, void *stream);
