@@ -34,6 +34,7 @@
 #include <mutex>
 
 #include "mdd_internal.h"
+#include "ctc_lse.h"
 
 namespace mdd {
 
@@ -47,22 +48,6 @@ __device__ __forceinline__ double lse2(double a, double b) {
     if (b == -INFINITY) return a;
     double m = fmax(a, b);
     return m + log(exp(a - m) + exp(b - m));
-}
-
-// ---- fp64 value, fp32 increment log-adds (see the header comment)
-__device__ __forceinline__ float fexp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896340736f); }
-__device__ __forceinline__ float flog(float x) { return __builtin_amdgcn_logf(x) * 0.693147180559945309417f; }
-__device__ __forceinline__ double wlse2(double a, double b) {
-    const double m = fmax(a, b);
-    const double mm = (m == -INFINITY) ? 0.0 : m;
-    const float s = fexp((float)(a - mm)) + fexp((float)(b - mm));
-    return mm + (double)flog(s);
-}
-__device__ __forceinline__ double wlse3(double a, double b, double c) {
-    const double m = fmax(a, fmax(b, c));
-    const double mm = (m == -INFINITY) ? 0.0 : m;
-    const float s = fexp((float)(a - mm)) + fexp((float)(b - mm)) + fexp((float)(c - mm));
-    return mm + (double)flog(s);
 }
 
 // lane i <- lane i-1 (SHR) / lane i+1 (SHL) across the whole wave; the edge lane gets -inf
@@ -91,19 +76,22 @@ __device__ __forceinline__ float wave_sum(float x) {   // every lane returns the
            __builtin_bit_cast(float, __builtin_amdgcn_readlane(xi, 32)) + __builtin_bit_cast(float, __builtin_amdgcn_readlane(xi, 48));
 }
 
+// I: the integer type of the labels and lengths -- int64_t for mdd_ctc_loss (torch's targets), int32_t for the lattice of
+// mdd_ctc_variants (what the decoders and mdd_ctc_align pass).  Both run the same scan.
+template <typename I>
 struct CtcArgs {
     const float *logp; int T, B, C;
-    const int64_t *targets; int Lmax;
-    const int64_t *in_len, *tgt_len;
+    const I *targets; int tgt_stride, Lmax;   // row b of the labels starts at targets + b * tgt_stride
+    const I *in_len, *tgt_len;
     int blank;
-    float *nll, *grad;
-    double *ws;      // [B][2][T][SP] alpha rows then beta rows (grad != null only)
+    float *nll, *grad;   // nll nullable (lattice only)
+    double *ws;      // [B][2][T][SP] alpha rows then beta rows; null = no rows kept and no beta scan
     int SP;          // row pitch in doubles = 2 * (Lmax + 1)
 };
 
 // dynamic LDS: lpt[Tb][C] f32 | lab[LC] i32 | cls_off[C+1] i32 | cls_idx[LC] i32 | gam[8][LC] f32   (LC = 64 * NL)
-template <int NL>
-__global__ __launch_bounds__(512) void ctc_wave_kernel(CtcArgs a) {
+template <int NL, typename I>
+__global__ __launch_bounds__(512) void ctc_wave_kernel(CtcArgs<I> a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char sm[];
     constexpr int LC = 64 * NL;
     const int T = a.T, B = a.B, C = a.C, blank = a.blank;
@@ -126,7 +114,7 @@ __global__ __launch_bounds__(512) void ctc_wave_kernel(CtcArgs a) {
     for (int i = tid; i < LC; i += blockDim.x) {
         int l = blank;
         if (i < L) {
-            const long long v = a.targets[(size_t)b * a.Lmax + i];
+            const long long v = a.targets[(size_t)b * a.tgt_stride + i];
             if (v < 0 || v >= C) { s_bad = 1; } else l = (int)v;
         }
         lab_s[i] = l;
@@ -143,7 +131,7 @@ __global__ __launch_bounds__(512) void ctc_wave_kernel(CtcArgs a) {
         }
     __syncthreads();
     if (s_bad || Tb == 0) {
-        if (tid == 0) a.nll[b] = s_bad ? NAN : ((L == 0) ? 0.f : INFINITY);
+        if (tid == 0 && a.nll) a.nll[b] = s_bad ? NAN : ((L == 0) ? 0.f : INFINITY);
         if (a.grad && s_bad)
             for (int e = tid; e < Tb * C; e += blockDim.x) { const int t = e / C, c = e - t * C; a.grad[((size_t)t * B + b) * C + c] = 0.f; }
         return;
@@ -237,7 +225,7 @@ __global__ __launch_bounds__(512) void ctc_wave_kernel(CtcArgs a) {
             if (i == L - 1) s_fin[1] = ao[j];
         }
         if (L == 0 && lane == 0) s_fin[1] = -INFINITY;
-    } else if (wave == 1 && a.grad) {
+    } else if (wave == 1 && a.ws) {
         // ---------------- beta, backwards
         bool skip[NL];
         const int right_lab = __shfl_down(lab[0], 1);
@@ -295,7 +283,7 @@ __global__ __launch_bounds__(512) void ctc_wave_kernel(CtcArgs a) {
     }
     __syncthreads();
     const double ll = wlse2(s_fin[0], s_fin[1]);
-    if (tid == 0) a.nll[b] = (float)(-ll);
+    if (tid == 0 && a.nll) a.nll[b] = (float)(-ll);
     if (!a.grad) return;
     // ---------------- gradient rows, all waves, frames dealt round-robin
     float *g = gam + wave * LC;
@@ -327,11 +315,13 @@ __global__ __launch_bounds__(512) void ctc_wave_kernel(CtcArgs a) {
 }
 
 // dynamic LDS: row[2][Smax] double | ab[Smax] double | lab[Smax] int
+// beta_ws (nullable, [B][T][Smax] like alpha_ws): the beta rows are kept too; without grad the backward sweep then only writes them
+template <typename I>
 __global__ __launch_bounds__(256) void ctc_generic_kernel(const float *__restrict__ logp, int T, int B, int C,
-                                                          const int64_t *__restrict__ targets, int Lmax,
-                                                          const int64_t *__restrict__ in_len, const int64_t *__restrict__ tgt_len,
+                                                          const I *__restrict__ targets, int tgt_stride, int Lmax,
+                                                          const I *__restrict__ in_len, const I *__restrict__ tgt_len,
                                                           int blank, float *__restrict__ nll_out, float *__restrict__ grad,
-                                                          double *__restrict__ alpha_ws, int Smax) {
+                                                          double *__restrict__ alpha_ws, double *__restrict__ beta_ws, int Smax) {
     extern __shared__ __attribute__((aligned(16))) unsigned char sm[];
     double *row = reinterpret_cast<double *>(sm);      // [2][Smax]
     double *ab = row + 2 * Smax;                       // [Smax]
@@ -350,7 +340,7 @@ __global__ __launch_bounds__(256) void ctc_generic_kernel(const float *__restric
     for (int s = tid; s < S; s += nth) {
         int l = blank;
         if (s & 1) {
-            const long long v = targets[(size_t)b * Lmax + (s >> 1)];
+            const long long v = targets[(size_t)b * tgt_stride + (s >> 1)];
             if (v < 0 || v >= C) s_bad = 1; else l = (int)v;
         }
         lab[s] = l;
@@ -362,7 +352,7 @@ __global__ __launch_bounds__(256) void ctc_generic_kernel(const float *__restric
         }
     __syncthreads();
     if (s_bad || Tb == 0) {
-        if (tid == 0) nll_out[b] = s_bad ? NAN : ((L == 0) ? 0.f : INFINITY);
+        if (tid == 0 && nll_out) nll_out[b] = s_bad ? NAN : ((L == 0) ? 0.f : INFINITY);
         if (grad && s_bad)
             for (size_t i = tid; i < (size_t)Tb * C; i += nth) { const size_t t = i / C, c = i - t * C; grad[(t * B + b) * C + c] = 0.f; }
         return;
@@ -395,11 +385,12 @@ __global__ __launch_bounds__(256) void ctc_generic_kernel(const float *__restric
         const double *lastrow = row + ((Tb - 1) & 1) * Smax;
         const double ll = lse2(lastrow[S - 1], S > 1 ? lastrow[S - 2] : -INFINITY);
         s_ll = ll;
-        nll_out[b] = (float)(-ll);
+        if (nll_out) nll_out[b] = (float)(-ll);
     }
     __syncthreads();
-    if (!grad) return;
+    if (!grad && !beta_ws) return;
     const double ll = s_ll;
+    double *bw = beta_ws ? beta_ws + (size_t)b * T * Smax : nullptr;
     // ---- beta (backwards) fused with the gradient of each frame
     for (int t = Tb - 1; t >= 0; t--) {
         double *curr = row + (t & 1) * Smax;
@@ -417,9 +408,11 @@ __global__ __launch_bounds__(256) void ctc_generic_kernel(const float *__restric
                 v = (m == -INFINITY) ? -INFINITY : m + LP(t, l);
             }
             curr[s] = v;
-            ab[s] = aw[(size_t)t * Smax + s] + v;
+            if (bw) bw[(size_t)t * Smax + s] = v;
+            if (grad) ab[s] = aw[(size_t)t * Smax + s] + v;
         }
         __syncthreads();
+        if (!grad) continue;
         for (int c = tid; c < C; c += nth) {
             double acc = -INFINITY;
             for (int s = 0; s < S; s++)
@@ -438,11 +431,73 @@ static size_t wave_smem(int T, int C, int NL) {
 }
 
 int init_ctc_attributes() {
-    MDD_HIP_CHECK(hipFuncSetAttribute((const void *)ctc_wave_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-    MDD_HIP_CHECK(hipFuncSetAttribute((const void *)ctc_wave_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-    MDD_HIP_CHECK(hipFuncSetAttribute((const void *)ctc_wave_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-    MDD_HIP_CHECK(hipFuncSetAttribute((const void *)ctc_generic_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+    const void *k[] = {(const void *)ctc_wave_kernel<1, int64_t>, (const void *)ctc_wave_kernel<2, int64_t>, (const void *)ctc_wave_kernel<4, int64_t>,
+                       (const void *)ctc_generic_kernel<int64_t>,  (const void *)ctc_wave_kernel<1, int32_t>, (const void *)ctc_wave_kernel<2, int32_t>,
+                       (const void *)ctc_wave_kernel<4, int32_t>, (const void *)ctc_generic_kernel<int32_t>};
+    for (const void *f : k) MDD_HIP_CHECK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
     return MDD_OK;
+}
+
+static int ensure_ctc_attributes() {   // kernel attributes, once per device
+    static std::mutex mu;
+    static bool done[64] = {false};
+    int dev = 0;
+    MDD_HIP_CHECK(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lock(mu);
+    if (!done[dev & 63]) { if (int rc = init_ctc_attributes()) return rc; done[dev & 63] = true; }
+    return MDD_OK;
+}
+
+static int ctc_nl(int Lmax) { return Lmax <= 63 ? 1 : (Lmax <= 127 ? 2 : 4); }
+
+static bool ctc_wave_form(int T, int C, int Lmax) {
+    return Lmax <= 255 && C <= 256 && wave_smem(T, C, ctc_nl(Lmax)) <= 128 * 1024 && !(getenv("MDD_CTC") && !strcmp(getenv("MDD_CTC"), "generic"));
+}
+
+// One launch of the scan for either integer type.  ws: the wave form's [B][2][T][2 (Lmax + 1)] rows, or the general form's alpha rows
+// [B][T][2 Lmax + 1] followed, when want_beta, by its beta rows; null = no rows.  The caller checks the launch.
+template <typename I>
+static int launch_ctc(const float *logp, int T, int B, int C, const I *targets, int tgt_stride, int Lmax, const I *in_len, const I *tgt_len,
+                      int blank, float *nll, float *grad, double *ws, bool want_beta, const char *who, hipStream_t st) {
+    if (ctc_wave_form(T, C, Lmax)) {
+        const int NL = ctc_nl(Lmax);
+        CtcArgs<I> a;
+        a.logp = logp; a.T = T; a.B = B; a.C = C; a.targets = targets; a.tgt_stride = tgt_stride; a.Lmax = Lmax; a.in_len = in_len; a.tgt_len = tgt_len;
+        a.blank = blank; a.nll = nll; a.grad = grad; a.ws = ws; a.SP = 2 * (Lmax + 1);
+        const size_t smem = wave_smem(T, C, NL);
+        if (NL == 1) hipLaunchKernelGGL((ctc_wave_kernel<1, I>), dim3(B), dim3(512), smem, st, a);
+        else if (NL == 2) hipLaunchKernelGGL((ctc_wave_kernel<2, I>), dim3(B), dim3(512), smem, st, a);
+        else hipLaunchKernelGGL((ctc_wave_kernel<4, I>), dim3(B), dim3(512), smem, st, a);
+    } else {
+        const int Smax = 2 * Lmax + 1;
+        const size_t smem = sizeof(double) * 3 * (size_t)Smax + sizeof(int) * (size_t)Smax;
+        if (smem > 150 * 1024) { set_error("%s: Lmax=%d too long for LDS", who, Lmax); return MDD_ERR_ARG; }
+        hipLaunchKernelGGL(ctc_generic_kernel<I>, dim3(B), dim3(256), smem, st, logp, T, B, C, targets, tgt_stride, Lmax, in_len, tgt_len, blank,
+                           nll, grad, ws, (ws && want_beta) ? ws + (size_t)B * T * Smax : nullptr, Smax);
+    }
+    return MDD_OK;
+}
+
+bool ctc_lattice_fits(int T, int C, int Lmax) {    // the general form keeps 28 bytes of LDS per state
+    return ctc_wave_form(T, C, Lmax) || (size_t)28 * (2 * (size_t)Lmax + 1) <= 150 * 1024;
+}
+
+int64_t ctc_lattice_bytes(int T, int B, int C, int Lmax) {
+    if (ctc_wave_form(T, C, Lmax)) return (int64_t)sizeof(double) * B * 2 * T * (2 * ((int64_t)Lmax + 1));
+    return (int64_t)sizeof(double) * 2 * B * T * (2 * (int64_t)Lmax + 1);
+}
+
+int ctc_lattice(const float *logp, int T, int B, int C, const int32_t *len, const int32_t *ids, int ids_stride, const int32_t *nids, int Lmax,
+                int blank, double *ws, hipStream_t st, CtcLattice *out) {
+    if (int rc = ensure_ctc_attributes()) return rc;
+    if (ctc_wave_form(T, C, Lmax)) {
+        const long long SP = 2 * ((long long)Lmax + 1);
+        out->alpha = ws; out->beta = ws + (size_t)T * SP; out->utt_stride = 2 * T * SP; out->pitch = (int)SP;
+    } else {
+        const long long Smax = 2 * (long long)Lmax + 1;
+        out->alpha = ws; out->beta = ws + (size_t)B * T * Smax; out->utt_stride = T * Smax; out->pitch = (int)Smax;
+    }
+    return launch_ctc<int32_t>(logp, T, B, C, ids, ids_stride, Lmax, len, nids, blank, nullptr, nullptr, ws, true, "mdd_ctc_variants", st);
 }
 
 }  // namespace mdd
@@ -450,9 +505,7 @@ int init_ctc_attributes() {
 // bytes of workspace mdd_ctc_loss needs for these shapes when a gradient is requested (0 without one)
 extern "C" int64_t mdd_ctc_workspace_bytes(int32_t T, int32_t B, int32_t C, int32_t Lmax, int32_t want_grad) {
     if (!want_grad || T <= 0 || B <= 0 || Lmax < 0) return 0;
-    const bool wave_form = Lmax <= 255 && C <= 256 && mdd::wave_smem(T, C, Lmax <= 63 ? 1 : (Lmax <= 127 ? 2 : 4)) <= 128 * 1024 &&
-                           !(getenv("MDD_CTC") && !strcmp(getenv("MDD_CTC"), "generic"));
-    if (wave_form) return (int64_t)sizeof(double) * B * 2 * T * (2 * ((int64_t)Lmax + 1));
+    if (mdd::ctc_wave_form(T, C, Lmax)) return (int64_t)sizeof(double) * B * 2 * T * (2 * ((int64_t)Lmax + 1));
     return (int64_t)sizeof(double) * B * T * (2 * (int64_t)Lmax + 1);
 }
 
@@ -465,14 +518,7 @@ extern "C" int mdd_ctc_loss(const float *logp_dev, int32_t T, int32_t B, int32_t
         set_error("mdd_ctc_loss: bad argument"); return MDD_ERR_ARG;
     }
     hipStream_t st = (hipStream_t)stream;
-    {   // kernel attributes, once per device
-        static std::mutex mu;
-        static bool done[64] = {false};
-        int dev = 0;
-        MDD_HIP_CHECK(hipGetDevice(&dev));
-        std::lock_guard<std::mutex> lock(mu);
-        if (!done[dev & 63]) { if (int rc = init_ctc_attributes()) return rc; done[dev & 63] = true; }
-    }
+    if (int rc = ensure_ctc_attributes()) return rc;
     const int64_t need = mdd_ctc_workspace_bytes(T, B, C, Lmax, grad_dev != nullptr);
     double *ws = reinterpret_cast<double *>(workspace_dev);
     bool own_ws = false;
@@ -481,24 +527,9 @@ extern "C" int mdd_ctc_loss(const float *logp_dev, int32_t T, int32_t B, int32_t
         MDD_HIP_CHECK(hipMallocAsync((void **)&ws, (size_t)need, st));   // no caller workspace: stream-ordered allocation
         own_ws = true;
     }
-    const int NL = Lmax <= 63 ? 1 : (Lmax <= 127 ? 2 : 4);
-    const bool wave_form = Lmax <= 255 && C <= 256 && wave_smem(T, C, NL) <= 128 * 1024 &&
-                           !(getenv("MDD_CTC") && !strcmp(getenv("MDD_CTC"), "generic"));
-    if (wave_form) {
-        CtcArgs a;
-        a.logp = logp_dev; a.T = T; a.B = B; a.C = C; a.targets = targets_dev; a.Lmax = Lmax; a.in_len = in_len_dev; a.tgt_len = tgt_len_dev;
-        a.blank = blank; a.nll = nll_dev; a.grad = grad_dev; a.ws = grad_dev ? ws : nullptr; a.SP = 2 * (Lmax + 1);
-        const size_t smem = wave_smem(T, C, NL);
-        if (NL == 1) hipLaunchKernelGGL(ctc_wave_kernel<1>, dim3(B), dim3(512), smem, st, a);
-        else if (NL == 2) hipLaunchKernelGGL(ctc_wave_kernel<2>, dim3(B), dim3(512), smem, st, a);
-        else hipLaunchKernelGGL(ctc_wave_kernel<4>, dim3(B), dim3(512), smem, st, a);
-    } else {
-        const int Smax = 2 * Lmax + 1;
-        const size_t smem = sizeof(double) * 3 * (size_t)Smax + sizeof(int) * (size_t)Smax;
-        if (smem > 150 * 1024) { if (own_ws) (void)hipFreeAsync(ws, st); set_error("mdd_ctc_loss: Lmax=%d too long for LDS", Lmax); return MDD_ERR_ARG; }
-        hipLaunchKernelGGL(ctc_generic_kernel, dim3(B), dim3(256), smem, st, logp_dev, T, B, C, targets_dev, Lmax, in_len_dev,
-                           tgt_len_dev, blank, nll_dev, grad_dev, grad_dev ? ws : nullptr, Smax);
-    }
+    const int rc = launch_ctc<int64_t>(logp_dev, T, B, C, targets_dev, Lmax, Lmax, in_len_dev, tgt_len_dev, blank, nll_dev, grad_dev,
+                                       grad_dev ? ws : nullptr, false, "mdd_ctc_loss", st);
+    if (rc) { if (own_ws) (void)hipFreeAsync(ws, st); return rc; }
     hipError_t le = hipGetLastError();
     if (own_ws) (void)hipFreeAsync(ws, st);
     if (le != hipSuccess) { set_error("ctc kernel launch failed: %s", hipGetErrorString(le)); return MDD_ERR_HIP; }

@@ -162,6 +162,14 @@ int launch_attn_tail(const float *S, int Lp, const float *X, const float *V, con
 
 int init_kernel_attributes();
 int init_ctc_attributes();
+// The alpha / beta lattice of ctc.hip on int32 ids (mdd_ctc_variants): row t of utterance b starts at alpha + b * utt_stride + t * pitch
+// (beta likewise) and holds states 0 .. 2 nids[b] (fp64, the emission at t included); frames >= len[b] and the utterances the scan rejects
+// (len 0, a label outside [0, C)) are not written.  ws: ctc_lattice_bytes(T, B, C, Lmax) bytes.
+struct CtcLattice { const double *alpha, *beta; long long utt_stride; int pitch; };
+int64_t ctc_lattice_bytes(int T, int B, int C, int Lmax);
+bool ctc_lattice_fits(int T, int C, int Lmax);   // false: Lmax is past what either form of the scan holds in LDS
+int ctc_lattice(const float *logp, int T, int B, int C, const int32_t *len, const int32_t *ids, int ids_stride, const int32_t *nids, int Lmax,
+                int blank, double *ws, hipStream_t st, CtcLattice *out);
 int init_lstm_attributes();
 // One launch for the whole layer (256 co-resident workgroups in 8-workgroup teams, data-tagged hand-off; see lstm.hip).
 int init_granule_attributes();

@@ -171,3 +171,39 @@ def ctc_align(logp, lens, ids, nids, blank=0, max_len=None, want_path=True, want
                                             ptr(nids), Lmax, blank, ptr(score), ptr(status), ptr(path), ptr(seg), ptr(seg_logp),
                                             ptr(ws), ws.numel() * 8, _lib.current_stream_ptr()))
     return AlignResult(score, status, path, seg, seg_logp)
+
+
+VariantResult = collections.namedtuple("VariantResult", "base sub ins status")
+
+
+def ctc_variants(logp, lens, ids, nids, blank=0, max_len=None, want_ins=True):
+    """CTC log-likelihood of every sequence one edit away from ``ids`` (mdd_ctc_variants), from two lattices per utterance.
+
+    logp [T,B,C] fp32 CUDA, lens [B], ids [B,stride] / nids [B] as ``ctc_align`` takes them (int32 CUDA tensors pass through with no
+    copy); ``max_len`` bounds nids (default: ids.shape[1], so the call needs no sync).  Returns
+    ``VariantResult(base [B] f64, sub [B,stride,C] f64, ins [B,stride+1,C] f64 | None, status [B] i32)``, absolute log-likelihoods:
+    sub[b,i,k] with ids[i] replaced by k (k == blank: ids[i] deleted; k == ids[i]: base), ins[b,g,k] with k inserted before position g
+    (k == blank: base); rows past nids[b] are -inf up to ``max_len`` and not written beyond it.  Nothing synchronises."""
+    assert logp.is_cuda and logp.dtype == torch.float32
+    logp = logp.contiguous()
+    T, B, Cn = logp.shape
+    dev = logp.device
+    lens = torch.as_tensor(lens).to(dev, torch.int32).contiguous()
+    ids = torch.as_tensor(ids).to(dev, torch.int32).contiguous()
+    nids = torch.as_tensor(nids).to(dev, torch.int32).contiguous()
+    if ids.dim() != 2 or ids.shape[0] != B or lens.shape != (B,) or nids.shape != (B,):
+        raise ValueError("ctc_variants: lens [B], ids [B, stride], nids [B]")
+    stride = ids.shape[1]
+    Lmax = stride if max_len is None else int(max_len)
+    base = torch.empty((B,), dtype=torch.float64, device=dev)
+    sub = torch.empty((B, stride, Cn), dtype=torch.float64, device=dev)
+    ins = torch.empty((B, stride + 1, Cn), dtype=torch.float64, device=dev) if want_ins else None
+    status = torch.empty((B,), dtype=torch.int32, device=dev)
+    nws = _lib.lib().mdd_ctc_variants_workspace_bytes(T, B, Cn, max(Lmax, 0))
+    ws = torch.empty((max(nws, 16) + 7) // 8, dtype=torch.float64, device=dev)      # torch's caching allocator, as ctc_loss
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().mdd_ctc_variants(ptr(logp), T, B, Cn, ptr(lens), C.c_void_p(ids.data_ptr() if stride else ws.data_ptr()), stride,
+                                               ptr(nids), Lmax, blank, ptr(base), C.c_void_p(sub.data_ptr() if stride else ws.data_ptr()),
+                                               ptr(ins), ptr(status), ptr(ws), ws.numel() * 8, _lib.current_stream_ptr()))
+    return VariantResult(base, sub, ins, status)

@@ -2,7 +2,7 @@
 (AA/infer.py:435-598, ``main``), run as
 
     python -m ctc_attention_mispronunciation_amd.infer --conf CONF --wav_transcript_path DIR [-p cmudict] [-f cmu]
-        [--cmvn PATH] [--cmudict PATH] [--precision f32x6|f32|bf16x3] [--decode_seq PATH] [--timestamps]
+        [--cmvn PATH] [--cmudict PATH] [--precision f32x6|f32|bf16x3] [--decode_seq PATH] [--timestamps] [--posteriors]
 
 The conf YAML is read as ``infer_init`` reads it (AA/infer.py:211-261): the checkpoint
 ``checkpoint_dir/exp_name/ctc_best_model.pkl``, ``vocab_file``, ``decode_type``, ``beam_width``, ``lm_path``, ``lm_alpha``,
@@ -52,6 +52,9 @@ def parse_args(argv=None):
     ap.add_argument("--timestamps", action="store_true",
                     help="add a 'time   :' line (start-end seconds and confidence per decoded phoneme) and a 'gop    :' line (mean "
                          "log-posterior per canonical phoneme) to each block; times are nominal frame starts")
+    ap.add_argument("--posteriors", action="store_true",
+                    help="add a 'post   :' line to each block: per canonical phoneme the probability that it was pronounced and the most "
+                         "probable alternative (its deletion or a substitute), from the CTC likelihood of every one-edit variant")
     return ap.parse_args(argv)
 
 
@@ -163,7 +166,7 @@ def main(argv=None):
                             n_downsample=getattr(opts, "n_downsample", 2))
     device = torch.device("cuda", torch.cuda.current_device())
     c1, c2, c3 = infer(phonetic, word_dict, loader, device, model, decoder, vocab, transcripts, False,
-                       decode_seq_path=args.decode_seq, timestamps=args.timestamps)
+                       decode_seq_path=args.decode_seq, timestamps=args.timestamps, posteriors=args.posteriors)
     print(c1, c2, c3)
     end = time.time()
     total = max(total_wav_time, 1e-9)

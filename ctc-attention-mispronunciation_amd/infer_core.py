@@ -90,6 +90,39 @@ def _tokens(phones):
     return phones.split() if isinstance(phones, str) else [p for p in phones if p]
 
 
+def diagnose_indexed(decoded_phones, canonical_phones, decoder, to_display=None):
+    """``diagnose`` plus, for every row of its ``path``, which token of the inputs the row shows: returns ``(d, rows)`` with rows[r] =
+    ``(decoded_index | None, canonical_index | None)`` into the token lists as given (None on the side a 'D' / 'I' row leaves empty).
+    The indices follow their tokens through the 'sil' strip, the 'err' removal and the leading-insertion drops of ``diagnose`` /
+    ``align_canonical_decoded``, so per-token data of any kind (spans, posteriors) can ride along; a path that does not fit the token
+    counts raises ValueError rather than mis-assigning an entry."""
+    dec, can = _tokens(decoded_phones), _tokens(canonical_phones)
+    d = diagnose(" ".join(dec), " ".join(can), decoder, to_display)
+    # the same strip as diagnose, with each token's index carried along ('err' is removed as a substring, as diagnose removes it)
+    dec_kept = [i for i, p in enumerate(dec) if p != "sil" and p.replace("err", "")]
+    can_kept = [i for i, p in enumerate(can) if p != "sil"]
+    hyp = " ".join(dec[i].replace("err", "") for i in dec_kept)
+    _, full = decoder.wer(hyp, " ".join(can[i] for i in can_kept))
+    dropped = len(full) - len(d["path"])
+    if dropped < 0 or list(full[dropped:]) != list(d["path"]) or any(op != "I" for op in full[:dropped]) \
+            or sum(op != "D" for op in full) != len(dec_kept) or sum(op != "I" for op in full) != len(can_kept):
+        raise ValueError("diagnose_indexed: the alignment path does not fit the phoneme counts")
+    rows = []
+    di, ci = dropped, 0                      # the dropped leading rows are insertions: decoded tokens only
+    for op in d["path"]:
+        i = c = None
+        if op != "D":
+            i = dec_kept[di]
+            di += 1
+        if op != "I":
+            c = can_kept[ci]
+            ci += 1
+        rows.append((i, c))
+    if di != len(dec_kept) or ci != len(can_kept):
+        raise ValueError("diagnose_indexed: the alignment path does not fit the phoneme counts")
+    return d, rows
+
+
 def diagnose_timed(decoded_phones, spans, canonical_phones, canon_spans, decoder, seconds_per_frame, to_display=None):
     """``diagnose`` plus timing and goodness of pronunciation.  decoded_phones / canonical_phones: the phoneme strings ``diagnose``
     takes (or token lists); spans / canon_spans: one ``(start_frame, end_frame, mean_logp)`` per token of each, from the forced
@@ -108,32 +141,16 @@ def diagnose_timed(decoded_phones, spans, canonical_phones, canon_spans, decoder
         raise ValueError("diagnose_timed: %d spans for %d decoded phonemes" % (len(spans), len(dec)))
     if canon_spans is not None and len(canon_spans) != len(can):
         raise ValueError("diagnose_timed: %d spans for %d canonical phonemes" % (len(canon_spans), len(can)))
-    d = diagnose(" ".join(dec), " ".join(can), decoder, to_display)
-    # the same strip as diagnose, with each token's index carried along ('err' is removed as a substring, as diagnose removes it)
-    dec_kept = [i for i, p in enumerate(dec) if p != "sil" and p.replace("err", "")]
-    can_kept = [i for i, p in enumerate(can) if p != "sil"]
-    hyp = " ".join(dec[i].replace("err", "") for i in dec_kept)
-    _, full = decoder.wer(hyp, " ".join(can[i] for i in can_kept))
-    dropped = len(full) - len(d["path"])
-    if dropped < 0 or list(full[dropped:]) != list(d["path"]) or any(op != "I" for op in full[:dropped]) \
-            or sum(op != "D" for op in full) != len(dec_kept) or sum(op != "I" for op in full) != len(can_kept):
-        raise ValueError("diagnose_timed: the alignment path does not fit the phoneme counts")
+    d, rows = diagnose_indexed(dec, can, decoder, to_display)
     times, gop = [], []
-    di, ci = dropped, 0                      # the dropped leading rows are insertions: decoded tokens only
-    for op in d["path"]:
+    for i, c in rows:
         t = g = None
-        if op != "D":
-            if spans is not None:
-                s, e, m = spans[dec_kept[di]]
-                t = (s * seconds_per_frame, e * seconds_per_frame, math.exp(m))
-            di += 1
-        if op != "I":
-            if canon_spans is not None:
-                g = canon_spans[can_kept[ci]][2]
-            ci += 1
+        if i is not None and spans is not None:
+            s, e, m = spans[i]
+            t = (s * seconds_per_frame, e * seconds_per_frame, math.exp(m))
+        if c is not None and canon_spans is not None:
+            g = canon_spans[c][2]
         times.append(t); gop.append(g)
-    if di != len(dec_kept) or ci != len(can_kept):
-        raise ValueError("diagnose_timed: the alignment path does not fit the phoneme counts")
     return dict(d, times=times, gop=gop)
 
 
@@ -143,6 +160,48 @@ def timed_lines(d):
     tl = ["%s[%s]" % (p, "-" if t is None else "%.2f-%.2f %.2f" % t) for p, t, op in zip(d["decoded"], d["times"], d["path"]) if op != "D"]
     gl = ["%s[%s]" % (p, "-" if g is None else "%.2f" % g) for p, g, op in zip(d["canonical"], d["gop"], d["path"]) if op != "I"]
     return "time   : " + " ".join(tl), "gop    : " + " ".join(gl)
+
+
+def diagnose_posterior(decoded_phones, canonical_phones, positions, decoder, names=None, to_display=None):
+    """``diagnose`` plus the per-phoneme posteriors of the canonical sequence.  positions: one ``(p_correct, p_deleted, alt_id, p_alt)``
+    per token of canonical_phones (the first element of an utterance's ``ctcDecoder.phoneme_posteriors`` result), or ``None`` when the
+    canonical ids have no alignment.  Returns ``diagnose``'s dict with one more key, index-aligned with ``path``:
+      post   (p_correct, p_deleted, alt, p_alt) of the canonical phoneme on '-', 'S' and 'D' rows -- alt is ``names[alt_id]`` when
+             ``names`` (index -> phoneme) is given, passed through ``to_display`` like the rows, else alt_id -- None on 'I' rows (and on
+             every row when ``positions`` is None).
+    The entries follow their canonical tokens through the 'sil' strip exactly as ``diagnose_timed`` carries ``canon_spans``
+    (``diagnose_indexed`` serves both)."""
+    can = _tokens(canonical_phones)
+    if positions is not None and len(positions) != len(can):
+        raise ValueError("diagnose_posterior: %d entries for %d canonical phonemes" % (len(positions), len(can)))
+    d, rows = diagnose_indexed(decoded_phones, can, decoder, to_display)
+
+    def named(p):
+        if names is None:
+            return p
+        alt = names[p[2]]
+        if to_display is not None:
+            alt = to_display.get(alt.upper(), alt)
+        return (p[0], p[1], alt, p[3])
+
+    post = [None if c is None or positions is None else named(positions[c]) for _, c in rows]
+    return dict(d, post=post)
+
+
+def posterior_line(d):
+    """The extra line of a printed block: ``post   : ph[p_correct alt:p_alt] ...`` over the canonical row without its 'I' placeholders;
+    alt is the most probable single alternative -- 'del' when that is the deletion of the phoneme, else the best substitute -- and '-'
+    stands for an unknown entry."""
+    toks = []
+    for p, q, op in zip(d["canonical"], d["post"], d["path"]):
+        if op == "I":
+            continue
+        if q is None:
+            toks.append("%s[-]" % p)
+        else:
+            alt, pa = ("del", q[1]) if q[1] >= q[3] else (q[2], q[3])
+            toks.append("%s[%.2f %s:%.2f]" % (p, q[0], alt, pa))
+    return "post   : " + " ".join(toks)
 
 
 def seconds_per_frame(test_loader, cnn_time_stride):
@@ -158,7 +217,7 @@ def seconds_per_frame(test_loader, cnn_time_stride):
 
 
 def infer(phonetic, word_dict, test_loader, device, model, decoder, vocab, test_transcipt_dict, use_ipa, out=None,
-          decode_seq_path=None, timestamps=False):
+          decode_seq_path=None, timestamps=False, posteriors=False):
     """AA/infer.py:282-372.  Per batch ``(inputs, input_sizes, _, _, trans, trans_sizes, utt_list)``: ``model(inputs, trans)``,
     frame counts ``(input_sizes * T').long()``, ``decoder.decode``, then per utterance the 'sil' strip, 'err' removal, ``wer``,
     alignment, fault lists and score (``diagnose``), printed as the reference's 13-line block to ``out`` (stdout by default).
@@ -171,7 +230,13 @@ def infer(phonetic, word_dict, test_loader, device, model, decoder, vocab, test_
 
     ``timestamps=True`` (no reference counterpart) adds two lines to each block between ``score  :`` and the closing empty line --
     ``time   :`` and ``gop    :`` (``diagnose_timed`` / ``timed_lines``) -- from two forced alignments per batch on the GPU: of the
-    decoder's own ids and of the canonical ids.  Times are nominal frame starts (``seconds_per_frame``); nothing else changes."""
+    decoder's own ids and of the canonical ids.  Times are nominal frame starts (``seconds_per_frame``); nothing else changes.
+
+    ``posteriors=True`` (no reference counterpart) adds one line, ``post   :`` (``diagnose_posterior`` / ``posterior_line``), before the
+    closing empty line and after the ``timestamps`` lines if both are asked for: per canonical phoneme the probability that it was
+    pronounced and the most probable alternative, from one ``phoneme_posteriors`` call per batch.  Without it nothing changes."""
+    if posteriors:
+        from .utils.ctcDecoder import phoneme_posteriors
     out = sys.stdout if out is None else out
     to_display = phonetic.cmu_to_ipa_wiki if use_ipa else None
     translate = getattr(phonetic, "api_word_translation", None)
@@ -193,6 +258,8 @@ def infer(phonetic, word_dict, test_loader, device, model, decoder, vocab, test_
                     spf = seconds_per_frame(test_loader, inputs.size(1) // probs.size(0))
                 else:
                     decoded = decoder.decode(probs, lens.numpy().tolist())
+                if posteriors:
+                    post = phoneme_posteriors(probs, lens.numpy().tolist(), trans, trans_sizes, decoder.blank_index)
                 trans, trans_sizes = trans.cpu().numpy(), trans_sizes.numpy()
                 for x in range(len(decoded)):
                     canonical = " ".join(vocab.index2word[num] for num in trans[x][:trans_sizes[x]])
@@ -210,6 +277,10 @@ def infer(phonetic, word_dict, test_loader, device, model, decoder, vocab, test_
                              "score  : " + str(d["score"]), ""]
                     if timestamps:
                         block[-1:-1] = timed_lines(d)
+                    if posteriors:
+                        dp = diagnose_posterior(decoded[x], canonical, None if post[x] is None else post[x][0], decoder, vocab.index2word,
+                                                to_display)
+                        block[-1:-1] = [posterior_line(dp)]
                     out.write("\n".join(block) + "\n")
                     total_correct_cnt += d["correct"]
                     total_cnt += d["correct"] + d["del_sub"]

@@ -165,6 +165,50 @@ def timed_spans(prob_tensor, frame_seq_len, ids, nids, blank=0):
     return out
 
 
+def phoneme_posteriors(prob_tensor, frame_seq_len, ids, nids, blank=0):
+    """Per-phoneme posteriors of the canonical ``ids`` / ``nids`` ([B, stride] / [B]) from the CTC likelihood of every sequence one edit
+    away (mdd_ctc_variants).  Per utterance ``None`` when the ids are no valid targets or have no alignment themselves, else
+    ``(positions, gaps)``: positions[i] = ``(p_correct, p_deleted, alt_id, p_alt)`` -- the softmax over the C entries of sub[b, i, :]
+    (the phoneme itself, its deletion, each substitute), alt_id the most probable substitute and p_alt its probability; gaps[g] =
+    ``(ins_id, p_ins)`` for 0 <= g <= nids[b] -- the most probable insertion before position g in the softmax over ins[b, g, :], whose
+    blank entry is "nothing inserted".  Variants without an alignment have probability 0."""
+    import numpy as np
+    from ..hip_model import ctc_variants
+    lp = _device_posteriors(prob_tensor)
+    T, B, _ = lp.shape
+    lens = _lens_tensor(frame_seq_len, B, T, lp.device)
+    ids_h, n = torch.as_tensor(ids).cpu().numpy(), torch.as_tensor(nids).cpu().numpy()
+    r = ctc_variants(lp, lens, ids, nids, blank=blank, max_len=min(max(int(n.max()), 0), ids_h.shape[1]))     # no slots past the longest row
+    status, sub, ins = r.status.cpu().numpy(), r.sub.cpu().numpy(), r.ins.cpu().numpy()
+
+    def softmax(row):
+        with np.errstate(under="ignore"):
+            e = np.exp(row - row.max())      # -inf entries: exactly 0
+        return e / e.sum()
+
+    out = []
+    for b in range(B):
+        if status[b] != 0:
+            out.append(None)
+            continue
+        positions, gaps = [], []
+        for i in range(int(n[b])):
+            p = softmax(sub[b, i])
+            own = int(ids_h[b, i])
+            alt = p.copy()
+            alt[own] = alt[blank] = -1.0
+            k = int(alt.argmax())
+            positions.append((float(p[own]), float(p[blank]), k, float(p[k])))
+        for g in range(int(n[b]) + 1):
+            p = softmax(ins[b, g])
+            alt = p.copy()
+            alt[blank] = -1.0
+            k = int(alt.argmax())
+            gaps.append((k, float(p[k])))
+        out.append((positions, gaps))
+    return out
+
+
 class GreedyDecoder(Decoder):
     """argmax per frame, collapse repeats, drop blanks (ctcDecoder.py:186-200)."""
 

@@ -217,6 +217,34 @@ int mdd_ctc_align(const float *logp_dev, int32_t T, int32_t B, int32_t C, const 
                   float *score_dev, int32_t *status_dev, int32_t *path_dev, int32_t *seg_dev, float *seg_logp_dev,
                   void *workspace_dev, int64_t workspace_bytes, void *stream);
 
+/* ---- Per-phoneme CTC posteriors (no reference counterpart): the CTC log-likelihood of every sequence one edit away from ids -- every
+ * substitution, deletion and insertion -- from the alpha / beta lattices of ids alone (csrc/ctc_variants.hip, DESIGN.md "One-edit
+ * variants").  Inputs as mdd_ctc_align (logp_dev [T,B,C], len_dev [B] clamped to [0,T], frames >= len never read; ids_dev [B,ids_stride] /
+ * nids_dev [B] int32; 0 <= Lmax <= ids_stride bounds nids).  Outputs, all absolute log-likelihoods in fp64:
+ *   base_dev [B]                  log P(ids)
+ *   sub_dev [B,ids_stride,C]      [i,k]: ids[i] replaced by k;  k == blank: ids[i] deleted;  k == ids[i]: base, the same bits;
+ *                                 rows nids[b] <= i < Lmax are -inf, rows >= Lmax are not written
+ *   ins_dev [B,ids_stride+1,C]    (nullable) [g,k]: k inserted before position g, 0 <= g <= nids[b];  k == blank: base, the same bits;
+ *                                 rows nids[b] < g <= Lmax are -inf, rows > Lmax are not written
+ *   status_dev [B]                mdd_align_status
+ * A variant without an alignment (a repeat that len cannot hold) is -inf; that is no error.  ids itself without an alignment:
+ * MDD_ALIGN_INFEASIBLE, base -inf, the variants still scored on their own.  len = 0: the empty variant scores 0, every other -inf.
+ * MDD_ALIGN_BAD_TARGET (a label outside [0,C) or equal to blank, nids[b] outside [0,Lmax]): every output row of that utterance is NaN;
+ * other utterances are unaffected.  Arithmetic: mdd_ctc_loss's (fp64 values, fp32 exp / log increments); no atomics, the same bits on
+ * every call.  base equals -nll of mdd_ctc_loss to fp32 rounding.
+ * workspace_dev: caller-owned scratch of at least mdd_ctc_variants_workspace_bytes(T,B,C,Lmax) bytes (16-byte aligned; the two lattices),
+ *   NULL = the library allocates stream-ordered for the call.  Nothing synchronises.  Env MDD_CTC_VARIANTS_WAVES = 1, 2, 4 or 8 (read per call, default 4) sets the
+ *   slots per workgroup of the variant kernel, for timing; the results do not depend on it.  Env MDD_CTC=generic selects the general lattice
+ *   kernel as for mdd_ctc_loss (it is also what Lmax > 255 runs).
+ * Bad host arguments (a required pointer NULL, T/B/C <= 0, C > 256, blank outside [0,C), Lmax < 0 or > ids_stride, an Lmax past 255 whose
+ *   2 Lmax + 1 lattice states do not fit the general kernel's LDS rows (Lmax > 2742), a caller workspace that is too small) return
+ *   MDD_ERR_ARG before any device work. */
+int64_t mdd_ctc_variants_workspace_bytes(int32_t T, int32_t B, int32_t C, int32_t Lmax);
+int mdd_ctc_variants(const float *logp_dev, int32_t T, int32_t B, int32_t C, const int32_t *len_dev,
+                     const int32_t *ids_dev, int32_t ids_stride, const int32_t *nids_dev, int32_t Lmax, int32_t blank,
+                     double *base_dev, double *sub_dev, double *ins_dev, int32_t *status_dev,
+                     void *workspace_dev, int64_t workspace_bytes, void *stream);
+
 /* ---- A10: Decoder.wer core = _edit_distance + printChanges (AA/utils/ctcDecoder.py:118-184), host.
  * a = hypothesis tokens, b = canonical tokens; ops (capacity >= na+nb): 0 '-', 1 'S', 2 'I', 3 'D'.
  * Either side empty -> MDD_ERR_EMPTY (reference: TypeError). */
