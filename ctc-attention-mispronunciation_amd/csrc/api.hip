@@ -103,13 +103,13 @@ static LstmStepArgs lstm_folded_out(mdd_model *m, int n, int T, int B, const int
 struct ProjIn { const float *f32; SplitPtr split; bool planes_written; };
 static int project(mdd_model *m, const ProjIn &in, int rows, int K, const LstmWeights &lw, const float *bias, hipStream_t st) {
     const int G2 = 8 * m->cfg.hidden;
-    if (m->plan.proj == Gemm::Bf16x3) return launch_gemm_bf16x3(in.split, lw.wih_s, bias, m->gx.p, nullptr, rows, G2, K, K, K, G2, 1, 0, 0, 0, st);
+    if (m->plan.proj == Gemm::Bf16x3) return launch_gemm_bf16x3({.p = in.split, .ld = K}, {.p = lw.wih_s, .ld = K}, m->gx.p, nullptr, G2, rows, G2, K, st, {.bias = bias});
     if (m->plan.proj == Gemm::F32x6) {   // fp32-grade arithmetic at 6/16 of the fp32 MFMA's cost (gemm_bf16x6.hip)
         if (!in.planes_written)
             if (int rc = launch_split3(in.f32, rows, K, K, as_u16(m->p3), st)) return rc;
         return launch_gemm_f32x6(as_u16(m->p3), (size_t)rows * K, lw.wih_3, (size_t)G2 * K, bias, m->gx.p, rows, G2, K, G2, st);
     }
-    return launch_gemm_nt(in.f32, lw.wih, bias, m->gx.p, rows, G2, K, K, K, G2, 1, 0, 0, 0, st);
+    return launch_gemm_nt({.p = in.f32, .ld = K}, {.p = lw.wih, .ld = K}, m->gx.p, G2, rows, G2, K, st, {.bias = bias});
 }
 
 // One stage of the forward: one or more kernel launches (none where a neighbour has absorbed it in this configuration); run enqueues it.
@@ -180,14 +180,15 @@ static std::vector<Stage> forward_stages(mdd_model *m, const ForwardCall &call) 
     s.push_back({"gemm_key", 1, 2.0 * (double)L * B * H2 * H2, [=](hipStream_t st) {
         if (x3) {
             const SplitPtr ks = split_view(m->key_s, trows * H2);
-            return launch_gemm_bf16x3(split_view(m->text_s, trows * H2), w->w_score_s, nullptr, nullptr, &ks, L * B, H2, H2, H2, H2, H2, 1, 0, 0, 0, st);
+            return launch_gemm_bf16x3({.p = split_view(m->text_s, trows * H2), .ld = H2}, {.p = w->w_score_s, .ld = H2}, nullptr, &ks, H2, L * B, H2, H2, st);
         }
-        return launch_gemm_nt(m->text.p, w->w_score, nullptr, m->key.p, L * B, H2, H2, H2, H2, H2, 1, 0, 0, 0, st);
+        return launch_gemm_nt({.p = m->text.p, .ld = H2}, {.p = w->w_score, .ld = H2}, m->key.p, H2, L * B, H2, H2, st);
     }});
     s.push_back({"gemm_score", 1, 2.0 * (double)B * Tp * L * H2, [=](hipStream_t st) {   // scores S[b][t][l] = X[t,b,:] . key[l,b,:]   (:204)
-        if (x3) return launch_gemm_bf16x3(split_view(m->x_s, rows * H2), split_view(m->key_s, trows * H2), nullptr, m->S.p, nullptr, Tp, L, H2, B * H2, B * H2, Lp,
-                                          B, H2, H2, (long)Tp * Lp, st);
-        return launch_gemm_nt(m->xraw.p, m->key.p, nullptr, m->S.p, Tp, L, H2, B * H2, B * H2, Lp, B, H2, H2, (long)Tp * Lp, st, m->sw.score_wide);
+        const GemmOpts per_utt{.batch = B, .sC = (long)Tp * Lp};
+        if (x3) return launch_gemm_bf16x3({.p = split_view(m->x_s, rows * H2), .ld = B * H2, .stride = H2}, {.p = split_view(m->key_s, trows * H2), .ld = B * H2, .stride = H2},
+                                          m->S.p, nullptr, Lp, Tp, L, H2, st, per_utt);
+        return launch_gemm_nt({.p = m->xraw.p, .ld = B * H2, .stride = H2}, {.p = m->key.p, .ld = B * H2, .stride = H2}, m->S.p, Lp, Tp, L, H2, st, per_utt, m->sw.score_wide);
     }});
     s.push_back({"attn_tail", 1, 2.0 * (double)B * Tp * ((double)L * H2 + 2.0 * H2 * c.num_class), [=](hipStream_t st) {
         return launch_attn_tail(m->S.p, Lp, m->xraw.p, m->text.p, w->fscale, w->fshift, w->w_fc, w->w_fcp, call.logp, Tp, B, L, H2, c.num_class, st, call.llen);

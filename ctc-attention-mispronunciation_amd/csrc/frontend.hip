@@ -461,7 +461,6 @@ __device__ __forceinline__ int cm_yoff(int slot, int col, int chunk) { return (s
 // STAMP (diagnostic instantiation, mdd_diag_conv_time): per wave, cycle sums of the CM_NPH phases of a block -> stamps[(workgroup * 8 +
 // wave) * CM_NPH + phase] for the first 512 workgroups: 0 wait for the previous block's readers, 1 x tile store, 2 barrier, 3 conv0 and the
 // next x request, 4 barrier, 5 conv1 and the K-half partials, 6 barrier, 7 conv1 epilogue, 8 barrier, 9 row stores (tools/conv_stamps.py)
-constexpr int CM_NPH = 10;
 template <int NP, int R, bool STAMP>
 __global__ __launch_bounds__(512, 1) void conv_fused_kernel(const float *__restrict__ x, const float *__restrict__ w0,
                                                             const float *__restrict__ sc0, const float *__restrict__ sh0,
@@ -765,93 +764,4 @@ int init_conv_attributes() {
     return MDD_OK;
 }
 
-__global__ void conv_diag_fill_kernel(float *x, size_t n, unsigned seed, float scale, float offset) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        unsigned h = (unsigned)i * 2654435761u + seed; h ^= h >> 15; h *= 2246822519u; h ^= h >> 13;
-        x[i] = ((float)(h & 0xffffff) / 8388608.f - 1.f) * scale + offset;
-    }
-}
-__global__ void conv_diag_split3_kernel(const float *w, int n, unsigned short *planes) {   // row-major hi | mid | lo planes of n elements
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        const float v = w[i];
-        const __bf16 h = (__bf16)v;
-        const float r1 = v - (float)h;
-        const __bf16 m = (__bf16)r1, l = (__bf16)(r1 - (float)m);
-        planes[i] = *reinterpret_cast<const unsigned short *>(&h);
-        planes[n + i] = *reinterpret_cast<const unsigned short *>(&m);
-        planes[2 * n + i] = *reinterpret_cast<const unsigned short *>(&l);
-    }
-}
-
 }  // namespace mdd
-
-// Timing aid: `reps` launches of the f32x6 conv front end on pseudo-random features and weights ([B, T, 243] -> T/2 * B rows) between
-// events -> mean ms.  which: 0 the default kernel, 1 the row-at-a-time kernel.  phases (nullable, which = 0 only): one extra launch of the
-// stamped instantiation; phases[wave * 10 + phase] receives the mean cycles per workgroup (over the first 512) of that wave in that phase.
-// mismatch (nullable) receives the number of output words in which the two kernels differ.
-extern "C" int mdd_diag_conv_time(int B, int T, int reps, int which, float *ms_out, double *phases, long long *mismatch) {
-    using namespace mdd;
-    if (B <= 0 || T < 2 || reps < 1 || which < 0 || which > 1 || !ms_out) { set_error("mdd_diag_conv_time: bad arguments"); return MDD_ERR_ARG; }
-    const int Tp = T / 2;
-    const size_t nx = (size_t)B * T * 243, nout = (size_t)3 * Tp * B * 1952;
-    DeviceBuf xb, wb;              // wb: w0 [288] | sc0 [32] | sh0 [32] | sc1 [32] | sh1 [32] | w1 [32 * 288]
-    DeviceArray<unsigned short> w13, out, out2;
-    DeviceArray<long long> sd;
-    if (int rc = init_conv_attributes()) return rc;
-    if (xb.need(nx) || wb.need(416 + 32 * 288) || w13.need(3 * 32 * 288) || out.need(nout) || (mismatch && out2.need(nout)) ||
-        (phases && sd.need((size_t)512 * 8 * CM_NPH))) return MDD_ERR_HIP;
-    hipLaunchKernelGGL(conv_diag_fill_kernel, dim3(4096), dim3(256), 0, 0, xb.p, nx, 1u, 2.f, 0.f);
-    hipLaunchKernelGGL(conv_diag_fill_kernel, dim3(4), dim3(256), 0, 0, wb.p, (size_t)288, 2u, 0.4f, 0.f);
-    hipLaunchKernelGGL(conv_diag_fill_kernel, dim3(1), dim3(64), 0, 0, wb.p + 288, (size_t)32, 3u, 0.2f, 1.f);
-    hipLaunchKernelGGL(conv_diag_fill_kernel, dim3(1), dim3(64), 0, 0, wb.p + 320, (size_t)32, 4u, 0.3f, 0.1f);
-    hipLaunchKernelGGL(conv_diag_fill_kernel, dim3(1), dim3(64), 0, 0, wb.p + 352, (size_t)32, 5u, 0.2f, 1.f);
-    hipLaunchKernelGGL(conv_diag_fill_kernel, dim3(1), dim3(64), 0, 0, wb.p + 384, (size_t)32, 6u, 0.3f, 0.1f);
-    hipLaunchKernelGGL(conv_diag_fill_kernel, dim3(36), dim3(256), 0, 0, wb.p + 416, (size_t)32 * 288, 7u, 0.1f, 0.f);
-    hipLaunchKernelGGL(conv_diag_split3_kernel, dim3(36), dim3(256), 0, 0, wb.p + 416, 32 * 288, w13.p);
-    MDD_LAUNCH_CHECK();
-    auto run = [&](int w, unsigned short *o, long long *stp) {
-        return launch_conv_fused3(xb.p, wb.p, wb.p + 288, wb.p + 320, w13.p, wb.p + 352, wb.p + 384, o, nullptr, B, T, 0, 0, w == 1, stp);
-    };
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    MDD_HIP_CHECK(hipEventCreate(&e0));
-    MDD_HIP_CHECK(hipEventCreate(&e1));
-    int rc = MDD_OK;
-    for (int r = -2; r < reps && !rc; r++) {
-        if (r == 0) (void)hipEventRecord(e0, 0);
-        rc = run(which, out.p, nullptr);
-    }
-    (void)hipEventRecord(e1, 0);
-    if (hipEventSynchronize(e1) != hipSuccess) rc = rc ? rc : MDD_ERR_HIP;
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, e0, e1);
-    *ms_out = ms / reps;
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    if (!rc && phases) {
-        const size_t ns = (size_t)512 * 8 * CM_NPH;
-        MDD_HIP_CHECK(hipMemset(sd.p, 0, ns * 8));
-        rc = run(0, out.p, sd.p);
-        std::vector<long long> h(ns);
-        MDD_HIP_CHECK(hipMemcpy(h.data(), sd.p, ns * 8, hipMemcpyDeviceToHost));
-        for (int i = 0; i < 8 * CM_NPH; i++) phases[i] = 0.0;
-        size_t cnt = 0;
-        for (size_t g = 0; g < 512; g++) {
-            long long any = 0;
-            for (int i = 0; i < 8 * CM_NPH; i++) any |= h[g * 8 * CM_NPH + i];
-            if (!any) continue;
-            for (int i = 0; i < 8 * CM_NPH; i++) phases[i] += (double)h[g * 8 * CM_NPH + i];
-            cnt++;
-        }
-        if (cnt) for (int i = 0; i < 8 * CM_NPH; i++) phases[i] /= (double)cnt;
-    }
-    if (!rc && mismatch) {
-        rc = run(0, out.p, nullptr);
-        if (!rc) rc = run(1, out2.p, nullptr);
-        std::vector<unsigned short> a(nout), b(nout);
-        MDD_HIP_CHECK(hipMemcpy(a.data(), out.p, nout * 2, hipMemcpyDeviceToHost));
-        MDD_HIP_CHECK(hipMemcpy(b.data(), out2.p, nout * 2, hipMemcpyDeviceToHost));
-        long long bad = 0;
-        for (size_t i = 0; i < nout; i++) bad += a[i] != b[i];
-        *mismatch = bad;
-    }
-    return rc;
-}

@@ -151,16 +151,18 @@ __global__ __launch_bounds__(256) void gemm_nt_f32_kernel(const float *__restric
 }
 
 // wide: the 128-column tile also where N <= 64 (MDD_SCORE_TILE=128, the comparison form of the attention scores)
-int launch_gemm_nt(const float *A, const float *W, const float *bias, float *C, int M, int N, int K, int lda, int ldw,
-                   int ldc, int batch, long sA, long sW, long sC, hipStream_t st, bool wide) {
-    if (M <= 0 || N <= 0 || K <= 0 || batch <= 0) { set_error("gemm: bad shape %d %d %d x%d", M, N, K, batch); return MDD_ERR_ARG; }
+int launch_gemm_nt(const GemmOperand &A, const GemmOperand &W, float *C, int ldc, int M, int N, int K, hipStream_t st, const GemmOpts &o, bool wide) {
+    if (A.k_major || W.k_major || o.accumulate || o.ksplit) {
+        set_error("gemm_nt: row-major operands, no accumulate, no split-K (launch_gemm_f32 runs those)"); return MDD_ERR_ARG;
+    }
+    if (M <= 0 || N <= 0 || K <= 0 || o.batch <= 0) { set_error("gemm: bad shape %d %d %d x%d", M, N, K, o.batch); return MDD_ERR_ARG; }
     const bool narrow = N <= 64 && !wide;
     int tiles_m = (M + BM - 1) / BM, tiles_n = narrow ? 1 : (N + BN - 1) / BN;
-    dim3 grid(tiles_m * tiles_n, 1, batch), block(256);
-    bool aligned = (lda % 4 == 0) && (ldw % 4 == 0) && (sA % 4 == 0) && (sW % 4 == 0) &&
-                   ((uintptr_t)A % 16 == 0) && ((uintptr_t)W % 16 == 0);
+    dim3 grid(tiles_m * tiles_n, 1, o.batch), block(256);
+    bool aligned = (A.ld % 4 == 0) && (W.ld % 4 == 0) && (A.stride % 4 == 0) && (W.stride % 4 == 0) &&
+                   ((uintptr_t)A.p % 16 == 0) && ((uintptr_t)W.p % 16 == 0);
     const bool seg = N <= 1024 && K > 64;
-#define GO(AL_, SEG_, BNT_) hipLaunchKernelGGL((gemm_nt_f32_kernel<AL_, SEG_, BNT_>), grid, block, 0, st, A, W, bias, C, M, N, K, lda, ldw, ldc, sA, sW, sC, tiles_n)
+#define GO(AL_, SEG_, BNT_) hipLaunchKernelGGL((gemm_nt_f32_kernel<AL_, SEG_, BNT_>), grid, block, 0, st, A.p, W.p, o.bias, C, M, N, K, A.ld, W.ld, ldc, A.stride, W.stride, o.sC, tiles_n)
     if (narrow) {
         if (aligned && seg) GO(true, true, 64); else if (aligned) GO(true, false, 64); else if (seg) GO(false, true, 64); else GO(false, false, 64);
     } else if (aligned && seg) GO(true, true, BN);

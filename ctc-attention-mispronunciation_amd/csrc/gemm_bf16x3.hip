@@ -18,12 +18,10 @@
 // kernel (large projections), the single-barrier 256x256 kernel it is screened against, and the 128x128 kernel (small / batched /
 // split-output GEMMs).  An output element is accumulated identically in all of them (batch-size independent bits).  The
 // register-staged and 32x32x16 forms of round 1 measured slower and are no longer built.
-#include <stdlib.h>
-#include <string.h>
-
-#include <algorithm>
-#include <vector>
-
+//
+// This file holds the kernels and their launchers only: the operand planes are made in split.hip, the timing and screening entries that
+// drive these launchers are in diag.hip.
+#include "bf16_split.h"
 #include "train.h"
 
 namespace mdd {
@@ -42,11 +40,6 @@ __device__ __forceinline__ bf16x8 x3_frag(const unsigned char *plane, int row, i
     return *reinterpret_cast<const bf16x8 *>(plane + row * XROW + ((((kbyte >> 4) ^ ((row >> 2) & 3))) << 4));
 }
 
-__device__ __forceinline__ unsigned short bf16_bits(float x) {   // round-to-nearest-even, NaN-preserving cast
-    __bf16 b = (__bf16)x;
-    return *reinterpret_cast<unsigned short *>(&b);
-}
-__device__ __forceinline__ float bf16_to_f32(unsigned short b) { return __uint_as_float((unsigned)b << 16); }
 // ---- LDS-DMA variant of the 128x128 kernel: tiles go global -> LDS directly (global_load_lds_dwordx4), no staging
 // registers and no ds_write pass.  The LDS image is lane-linear per wave-instruction (64 x 16 B = 16 rows of one plane),
 // so the XOR swizzle is applied to the per-lane SOURCE address; fragment reads use the same swizzle (x3_frag).
@@ -239,7 +232,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16x3_glds256_kernel(const unsig
 // Hazards: a half-tile issued in phase p is waited for at the end of L(p+2) by every wave, read in L(p+3) -- for the
 // late group that is after one more barrier than the early group's wait, as the stagger requires -- and its buffer is
 // refilled eight phases later.
-template <bool DMA_IN_M, bool STAMP = false, bool WFIRST = true>
+template <bool STAMP>
 __global__ __launch_bounds__(512, 2) void gemm_bf16x3_ph8_kernel(const unsigned short *__restrict__ Ah, const unsigned short *__restrict__ Al,
                                                                  const unsigned short *__restrict__ Wh, const unsigned short *__restrict__ Wl,
                                                                  const float *__restrict__ bias, float *__restrict__ C, int M, int N, int K,
@@ -304,28 +297,14 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16x3_ph8_kernel(const unsigned 
             fah[i] = x3_frag(st, (a_) * 128 + wr * 64 + i * 16 + l16, kq16); fal[i] = x3_frag(st + PL, (a_) * 128 + wr * 64 + i * 16 + l16, kq16); }
 #define PH8_LOAD_W(b_) _Pragma("unroll") for (int j = 0; j < 2; j++) { \
             fwh[b_][j] = x3_frag(st + 2 * PL, (b_) * 128 + wc * 32 + j * 16 + l16, kq16); fwl[b_][j] = x3_frag(st + 3 * PL, (b_) * 128 + wc * 32 + j * 16 + l16, kq16); }
-#define PH8_MM(x_, y_, c_) (WFIRST ? __builtin_amdgcn_mfma_f32_16x16x32_bf16(x_, y_, c_, 0, 0, 0) : __builtin_amdgcn_mfma_f32_16x16x32_bf16(y_, x_, c_, 0, 0, 0))
 #define PH8_MFMA(a_, b_) _Pragma("unroll") for (int i = 0; i < 4; i++) { \
-            _Pragma("unroll") for (int j = 0; j < 2; j++) acc[a_][b_][i][j] = PH8_MM(fwl[b_][j], fah[i], acc[a_][b_][i][j]); \
-            _Pragma("unroll") for (int j = 0; j < 2; j++) acc[a_][b_][i][j] = PH8_MM(fwh[b_][j], fal[i], acc[a_][b_][i][j]); \
-            _Pragma("unroll") for (int j = 0; j < 2; j++) acc[a_][b_][i][j] = PH8_MM(fwh[b_][j], fah[i], acc[a_][b_][i][j]); }
-    // DMA_IN_M (experiment, not the default): the two LDS-DMA pieces of a phase pair are issued from inside the MFMA phase (behind
-    // its first MFMA group) instead of from the load phase; each counted wait then sees one issue less in front of it (vmcnt(2) where
-    // the load-phase form has vmcnt(4)).  Stamps (profiles/round2_gemm_phase_stamps.txt): the MFMA phases, not the load phases, set
-    // the length of a barrier interval (per K-tile and wave: MFMA bodies 1744 cycles against load bodies 1336), so moving issue work
-    // into them lengthens the interval: 5-8 % slower.
-#define PH8_MFMA_DMA(a_, b_, ht_) do { if (DMA_IN_M) { \
-            _Pragma("unroll") for (int j = 0; j < 2; j++) acc[a_][b_][0][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fwl[b_][j], fah[0], acc[a_][b_][0][j], 0, 0, 0); \
-            _Pragma("unroll") for (int j = 0; j < 2; j++) acc[a_][b_][0][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fwh[b_][j], fal[0], acc[a_][b_][0][j], 0, 0, 0); \
-            _Pragma("unroll") for (int j = 0; j < 2; j++) acc[a_][b_][0][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fwh[b_][j], fah[0], acc[a_][b_][0][j], 0, 0, 0); \
-            __builtin_amdgcn_sched_barrier(0); \
-            if (more) issue(ht_, nk0, nst); \
-            __builtin_amdgcn_sched_barrier(0); \
-            _Pragma("unroll") for (int i = 1; i < 4; i++) { \
             _Pragma("unroll") for (int j = 0; j < 2; j++) acc[a_][b_][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fwl[b_][j], fah[i], acc[a_][b_][i][j], 0, 0, 0); \
             _Pragma("unroll") for (int j = 0; j < 2; j++) acc[a_][b_][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fwh[b_][j], fal[i], acc[a_][b_][i][j], 0, 0, 0); \
-            _Pragma("unroll") for (int j = 0; j < 2; j++) acc[a_][b_][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fwh[b_][j], fah[i], acc[a_][b_][i][j], 0, 0, 0); } \
-        } else { PH8_MFMA(a_, b_) } } while (0)
+            _Pragma("unroll") for (int j = 0; j < 2; j++) acc[a_][b_][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fwh[b_][j], fah[i], acc[a_][b_][i][j], 0, 0, 0); }
+    // The LDS-DMA pieces are issued from the load phases.  The form that issued the two pieces of a phase pair from inside the MFMA phase
+    // (behind its first MFMA group; each counted wait then saw one issue less, vmcnt(2) for vmcnt(4)) lost and is no longer built.  Stamps
+    // (profiles/round2_gemm_phase_stamps.txt): the MFMA phases, not the load phases, set the length of a barrier interval (per K-tile and
+    // wave: MFMA bodies 1744 cycles against load bodies 1336), so moving issue work into them lengthens the interval: 5-8 % slower.
     if (STAMP) stt = (long long)__builtin_readcyclecounter();
     for (int kt = 0; kt < nk; kt++) {
         const unsigned char *st = glds_smem + (kt & 1) * 4 * PL;
@@ -334,50 +313,38 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16x3_ph8_kernel(const unsigned 
         const int nk0 = (kt + 1) * XBK;
         // ---- quadrant (0,0)
         PH8_LOAD_A(0) PH8_LOAD_W(0)
-        if (DMA_IN_M) {
-            asm volatile("s_waitcnt vmcnt(2)" ::: "memory");                                                              // W1 of this K-tile
-        } else {
-            if (more) issue(0, nk0, nst);
-            if (more) asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");   // W1 of this K-tile
-        }
+        if (more) issue(0, nk0, nst);
+        if (more) asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");   // W1 of this K-tile
         __builtin_amdgcn_sched_barrier(0);
         PH8_END_L();
-        PH8_MFMA_DMA(0, 0, 0);
+        PH8_MFMA(0, 0)
         __builtin_amdgcn_sched_barrier(0);
         PH8_END_M();
         // ---- quadrant (0,1)
         PH8_LOAD_W(1)
-        if (DMA_IN_M) {
-            if (more) asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // A1 of this K-tile
-        } else {
-            if (more) issue(1, nk0, nst);
-            if (more) asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // A1 of this K-tile
-        }
+        if (more) issue(1, nk0, nst);
+        if (more) asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // A1 of this K-tile
         __builtin_amdgcn_sched_barrier(0);
         PH8_END_L();
-        PH8_MFMA_DMA(0, 1, 1);
+        PH8_MFMA(0, 1)
         __builtin_amdgcn_sched_barrier(0);
         PH8_END_M();
         // ---- quadrant (1,1)
         PH8_LOAD_A(1)
-        if (!DMA_IN_M && more) issue(2, nk0, nst);
+        if (more) issue(2, nk0, nst);
         __builtin_amdgcn_sched_barrier(0);
         PH8_END_L();
-        PH8_MFMA_DMA(1, 1, 2);
+        PH8_MFMA(1, 1)
         __builtin_amdgcn_sched_barrier(0);
         PH8_END_M();
         // ---- quadrant (1,0): its fragments are already in registers
-        if (DMA_IN_M) {
-            if (more) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");                                                  // A0, W0 of the next K-tile
-        } else if (more) { issue(3, nk0, nst); asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); }                        // A0, W0 of the next K-tile
+        if (more) { issue(3, nk0, nst); asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); }                             // A0, W0 of the next K-tile
         __builtin_amdgcn_sched_barrier(0);
         PH8_END_L();
-        PH8_MFMA_DMA(1, 0, 3);
+        PH8_MFMA(1, 0)
         __builtin_amdgcn_sched_barrier(0);
         PH8_END_M();
     }
-#undef PH8_MFMA_DMA
-#undef PH8_MM
     if (STAMP && stamps && lane == 0 && blockIdx.x < 256)
         for (int i = 0; i < 4; i++) stamps[((size_t)blockIdx.x * 8 + wave) * 4 + i] = sacc[i];
 #undef PH8_T
@@ -391,39 +358,6 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16x3_ph8_kernel(const unsigned 
     // rows): D row = 4*(lane>>4) + r, D col = lane&15, so a lane's four accumulator registers are FOUR CONSECUTIVE COLUMNS of one C
     // row -- the tile leaves as 16-byte stores (32 per wave, 16 rows x 64 B each) instead of 128 scalar ones.
     const int q4 = (lane >> 4) * 4;
-    if (!WFIRST) {   // measurement form only (A fragment first: D row = C row, D col = C column; scalar stores)
-#pragma unroll
-        for (int a = 0; a < 2; a++)
-#pragma unroll
-            for (int b = 0; b < 2; b++)
-#pragma unroll
-                for (int i = 0; i < 4; i++)
-#pragma unroll
-                    for (int j = 0; j < 2; j++) {
-                        const int col = n0 + b * 128 + wc * 32 + j * 16 + l16;
-                        if (col >= N) continue;
-                        const float bv = bias ? bias[col] : 0.f;
-#pragma unroll
-                        for (int r = 0; r < 4; r++) {
-                            const int row = m0 + a * 128 + wr * 64 + i * 16 + q4 + r;
-                            if (row < M) C[(size_t)row * ldc + col] = acc[a][b][i][j][r] + bv;
-                        }
-                    }
-        return;
-    }
-    if (STAMP && stamps == nullptr) {   // diagnostic form: no C stores at all (what the epilogue's HBM writes cost the launch); keep the accumulators alive
-        float keep = 0.f;
-#pragma unroll
-        for (int a = 0; a < 2; a++)
-#pragma unroll
-            for (int b = 0; b < 2; b++)
-#pragma unroll
-                for (int i = 0; i < 4; i++)
-#pragma unroll
-                    for (int j = 0; j < 2; j++) keep += acc[a][b][i][j][0] + acc[a][b][i][j][1] + acc[a][b][i][j][2] + acc[a][b][i][j][3];
-        if (keep == 12345.678f) C[0] = keep;
-        return;
-    }
     const bool n_vec = (ldc % 4 == 0) && (((size_t)C & 15) == 0);
 #pragma unroll
     for (int a = 0; a < 2; a++)
@@ -454,36 +388,46 @@ int init_gemm_attributes() {
     MDD_HIP_CHECK(hipFuncSetAttribute((const void *)gemm_bf16x3_glds256_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 4 * 256 * XROW));
     MDD_HIP_CHECK(hipFuncSetAttribute((const void *)gemm_bf16x3_ph8_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 4 * 256 * XROW));
     MDD_HIP_CHECK(hipFuncSetAttribute((const void *)gemm_bf16x3_ph8_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 4 * 256 * XROW));
-    MDD_HIP_CHECK(hipFuncSetAttribute((const void *)(gemm_bf16x3_ph8_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 4 * 256 * XROW));
-    MDD_HIP_CHECK(hipFuncSetAttribute((const void *)(gemm_bf16x3_ph8_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 4 * 256 * XROW));
-    MDD_HIP_CHECK(hipFuncSetAttribute((const void *)(gemm_bf16x3_ph8_kernel<false, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 4 * 256 * XROW));
     return MDD_OK;
 }
 
-int launch_gemm_bf16x3(const SplitPtr &A, const SplitPtr &W, const float *bias, float *C, const SplitPtr *Csplit, int M, int N,
-                       int K, int lda, int ldw, int ldc, int batch, long sA, long sW, long sC, hipStream_t st) {
-    if (M <= 0 || N <= 0 || K <= 0 || batch <= 0 || K % XBK || lda % 8 || ldw % 8 || sA % 8 || sW % 8) {
-        set_error("gemm_bf16x3: bad shape M=%d N=%d K=%d lda=%d ldw=%d (K must be a multiple of %d)", M, N, K, lda, ldw, XBK);
-        return MDD_ERR_ARG;
-    }
-    if (!Csplit && batch == 1 && M >= 1024 && N >= 512) {   // large projection: 256x256 tiles
-        const int tn = (N + 255) / 256;
-        const dim3 grid(((M + 255) / 256) * tn), block(512);
-        const size_t smem = 2 * 4 * 256 * XROW;
-        // the 8-phase kernel with the LDS-DMA issued from the load phases (5-8 % faster than from inside the MFMA phases:
-        // profiles/round2_gemm_phase_stamps.txt; that form and the single-barrier kernel run in mdd_diag_gemm_ph8's race screen)
-        hipLaunchKernelGGL(gemm_bf16x3_ph8_kernel<false>, grid, block, smem, st, A.hi, A.lo, W.hi, W.lo, bias, C, M, N, K, lda, ldw, ldc, tn);
-        MDD_LAUNCH_CHECK();
-        return MDD_OK;
-    }
+static bool x3_args_ok(const SplitOperand &A, const SplitOperand &W, int M, int N, int K, int batch) {
+    if (M > 0 && N > 0 && K > 0 && batch > 0 && K % XBK == 0 && A.ld % 8 == 0 && W.ld % 8 == 0 && A.stride % 8 == 0 && W.stride % 8 == 0) return true;
+    set_error("gemm_bf16x3: bad shape M=%d N=%d K=%d lda=%d ldw=%d (K must be a multiple of %d)", M, N, K, A.ld, W.ld, XBK);
+    return false;
+}
+
+// One of the 256x256-tile kernels on one product (no batch, fp32 output).  The 8-phase kernel is production's; the single-barrier kernel
+// and the stamped instantiation run in the diagnostics only (stamps: nullable, the stamped form's phase cycle sums).
+int launch_gemm_bf16x3_256(X3Form form, const SplitOperand &A, const SplitOperand &W, float *C, int ldc, int M, int N, int K, hipStream_t st,
+                           const float *bias, long long *stamps) {
+    if (!x3_args_ok(A, W, M, N, K, 1)) return MDD_ERR_ARG;
+    const int tn = (N + 255) / 256;
+    const dim3 grid(((M + 255) / 256) * tn), block(512);
+    const size_t smem = 2 * 4 * 256 * XROW;
+#define GO(kernel_, ...) hipLaunchKernelGGL(kernel_, grid, block, smem, st, A.p.hi, A.p.lo, W.p.hi, W.p.lo, bias, C, M, N, K, A.ld, W.ld, ldc, tn, ##__VA_ARGS__)
+    if (form == X3Form::SingleBarrier) GO(gemm_bf16x3_glds256_kernel);
+    else if (form == X3Form::Phase8) GO(gemm_bf16x3_ph8_kernel<false>, (long long *)nullptr);
+    else GO(gemm_bf16x3_ph8_kernel<true>, stamps);
+#undef GO
+    MDD_LAUNCH_CHECK();
+    return MDD_OK;
+}
+
+int launch_gemm_bf16x3(const SplitOperand &A, const SplitOperand &W, float *C, const SplitPtr *Csplit, int ldc, int M, int N, int K, hipStream_t st,
+                       const GemmOpts &o, bool tile128) {
+    if (o.accumulate || o.ksplit) { set_error("gemm_bf16x3: no accumulate, no split-K (a batch of partial products stands in for it)"); return MDD_ERR_ARG; }
+    if (!x3_args_ok(A, W, M, N, K, o.batch)) return MDD_ERR_ARG;
+    // large projection: 256x256 tiles, the 8-phase kernel (the single-barrier kernel it is screened against: mdd_diag_gemm_ph8)
+    if (!Csplit && o.batch == 1 && M >= 1024 && N >= 512 && !tile128) return launch_gemm_bf16x3_256(X3Form::Phase8, A, W, C, ldc, M, N, K, st, o.bias);
     const int tm = (M + XBM - 1) / XBM, tn = (N + XBN - 1) / XBN;   // 128x128 tiles (also batched / split output)
-    dim3 grid(tm * tn, 1, batch), block(256);
+    dim3 grid(tm * tn, 1, o.batch), block(256);
     if (Csplit)
-        hipLaunchKernelGGL(gemm_bf16x3_glds_kernel<1>, grid, block, 0, st, A.hi, A.lo, W.hi, W.lo, bias, (float *)nullptr, Csplit->hi, Csplit->lo,
-                           M, N, K, lda, ldw, ldc, sA, sW, sC, tn);
+        hipLaunchKernelGGL(gemm_bf16x3_glds_kernel<1>, grid, block, 0, st, A.p.hi, A.p.lo, W.p.hi, W.p.lo, o.bias, (float *)nullptr, Csplit->hi, Csplit->lo,
+                           M, N, K, A.ld, W.ld, ldc, A.stride, W.stride, o.sC, tn);
     else
-        hipLaunchKernelGGL(gemm_bf16x3_glds_kernel<0>, grid, block, 0, st, A.hi, A.lo, W.hi, W.lo, bias, C, (unsigned short *)nullptr,
-                           (unsigned short *)nullptr, M, N, K, lda, ldw, ldc, sA, sW, sC, tn);
+        hipLaunchKernelGGL(gemm_bf16x3_glds_kernel<0>, grid, block, 0, st, A.p.hi, A.p.lo, W.p.hi, W.p.lo, o.bias, C, (unsigned short *)nullptr,
+                           (unsigned short *)nullptr, M, N, K, A.ld, W.ld, ldc, A.stride, W.stride, o.sC, tn);
     MDD_LAUNCH_CHECK();
     return MDD_OK;
 }
@@ -502,161 +446,10 @@ int gemm_bf16x3_ops(const GemmOperand &A, const GemmOperand &B, const float *bia
     SplitPtr sb{reinterpret_cast<unsigned short *>(xs_b.p), reinterpret_cast<unsigned short *>(xs_b.p) + (size_t)N * Kp};
     if (int rc = A.k_major ? launch_transpose_split(A.p, A.ld, K, M, Kp, sa.hi, sa.lo, st) : launch_split_rows(A.p, A.ld, (size_t)M, K, Kp, sa.hi, sa.lo, st)) return rc;
     if (int rc = B.k_major ? launch_transpose_split(B.p, B.ld, K, N, Kp, sb.hi, sb.lo, st) : launch_split_rows(B.p, B.ld, (size_t)N, K, Kp, sb.hi, sb.lo, st)) return rc;
-    if (S == 1) return launch_gemm_bf16x3(sa, sb, bias, C, nullptr, M, N, Kp, Kp, Kp, ldc, 1, 0, 0, 0, st);
-    return sum_parts(part, S, (size_t)M * N, C, st,
-                     [&](float *p) { return launch_gemm_bf16x3(sa, sb, nullptr, p, nullptr, M, N, Kc, Kp, Kp, N, S, Kc, Kc, (long)M * N, st); });
-}
-
-}  // namespace mdd
-namespace mdd {
-__global__ void diag_fill_kernel(unsigned short *p, size_t n, unsigned seed) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        unsigned h = (unsigned)i * 2654435761u + seed; h ^= h >> 15; h *= 2246822519u; h ^= h >> 13;
-        p[i] = (unsigned short)(0x3c00u + (h & 0x3ffu) + ((h >> 10) & 1u) * 0x8000u);   // bf16 of magnitude 0.0078..0.031, random sign
-    }
-}
-__global__ void diag_diff_kernel(const unsigned *a, const unsigned *b, size_t n, unsigned *count) {
-    unsigned c = 0;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) c += a[i] != b[i];
-    if (c) atomicAdd(count, c);
-}
-}  // namespace mdd
-
-// Race screen for the 8-phase kernel (tests/test_gpu_parity.py): the same pseudo-random split operands through the single-barrier
-// kernel once and through BOTH forms of the 8-phase kernel (LDS-DMA issued from the load phases / from the MFMA phases) `reps` times
-// each; returns the number of C words that ever differed (all perform the same arithmetic per element, so it must be 0).
-// ms_out (nullable): [single-barrier, 8-phase DMA-in-L, 8-phase DMA-in-M] mean kernel time over the repetitions, HIP events.
-extern "C" int mdd_diag_gemm_ph8(int M, int N, int K, int reps, unsigned seed, unsigned *mismatches_out, float *ms_out) {
-    using namespace mdd;
-    if (M <= 0 || N <= 0 || K < XBK || K % XBK || !mismatches_out || reps < 1) { set_error("mdd_diag_gemm_ph8: bad shape"); return MDD_ERR_ARG; }
-    static bool at = false; if (!at) { if (int rc = init_gemm_attributes()) return rc; at = true; }
-    unsigned short *A = nullptr, *W = nullptr; float *C1 = nullptr, *C2 = nullptr; unsigned *cnt = nullptr;
-    MDD_HIP_CHECK(hipMalloc((void **)&A, (size_t)2 * M * K * 2));
-    MDD_HIP_CHECK(hipMalloc((void **)&W, (size_t)2 * N * K * 2));
-    MDD_HIP_CHECK(hipMalloc((void **)&C1, (size_t)M * N * 4));
-    MDD_HIP_CHECK(hipMalloc((void **)&C2, (size_t)M * N * 4));
-    MDD_HIP_CHECK(hipMalloc((void **)&cnt, 4));
-    MDD_HIP_CHECK(hipMemset(cnt, 0, 4));
-    hipEvent_t e0, e1; MDD_HIP_CHECK(hipEventCreate(&e0)); MDD_HIP_CHECK(hipEventCreate(&e1));
-    hipLaunchKernelGGL(diag_fill_kernel, dim3(1024), dim3(256), 0, nullptr, A, (size_t)2 * M * K, seed);
-    hipLaunchKernelGGL(diag_fill_kernel, dim3(1024), dim3(256), 0, nullptr, W, (size_t)2 * N * K, seed * 7919u + 13u);
-    const int tn = (N + 255) / 256;
-    const dim3 grid(((M + 255) / 256) * tn), block(512);
-    float ms[3] = {0.f, 0.f, 0.f};
-    for (int form = 0; form < 3; form++) {
-        for (int r = 0; r < reps; r++) {
-            float *dst = form == 0 ? C1 : C2;
-            if (form) MDD_HIP_CHECK(hipMemsetAsync(C2, 0xff, (size_t)M * N * 4, nullptr));
-            MDD_HIP_CHECK(hipEventRecord(e0, nullptr));
-            if (form == 0) hipLaunchKernelGGL(gemm_bf16x3_glds256_kernel, grid, block, 2 * 4 * 256 * XROW, nullptr, A, A + (size_t)M * K, W, W + (size_t)N * K,
-                                              (const float *)nullptr, dst, M, N, K, K, K, N, tn);
-            else if (form == 1) hipLaunchKernelGGL(gemm_bf16x3_ph8_kernel<false>, grid, block, 2 * 4 * 256 * XROW, nullptr, A, A + (size_t)M * K, W, W + (size_t)N * K,
-                                                   (const float *)nullptr, dst, M, N, K, K, K, N, tn);
-            else hipLaunchKernelGGL(gemm_bf16x3_ph8_kernel<true>, grid, block, 2 * 4 * 256 * XROW, nullptr, A, A + (size_t)M * K, W, W + (size_t)N * K,
-                                    (const float *)nullptr, dst, M, N, K, K, K, N, tn);
-            MDD_HIP_CHECK(hipEventRecord(e1, nullptr));
-            MDD_HIP_CHECK(hipEventSynchronize(e1));
-            float t = 0.f; MDD_HIP_CHECK(hipEventElapsedTime(&t, e0, e1));
-            if (r > 0 || reps == 1) ms[form] += t;
-            if (form) hipLaunchKernelGGL(diag_diff_kernel, dim3(1024), dim3(256), 0, nullptr, reinterpret_cast<const unsigned *>(C1),
-                                         reinterpret_cast<const unsigned *>(C2), (size_t)M * N, cnt);
-        }
-        ms[form] /= (float)(reps > 1 ? reps - 1 : 1);
-    }
-    MDD_HIP_CHECK(hipMemcpy(mismatches_out, cnt, 4, hipMemcpyDeviceToHost));
-    if (ms_out) { ms_out[0] = ms[0]; ms_out[1] = ms[1]; ms_out[2] = ms[2]; }
-    if (ms_out && getenv("MDD_GEMM_AFIRST")) {   // the 8-phase kernel with the A fragment as first MFMA operand (scalar C stores): ms_out[11]
-        float tot = 0.f;
-        for (int r = 0; r < reps; r++) {
-            MDD_HIP_CHECK(hipEventRecord(e0, nullptr));
-            hipLaunchKernelGGL((gemm_bf16x3_ph8_kernel<false, false, false>), grid, block, 2 * 4 * 256 * XROW, nullptr, A, A + (size_t)M * K, W, W + (size_t)N * K,
-                               (const float *)nullptr, C2, M, N, K, K, K, N, tn, (long long *)nullptr);
-            MDD_HIP_CHECK(hipEventRecord(e1, nullptr));
-            MDD_HIP_CHECK(hipEventSynchronize(e1));
-            float t = 0.f; MDD_HIP_CHECK(hipEventElapsedTime(&t, e0, e1));
-            if (r > 0) tot += t;
-        }
-        ms_out[11] = tot / (float)(reps - 1);
-    }
-    if (ms_out && getenv("MDD_GEMM_T128")) {   // ms_out[14]: the 128x128 kernel (two workgroups per CU) on the same problem
-        const int tm1 = (M + XBM - 1) / XBM, tn1 = (N + XBN - 1) / XBN;
-        float tot = 0.f;
-        for (int r = 0; r < reps; r++) {
-            MDD_HIP_CHECK(hipEventRecord(e0, nullptr));
-            hipLaunchKernelGGL(gemm_bf16x3_glds_kernel<0>, dim3(tm1 * tn1), dim3(256), 0, nullptr, A, A + (size_t)M * K, W, W + (size_t)N * K, (const float *)nullptr, C2,
-                               (unsigned short *)nullptr, (unsigned short *)nullptr, M, N, K, K, K, N, 0l, 0l, 0l, tn1);
-            MDD_HIP_CHECK(hipEventRecord(e1, nullptr));
-            MDD_HIP_CHECK(hipEventSynchronize(e1));
-            float t = 0.f; MDD_HIP_CHECK(hipEventElapsedTime(&t, e0, e1));
-            if (r > 0) tot += t;
-        }
-        ms_out[14] = tot / (float)(reps - 1);
-    }
-    if (ms_out && getenv("MDD_GEMM_NOSTORE")) {   // ms_out[12]: the 8-phase kernel without its C stores
-        float tot = 0.f;
-        for (int r = 0; r < reps; r++) {
-            MDD_HIP_CHECK(hipEventRecord(e0, nullptr));
-            hipLaunchKernelGGL((gemm_bf16x3_ph8_kernel<false, true>), grid, block, 2 * 4 * 256 * XROW, nullptr, A, A + (size_t)M * K, W, W + (size_t)N * K,
-                               (const float *)nullptr, C2, M, N, K, K, K, N, tn, (long long *)nullptr);
-            MDD_HIP_CHECK(hipEventRecord(e1, nullptr));
-            MDD_HIP_CHECK(hipEventSynchronize(e1));
-            float t = 0.f; MDD_HIP_CHECK(hipEventElapsedTime(&t, e0, e1));
-            if (r > 0) tot += t;
-        }
-        ms_out[12] = tot / (float)(reps - 1);
-    }
-    if (ms_out && getenv("MDD_GEMM_STAMP")) {   // phase stamps of both forms: ms_out[3..6] (DMA in L) and [7..10] (DMA in M), mean cycles per K-tile and wave
-        long long *sd = nullptr;
-        MDD_HIP_CHECK(hipMalloc((void **)&sd, sizeof(long long) * 256 * 8 * 4));
-        std::vector<long long> hs(256 * 8 * 4);
-        for (int form = 0; form < 2; form++) {
-            MDD_HIP_CHECK(hipMemset(sd, 0, sizeof(long long) * 256 * 8 * 4));
-            if (form == 0) hipLaunchKernelGGL((gemm_bf16x3_ph8_kernel<false, true>), grid, block, 2 * 4 * 256 * XROW, nullptr, A, A + (size_t)M * K, W, W + (size_t)N * K,
-                                              (const float *)nullptr, C2, M, N, K, K, K, N, tn, sd);
-            else hipLaunchKernelGGL((gemm_bf16x3_ph8_kernel<true, true>), grid, block, 2 * 4 * 256 * XROW, nullptr, A, A + (size_t)M * K, W, W + (size_t)N * K,
-                                    (const float *)nullptr, C2, M, N, K, K, K, N, tn, sd);
-            MDD_HIP_CHECK(hipMemcpy(hs.data(), sd, sizeof(long long) * 256 * 8 * 4, hipMemcpyDeviceToHost));
-            const int nwg = std::min(256, (int)grid.x);
-            for (int i = 0; i < 4; i++) {
-                double tot = 0;
-                for (int w = 0; w < nwg * 8; w++) tot += (double)hs[(size_t)w * 4 + i];
-                ms_out[3 + form * 4 + i] = (float)(tot / (nwg * 8) / (K / XBK));
-            }
-        }
-        (void)hipFree(sd);
-    }
-    (void)hipFree(A); (void)hipFree(W); (void)hipFree(C1); (void)hipFree(C2); (void)hipFree(cnt); (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    MDD_LAUNCH_CHECK();
-    return MDD_OK;
-}
-
-namespace mdd {
-
-// fp32 [n] -> hi/lo planes (used for weights at load time and by the tap / test helpers)
-__global__ void split_kernel(const float *__restrict__ x, size_t n, unsigned short *__restrict__ hi, unsigned short *__restrict__ lo) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const float v = x[i];
-        const unsigned short h = bf16_bits(v);
-        hi[i] = h;
-        lo[i] = bf16_bits(v - bf16_to_f32(h));
-    }
-}
-__global__ void unsplit_kernel(const unsigned short *__restrict__ hi, const unsigned short *__restrict__ lo, size_t n, float *__restrict__ x) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-        x[i] = bf16_to_f32(hi[i]) + bf16_to_f32(lo[i]);
-}
-
-int launch_split(const float *x, size_t n, const SplitPtr &out, hipStream_t st) {
-    int grid = (int)((n + 255) / 256); if (grid > 4096) grid = 4096; if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(split_kernel, dim3(grid), dim3(256), 0, st, x, n, out.hi, out.lo);
-    MDD_LAUNCH_CHECK();
-    return MDD_OK;
-}
-int launch_unsplit(const SplitPtr &in, size_t n, float *x, hipStream_t st) {
-    int grid = (int)((n + 255) / 256); if (grid > 4096) grid = 4096; if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(unsplit_kernel, dim3(grid), dim3(256), 0, st, in.hi, in.lo, n, x);
-    MDD_LAUNCH_CHECK();
-    return MDD_OK;
+    if (S == 1) return launch_gemm_bf16x3({.p = sa, .ld = Kp}, {.p = sb, .ld = Kp}, C, nullptr, ldc, M, N, Kp, st, {.bias = bias});
+    return sum_parts(part, S, (size_t)M * N, C, st, [&](float *p) {
+        return launch_gemm_bf16x3({.p = sa, .ld = Kp, .stride = Kc}, {.p = sb, .ld = Kp, .stride = Kc}, p, nullptr, N, M, N, Kc, st, {.batch = S, .sC = (long)M * N});
+    });
 }
 
 }  // namespace mdd

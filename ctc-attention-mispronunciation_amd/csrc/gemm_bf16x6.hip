@@ -9,175 +9,12 @@
 // (one rounding per 32 products) and the five small products in a second one (their roundings happen at 2^-8 of the scale),
 // combined once at the end.  Emulated and measured (tests/test_gpu_parity.py::test_gemm_f32x6_accuracy): closer to the float64
 // product than ATen's fp32 GEMM on the CPU and ~3x closer than the exact-fp32 MFMA GEMM, which is one rounding per 2 products.
-#include <stdio.h>
-#include <stdlib.h>
-
-#include <vector>
-
+//
+// This file holds the kernel, its launchers and gemm_f32x6_ops, the training step's entry.  The operand planes are made in split.hip (and by
+// the producers that write them directly: the fused conv front end, the f32x6 BiLSTM layer); the timing entries are in diag.hip.
 #include "train.h"
 
 namespace mdd {
-
-__device__ __forceinline__ unsigned short bf16_rn(float x) { __bf16 b = (__bf16)x; return *reinterpret_cast<unsigned short *>(&b); }
-__device__ __forceinline__ float bf16_f32(unsigned short b) { return __uint_as_float((unsigned)b << 16); }
-
-// x [rows][ld] fp32 (K leading columns used) -> three bf16 planes (hi, mid, lo) with hi + mid + lo == x exactly (finite x; overflow /
-// NaN land in hi), each plane in the K-TILE-MAJOR order the f32x6 kernel streams: plane[kt][row][32] (kt = k / 32), so that the 16 rows x
-// 64 bytes one LDS-DMA instruction moves are 1 KB of CONTIGUOUS memory (eight whole 128-byte lines, every byte used).  With row-major
-// planes the same instruction touched 16 half-lines, and the kernel ran at the rate a CU ingests lines from L2 (~25 useful B/clk).
-// One wave per (16-row group, K-tile): lane (row = lane / 4, chunk = lane % 4) reads 8 floats, writes 16 bytes per plane.
-__global__ void split3_kernel(const float *__restrict__ x, int rows, int K, int ld, unsigned short *__restrict__ planes, size_t plane_elems) {
-    typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
-    const int lane = threadIdx.x & 63;
-    const int nkt = K / 32, ngr = (rows + 15) / 16;
-    const size_t total = (size_t)ngr * nkt;
-    for (size_t w = (size_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); w < total; w += (size_t)gridDim.x * (blockDim.x >> 6)) {
-        const int g = (int)(w / nkt), kt = (int)(w - (size_t)g * nkt);
-        const int row = g * 16 + (lane >> 2), c = lane & 3;
-        if (row >= rows) continue;
-        const float4 *src = reinterpret_cast<const float4 *>(x + (size_t)row * ld + kt * 32 + c * 8);
-        const float4 v0 = src[0], v1 = src[1];
-        const float f[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-        u16x8 h, m, l;
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-            h[k] = bf16_rn(f[k]);
-            const float r1 = f[k] - bf16_f32(h[k]);
-            m[k] = bf16_rn(r1);
-            l[k] = bf16_rn(r1 - bf16_f32(m[k]));
-        }
-        const size_t off = ((size_t)kt * rows + row) * 32 + c * 8;
-        *reinterpret_cast<u16x8 *>(planes + off) = h;
-        *reinterpret_cast<u16x8 *>(planes + plane_elems + off) = m;
-        *reinterpret_cast<u16x8 *>(planes + 2 * plane_elems + off) = l;
-    }
-}
-
-// planes: 3 x rows x K elements (hi | mid | lo, each K-tile-major)
-int launch_split3(const float *x, int rows, int K, int ld, unsigned short *planes, hipStream_t st) {
-    if (rows <= 0 || K <= 0 || K % 32 || ld % 4) { set_error("split3: rows=%d K=%d ld=%d (K a multiple of 32, ld of 4)", rows, K, ld); return MDD_ERR_ARG; }
-    const size_t waves = (size_t)((rows + 15) / 16) * (K / 32);
-    int grid = (int)((waves + 3) / 4); if (grid > 16384) grid = 16384; if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(split3_kernel, dim3(grid), dim3(256), 0, st, x, rows, K, ld, planes, (size_t)rows * K);
-    MDD_LAUNCH_CHECK();
-    return MDD_OK;
-}
-
-// ---- operand planes of the training step's contractions (gemm_f32x6_ops below).  Both kernels write planes of `rows` x Kp elements,
-// plane_elems apart, in split3_kernel's K-tile-major order, with the contraction axis zero-padded from K to Kp (a multiple of 32): a padded
-// position is zero in all three planes, so a padded K-tile adds exact zeros to every accumulator.
-__device__ __forceinline__ void split3_store8(const float (&f)[8], unsigned short *planes, size_t plane_elems, size_t off) {
-    typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
-    u16x8 h, m, l;
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-        h[k] = bf16_rn(f[k]);
-        const float r1 = f[k] - bf16_f32(h[k]);
-        m[k] = bf16_rn(r1);
-        l[k] = bf16_rn(r1 - bf16_f32(m[k]));
-    }
-    *reinterpret_cast<u16x8 *>(planes + off) = h;
-    *reinterpret_cast<u16x8 *>(planes + plane_elems + off) = m;
-    *reinterpret_cast<u16x8 *>(planes + 2 * plane_elems + off) = l;
-}
-
-// The row operand, x [rows][ld] with K leading columns used (any K): split3_kernel's wave shape; a lane whose eight columns reach past K
-// reads what is there one float at a time and zeros for the rest.
-__global__ void split3_pad_kernel(const float *__restrict__ x, int rows, int K, int ld, int Kp, unsigned short *__restrict__ planes, size_t plane_elems) {
-    const int lane = threadIdx.x & 63;
-    const int nkt = Kp / 32, ngr = (rows + 15) / 16;
-    const size_t total = (size_t)ngr * nkt;
-    for (size_t w = (size_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); w < total; w += (size_t)gridDim.x * (blockDim.x >> 6)) {
-        const int g = (int)(w / nkt), kt = (int)(w - (size_t)g * nkt);
-        const int row = g * 16 + (lane >> 2), c = lane & 3, k0 = kt * 32 + c * 8;
-        if (row >= rows) continue;
-        const float *src = x + (size_t)row * ld + k0;
-        float f[8];
-        if (k0 + 8 <= K) {
-            const float4 v0 = reinterpret_cast<const float4 *>(src)[0], v1 = reinterpret_cast<const float4 *>(src)[1];
-            f[0] = v0.x; f[1] = v0.y; f[2] = v0.z; f[3] = v0.w; f[4] = v1.x; f[5] = v1.y; f[6] = v1.z; f[7] = v1.w;
-        } else {
-#pragma unroll
-            for (int k = 0; k < 8; k++) f[k] = k0 + k < K ? src[k] : 0.f;
-        }
-        split3_store8(f, planes, plane_elems, ((size_t)kt * rows + row) * 32 + c * 8);
-    }
-}
-
-// The transposed operand: x is stored [K][ld] with `rows` leading columns used, and the operand's row r is x's COLUMN r (the contraction runs
-// down x's rows).  One workgroup per (K-tile, 64 operand rows): the 32 x 64 block is read along x's rows (16 lanes x 16 bytes = 256 contiguous
-// bytes per x row), turned in LDS, and leaves as 64 rows x 64 bytes per plane = 4 KB of contiguous memory, 16 bytes per lane.
-// LDS row pitch 33 words: the turn's writes (bank 4 m4 + k) and its reads (bank r + 8 c + j) both spread over the banks.
-constexpr int TS3_R = 64;
-__global__ __launch_bounds__(256) void transpose_split3_kernel(const float *__restrict__ x, int K, int rows, int ld, unsigned short *__restrict__ planes,
-                                                               size_t plane_elems) {
-    __shared__ float tile[TS3_R][33];
-    const int kt = blockIdx.x, r0 = blockIdx.y * TS3_R, tid = threadIdx.x;
-    {
-        const int m4 = tid & 15, rr = r0 + m4 * 4;
-#pragma unroll
-        for (int h = 0; h < 2; h++) {
-            const int kl = (tid >> 4) + h * 16, k = kt * 32 + kl;
-            float4 v = {0.f, 0.f, 0.f, 0.f};
-            if (k < K) {
-                const float *src = x + (size_t)k * ld + rr;
-                if (rr + 3 < rows) v = *reinterpret_cast<const float4 *>(src);
-                else { if (rr < rows) v.x = src[0]; if (rr + 1 < rows) v.y = src[1]; if (rr + 2 < rows) v.z = src[2]; }
-            }
-            tile[m4 * 4 + 0][kl] = v.x; tile[m4 * 4 + 1][kl] = v.y; tile[m4 * 4 + 2][kl] = v.z; tile[m4 * 4 + 3][kl] = v.w;
-        }
-    }
-    __syncthreads();
-    const int rl = tid >> 2, c = tid & 3, row = r0 + rl;
-    if (row >= rows) return;
-    float f[8];
-#pragma unroll
-    for (int k = 0; k < 8; k++) f[k] = tile[rl][c * 8 + k];
-    split3_store8(f, planes, plane_elems, ((size_t)kt * rows + row) * 32 + c * 8);
-}
-
-static bool split3_args_ok(const float *x, int rows, int K, int ld, int Kp, const unsigned short *planes, size_t plane_elems) {
-    return x && planes && rows > 0 && K > 0 && Kp >= K && Kp % 32 == 0 && ld % 4 == 0 && (uintptr_t)x % 16 == 0 && (uintptr_t)planes % 16 == 0 &&
-           plane_elems % 8 == 0 && plane_elems >= (size_t)rows * Kp;
-}
-int launch_split3_pad(const float *x, int rows, int K, int ld, int Kp, unsigned short *planes, size_t plane_elems, hipStream_t st) {
-    if (!split3_args_ok(x, rows, K, ld, Kp, planes, plane_elems) || ld < K) {
-        set_error("split3_pad: rows=%d K=%d ld=%d Kp=%d (Kp a multiple of 32 >= K, ld a multiple of 4 >= K, 16-byte aligned)", rows, K, ld, Kp); return MDD_ERR_ARG;
-    }
-    const size_t waves = (size_t)((rows + 15) / 16) * (Kp / 32);
-    int grid = (int)((waves + 3) / 4); if (grid > 16384) grid = 16384;
-    hipLaunchKernelGGL(split3_pad_kernel, dim3(grid), dim3(256), 0, st, x, rows, K, ld, Kp, planes, plane_elems);
-    MDD_LAUNCH_CHECK();
-    return MDD_OK;
-}
-int launch_transpose_split3(const float *x, int K, int rows, int ld, int Kp, unsigned short *planes, size_t plane_elems, hipStream_t st) {
-    if (!split3_args_ok(x, rows, K, ld, Kp, planes, plane_elems) || ld < rows || (rows + TS3_R - 1) / TS3_R > 65535) {
-        set_error("transpose_split3: K=%d rows=%d ld=%d Kp=%d (Kp a multiple of 32 >= K, ld a multiple of 4 >= rows, 16-byte aligned)", K, rows, ld, Kp); return MDD_ERR_ARG;
-    }
-    hipLaunchKernelGGL(transpose_split3_kernel, dim3(Kp / 32, (rows + TS3_R - 1) / TS3_R), dim3(256), 0, st, x, K, rows, ld, planes, plane_elems);
-    MDD_LAUNCH_CHECK();
-    return MDD_OK;
-}
-
-// (prototype only) row-major three-plane split, for the x3 kernel's operand layout
-__global__ void split3_rowmajor_kernel(const float *__restrict__ x, size_t n, unsigned short *__restrict__ p0, unsigned short *__restrict__ p1, unsigned short *__restrict__ p2) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const float v = x[i];
-        const unsigned short h = bf16_rn(v);
-        const float r1 = v - bf16_f32(h);
-        const unsigned short m = bf16_rn(r1);
-        p0[i] = h; p1[i] = m; p2[i] = bf16_rn(r1 - bf16_f32(m));
-    }
-}
-static int launch_split3_rowmajor(const float *x, size_t n, unsigned short *planes, hipStream_t st) {
-    hipLaunchKernelGGL(split3_rowmajor_kernel, dim3(4096), dim3(256), 0, st, x, n, planes, planes + n, planes + 2 * n);
-    MDD_LAUNCH_CHECK();
-    return MDD_OK;
-}
-
-__global__ void add3_kernel(float *__restrict__ c, const float *__restrict__ s1, const float *__restrict__ s2, size_t n) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) c[i] = c[i] + (s1[i] + s2[i]);
-}
 
 // ---- the kernel: 192 x 128 tile of C per workgroup, FOUR waves (one per SIMD, 512 registers each), K-tile 32.
 // A wave owns 48 rows x all 128 columns: 3 x 8 MFMA tiles x THREE accumulator sets -- hh (hi.hi), sm (the five small products), tot (hh
@@ -199,8 +36,7 @@ __global__ void add3_kernel(float *__restrict__ c, const float *__restrict__ s1,
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) void lds_void6;
-constexpr int X6_RT = 3;                                              // 16-row MFMA tiles per wave
-constexpr int X6_BM = 4 * 16 * X6_RT, X6_BN = 128, X6_BK = 32, X6_ROW = 64;   // X6_ROW: bytes per LDS row (32 bf16)
+constexpr int X6_BM = 4 * 16 * X6_RT, X6_BN = 128, X6_BK = 32, X6_ROW = 64;   // X6_RT (mdd_internal.h): 16-row MFMA tiles per wave; X6_ROW: bytes per LDS row (32 bf16)
 constexpr int X6_PW = X6_BN * X6_ROW;                                 // bytes per W plane of a stage (8 KB)
 constexpr int X6_STAGE = 3 * X6_PW;                                   // 24 KB
 constexpr int X6_NS = 2;                                              // stages
@@ -473,134 +309,3 @@ int gemm_f32x6_ops(const GemmOperand &A, const GemmOperand &B, const float *bias
 }
 
 }  // namespace mdd
-
-using namespace mdd;
-
-extern "C" int mdd_diag_gemm_ops(int mode, int ta, int tb, const float *A_dev, int lda, const float *B_dev, int ldb, float *C_dev, int ldc, int M, int N, int K,
-                                 int splits, void *stream) {
-    hipStream_t st = (hipStream_t)stream;
-    if (!A_dev || !B_dev || !C_dev || M <= 0 || N <= 0 || K <= 0 || splits < 1 || lda < (ta ? M : K) || ldb < (tb ? N : K) || ldc < N) {
-        set_error("mdd_diag_gemm_ops: bad arguments"); return MDD_ERR_ARG;
-    }
-    int rc;
-    const GemmOperand A{A_dev, lda, ta != 0}, B{B_dev, ldb, tb != 0};
-    if (mode == 0) rc = launch_gemm_f32(A, B, C_dev, ldc, M, N, K, st);
-    else if (mode == 3) {
-        DeviceBuf xa, xb, part;     // freed on return, behind the synchronisation
-        rc = init_gemm_x6_attributes();
-        if (!rc) rc = gemm_f32x6_ops(A, B, nullptr, C_dev, ldc, M, N, K, splits, xa, xb, part, st);
-        if (hipStreamSynchronize(st) != hipSuccess && !rc) { set_error("mdd_diag_gemm_ops: the stream failed"); rc = MDD_ERR_HIP; }
-        return rc;
-    } else { set_error("mdd_diag_gemm_ops: mode %d (0 exact fp32, 3 f32x6)", mode); return MDD_ERR_ARG; }
-    if (hipStreamSynchronize(st) != hipSuccess && !rc) { set_error("mdd_diag_gemm_ops: the stream failed"); rc = MDD_ERR_HIP; }
-    return rc;
-}
-
-// Diagnostic / test entry: one GEMM through a chosen arithmetic, fp32 operands and result on the device.
-//   mode 0: exact fp32 MFMA (gemm_nt_f32_kernel)      1: split-bf16 x3 (operands split here)
-//   mode 3: the f32x6 kernel (operands split into three planes here)
-//   mode 2: f32x6 PROTOTYPE -- the six products through three launches of the x3 kernel (hi.hi alone; {hi.lo, mid.mid, hi.mid};
-//           {mid.hi, lo.hi}) and one combine pass: the arithmetic of the x6 kernel at none of its speed
-extern "C" int mdd_diag_gemm(int mode, const float *A_dev, const float *W_dev, float *C_dev, int M, int N, int K, void *stream) {
-    hipStream_t st = (hipStream_t)stream;
-    if (!A_dev || !W_dev || !C_dev || M <= 0 || N <= 0 || K <= 0 || K % 32) { set_error("mdd_diag_gemm: bad arguments"); return MDD_ERR_ARG; }
-    if (mode == 0) return launch_gemm_nt(A_dev, W_dev, nullptr, C_dev, M, N, K, K, K, N, 1, 0, 0, 0, st);
-    const size_t na = (size_t)M * K, nw = (size_t)N * K, nc = (size_t)M * N;
-    unsigned short *pa = nullptr, *pw = nullptr, *zero = nullptr;
-    float *t1 = nullptr, *t2 = nullptr;
-    int rc = MDD_OK;
-    const size_t nz = na > nw ? na : nw;
-    if (hipMalloc((void **)&pa, 3 * na * 2) != hipSuccess || hipMalloc((void **)&pw, 3 * nw * 2) != hipSuccess || hipMalloc((void **)&zero, nz * 2) != hipSuccess ||
-        hipMalloc((void **)&t1, nc * 4) != hipSuccess || hipMalloc((void **)&t2, nc * 4) != hipSuccess) { set_error("mdd_diag_gemm: out of memory"); rc = MDD_ERR_NOMEM; }
-    if (!rc && hipMemsetAsync(zero, 0, nz * 2, st) != hipSuccess) rc = MDD_ERR_HIP;
-    if (!rc) {
-        if (mode == 1) {
-            SplitPtr a{pa, pa + na}, w{pw, pw + nw};
-            if (!(rc = launch_split(A_dev, na, a, st)) && !(rc = launch_split(W_dev, nw, w, st)))
-                rc = launch_gemm_bf16x3(a, w, nullptr, C_dev, nullptr, M, N, K, K, K, N, 1, 0, 0, 0, st);
-        } else if (mode == 2) {
-            rc = launch_split3_rowmajor(A_dev, na, pa, st);
-            if (!rc) rc = launch_split3_rowmajor(W_dev, nw, pw, st);
-            // launch_gemm_bf16x3(A = (X, Y), W = (U, V)) computes X.V + Y.U + X.U
-            SplitPtr a_hh{pa, zero}, w_hh{pw, zero};                                   // hi.hi
-            SplitPtr a_s1{pa, pa + na}, w_s1{pw + nw, pw + 2 * nw};                   // X=Ah Y=Am U=Wm V=Wl: Ah.Wl + Am.Wm + Ah.Wm
-            SplitPtr a_s2{pa + 2 * na, pa + na}, w_s2{pw, zero};                      // X=Al Y=Am U=Wh V=0 : Am.Wh + Al.Wh
-            if (!rc) rc = launch_gemm_bf16x3(a_hh, w_hh, nullptr, C_dev, nullptr, M, N, K, K, K, N, 1, 0, 0, 0, st);
-            if (!rc) rc = launch_gemm_bf16x3(a_s1, w_s1, nullptr, t1, nullptr, M, N, K, K, K, N, 1, 0, 0, 0, st);
-            if (!rc) rc = launch_gemm_bf16x3(a_s2, w_s2, nullptr, t2, nullptr, M, N, K, K, K, N, 1, 0, 0, 0, st);
-            if (!rc) { hipLaunchKernelGGL(add3_kernel, dim3(2048), dim3(256), 0, st, C_dev, t1, t2, nc); if (hipGetLastError() != hipSuccess) rc = MDD_ERR_HIP; }
-        } else if (mode == 3) {
-            static bool attr = false;
-            if (!attr) { rc = init_gemm_x6_attributes(); attr = true; }
-            if (!rc) rc = launch_split3(A_dev, M, K, K, pa, st);
-            if (!rc) rc = launch_split3(W_dev, N, K, K, pw, st);
-            if (!rc) rc = launch_gemm_f32x6(pa, na, pw, nw, nullptr, C_dev, M, N, K, N, st, nullptr);
-        } else { set_error("mdd_diag_gemm: mode %d", mode); rc = MDD_ERR_ARG; }
-    }
-    (void)hipStreamSynchronize(st);
-    (void)hipFree(pa); (void)hipFree(pw); (void)hipFree(zero); (void)hipFree(t1); (void)hipFree(t2);
-    return rc;
-}
-
-namespace mdd {
-__global__ void fill_pattern_kernel(float *x, size_t n, unsigned seed) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        unsigned h = (unsigned)i * 2654435761u + seed; h ^= h >> 15; h *= 2246822519u; h ^= h >> 13;
-        x[i] = ((float)(h & 0xffffff) / 8388608.f - 1.f) * ((h >> 24) & 1 ? 1.f : 0.05f);
-    }
-}
-}  // namespace mdd
-
-// Timing aid: `reps` launches of one GEMM kernel (operands resident and pre-split; events on the launch stream) -> mean ms.
-//   mode 0 exact fp32 MFMA, 1 split-bf16 x3, 3 f32x6
-extern "C" int mdd_diag_gemm_time(int mode, int M, int N, int K, int reps, float *ms_out) {
-    // MDD_GEMM_STAMP (mode 3): one extra launch of the stamped instantiation; per-K-tile cycle means of the first 1024 workgroups are printed
-    const bool want_stamps = mode == 3 && getenv("MDD_GEMM_STAMP") != nullptr;
-    if (M <= 0 || N <= 0 || K <= 0 || K % 32 || reps < 1 || !ms_out) { set_error("mdd_diag_gemm_time: bad arguments"); return MDD_ERR_ARG; }
-    const size_t na = (size_t)M * K, nw = (size_t)N * K, nc = (size_t)M * N;
-    float *A = nullptr, *W = nullptr, *Cm = nullptr;
-    unsigned short *pa = nullptr, *pw = nullptr;
-    int rc = MDD_OK;
-    if (hipMalloc((void **)&A, na * 4) != hipSuccess || hipMalloc((void **)&W, nw * 4) != hipSuccess || hipMalloc((void **)&Cm, nc * 4) != hipSuccess ||
-        hipMalloc((void **)&pa, 3 * na * 2) != hipSuccess || hipMalloc((void **)&pw, 3 * nw * 2) != hipSuccess) { set_error("mdd_diag_gemm_time: out of memory"); rc = MDD_ERR_NOMEM; }
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (!rc) {
-        hipLaunchKernelGGL(fill_pattern_kernel, dim3(4096), dim3(256), 0, 0, A, na, 1u);
-        hipLaunchKernelGGL(fill_pattern_kernel, dim3(4096), dim3(256), 0, 0, W, nw, 2u);
-        SplitPtr a{pa, pa + na}, w{pw, pw + nw};
-        if (mode == 1) { rc = launch_split(A, na, a, 0); if (!rc) rc = launch_split(W, nw, w, 0); }
-        if (mode == 3) { rc = init_gemm_x6_attributes(); if (!rc) rc = launch_split3(A, M, K, K, pa, 0); if (!rc) rc = launch_split3(W, N, K, K, pw, 0); }
-        (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
-        for (int r = -2; r < reps && !rc; r++) {
-            if (r == 0) (void)hipEventRecord(e0, 0);
-            if (mode == 0) rc = launch_gemm_nt(A, W, nullptr, Cm, M, N, K, K, K, N, 1, 0, 0, 0, 0);
-            else if (mode == 1) rc = launch_gemm_bf16x3(a, w, nullptr, Cm, nullptr, M, N, K, K, K, N, 1, 0, 0, 0, 0);
-            else if (mode == 3) rc = launch_gemm_f32x6(pa, na, pw, nw, nullptr, Cm, M, N, K, N, 0, nullptr);
-            else { set_error("mdd_diag_gemm_time: mode %d", mode); rc = MDD_ERR_ARG; }
-        }
-        (void)hipEventRecord(e1, 0);
-        if (hipEventSynchronize(e1) != hipSuccess) rc = rc ? rc : MDD_ERR_HIP;
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, e0, e1);
-        *ms_out = ms / reps;
-        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-        if (want_stamps && !rc) {
-            long long *sd = nullptr;
-            const size_t ns = (size_t)1024 * 4 * 4;
-            if (hipMalloc((void **)&sd, ns * 8) == hipSuccess && hipMemset(sd, 0, ns * 8) == hipSuccess) {
-                rc = launch_gemm_f32x6(pa, na, pw, nw, nullptr, Cm, M, N, K, N, 0, sd);
-                std::vector<long long> h(ns);
-                (void)hipMemcpy(h.data(), sd, ns * 8, hipMemcpyDeviceToHost);
-                double sum[4] = {0, 0, 0, 0}; size_t cnt = 0;
-                for (size_t w_ = 0; w_ < 1024 * 4; w_++) if (h[w_ * 4 + 0] > 0) { for (int i = 0; i < 4; i++) sum[i] += (double)h[w_ * 4 + i]; cnt++; }
-                const double d = (double)cnt * (K / 32);
-                if (cnt) printf("  f32x6 stamps, cycles per K-tile and wave: MFMA stream %.0f (ideal %d), memory wait %.0f, barrier %.0f\n",
-                                sum[0] / d, X6_RT * 8 * 6 * 16, sum[1] / d, sum[2] / d);
-                fflush(stdout);
-            }
-            (void)hipFree(sd);
-        }
-    }
-    (void)hipFree(A); (void)hipFree(W); (void)hipFree(Cm); (void)hipFree(pa); (void)hipFree(pw);
-    return rc;
-}

@@ -346,16 +346,4 @@ int persistent_f32_grid_fits(int n_cu) {
     return persist_grid_fits(n_cu, (const void *)lstm_layer_f32_kernel<384, 4>, team8_lds_bytes(384, 4));
 }
 
-__global__ void diag_gates_kernel(const float *x, float *sg, float *th, long long n) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) { sg[i] = gate_sigmoid(x[i]); th[i] = gate_tanh(x[i]); }
-}
-
 }  // namespace mdd
-
-extern "C" int mdd_diag_gates(const float *x_dev, float *sig_dev, float *tanh_dev, int64_t n, void *stream) {
-    if (!x_dev || !sig_dev || !tanh_dev || n <= 0) { mdd::set_error("mdd_diag_gates: bad arguments"); return MDD_ERR_ARG; }
-    hipLaunchKernelGGL(mdd::diag_gates_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x_dev, sig_dev, tanh_dev, (long long)n);
-    MDD_LAUNCH_CHECK();
-    return MDD_OK;
-}

@@ -15,8 +15,8 @@
 // the schedule is SKEWED: the cell update and publish of a tile run inside the next tile's product loop.
 // The layer outputs leave through the wave that owns no cell update (wave (1, 1), which would otherwise wait at the phase's barrier for the
 // three owners): the owners leave the output tile in LDS (double-buffered by phase), and a barrier later that wave stores it -- as fp32
-// (`out`, `out_raw`) and / or as the next projection's A operand: three K-tile-major bf16 planes (split3_kernel's layout and arithmetic,
-// gemm_bf16x6.hip), so that no fp32 copy of the layer output and no split pass over it exist (X6Args::planes).
+// (`out`, `out_raw`) and / or as the next projection's A operand: three K-tile-major bf16 planes (split3_pad_kernel's layout and arithmetic,
+// split.hip), so that no fp32 copy of the layer output and no split pass over it exist (X6Args::planes).
 // Hand-off as in lstm_f32.hip (data-tagged, no counter, no drain): h travels as 16-byte granules = eight consecutive units of one batch
 // row of ONE plane; |h| <= 1 leaves bit 14 of every bf16 element (the top exponent bit) free in all three planes, the epoch tag
 // (step % 3 + 1) rides there in the granule's first two elements and is cleared on the MFMA operand registers (one v_and per fragment).
@@ -359,7 +359,7 @@ __global__ __launch_bounds__(256, 1) void lstm_layer_x6_kernel(X6Args a) {
         }
     };
     // The layer outputs of (tile bt, step st), by wave (1, 1), from the LDS tiles [ob] the owners' part 1 filled before the last barrier:
-    // the planes (lane -> (row, chunk column): eight consecutive units of one row, split by split3_kernel's arithmetic, one 16-byte store
+    // the planes (lane -> (row, chunk column): eight consecutive units of one row, split by split3_pad_kernel's arithmetic, one 16-byte store
     // per plane at element ((k / 32) * rows + row) * 32 + k % 32 -- UW and H are multiples of 8, a granule never straddles a K-tile) and
     // the fp32 forms (lane -> (row, 16-byte piece)).  Rows past tile_rows(bt), and everything when `on` is false, land out of bounds =
     // are dropped; the number of store instructions is always n_out: the wave's wait at the end of a phase counts them.
@@ -374,7 +374,7 @@ __global__ __launch_bounds__(256, 1) void lstm_layer_x6_kernel(X6Args a) {
             const int cc = min(kq, CPM - 1);
             const bool mine = kq < CPM && li < nr;
             const f32x4 v0 = *reinterpret_cast<const f32x4 *>(os + li * UW + cc * 8), v1 = *reinterpret_cast<const f32x4 *>(os + li * UW + cc * 8 + 4);
-            // two values at a time: one packed conversion per plane (round to nearest even, as split3_kernel's scalar ones), a bf16 back to
+            // two values at a time: one packed conversion per plane (round to nearest even, as split3_pad_kernel's scalar ones), a bf16 back to
             // fp32 is a shift (low half) or a mask (high half) of the packed word
             typedef float f32x2 __attribute__((ext_vector_type(2)));
             typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));

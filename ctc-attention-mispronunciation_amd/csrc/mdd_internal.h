@@ -53,12 +53,7 @@ using DeviceBuf = DeviceArray<float>;
 struct SplitPtr { unsigned short *hi, *lo; };
 
 // ---- kernel launchers (each enqueues on `st`, returns an mdd_status) -------------------------
-// C[M,N] = A[M,K] . W[N,K]^T (+ bias[N]); fp32 MFMA (v_mfma_f32_32x32x2_f32).  Batched over
-// `batch` with element strides sA/sW/sC.
-int launch_gemm_nt(const float *A, const float *W, const float *bias, float *C, int M, int N, int K, int lda, int ldw,
-                   int ldc, int batch, long sA, long sW, long sC, hipStream_t st, bool wide = false);   // N <= 64: a 128x64 tile unless `wide`
-
-// General fp32 GEMM (training step): C[m,n] (+)= sum_k opA[m,k] opB[n,k] (see gemm.hip).  Written at the call site with the field names:
+// Every GEMM launcher takes its operands and options in one shape, written at the call site with the field names:
 //   launch_gemm_f32({.p = dS, .ld = L, .stride = (long)Tp * L}, {.p = key, .ld = B * H2, .k_major = true, .stride = H2}, dX, B * H2, Tp, H2, L, st,
 //                   {.batch = B, .sC = H2, .accumulate = true});
 struct GemmOperand {
@@ -72,22 +67,43 @@ struct GemmOpts {
     bool accumulate = false;       // C += the product
     int ksplit = 0;                // > 0: split-K instead of a batch -- partial product z contracts k in [z * ksplit, (z + 1) * ksplit) into C + z * sC
 };
+// General fp32 GEMM (training step): C[m,n] (+)= sum_k opA[m,k] opB[n,k] (see gemm.hip).
 int launch_gemm_f32(const GemmOperand &A, const GemmOperand &B, float *C, int ldc, int M, int N, int K, hipStream_t st, const GemmOpts &o = GemmOpts());
+// The decode path's C[M,N] = A[M,K] . W[N,K]^T (+ bias[N]); fp32 MFMA (v_mfma_f32_32x32x2_f32), batched over o.batch.  Row-major operands
+// only: k_major, accumulate and ksplit are refused.  N <= 64: a 128x64 tile unless `wide`.
+int launch_gemm_nt(const GemmOperand &A, const GemmOperand &W, float *C, int ldc, int M, int N, int K, hipStream_t st, const GemmOpts &o = GemmOpts(),
+                   bool wide = false);
 
-// C = A . W^T on the bf16 matrix cores with split-bf16 operands (see gemm_bf16x3.hip).  Output fp32 C, or a
-// split-bf16 tensor when Csplit != nullptr.  K % 32 == 0, ld* % 8 == 0.
-int launch_gemm_bf16x3(const SplitPtr &A, const SplitPtr &W, const float *bias, float *C, const SplitPtr *Csplit, int M, int N,
-                       int K, int lda, int ldw, int ldc, int batch, long sA, long sW, long sC, hipStream_t st);
+// C = A . W^T on the bf16 matrix cores with split-bf16 operands (see gemm_bf16x3.hip).  Output fp32 C, or a split-bf16 tensor when
+// Csplit != nullptr.  K % 32 == 0, ld and stride % 8 == 0; accumulate and ksplit are refused.  tile128: the 128x128 kernel also on a large
+// projection (timing aid).
+struct SplitOperand { SplitPtr p; int ld; long stride = 0; };
+int launch_gemm_bf16x3(const SplitOperand &A, const SplitOperand &W, float *C, const SplitPtr *Csplit, int ldc, int M, int N, int K, hipStream_t st,
+                       const GemmOpts &o = GemmOpts(), bool tile128 = false);
+// One product through one of the 256x256-tile kernels: the 8-phase kernel (what launch_gemm_bf16x3 takes for a large projection), the
+// single-barrier kernel it is screened against, or its stamped instantiation (stamps nullable: [(workgroup * 8 + wave) * 4 + phase] cycle sums
+// of the first 256 workgroups).
+enum class X3Form { SingleBarrier, Phase8, Phase8Stamped };
+int launch_gemm_bf16x3_256(X3Form form, const SplitOperand &A, const SplitOperand &W, float *C, int ldc, int M, int N, int K, hipStream_t st,
+                           const float *bias = nullptr, long long *stamps = nullptr);
 int init_gemm_attributes();
+
+// ---- fp32 -> bf16 planes (split.hip).  Two row-major planes hi | lo for the x3 GEMM:
 int launch_split(const float *x, size_t n, const SplitPtr &out, hipStream_t st);
 int launch_unsplit(const SplitPtr &in, size_t n, float *x, hipStream_t st);
+// a matrix as it stands (the contraction along its columns, zero-padded to cols_pad) or transposed (out[c][r] = src[r][c], zero-padded to rows_pad)
+int launch_split_rows(const float *src, int ld, size_t rows, int cols, int cols_pad, unsigned short *hi, unsigned short *lo, hipStream_t st);
+int launch_transpose_split(const float *src, int ld, int rows, int cols, int rows_pad, unsigned short *hi, unsigned short *lo, hipStream_t st);
 // x [rows][ld] (K columns used) -> three bf16 planes hi | mid | lo (rows x K elements each, consecutive), hi + mid + lo == x exactly,
-// each in the K-tile-major order [K / 32][rows][32] the f32x6 kernel streams (gemm_bf16x6.hip)
+// each in the K-tile-major order [K / 32][rows][32] the f32x6 kernel streams (split3_pad_kernel with Kp == K)
 int launch_split3(const float *x, int rows, int K, int ld, unsigned short *planes, hipStream_t st);
+// three row-major planes hi | mid | lo of n elements each
+int launch_split3_rowmajor(const float *w, int n, unsigned short *planes, hipStream_t st);
 // C = A . W^T with fp32-grade arithmetic on the bf16 matrix cores: operands as three K-tile-major bf16 planes each (gemm_bf16x6.hip)
 int launch_gemm_f32x6(const unsigned short *A3, size_t a_plane, const unsigned short *W3, size_t w_plane, const float *bias, float *C, int M, int N, int K,
                       int ldc, hipStream_t st, long long *stamps = nullptr);
 int init_gemm_x6_attributes();
+constexpr int X6_RT = 3;    // 16-row MFMA tiles per wave of the f32x6 kernel
 // The same planes for the training step's operands: the contraction zero-padded from K to Kp (a multiple of 32), planes plane_elems apart.
 // launch_split3_pad: x [rows][ld], K leading columns; launch_transpose_split3: x stored [K][ld], operand row r = column r of x.
 int launch_split3_pad(const float *x, int rows, int K, int ld, int Kp, unsigned short *planes, size_t plane_elems, hipStream_t st);
@@ -113,6 +129,7 @@ int launch_conv_fused3(const float *x, const float *w0, const float *sc0, const 
                        bool rowwise = false,    // f32x6 form: three K-tile-major planes out (rowwise: the row-at-a-time kernel, MDD_CONV=rowwise)
                        long long *stamps = nullptr);   // stamps (diagnostic, default kernel only): the stamped instantiation's phase cycle sums
 int init_conv_attributes();
+constexpr int CM_NPH = 10;  // stamped phases per wave of the default fused3 kernel (frontend.hip)
 
 // C = opA . opB^T (+ bias) as f32x6 in the training step's operand forms (ta / tb: stored [K, rows]); S > 1: split-K into `part` and a sum.
 // x6_ops_ok: the alignment half of the rule (leading dimensions multiples of 4, 16-byte aligned pointers).

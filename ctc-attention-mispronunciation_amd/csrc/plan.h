@@ -27,7 +27,7 @@
 //                        MFMA section early, so that the redo path runs
 //   MDD_X6_FORCE_REDO=n  f32x6 layer kernel: every n-th phase declared stale (n a     create    test_persistent_x6_lstm_redo_branch
 //                        power of two), so that the refetch branch runs
-//   MDD_X6_OUT=fp32      f32x6 layer kernel: fp32 layer outputs and a split3_kernel   create    tests/test_x6_plane_output.py
+//   MDD_X6_OUT=fp32      f32x6 layer kernel: fp32 layer outputs and a launch_split3   create    tests/test_x6_plane_output.py
 //                        pass in front of the next projection, instead of the layer
 //                        kernel writing that projection's bf16 planes itself
 //   MDD_TEXT_PROJ=gemm   modes 0 and 2: the text encoder's input projection as a GEMM  create    tests/test_text_table.py
@@ -138,7 +138,7 @@ struct ForwardPlan {
     bool gated;         // a persistent layer kernel runs: the forward is ordered behind the device's previous one
     size_t hx_floats;   // the persistent kernels' exchange buffer with the stamp area (0 when none runs)
     size_t stamps_at;   // where the stamps start in it
-    bool planes_out;    // BiLSTM layers 0 .. layers - 2 write the next projection's three bf16 planes themselves: no fp32 copy, no split3_kernel pass
+    bool planes_out;    // BiLSTM layers 0 .. layers - 2 write the next projection's three bf16 planes themselves: no fp32 copy, no launch_split3 pass
     bool text_table;    // gemm_text gathers rows of the weight set's projected embedding table (DecodeWeights::text_table) instead of multiplying
 };
 

@@ -150,7 +150,7 @@ int build_weights(mdd_model *m, DecodeWeights &w) {
         const LstmWeights &tw = w.rnn[c.layers];
         const int G2 = 8 * H, E = c.emb_dim, V = c.emb_rows;
         if ((rc = w.alloc(&w.text_table[0], (size_t)V * G2))) return rc;
-        if ((rc = launch_gemm_nt(w.emb, tw.wih, w.t_bias, w.text_table[0], V, G2, E, E, E, G2, 1, 0, 0, 0, nullptr))) return rc;
+        if ((rc = launch_gemm_nt({.p = w.emb, .ld = E}, {.p = tw.wih, .ld = E}, w.text_table[0], G2, V, G2, E, nullptr, {.bias = w.t_bias}))) return rc;
         if (tw.wih_3) {
             unsigned short *planes = nullptr;   // (kept with the set: the GEMM below reads it after this function has returned)
             if ((rc = w.alloc(&planes, (size_t)3 * V * E)) || (rc = w.alloc(&w.text_table[1], (size_t)V * G2))) return rc;

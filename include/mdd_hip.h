@@ -356,13 +356,15 @@ int mdd_adam_step(float *const *params, float *const *grads, float *const *exp_a
 
 /* ---- Diagnostics (test and measurement aid; no reference counterpart).
  * mdd_diag_gemm_ph8: race screen of the 8-phase projection GEMM -- the same pseudo-random operands through the single-barrier
- * kernel once and the 8-phase kernel (both DMA placements) `reps` times each; *mismatches_out = C words that ever
- * differed (must be 0; tests/test_gpu_parity.py::test_gemm_8phase_race_screen).  ms_out (nullable, 16 floats): mean kernel times. */
+ * kernel and the 8-phase kernel, `reps` times each; *mismatches_out = C words of the 8-phase kernel that ever differed
+ * (must be 0; tests/test_gpu_parity.py::test_gemm_8phase_race_screen).  ms_out (nullable, 16 floats; other slots are left alone):
+ * [0] single-barrier, [1] 8-phase mean kernel ms; with MDD_GEMM_STAMP set [3..6] the 8-phase kernel's load-phase / load-barrier /
+ * MFMA-phase / MFMA-barrier cycles per K-tile and wave; with MDD_GEMM_T128 set [14] the 128x128 kernel's mean ms on the same problem. */
 int mdd_diag_gemm_ph8(int M, int N, int K, int reps, unsigned seed, unsigned *mismatches_out, float *ms_out);
 /* mdd_diag_gates: the gate nonlinearities of the reference-width recurrences (csrc/lstm_persist.h) evaluated on n device floats:
  * sig_dev[i] = sigmoid(x_dev[i]), tanh_dev[i] = tanh(x_dev[i]) (tests/test_gpu_parity.py::test_gate_functions_accuracy). */
-/* mdd_diag_gemm: C_dev[M,N] = A_dev[M,K] . W_dev[N,K]^T through one arithmetic (0 exact fp32 MFMA, 1 split-bf16 x3, 2 the f32x6
- * prototype, 3 the f32x6 kernel), fp32 operands and result on the device; synchronises (tests/test_gpu_parity.py::test_gemm_f32x6_accuracy). */
+/* mdd_diag_gemm: C_dev[M,N] = A_dev[M,K] . W_dev[N,K]^T through one arithmetic (0 exact fp32 MFMA, 1 split-bf16 x3,
+ * 3 the f32x6 kernel; any other mode is MDD_ERR_ARG), fp32 operands and result on the device; synchronises (tests/test_gpu_parity.py::test_gemm_f32x6_accuracy). */
 int mdd_diag_gemm(int mode, const float *A_dev, const float *W_dev, float *C_dev, int M, int N, int K, void *stream);
 /* mdd_diag_gemm_ops: C_dev[M,N] (row stride ldc) = opA . opB^T in the operand forms of the training step's large contractions:
  * opA[m,k] = ta ? A_dev[k*lda + m] : A_dev[m*lda + k], opB[n,k] likewise with tb / ldb.  mode 0: the exact-fp32 kernels; mode 3: the f32x6

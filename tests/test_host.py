@@ -307,6 +307,55 @@ print("sanitized host entry points ok")
     assert r.returncode == 0 and "sanitized host entry points ok" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
 
 
+_GEMM_ARGS_DRIVER = r'''
+#include <stdio.h>
+#include <string.h>
+#include "mdd_internal.h"
+using namespace mdd;
+// Every call must be refused with MDD_ERR_ARG before anything is launched: the pointers are never dereferenced.
+int main() {
+    static float a[64], w[64], c[64];
+    static unsigned short h[64];
+    const GemmOperand A{.p = a, .ld = 32}, W{.p = w, .ld = 32};
+    const SplitOperand As{.p = {h, h}, .ld = 32}, Ws{.p = {h, h}, .ld = 32};
+    int bad = 0;
+    const auto refused = [&](const char *what, int rc) {
+        const bool ok = rc == MDD_ERR_ARG && strlen(mdd_last_error()) > 0;
+        printf("%s: rc %d (%s)%s\n", what, rc, mdd_last_error(), ok ? "" : "  <-- not refused");
+        bad += !ok;
+    };
+    refused("gemm_nt, A k_major", launch_gemm_nt({.p = a, .ld = 32, .k_major = true}, W, c, 32, 1, 1, 32, nullptr));
+    refused("gemm_nt, W k_major", launch_gemm_nt(A, {.p = w, .ld = 32, .k_major = true}, c, 32, 1, 1, 32, nullptr));
+    refused("gemm_nt, accumulate", launch_gemm_nt(A, W, c, 32, 1, 1, 32, nullptr, {.accumulate = true}));
+    refused("gemm_nt, ksplit", launch_gemm_nt(A, W, c, 32, 1, 1, 32, nullptr, {.ksplit = 16}));
+    refused("gemm_nt, batch 0", launch_gemm_nt(A, W, c, 32, 1, 1, 32, nullptr, {.batch = 0}));
+    refused("gemm_bf16x3, accumulate", launch_gemm_bf16x3(As, Ws, c, nullptr, 32, 1, 1, 32, nullptr, {.accumulate = true}));
+    refused("gemm_bf16x3, ksplit", launch_gemm_bf16x3(As, Ws, c, nullptr, 32, 1, 1, 32, nullptr, {.ksplit = 16}));
+    refused("gemm_bf16x3, K % 32", launch_gemm_bf16x3(As, Ws, c, nullptr, 32, 1, 1, 24, nullptr));
+    refused("gemm_bf16x3, stride % 8", launch_gemm_bf16x3({.p = {h, h}, .ld = 32, .stride = 4}, Ws, c, nullptr, 32, 1, 1, 32, nullptr, {.batch = 2}));
+    printf("%d not refused\n", bad);
+    return bad != 0;
+}
+'''
+
+
+def test_decode_gemm_launchers_refuse_what_they_do_not_run(tmp_path):
+    """launch_gemm_nt and launch_gemm_bf16x3 take launch_gemm_f32's operand and option structs but run only row-major operands without
+    accumulation or split-K: a stand-alone program linked against the built library sets each such field and must get MDD_ERR_ARG with a
+    message (no entry of the C ABI can set them).  The checks come before any launch, so no GPU is needed."""
+    import shutil
+    import subprocess
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    pkg = os.path.join(ROOT, "ctc-attention-mispronunciation_amd")
+    src, exe = str(tmp_path / "gemm_args.hip"), str(tmp_path / "gemm_args")
+    with open(src, "w") as f:
+        f.write(_GEMM_ARGS_DRIVER)
+    subprocess.check_call([hipcc, "-std=c++17", "-O1", "--offload-arch=gfx950", "-Wall", "-Werror", "-I", os.path.join(pkg, "csrc"), src, "-o", exe,
+                           "-L", pkg, "-lmdd_hip", "-Wl,-rpath," + pkg])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and "0 not refused" in r.stdout, r.stdout + r.stderr
+
+
 def test_asm_mfma_hazards(tmp_path):
     """The kernels that issue MFMAs from inline asm (the persistent BiLSTM layers, the f32x6 GEMM) hide those instructions' register reads
     from the compiler's hazard recognizer.  The gfx950 ISA of those translation units, rebuilt here, must be free of the two patterns that
