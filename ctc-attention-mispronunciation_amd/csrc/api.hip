@@ -232,11 +232,7 @@ extern "C" int mdd_version(void) { return 100; }
 
 extern "C" int mdd_create(const mdd_config *cfg, int device, mdd_model **out) {
     if (!cfg || !out) { set_error("mdd_create: null argument"); return MDD_ERR_ARG; }
-    if (cfg->hidden <= 0 || cfg->hidden % 4 || cfg->layers < 1 || cfg->num_class < 2 || cfg->feat < 3 ||
-        (cfg->channels != 32 && cfg->channels != 4) || cfg->emb_rows < 1 || cfg->emb_dim < 1) {
-        set_error("mdd_create: unsupported geometry (hidden %% 4 == 0, channels in {32,4})");
-        return MDD_ERR_ARG;
-    }
+    if (const char *why = geometry_error(*cfg)) { set_error("mdd_create: unsupported geometry: %s", why); return MDD_ERR_ARG; }
     int ndev = 0;
     MDD_HIP_CHECK(hipGetDeviceCount(&ndev));
     if (device < 0 || device >= ndev) { set_error("mdd_create: device %d of %d", device, ndev); return MDD_ERR_ARG; }

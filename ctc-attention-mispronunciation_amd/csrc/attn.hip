@@ -161,7 +161,7 @@ __global__ __launch_bounds__(256) void attn_tail_kernel(const float *__restrict_
     }
 }
 
-// ---- MFMA variant (4H % 64 == 0): the context product and the classifier run on v_mfma_f32_16x16x4_f32.
+// ---- MFMA variant (4H % 256 == 0 and C <= 48: mfma_tail, plan.h): the context product and the classifier run on v_mfma_f32_16x16x4_f32.
 //   ctx[16 x 2H]  = attw[16 x L] . V_b[L x 2H]     : wave w owns column tiles w, w+4, ..
 //   logits[16x48] = y[16 x 4H] . Wfc^T             : K split over the 4 waves, partials summed through LDS
 // Wfc is repacked at weight-load time into the order the lanes consume it (zero rows for n >= C):
@@ -192,7 +192,7 @@ __global__ __launch_bounds__(256, 2) void attn_tail_mfma_kernel(const float *__r
     const int nt_rows = min(16, Tp - t0);
 
     // classifier operand addresses
-    const int J = D2 / 64;               // float4 groups per wave quarter (J % 4 == 0: D2 % 256 == 0 for H in {256, 384})
+    const int J = D2 / 64;               // float4 groups per wave quarter (J % 4 == 0: the launcher takes this kernel where D2 % 256 == 0, i.e. H % 64 == 0)
     const float4 *wp = reinterpret_cast<const float4 *>(wfcp) + (size_t)wave * 3 * J * 64 + lane;
     const bool xhalf = wave < 2;         // this wave's K quarter [wave*D2/4, +D2/4) lies in the x half (H2 = 2 quarters)
     const int xrow = min(t0 + li, Tp - 1);
@@ -356,7 +356,7 @@ __global__ __launch_bounds__(256, 2) void attn_tail_mfma_kernel(const float *__r
 int launch_attn_tail(const float *S, int Lp, const float *X, const float *V, const float *fscale, const float *fshift,
                      const float *wfc, const float *wfcp, float *logp, int Tp, int B, int L, int H2, int C, hipStream_t st, const int *llen) {
     if (wfcp && (2 * H2) % 256 == 0 && C <= 48) {
-        const int D2 = 2 * H2, LA = (L + 3) & ~3;
+        const int LA = (L + 3) & ~3;
         size_t smem = sizeof(float) * ((size_t)16 * LA + (size_t)16 * (H2 + 4) + 4 * 16 * 48);
         if (smem > 160 * 1024) { set_error("attn_tail: L=%d too long for the LDS tile (%zu B)", L, smem); return MDD_ERR_ARG; }
         hipLaunchKernelGGL(attn_tail_mfma_kernel, dim3((Tp + 15) / 16, B), dim3(256), smem, st, S, Lp, X, V, fscale, fshift, wfcp,

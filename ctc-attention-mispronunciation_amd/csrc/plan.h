@@ -114,6 +114,36 @@ inline int rnn_in(const mdd_config &c) { return c.channels * conv_out(conv_out(c
 // split-bf16 step kernel are built for these hidden sizes only.
 inline bool packed_whh(const mdd_config &c) { return c.hidden == 384 || c.hidden == 256; }
 
+// The attention tail (attn.hip) keeps 16 rows of attention weights in LDS next to its classifier operands, 160 KB in all, which bounds
+// the canonical length L of a forward.  mfma_tail: the matrix-core tail's condition (J = 4H / 64 float4 groups per wave quarter, four at a
+// time; three 16-column classifier tiles); every other geometry runs the scalar tail.  launch_attn_tail checks the same sums per call.
+inline bool mfma_tail(const mdd_config &c) { return (4 * c.hidden) % 256 == 0 && c.num_class <= 48; }
+inline long max_canonical_len(const mdd_config &c) {
+    //   matrix-core tail  4 * (16 * ((L + 3) & ~3) + 16 * (2H + 4) + 4 * 16 * 48) <= 163840   ->   L <= 2364 - 2H
+    //   scalar tail       4 * (16 * L + 16 * 4H + 16 * C) <= 163840                           ->   L <= 2560 - 4H - C
+    return mfma_tail(c) ? 2364L - 2L * c.hidden : 2560L - 4L * c.hidden - c.num_class;
+}
+
+// The geometries mdd_create and mdd_train_create accept (include/mdd_hip.h at mdd_config): nullptr, or what is wrong with c.
+//   hidden    a multiple of 4 (the gate-packed rows u * 4 + g and the float4 gate loads of every recurrence), at most 1024 (the training
+//             step's column statistics hold 8H sums), and small enough that the attention tail holds at least one canonical phoneme
+//   channels  32 or 4: the instantiations of the convolution kernels
+//   emb_dim   a multiple of 4: an embedding row, and a row of the text projection's operand, is then whole 16-byte vectors (the only form
+//             the training handle has ever accepted; the decode GEMM would take its scalar-load form otherwise, which no test runs)
+static constexpr int kMaxHidden = 1024;
+inline const char *geometry_error(const mdd_config &c) {
+    if (c.feat < 3) return "feat must be at least 3";
+    if (c.hidden < 4 || c.hidden % 4) return "hidden must be a positive multiple of 4";
+    if (c.hidden > kMaxHidden) return "hidden must be at most 1024";
+    if (c.layers < 1) return "layers must be at least 1";
+    if (c.num_class < 2) return "num_class must be at least 2";
+    if (c.channels != 32 && c.channels != 4) return "channels must be 32 or 4";
+    if (c.emb_rows < 1) return "emb_rows must be at least 1";
+    if (c.emb_dim < 4 || c.emb_dim % 4) return "emb_dim must be a positive multiple of 4";
+    if (max_canonical_len(c) < 1) return "hidden and num_class leave the attention tail no room for a canonical phoneme (L <= 2560 - 4 hidden - num_class)";
+    return nullptr;
+}
+
 // Exchange buffers of the persistent layer kernels: batch rows per group of the 8-workgroup teams (lstm.hip, lstm_f32.hip; 16 groups,
 // padded to whole 16-row tiles), and the bytes of the 16-workgroup teams' buffer (lstm_x6.hip).  Both cover at most 1024 rows.
 inline int granule_bg(int B) { const int r = (B + 15) / 16; return (r + 15) / 16 * 16; }

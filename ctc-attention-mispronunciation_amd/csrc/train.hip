@@ -213,9 +213,7 @@ extern "C" int mdd_train_set_precision(mdd_train_ws *w, int32_t mode) {
 
 extern "C" int mdd_train_create(const mdd_config *cfg, int device, mdd_train_ws **out) {
     if (!cfg || !out) { set_error("mdd_train_create: null argument"); return MDD_ERR_ARG; }
-    if (cfg->hidden <= 0 || cfg->hidden % 4 || cfg->layers < 1 || (cfg->channels != 32 && cfg->channels != 4) || cfg->emb_dim % 4) {
-        set_error("mdd_train_create: unsupported geometry"); return MDD_ERR_ARG;
-    }
+    if (const char *why = geometry_error(*cfg)) { set_error("mdd_train_create: unsupported geometry: %s", why); return MDD_ERR_ARG; }
     MDD_HIP_CHECK(hipSetDevice(device));
     std::unique_ptr<mdd_train_ws> w(new mdd_train_ws());
     w->cfg = *cfg; w->device = device;
@@ -230,7 +228,7 @@ extern "C" int mdd_train_create(const mdd_config *cfg, int device, mdd_train_ws 
     }
     TRY(init_gemm_attributes()); TRY(init_gemm_x6_attributes()); TRY(init_granule_attributes()); TRY(init_conv1_attributes());
     { int n_cu = 0; w->persist_ok = hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && persistent_grid_fits(n_cu) && !sw.lstm_step; }
-    if (8 * cfg->hidden > 8192) { set_error("mdd_train_create: hidden too large for the statistics scratch"); return MDD_ERR_ARG; }
+    static_assert(2 * 8192 >= 2 * 8 * kMaxHidden, "dacc holds the two column sums of 8H features up to the largest hidden size (plan.h)");
     *out = w.release();
     return MDD_OK;
 }

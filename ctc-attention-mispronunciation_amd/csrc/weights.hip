@@ -166,7 +166,7 @@ int build_weights(mdd_model *m, DecodeWeights &w) {
         if ((rc = upload(w, *ws, &w.w_score)) || (rc = upload(w, *wf, &w.w_fc)) || (rc = upload(w, sc, &w.fscale)) ||
             (rc = upload(w, sh, &w.fshift))) return rc;
         const int D2 = 4 * H;
-        if (D2 % 64 == 0 && c.num_class <= 48) {   // consumer-order repack for attn_tail_mfma_kernel
+        if (mfma_tail(c)) {   // consumer-order repack for attn_tail_mfma_kernel, where launch_attn_tail takes it (plan.h)
             const int J = D2 / 64;
             std::vector<float> pk((size_t)4 * 3 * J * 64 * 4, 0.f);
             for (int wv = 0; wv < 4; wv++)

@@ -42,15 +42,24 @@ enum mdd_beam_status { MDD_BEAM_OK = 0, MDD_BEAM_INDEX_ERROR = 1, MDD_BEAM_VALUE
 
 /* Geometry of CTC_Model.__init__ (AA/models/model_ctc.py:84-158) for the one architecture the
  * reference recipe builds: 2x LayerCNN(k3x3, strides (1,2),(2,2), pad 1) -> `layers` x BiLSTM(hidden)
- * -> Embedding(emb_rows, emb_dim) + BiLSTM text encoder -> dot attention -> BN + Linear(num_class). */
+ * -> Embedding(emb_rows, emb_dim) + BiLSTM text encoder -> dot attention -> BN + Linear(num_class).
+ * mdd_create and mdd_train_create accept the same geometries (geometry_error, csrc/plan.h) and return MDD_ERR_ARG, with
+ * mdd_last_error() naming the field, for any other:
+ *   feat >= 3;  hidden a multiple of 4, 4 <= hidden <= 1024;  layers >= 1;  num_class >= 2;  channels 32 or 4;  emb_rows >= 1;
+ *   emb_dim a multiple of 4;  and room for at least one canonical phoneme in the attention tail (the L limit at mdd_forward >= 1:
+ *   always so with the matrix-core tail, 4 hidden + num_class <= 2559 with the scalar one).
+ * Every accepted geometry runs in every mode; which kernels it gets is decided in csrc/plan.h.  The fast forms need: feat = 243 and
+ * channels = 32 (the fused conv front end), hidden 256 or 384 (the persistent layer kernels and mode 1), contraction lengths
+ * channels x W2, 2 x hidden and emb_dim that are multiples of 32 (modes 1 and 2), hidden a multiple of 64 and num_class <= 48 (the
+ * matrix-core attention tail).  tests/geometry_cases.py lists the geometries the suite runs and the kernels each is expected to get. */
 typedef struct mdd_config {
-    int32_t feat;       /* stacked input width F (243 = 3 x 81), rnn_param["rnn_input_size"] */
-    int32_t hidden;     /* rnn_hidden_size H (384; 256 for BASELINE.json's variant); multiple of 16 */
-    int32_t layers;     /* rnn_layers (4) */
-    int32_t num_class;  /* C (45 for the 41-phone set) */
-    int32_t channels;   /* CNN channels (32) */
-    int32_t emb_rows;   /* 44  (model_ctc.py:149) */
-    int32_t emb_dim;    /* 512 (model_ctc.py:149-150); multiple of 4 */
+    int32_t feat;       /* stacked input width F (243 = 3 x 81), rnn_param["rnn_input_size"]; >= 3 (mdd_forward_raw: a multiple of 3) */
+    int32_t hidden;     /* rnn_hidden_size H (384; 256 for BASELINE.json's variant); a multiple of 4, at most 1024 */
+    int32_t layers;     /* rnn_layers (4); >= 1 */
+    int32_t num_class;  /* C (45 for the 41-phone set); >= 2 */
+    int32_t channels;   /* CNN channels (32); 32 or 4 */
+    int32_t emb_rows;   /* 44  (model_ctc.py:149); >= 1 */
+    int32_t emb_dim;    /* 512 (model_ctc.py:149-150); a multiple of 4 */
     float bn_eps;       /* 1e-5 */
 } mdd_config;
 
@@ -88,6 +97,8 @@ int mdd_finalize_weights(mdd_model *m);
  *     <= 2.0e-4 at x 64 (|score| ~ 50) and <= 6.1e-4 at x 256 (|score| ~ 200, rows dominated by one key) -- i.e. past the 1e-4
  *     tolerance once scores reach a few tens, where modes 0 and 2 stay <= 2.2e-5.  Use mode 2 or 0 for a model with peaked attention.
  *     Falls back to 0 when a contraction length is not a multiple of 32 or H is not 256 / 384.
+ * The contraction lengths are channels x W2 (W2 = the width after both convolutions: always a multiple of 32 with 32 channels), 2H and
+ * emb_dim.  In mode 2 a hidden size other than 256 / 384 keeps the f32x6 projections and runs the recurrences per step in exact fp32.
  * Env MDD_PRECISION=f32x6 / f32 / bf16x3 selects the mode at mdd_create.  mdd_get_precision returns the mode actually in use. */
 int mdd_set_precision(mdd_model *m, int32_t mode);
 int32_t mdd_get_precision(mdd_model *m);
@@ -106,8 +117,9 @@ int32_t mdd_len_frames(int32_t len, int32_t maxlen, int32_t t_out);
  * logp_dev [T/2,B,C] fp32 log-probabilities.  ids outside [0,emb_rows) are an error
  * (the reference raises IndexError) and are reported by the next mdd_sync().
  * Canonical length: the attention tail keeps 16 rows of attention weights in LDS next to its classifier operands (160 KB in all),
- * which bounds L.  With the matrix-core tail (4H a multiple of 256, C <= 48: the reference geometries) L <= 2364 - 2H, i.e. 1596 at
- * H = 384 and 1852 at H = 256; with the scalar tail (any other geometry) L <= 2560 - 4H - C.  A longer L returns MDD_ERR_ARG
+ * which bounds L (max_canonical_len, csrc/plan.h).  With the matrix-core tail (hidden a multiple of 64 and C <= 48) L <= 2364 - 2H:
+ * 1596 at H = 384, 1852 at H = 256, 2108 at H = 128; with the scalar tail (every other geometry) L <= 2560 - 4H - C: 1999 at
+ * H = 128, C = 49.  A longer L returns MDD_ERR_ARG
  * (mdd_last_error() names L) from mdd_forward, mdd_forward_fused (whose bound applies to the common L) and mdd_forward_raw.  It is a
  * host check: logp_dev is untouched and the handle stays usable; in the default graph mode it fires while the library's own capture
  * is open, so nothing of that forward has been enqueued (with MDD_GRAPH=0 the stages before the tail have run into the workspace). */
@@ -338,7 +350,10 @@ int mdd_eval_batch(const int32_t *dec, const int32_t *dec_len, const int32_t *la
  *               one launch and are summed afterwards (no atomics: run-to-run deterministic).  The recurrences -- forward and backward,
  *               about half of the exact step -- and everything else are mode 0's kernels and bits; mode 2 meets mode 0's bounds.
  * Fallback: in modes 1 and 2 a contraction outside the mode's size / alignment rule (the header comment of gemm_big, csrc/train.hip;
- * mode 2: M, N >= 128, K >= 64, M.N.K >= 2^27, leading dimensions multiples of 4, 16-byte aligned operands) runs as in mode 0. */
+ * mode 2: M, N >= 128, K >= 64, M.N.K >= 2^27, leading dimensions multiples of 4, 16-byte aligned operands) runs as in mode 0.
+ * Mode 1's persistent recurrences are built for hidden 256 / 384 (forward up to 512 rows, backward up to 256); any other hidden size or
+ * batch runs the exact per-step recurrences of mode 0, decided before anything is enqueued.  A geometry whose contractions are all under
+ * the mode's thresholds therefore computes mode 0's step in modes 1 and 2. */
 typedef struct mdd_train_ws mdd_train_ws;
 int mdd_train_create(const mdd_config *cfg, int device, mdd_train_ws **out);
 int mdd_train_set_precision(mdd_train_ws *w, int32_t mode);   /* 0 exact fp32 (default), 1 split-bf16 x3, 2 f32x6 contractions */
