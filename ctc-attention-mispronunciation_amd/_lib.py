@@ -13,7 +13,7 @@ LIB_PATH = os.environ.get("MDD_LIB_PATH") or os.path.join(_HERE, "libmdd_hip.so"
 MDD_ERR_EMPTY = -5   # include/mdd_hip.h: an empty sequence where the reference raises TypeError
 
 EXPORTS = (
-    "mdd_last_error", "mdd_version", "mdd_create", "mdd_destroy", "mdd_load_weight", "mdd_finalize_weights",
+    "mdd_last_error", "mdd_version", "mdd_create", "mdd_create_ctc", "mdd_is_ctc_only", "mdd_destroy", "mdd_load_weight", "mdd_finalize_weights",
     "mdd_set_precision", "mdd_get_precision", "mdd_stack_len", "mdd_stack_skip", "mdd_len_frames", "mdd_forward", "mdd_forward_fused", "mdd_forward_raw", "mdd_forward_num_stages", "mdd_forward_profile", "mdd_tap", "mdd_tap_copy", "mdd_enable_taps", "mdd_sync",
     "mdd_greedy", "mdd_beam", "mdd_ctc_loss", "mdd_ctc_workspace_bytes", "mdd_ctc_align", "mdd_ctc_align_workspace_bytes", "mdd_ctc_variants", "mdd_ctc_variants_workspace_bytes", "mdd_align", "mdd_align_batch", "mdd_eval_batch", "mdd_fbank_num_frames", "mdd_fbank", "mdd_fbank_batch_len", "mdd_fbank_batch",
     "mdd_resample_len", "mdd_resample_filter", "mdd_resample_batch",
@@ -50,6 +50,9 @@ def lib():
     vp, i32, i64p, f32p = C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_float)
     L.mdd_last_error.restype = C.c_char_p
     L.mdd_create.argtypes = [C.POINTER(MddConfig), C.c_int, C.POINTER(vp)]
+    L.mdd_create_ctc.argtypes = [C.POINTER(MddConfig), C.c_int, C.POINTER(vp)]
+    L.mdd_is_ctc_only.argtypes = [vp]
+    L.mdd_is_ctc_only.restype = i32
     L.mdd_destroy.argtypes = [vp]
     L.mdd_destroy.restype = None
     L.mdd_load_weight.argtypes = [vp, C.c_char_p, vp, i64p, i32]

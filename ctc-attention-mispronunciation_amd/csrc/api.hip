@@ -59,7 +59,7 @@ static int ensure(DeviceBuf &b, size_t n, hipStream_t zero_stream, bool *moved) 
 }
 
 // The kernels a forward of B rows runs on this handle as it stands now (plan.h)
-static ForwardPlan plan_of(const mdd_model *m, int B) { return plan_forward(m->cfg, m->precision, m->sw, m->fit, B); }
+static ForwardPlan plan_of(const mdd_model *m, int B) { return plan_forward(m->cfg, m->precision, m->sw, m->fit, B, m->ctc_only); }
 
 // One BiLSTM layer: the caller sets a.T, a.B, a.seqlen and the outputs, the rest is filled here.  The persistent layer kernel where
 // the plan has one (f32x6, split-bf16 or exact-fp32 teams), else one launch per step (launch_lstm_layer: hsplit selects the x3 step).
@@ -161,6 +161,13 @@ static std::vector<Stage> forward_stages(mdd_model *m, const ForwardCall &call) 
         s.push_back({"lstm" + std::to_string(n), p.gated ? 1 : Tp, step_flops * Tp, [=](hipStream_t st) { return run_lstm(m, *lw, a, st); }});
     }
 
+    if (m->ctc_only) {   // the CTC-only model ends here: the classifier on the last layer's raw output (CRC/models/cnn_rnn.py:168-172)
+        s.push_back({"ctc_tail", 1, 2.0 * (double)rows * H2 * c.num_class, [=](hipStream_t st) {
+            return launch_ctc_tail(m->xraw.p, w->fscale, w->fshift, w->w_fc, w->w_fcp, call.logp, Tp * B, H2, c.num_class, st);
+        }});
+        return s;
+    }
+
     const LstmWeights *tw = &w->rnn[nl];   // the text encoder (model_ctc.py:193,198) and keys (:201)
     // Its input projection multiplies two weights: emb[id] . W_ih'^T + bias is one of emb_rows constant rows.  Where the plan says so the two
     // stages are the id check with the row indices, and a gather from the weight set's table of those rows; gemm_text keeps the flops of the
@@ -230,12 +237,13 @@ using namespace mdd;
 extern "C" const char *mdd_last_error(void) { return g_err; }
 extern "C" int mdd_version(void) { return 100; }
 
-extern "C" int mdd_create(const mdd_config *cfg, int device, mdd_model **out) {
-    if (!cfg || !out) { set_error("mdd_create: null argument"); return MDD_ERR_ARG; }
-    if (const char *why = geometry_error(*cfg)) { set_error("mdd_create: unsupported geometry: %s", why); return MDD_ERR_ARG; }
+// mdd_create and mdd_create_ctc: `what` names the entry point in messages, the geometry contract is the one thing that differs
+static int create_handle(const char *what, bool ctc_only, const mdd_config *cfg, int device, mdd_model **out) {
+    if (!cfg || !out) { set_error("%s: null argument", what); return MDD_ERR_ARG; }
+    if (const char *why = ctc_only ? ctc_geometry_error(*cfg) : geometry_error(*cfg)) { set_error("%s: unsupported geometry: %s", what, why); return MDD_ERR_ARG; }
     int ndev = 0;
     MDD_HIP_CHECK(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) { set_error("mdd_create: device %d of %d", device, ndev); return MDD_ERR_ARG; }
+    if (device < 0 || device >= ndev) { set_error("%s: device %d of %d", what, device, ndev); return MDD_ERR_ARG; }
     MDD_HIP_CHECK(hipSetDevice(device));
     hipDeviceProp_t prop;
     MDD_HIP_CHECK(hipGetDeviceProperties(&prop, device));
@@ -246,6 +254,7 @@ extern "C" int mdd_create(const mdd_config *cfg, int device, mdd_model **out) {
     std::unique_ptr<mdd_model> m(new mdd_model());
     m->cfg = *cfg;
     m->device = device;
+    m->ctc_only = ctc_only;
     m->sw = read_switches();
     m->precision = m->sw.precision;
     for (auto init : {init_kernel_attributes, init_lstm_attributes, init_granule_attributes, init_lstm_f32_attributes, init_lstm_x6_attributes,
@@ -257,10 +266,14 @@ extern "C" int mdd_create(const mdd_config *cfg, int device, mdd_model **out) {
     if (int rc = m->sync_words.need(32)) return rc;
     hipError_t e = hipMemset(m->err_flag.p, 0, sizeof(int));
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&m->cap_stream, hipStreamNonBlocking);
-    if (e != hipSuccess) { set_error("mdd_create: %s", hipGetErrorString(e)); return MDD_ERR_HIP; }
+    if (e != hipSuccess) { set_error("%s: %s", what, hipGetErrorString(e)); return MDD_ERR_HIP; }
     *out = m.release();
     return MDD_OK;
 }
+
+extern "C" int mdd_create(const mdd_config *cfg, int device, mdd_model **out) { return create_handle("mdd_create", false, cfg, device, out); }
+extern "C" int mdd_create_ctc(const mdd_config *cfg, int device, mdd_model **out) { return create_handle("mdd_create_ctc", true, cfg, device, out); }
+extern "C" int32_t mdd_is_ctc_only(mdd_model *m) { return m && m->ctc_only ? 1 : 0; }
 
 extern "C" void mdd_destroy(mdd_model *m) {
     if (!m) return;
@@ -275,6 +288,8 @@ extern "C" int mdd_load_weight(mdd_model *m, const char *key, const float *data,
     if (k.size() > 19 && k.compare(k.size() - 19, 19, "num_batches_tracked") == 0) return MDD_OK;  // unused in eval
     size_t n = 1;
     for (int i = 0; i < ndim; i++) { if (shape[i] < 0) { set_error("negative dim"); return MDD_ERR_ARG; } n *= (size_t)shape[i]; }
+    if (m->ctc_only)
+        if (int rc = check_ctc_entry(m, k, shape, ndim)) return rc;
     m->host[k].assign(data, data + n);
     m->finalized = false;
     return MDD_OK;
@@ -341,9 +356,11 @@ static int capture(mdd_model *m, const char *what, const std::function<int(hipSt
 // place that drops the captured graphs because a workspace buffer moved.
 static int prepare(mdd_model *m, const ForwardCall &call) {
     const int B = call.B, T = call.T, L = call.L;
-    if (!m || !call.x || !call.x1 || !call.logp) { set_error("mdd_forward: null pointer"); return MDD_ERR_ARG; }
+    if (!m || !call.x || !call.logp) { set_error("mdd_forward: null pointer"); return MDD_ERR_ARG; }
+    const bool ctc = m->ctc_only;   // (its calls come with x1 = null and L = 0: plain_call)
+    if (!ctc && !call.x1) { set_error("mdd_forward: null pointer"); return MDD_ERR_ARG; }
     if (!m->finalized) { set_error("mdd_forward: call mdd_finalize_weights first"); return MDD_ERR_STATE; }
-    if (B <= 0 || T < 2 || L <= 0) { set_error("mdd_forward: bad shape B=%d T=%d L=%d", B, T, L); return MDD_ERR_ARG; }
+    if (B <= 0 || T < 2 || (!ctc && L <= 0)) { set_error("mdd_forward: bad shape B=%d T=%d L=%d", B, T, L); return MDD_ERR_ARG; }
     if (T % 2) { set_error("mdd_forward: T must be even (data_loader.py:140-142 pads to n_downsample)"); return MDD_ERR_ARG; }
     MDD_HIP_CHECK(hipSetDevice(m->device));
     std::lock_guard<std::mutex> prep_lock(g_prep_mu);
@@ -362,12 +379,13 @@ static int prepare(mdd_model *m, const ForwardCall &call) {
     bool ok = (!(call.Traw > 0 && separate) || grow(m->xstack, (size_t)B * T * c.feat)) && (!separate || grow(m->y0, (size_t)B * c.channels * T * m->W1())) &&
               grow(m->seq0, rows * K0) && grow(m->gx, mrows * 8 * H) && grow(m->act[0], rows * 2 * H) && grow(m->act[1], rows * 2 * H) &&
               grow(m->xraw, rows * 2 * H) && grow(m->hbuf, (size_t)4 * Bpad * H) && grow(m->cbuf, (size_t)2 * Bpad * H) &&
-              (p.text_table ? grow(m->tidx, trows) : grow(m->embo, trows * emb)) && grow(m->text, trows * 2 * H) && grow(m->key, trows * 2 * H) && grow(m->S, (size_t)B * Tp * L) &&
+              (ctc || ((p.text_table ? grow(m->tidx, trows) : grow(m->embo, trows * emb)) && grow(m->text, trows * 2 * H) && grow(m->key, trows * 2 * H) &&
+                       grow(m->S, (size_t)B * Tp * L))) &&   // (a CTC-only handle has no text side)
               (p.proj != Gemm::F32x6 || grow(m->p3, p3_floats)) &&
               (!p.hx_floats || grow(m->hx, p.hx_floats));   // the exchange buffer of the persistent layers + stamps
     if (ok && x3)
         ok = grow(m->seq0_s, rows * K0) && grow(m->act_s[0], rows * 2 * H) && grow(m->act_s[1], rows * 2 * H) && grow(m->x_s, rows * 2 * H) &&
-             grow(m->embo_s, trows * emb) && grow(m->text_s, trows * 2 * H) && grow(m->key_s, trows * 2 * H) && grow(m->hsplit, (size_t)4 * B * H);
+             (ctc || (grow(m->embo_s, trows * emb) && grow(m->text_s, trows * 2 * H) && grow(m->key_s, trows * 2 * H))) && grow(m->hsplit, (size_t)4 * B * H);
     if (ok && m->taps) {
         m->tap_rnn.resize(c.layers);
         for (int n = 0; ok && n + 1 < c.layers; n++) ok = grow(m->tap_rnn[n], rows * 2 * H);
@@ -405,15 +423,18 @@ static int forward(mdd_model *m, ForwardCall call, hipStream_t st) {
     return device_gate_leave(m->device, st, held, rc);
 }
 
-static ForwardCall plain_call(const float *x, int B, int T, const int64_t *x1, int L, float *logp) {
+// A CTC-only handle ignores the canonical side of every entry point: the pointers are dropped here, before anything could read them or
+// key a captured graph on them.
+static ForwardCall plain_call(const mdd_model *m, const float *x, int B, int T, const int64_t *x1, int L, float *logp) {
     ForwardCall call;
-    call.x = x; call.x1 = x1; call.logp = logp; call.B = B; call.T = T; call.L = L;
+    call.x = x; call.logp = logp; call.B = B; call.T = T;
+    if (!(m && m->ctc_only)) { call.x1 = x1; call.L = L; }
     return call;
 }
 
 extern "C" int mdd_forward(mdd_model *m, const float *x_dev, int32_t B, int32_t T, const int64_t *x1_dev, int32_t L,
                            float *logp_dev, void *stream) {
-    return forward(m, plain_call(x_dev, B, T, x1_dev, L, logp_dev), (hipStream_t)stream);
+    return forward(m, plain_call(m, x_dev, B, T, x1_dev, L, logp_dev), (hipStream_t)stream);
 }
 
 // Several reference batches of different padded lengths in one launch sequence (contract: include/mdd_hip.h).  What depends on a batch's
@@ -421,9 +442,9 @@ extern "C" int mdd_forward(mdd_model *m, const float *x_dev, int32_t B, int32_t 
 // (LstmStepArgs::seqlen, launch_attn_tail's llen); everything else is row-local.
 extern "C" int mdd_forward_fused(mdd_model *m, const float *x_dev, int32_t B, int32_t T, const int64_t *x1_dev, int32_t L,
                                  const int32_t *frames_dev, const int32_t *canon_dev, float *logp_dev, void *stream) {
-    if (!m || !frames_dev || !canon_dev) { set_error("mdd_forward_fused: null pointer"); return MDD_ERR_ARG; }
-    ForwardCall call = plain_call(x_dev, B, T, x1_dev, L, logp_dev);
-    call.tlen = frames_dev; call.llen = canon_dev;
+    if (!m || !frames_dev || (!canon_dev && !m->ctc_only)) { set_error("mdd_forward_fused: null pointer"); return MDD_ERR_ARG; }
+    ForwardCall call = plain_call(m, x_dev, B, T, x1_dev, L, logp_dev);
+    call.tlen = frames_dev; call.llen = m->ctc_only ? nullptr : canon_dev;
     return forward(m, call, (hipStream_t)stream);
 }
 
@@ -433,17 +454,17 @@ extern "C" int mdd_forward_raw(mdd_model *m, const float *raw_dev, int32_t B, in
                                float *logp_dev, void *stream) {
     if (!m || !raw_dev || B <= 0 || T_raw < 1) { set_error("mdd_forward_raw: bad argument"); return MDD_ERR_ARG; }
     if (m->cfg.feat % 3) { set_error("mdd_forward_raw: feat=%d is not 3 stacked frames", m->cfg.feat); return MDD_ERR_ARG; }
-    ForwardCall call = plain_call(raw_dev, B, mdd_stack_len(T_raw, 2, 2), x1_dev, L, logp_dev);
+    ForwardCall call = plain_call(m, raw_dev, B, mdd_stack_len(T_raw, 2, 2), x1_dev, L, logp_dev);
     call.Traw = T_raw;
     return forward(m, call, (hipStream_t)stream);
 }
 
-extern "C" int32_t mdd_forward_num_stages(mdd_model *m) { return m ? 2 + 2 * m->cfg.layers + 6 : 0; }
+extern "C" int32_t mdd_forward_num_stages(mdd_model *m) { return m ? 2 + 2 * m->cfg.layers + (m->ctc_only ? 1 : 6) : 0; }
 
 extern "C" int mdd_forward_profile(mdd_model *m, const float *x_dev, int32_t B, int32_t T, const int64_t *x1_dev, int32_t L,
                                    float *logp_dev, void *stream, char *names, int32_t names_cap, float *ms,
                                    int32_t *launches, double *flops, int32_t cap) {
-    const ForwardCall call = plain_call(x_dev, B, T, x1_dev, L, logp_dev);
+    const ForwardCall call = plain_call(m, x_dev, B, T, x1_dev, L, logp_dev);
     int rc = prepare(m, call);
     if (rc) return rc;
     const std::vector<Stage> stages = forward_stages(m, call);
@@ -487,6 +508,7 @@ extern "C" const float *mdd_tap(mdd_model *m, const char *name, int64_t *numel) 
     float *p = nullptr;
     int64_t ne = 0;
     if (n == "conv1") { p = m->seq0.p; ne = rows * m->rnn_in(); }
+    else if (m->ctc_only && (n == "text" || n == "key" || n == "score")) return nullptr;   // stages a CTC-only forward does not have
     else if (n == "text") { p = m->text.p; ne = trows * H2; }
     else if (n == "key") { p = m->key.p; ne = trows * H2; }
     else if (n == "score") { p = m->S.p; ne = B * (m->lastT / 2) * m->lastL; }   // S[b][t][l]

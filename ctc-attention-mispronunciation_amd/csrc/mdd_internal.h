@@ -177,6 +177,11 @@ int launch_attn_tail(const float *S, int Lp, const float *X, const float *V, con
                      const float *wfc, const float *wfcp, float *logp, int Tp, int B, int L, int H2, int C, hipStream_t st,
                      const int *llen = nullptr);   // llen[b]: canonical length of b's own batch (softmax / context over l < llen[b]); null = L
 
+// The CTC-only model's tail (ctc_tail.hip): logp[r, :] = log_softmax((X[r, :] * fscale + fshift) . Wfc^T) over R rows of K = 2H values; wfcp: Wfc in
+// the matrix-core form's lane order (DecodeWeights::w_fcp), null where the geometry runs the scalar form
+int launch_ctc_tail(const float *X, const float *fscale, const float *fshift, const float *wfc, const float *wfcp, float *logp, int R, int K, int C,
+                    hipStream_t st);
+
 int init_kernel_attributes();
 int init_ctc_attributes();
 // The alpha / beta lattice of ctc.hip on int32 ids (mdd_ctc_variants): row t of utterance b starts at alpha + b * utt_stride + t * pitch

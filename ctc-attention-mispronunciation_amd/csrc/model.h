@@ -35,7 +35,7 @@ using Event = HipOwned<hipEvent_t, hipEventDestroy>;
 using Graph = HipOwned<hipGraph_t, hipGraphDestroy>;
 using GraphExec = HipOwned<hipGraphExec_t, hipGraphExecDestroy>;
 
-// The weights of one BiLSTM layer on the device; the text encoder's sit at index cfg.layers.
+// The weights of one BiLSTM layer on the device; the text encoder's sit at index cfg.layers (a CTC-only handle has none).
 struct LstmWeights {
     float *wih = nullptr, *whh = nullptr;          // fp32, gate rows permuted (whh in the packed layout where packed_whh)
     SplitPtr wih_s{nullptr, nullptr}, whh_s{nullptr, nullptr};   // split-bf16 copies (whh row-major)
@@ -50,12 +50,14 @@ struct DecodeWeights {
     float *w_conv1t = nullptr, *sc1 = nullptr, *sh1 = nullptr;
     SplitPtr w_conv1_s{nullptr, nullptr};
     unsigned short *w_conv1_3 = nullptr;           // conv1 weights [co][kh][kw][ci] as three row-major planes
-    std::vector<LstmWeights> rnn;                  // cfg.layers + 1
+    std::vector<LstmWeights> rnn;                  // cfg.layers + 1; cfg.layers in a CTC-only handle
     float *emb = nullptr, *t_bias = nullptr;
     // The text encoder's input projection of every embedding row, [emb_rows][8H]: text_table[v] = emb[v] . W_ih_text'^T + t_bias, made at finalize
     // by the forward's own GEMM of each arithmetic on emb itself, so a row carries the bits gemm_text would produce for it.  [0]: the exact
     // fp32 MFMA GEMM (mode 0), [1]: f32x6 (mode 2; null where the geometry has no f32x6 planes).  Mode 1 has none (plan.h, text_table).
     float *text_table[2] = {nullptr, nullptr};
+    // the classifier: BatchNorm folded to fscale / fshift, Linear as it is and in the matrix-core tail's lane order.  4H wide; 2H wide in a
+    // CTC-only handle, which has no emb, t_bias, text_table or w_score
     float *w_score = nullptr, *fscale = nullptr, *fshift = nullptr, *w_fc = nullptr, *w_fcp = nullptr;
     SplitPtr w_score_s{nullptr, nullptr};
     std::vector<DeviceArray<unsigned char>> mem;   // the allocations behind every pointer above
@@ -69,12 +71,16 @@ struct DecodeWeights {
 };
 // Build a complete weight set from the loaded state_dict into `w` (a fresh set: on failure it is discarded whole).  weights.hip
 int build_weights(mdd_model *m, DecodeWeights &w);
+// A CTC-only handle checks every entry as it is loaded: MDD_OK, or MDD_ERR_ARG with the key named (a key of the attention branch, a key the
+// CTC-only state_dict does not have, a shape other than the geometry's).  weights.hip
+int check_ctc_entry(const mdd_model *m, const std::string &key, const int64_t *shape, int ndim);
 
 }  // namespace mdd
 
 struct mdd_model {
     mdd_config cfg;
     int device = 0;
+    bool ctc_only = false;   // mdd_create_ctc: the acoustic model with the classifier on it, no text side (ctc_tail instead of the attention tail)
     bool finalized = false, taps = false;
     int precision = 2;   // 2 (default): fp32-grade, the large contractions as f32x6 on the bf16 matrix cores (falls back to 0 when the geometry does not allow);
                          // 0: exact fp32 MFMA everywhere; 1: split-bf16 x3 for every contraction (narrower than fp32: flagged variant)

@@ -2,7 +2,7 @@
 // geometry, the arithmetic mode, the environment switches, what the device can hold and the batch size; and the sizes of the persistent layers'
 // exchange buffers.  Host only: no HIP, no device code (tests/test_host.py builds it with the host compiler and checks the selection table).
 //
-// Environment switches.  read_switches() parses them once, in mdd_create and in mdd_train_create; a handle keeps what it read for its
+// Environment switches.  read_switches() parses them once, in mdd_create, mdd_create_ctc and mdd_train_create; a handle keeps what it read for its
 // whole life, so a switch is set before the handle is created.  Any other value of a switch is its default.
 //
 //   switch               selects                                                      read at   relied on by
@@ -131,18 +131,39 @@ inline long max_canonical_len(const mdd_config &c) {
 //   emb_dim   a multiple of 4: an embedding row, and a row of the text projection's operand, is then whole 16-byte vectors (the only form
 //             the training handle has ever accepted; the decode GEMM would take its scalar-load form otherwise, which no test runs)
 static constexpr int kMaxHidden = 1024;
-inline const char *geometry_error(const mdd_config &c) {
+// the fields both model families share, in the order the messages have always come
+inline const char *acoustic_geometry_error(const mdd_config &c) {
     if (c.feat < 3) return "feat must be at least 3";
     if (c.hidden < 4 || c.hidden % 4) return "hidden must be a positive multiple of 4";
     if (c.hidden > kMaxHidden) return "hidden must be at most 1024";
     if (c.layers < 1) return "layers must be at least 1";
     if (c.num_class < 2) return "num_class must be at least 2";
     if (c.channels != 32 && c.channels != 4) return "channels must be 32 or 4";
+    return nullptr;
+}
+inline const char *geometry_error(const mdd_config &c) {
+    if (const char *why = acoustic_geometry_error(c)) return why;
     if (c.emb_rows < 1) return "emb_rows must be at least 1";
     if (c.emb_dim < 4 || c.emb_dim % 4) return "emb_dim must be a positive multiple of 4";
     if (max_canonical_len(c) < 1) return "hidden and num_class leave the attention tail no room for a canonical phoneme (L <= 2560 - 4 hidden - num_class)";
     return nullptr;
 }
+
+// The geometries mdd_create_ctc accepts (include/mdd_hip.h at mdd_create_ctc): the CTC-only model (the reference's egs/cnn-rnn-ctc) is the
+// acoustic model alone -- no embedding, no text encoder, no attention -- with the classifier BatchNorm1d(2H) + Linear(2H -> C) on the last
+// BiLSTM layer's output.
+//   feat, hidden, layers, num_class, channels   as geometry_error above, the same messages
+//   emb_rows, emb_dim                           both 0: the model has no embedding (a handle for a model that has one comes from mdd_create)
+// The attention tail's room condition does not apply: ctc_tail (ctc_tail.hip) holds no more than one row of 2H values per wave in LDS.
+inline const char *ctc_geometry_error(const mdd_config &c) {
+    if (const char *why = acoustic_geometry_error(c)) return why;
+    if (c.emb_rows != 0) return "emb_rows must be 0 for a CTC-only model";
+    if (c.emb_dim != 0) return "emb_dim must be 0 for a CTC-only model";
+    return nullptr;
+}
+// ctc_tail's matrix-core form (J = 2H / 16 float4 groups per lane, four at a time; three 16-column classifier tiles); every other
+// geometry runs its scalar form.  launch_ctc_tail checks the same sums per call.
+inline bool mfma_ctc_tail(const mdd_config &c) { return (2 * c.hidden) % 64 == 0 && c.num_class <= 48; }
 
 // Exchange buffers of the persistent layer kernels: batch rows per group of the 8-workgroup teams (lstm.hip, lstm_f32.hip; 16 groups,
 // padded to whole 16-row tiles), and the bytes of the 16-workgroup teams' buffer (lstm_x6.hip).  Both cover at most 1024 rows.
@@ -172,12 +193,14 @@ struct ForwardPlan {
     bool text_table;    // gemm_text gathers rows of the weight set's projected embedding table (DecodeWeights::text_table) instead of multiplying
 };
 
-inline ForwardPlan plan_forward(const mdd_config &c, int precision, const Switches &sw, const DeviceFit &fit, int B) {
+// ctc_only: a handle of mdd_create_ctc.  Its forward has no text side: emb_dim (0 there) is no contraction length, and there is no text table.
+inline ForwardPlan plan_forward(const mdd_config &c, int precision, const Switches &sw, const DeviceFit &fit, int B, bool ctc_only = false) {
     const int H = c.hidden, K0 = rnn_in(c);
     const bool packed = packed_whh(c);
     // bf16x3 and f32x6 need every contraction length a multiple of 32 (bf16x3 also the packed LSTM layouts); mode 0 otherwise
-    const bool x3 = precision == 1 && packed && K0 % 32 == 0 && c.emb_dim % 32 == 0;
-    const bool x6 = precision == 2 && K0 % 32 == 0 && (2 * H) % 32 == 0 && c.emb_dim % 32 == 0;
+    const bool emb_ok = ctc_only || c.emb_dim % 32 == 0;
+    const bool x3 = precision == 1 && packed && K0 % 32 == 0 && emb_ok;
+    const bool x6 = precision == 2 && K0 % 32 == 0 && (2 * H) % 32 == 0 && emb_ok;
     ForwardPlan p{};
     p.precision = x3 ? 1 : x6 ? 2 : 0;
     if ((x3 || x6) && c.feat == 243 && c.channels == 32) p.conv = x3 ? Conv::FusedX3 : sw.conv_rowwise ? Conv::FusedX6Rowwise : Conv::FusedX6;
@@ -197,7 +220,7 @@ inline ForwardPlan plan_forward(const mdd_config &c, int precision, const Switch
     p.planes_out = p.proj == Gemm::F32x6 && lx6 && !sw.x6_out_fp32;
     // The table's rows carry the bits of the per-call projection where a C element depends on its own A row and W row alone, in one K order:
     // gemm_nt_f32_kernel and gemm_f32x6_kernel.  The bf16x3 launcher picks its kernel by problem size, so mode 1 keeps the per-call GEMM.
-    p.text_table = p.proj != Gemm::Bf16x3 && !sw.text_gemm;
+    p.text_table = !ctc_only && p.proj != Gemm::Bf16x3 && !sw.text_gemm;
     if (persist) {   // u64 granules of the 8-workgroup teams or the three bf16 planes of the 16-workgroup ones, in floats; 256 x 6 stamps behind
         const size_t granules = team8_hx_alloc_floats(H, B), planes = lstm_x6_hx_bytes(H, B) / 4;
         p.stamps_at = lx6 ? planes : granules;

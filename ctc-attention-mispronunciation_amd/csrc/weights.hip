@@ -92,9 +92,57 @@ static void pack_whh(const std::vector<float> &w, int H, std::vector<float> &out
                             w[((size_t)d * 4 * H + ut * 16 + (lane & 15)) * H + 16 * j + 4 * (lane >> 4) + mm];
 }
 
+// The float entries of the CTC-only state_dict (CRC/models/cnn_rnn.py:82-145) with their shapes: 12 + 4 layers + 4 (layers - 1) + 5.
+static std::map<std::string, std::vector<int64_t>> ctc_entries(const mdd_model *m) {
+    const mdd_config &c = m->cfg;
+    const int64_t ch = c.channels, H = c.hidden;
+    std::map<std::string, std::vector<int64_t>> e;
+    const auto bn = [&e](const std::string &prefix, int64_t n) {
+        for (const char *s : {".weight", ".bias", ".running_mean", ".running_var"}) e[prefix + s] = {n};
+    };
+    e["conv.0.conv.weight"] = {ch, 1, 3, 3}; e["conv.0.conv.bias"] = {ch}; bn("conv.0.batch_norm", ch);
+    e["conv.1.conv.weight"] = {ch, ch, 3, 3}; e["conv.1.conv.bias"] = {ch}; bn("conv.1.batch_norm", ch);
+    for (int n = 0; n < c.layers; n++) {
+        const std::string base = "rnns." + std::to_string(n);
+        if (n > 0) bn(base + ".batch_norm", 2 * H);
+        for (const char *d : {"", "_reverse"}) {
+            e[base + ".rnn.weight_ih_l0" + d] = {4 * H, n == 0 ? (int64_t)m->rnn_in() : 2 * H};
+            e[base + ".rnn.weight_hh_l0" + d] = {4 * H, H};
+        }
+    }
+    bn("fc.0", 2 * H);
+    e["fc.1.weight"] = {c.num_class, 2 * H};
+    return e;
+}
+
+int check_ctc_entry(const mdd_model *m, const std::string &key, const int64_t *shape, int ndim) {
+    if (key == "embeds.weight" || key == "score.weight" || key.compare(0, 12, "lstm_embeds.") == 0) {
+        set_error("mdd_load_weight: '%s' belongs to the attention branch, which a CTC-only model does not have (mdd_create makes a handle for it)", key.c_str());
+        return MDD_ERR_ARG;
+    }
+    const auto entries = ctc_entries(m);
+    const auto it = entries.find(key);
+    if (it == entries.end()) { set_error("mdd_load_weight: '%s' is no entry of the CTC-only state_dict", key.c_str()); return MDD_ERR_ARG; }
+    const std::vector<int64_t> &want = it->second;
+    bool same = ndim == (int)want.size();
+    for (int i = 0; same && i < ndim; i++) same = shape[i] == want[i];
+    if (!same) {
+        std::string got, exp;
+        for (int i = 0; i < ndim; i++) got += (i ? ", " : "") + std::to_string(shape[i]);
+        for (size_t i = 0; i < want.size(); i++) exp += (i ? ", " : "") + std::to_string(want[i]);
+        set_error("mdd_load_weight: '%s' has shape [%s], the CTC-only geometry expects [%s]", key.c_str(), got.c_str(), exp.c_str());
+        return MDD_ERR_ARG;
+    }
+    return MDD_OK;
+}
+
 int build_weights(mdd_model *m, DecodeWeights &w) {
     const mdd_config &c = m->cfg;
     const int ch = c.channels, H = c.hidden;
+    const bool ctc = m->ctc_only;
+    if (ctc)   // name the first missing entry of the 45 (at 4 layers) before anything is built
+        for (const auto &e : ctc_entries(m))
+            if (!m->host.count(e.first)) { set_error("weight '%s' was never loaded", e.first.c_str()); return MDD_ERR_STATE; }
     int rc;
     std::vector<float> sc, sh, tmp;
     {   // conv0 / conv1: fold bias + BN into scale/shift; conv1 weights -> [ci][kh][kw][co]
@@ -116,8 +164,9 @@ int build_weights(mdd_model *m, DecodeWeights &w) {
         if ((rc = upload(w, tmp, &w.w_conv1t)) || (rc = upload(w, sc, &w.sc1)) || (rc = upload(w, sh, &w.sh1))) return rc;
         if ((rc = upload_split(w, tmp2, &w.w_conv1_s)) || (rc = upload_planes(w, tmp2, 3, &w.w_conv1_3))) return rc;
     }
-    w.rnn.resize(c.layers + 1);
-    for (int n = 0; n <= c.layers; n++) {   // the BiLSTM layers, then the text encoder
+    const int n_rnn = ctc ? c.layers : c.layers + 1;
+    w.rnn.resize(n_rnn);
+    for (int n = 0; n < n_rnn; n++) {   // the BiLSTM layers, then the text encoder (none in a CTC-only model)
         LstmWeights &lw = w.rnn[n];
         char base[64];
         if (n < c.layers) snprintf(base, sizeof(base), "rnns.%d.rnn.", n);
@@ -138,7 +187,7 @@ int build_weights(mdd_model *m, DecodeWeights &w) {
             if ((rc = upload(w, sc, &lw.scale)) || (rc = upload(w, sh, &lw.shift))) return rc;
         }
     }
-    {   // text encoder: the embedding table; bias_ih + bias_hh folded into the input projection's epilogue
+    if (!ctc) {   // text encoder: the embedding table; bias_ih + bias_hh folded into the input projection's epilogue
         const auto *e = get(m, "embeds.weight", (size_t)c.emb_rows * c.emb_dim);
         if (!e) return MDD_ERR_STATE;
         if ((rc = upload(w, *e, &w.emb))) return rc;
@@ -158,7 +207,24 @@ int build_weights(mdd_model *m, DecodeWeights &w) {
             if ((rc = launch_gemm_f32x6(planes, (size_t)V * E, tw.wih_3, (size_t)G2 * E, w.t_bias, w.text_table[1], V, G2, E, G2, nullptr))) return rc;
         }
     }
-    {
+    if (ctc) {   // the classifier on the last layer's 2H outputs (CRC/models/cnn_rnn.py:140-142): no score, no 4H operands
+        const int K = 2 * H;
+        const auto *wf = get(m, "fc.1.weight", (size_t)c.num_class * K);
+        if (!wf || !bn_fold(m, "fc.0", K, sc, sh)) return MDD_ERR_STATE;
+        if ((rc = upload(w, *wf, &w.w_fc)) || (rc = upload(w, sc, &w.fscale)) || (rc = upload(w, sh, &w.fshift))) return rc;
+        if (mfma_ctc_tail(c)) {   // consumer-order repack for ctc_tail_mfma_kernel, where launch_ctc_tail takes it (plan.h)
+            const int J = K / 16;
+            std::vector<float> pk((size_t)3 * J * 64 * 4, 0.f);
+            for (int nt = 0; nt < 3; nt++)
+                for (int j = 0; j < J; j++)
+                    for (int lane = 0; lane < 64; lane++)
+                        for (int mm = 0; mm < 4; mm++) {
+                            const int n = nt * 16 + (lane & 15), k = 16 * j + 4 * (lane >> 4) + mm;
+                            if (n < c.num_class) pk[(((size_t)nt * J + j) * 64 + lane) * 4 + mm] = (*wf)[(size_t)n * K + k];
+                        }
+            if ((rc = upload(w, pk, &w.w_fcp))) return rc;
+        }
+    } else {
         const auto *ws = get(m, "score.weight", (size_t)4 * H * H), *wf = get(m, "fc.1.weight", (size_t)c.num_class * 4 * H);
         if (!ws || !wf) return MDD_ERR_STATE;
         if (!bn_fold(m, "fc.0", 4 * H, sc, sh)) return MDD_ERR_STATE;

@@ -18,7 +18,9 @@ class HipModel(object):
         self.handle = C.c_void_p()
         cfg = _lib.MddConfig(feat=geom.feat, hidden=geom.hidden, layers=geom.layers, num_class=geom.num_class,
                              channels=geom.channels, emb_rows=geom.emb_rows, emb_dim=geom.emb_dim, bn_eps=1e-5)
-        _lib.check(_lib.lib().mdd_create(C.byref(cfg), device, C.byref(self.handle)))
+        # a CTC-only geometry (synth.Geometry(ctc_only=True): the reference's cnn-rnn-ctc model) gets the handle without a text side
+        create = _lib.lib().mdd_create_ctc if getattr(geom, "ctc_only", False) else _lib.lib().mdd_create
+        _lib.check(create(C.byref(cfg), device, C.byref(self.handle)))
         if precision is not None:      # 'f32x6' (fp32-grade on the bf16 matrix cores: the default), 'f32' (exact fp32 MFMA) or 'bf16x3' (flagged variant)
             _lib.check(_lib.lib().mdd_set_precision(self.handle, {'f32': 0, 'bf16x3': 1, 'f32x6': 2}[precision]))
         self.load_state_dict(state_dict)
@@ -51,45 +53,54 @@ class HipModel(object):
                 raise IndexError(_lib.lib().mdd_last_error().decode())
         return out
 
-    def forward(self, x, x1, out=None, sync_errors=False):
-        """x [B,T,F] f32 cuda, x1 [B,L] i64 cuda -> logp [T/2,B,C] (enqueued on the current stream)."""
-        assert x.is_cuda and x1.is_cuda and x.dtype == torch.float32 and x1.dtype == torch.int64
-        x, x1 = x.contiguous(), x1.contiguous()
-        B, T, _ = x.shape
-        return self._run(_lib.lib().mdd_forward, x, B, T, out, sync_errors,
-                         (C.c_void_p(x.data_ptr()), B, T, C.c_void_p(x1.data_ptr()), x1.shape[1]))
+    @staticmethod
+    def _ids(x1):
+        """(device pointer, L) of the canonical ids; x1 = None (a CTC-only handle ignores them) passes NULL, 0."""
+        if x1 is None:
+            return None, 0
+        assert x1.is_cuda and x1.dtype == torch.int64 and x1.is_contiguous()
+        return C.c_void_p(x1.data_ptr()), x1.shape[1]
 
-    def forward_fused(self, x, x1, frames, canon, out=None, sync_errors=False):
+    def forward(self, x, x1=None, out=None, sync_errors=False):
+        """x [B,T,F] f32 cuda, x1 [B,L] i64 cuda (None for a CTC-only model) -> logp [T/2,B,C] (enqueued on the current stream)."""
+        assert x.is_cuda and x.dtype == torch.float32
+        x, x1 = x.contiguous(), (None if x1 is None else x1.contiguous())
+        B, T, _ = x.shape
+        return self._run(_lib.lib().mdd_forward, x, B, T, out, sync_errors, (C.c_void_p(x.data_ptr()), B, T) + self._ids(x1))
+
+    def forward_fused(self, x, x1, frames, canon=None, out=None, sync_errors=False):
         """Several reference batches of different padded lengths in one launch sequence (mdd_forward_fused): x [B,T,F] with every
         batch zero-padded to the common T, x1 [B,L]; frames [B] int32 = T_g/2 and canon [B] int32 = L_g of each row's own batch.
-        Rows t < frames[b] of the result equal forward() on that batch alone, bit for bit."""
-        assert x.is_cuda and x1.is_cuda and x.dtype == torch.float32 and x1.dtype == torch.int64
-        assert frames.is_cuda and canon.is_cuda and frames.dtype == torch.int32 and canon.dtype == torch.int32
-        x, x1, frames, canon = x.contiguous(), x1.contiguous(), frames.contiguous(), canon.contiguous()
+        Rows t < frames[b] of the result equal forward() on that batch alone, bit for bit.  A CTC-only model takes x1 = canon = None."""
+        assert x.is_cuda and x.dtype == torch.float32 and frames.is_cuda and frames.dtype == torch.int32
+        assert canon is None or (canon.is_cuda and canon.dtype == torch.int32)
+        x, frames = x.contiguous(), frames.contiguous()
+        x1, canon = (None if x1 is None else x1.contiguous()), (None if canon is None else canon.contiguous())
         B, T, _ = x.shape
         return self._run(_lib.lib().mdd_forward_fused, x, B, T, out, sync_errors,
-                         (C.c_void_p(x.data_ptr()), B, T, C.c_void_p(x1.data_ptr()), x1.shape[1],
-                          C.c_void_p(frames.data_ptr()), C.c_void_p(canon.data_ptr())))
+                         (C.c_void_p(x.data_ptr()), B, T) + self._ids(x1) +
+                         (C.c_void_p(frames.data_ptr()), None if canon is None else C.c_void_p(canon.data_ptr())))
 
-    def forward_raw(self, raw, x1, out=None, sync_errors=False):
+    def forward_raw(self, raw, x1=None, out=None, sync_errors=False):
         """raw [B,T_raw,F/3] f32 cuda (unstacked frames), x1 [B,L] i64 cuda -> logp, exactly as
         forward(stack_features(raw), x1): the stack/skip of data_loader.py:138-142 is applied on the fly."""
-        assert raw.is_cuda and x1.is_cuda and raw.dtype == torch.float32 and x1.dtype == torch.int64
-        raw, x1 = raw.contiguous(), x1.contiguous()
+        assert raw.is_cuda and raw.dtype == torch.float32
+        raw, x1 = raw.contiguous(), (None if x1 is None else x1.contiguous())
         B, T_raw, D = raw.shape
         assert 3 * D == self.geom.feat
         return self._run(_lib.lib().mdd_forward_raw, raw, B, _lib.lib().mdd_stack_len(T_raw, 2, 2), out, sync_errors,
-                         (C.c_void_p(raw.data_ptr()), B, T_raw, C.c_void_p(x1.data_ptr()), x1.shape[1]))
+                         (C.c_void_p(raw.data_ptr()), B, T_raw) + self._ids(x1))
 
-    def profile(self, x, x1):
+    def profile(self, x, x1=None):
         """Per-stage (name, ms, launches, flops) of one forward replayed stage by stage between HIP events."""
         B, T, _ = x.shape
+        x1p, L = self._ids(x1)
         out = torch.empty((T // 2, B, self.geom.num_class), dtype=torch.float32, device=x.device)
         n = _lib.lib().mdd_forward_num_stages(self.handle)
         names = C.create_string_buffer(64 * n)
         ms, launches, flops = (C.c_float * n)(), (C.c_int32 * n)(), (C.c_double * n)()
-        _lib.check(_lib.lib().mdd_forward_profile(self.handle, C.c_void_p(x.data_ptr()), B, T, C.c_void_p(x1.data_ptr()),
-                                                  x1.shape[1], C.c_void_p(out.data_ptr()), _lib.current_stream_ptr(),
+        _lib.check(_lib.lib().mdd_forward_profile(self.handle, C.c_void_p(x.data_ptr()), B, T, x1p,
+                                                  L, C.c_void_p(out.data_ptr()), _lib.current_stream_ptr(),
                                                   names, 64 * n, ms, launches, flops, n))
         return list(zip(names.value.decode().split(","), list(ms), list(launches), list(flops)))
 

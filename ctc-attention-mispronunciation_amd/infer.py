@@ -64,14 +64,19 @@ def refuse(msg):
 
 
 def load_model(opts, precision=None):
-    """infer_init's checkpoint load (AA/infer.py:227-254) onto the MI355X path."""
+    """infer_init's checkpoint load (AA/infer.py:227-254) onto the MI355X path.  The class follows the checkpoint: a state_dict without
+    ``embeds.weight`` is the CTC-only baseline model (models.cnn_rnn), which recognises without the canonical phones; the rest of the
+    program is the same for both, the canonical phones then serving the diagnosis only."""
     import torch
     import torch.nn as nn  # noqa: F401  (a checkpoint pickles nn.LSTM / nn.ReLU by reference)
-    from .models.model_ctc import CTC_Model
     if precision is not None:          # read by mdd_create when the model's handle is made
         os.environ["MDD_PRECISION"] = precision
     path = os.path.join(opts.checkpoint_dir, opts.exp_name, "ctc_best_model.pkl")
     package = torch.load(path, map_location="cpu", weights_only=False)
+    if "embeds.weight" in package["state_dict"]:
+        from .models.model_ctc import CTC_Model
+    else:
+        from .models.cnn_rnn import CTC_Model
     model = CTC_Model(rnn_param=package["rnn_param"], add_cnn=package["add_cnn"], cnn_param=package["cnn_param"],
                       num_class=package["num_class"], drop_out=package["_drop_out"])
     model.load_state_dict(package["state_dict"])

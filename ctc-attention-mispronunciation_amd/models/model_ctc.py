@@ -68,6 +68,10 @@ class LayerCNN(nn.Module):
 
 
 class CTC_Model(nn.Module):
+    # models/cnn_rnn.py derives the reference's CTC-only baseline model (CRC/models/cnn_rnn.py) from this class by setting the flag: no
+    # embedding, text encoder or score; the classifier on the 2H outputs of the last BiLSTM; a handle of mdd_create_ctc
+    _ctc_only = False
+
     def __init__(self, add_cnn=False, cnn_param=None, rnn_param=None, num_class=39, drop_out=0.1):
         super(CTC_Model, self).__init__()
         self.add_cnn = add_cnn
@@ -97,14 +101,15 @@ class CTC_Model(nn.Module):
                                                   bidirectional=rnn_param["bidirectional"], dropout=drop_out,
                                                   batch_norm=rnn_param["batch_norm"])))
         self.rnns = nn.Sequential(OrderedDict(rnns))
-        self.embeds = nn.Embedding(44, 512)                                       # model_ctc.py:149
-        self.lstm_embeds = nn.LSTM(512, H, batch_first=True, bidirectional=True)  # :150
-        self.score = nn.Linear(H * 2, H * 2, bias=False)                          # :151
+        if not self._ctc_only:
+            self.embeds = nn.Embedding(44, 512)                                       # model_ctc.py:149
+            self.lstm_embeds = nn.LSTM(512, H, batch_first=True, bidirectional=True)  # :150
+            self.score = nn.Linear(H * 2, H * 2, bias=False)                          # :151
+        fc_in = self.num_directions * H * (1 if self._ctc_only else 2)   # cat(X, context), or X alone (cnn_rnn.py:140-142)
         if rnn_param["batch_norm"]:
-            self.fc = nn.Sequential(nn.BatchNorm1d(self.num_directions * H * 2),
-                                    nn.Linear(self.num_directions * H * 2, num_class, bias=False))
+            self.fc = nn.Sequential(nn.BatchNorm1d(fc_in), nn.Linear(fc_in, num_class, bias=False))
         else:
-            self.fc = nn.Linear(self.num_directions * H * 2, num_class, bias=False)
+            self.fc = nn.Linear(fc_in, num_class, bias=False)
         self.log_softmax = nn.LogSoftmax(dim=-1)
         self._handle = None
         self._dirty = True
@@ -126,8 +131,9 @@ class CTC_Model(nn.Module):
     def _config(self):
         return _lib.MddConfig(feat=self.rnn_param["rnn_input_size"], hidden=self.rnn_param["rnn_hidden_size"],
                               layers=self.rnn_param["rnn_layers"], num_class=self.num_class,
-                              channels=self.cnn_param["layer"][0][0][1], emb_rows=self.embeds.num_embeddings,
-                              emb_dim=self.embeds.embedding_dim, bn_eps=self.fc[0].eps)
+                              channels=self.cnn_param["layer"][0][0][1],
+                              emb_rows=0 if self._ctc_only else self.embeds.num_embeddings,
+                              emb_dim=0 if self._ctc_only else self.embeds.embedding_dim, bn_eps=self.fc[0].eps)
 
     def _sync_weights(self, device_index):
         L = _lib.lib()
@@ -135,7 +141,7 @@ class CTC_Model(nn.Module):
             self._check_supported()
             h = C.c_void_p()
             cfg = self._config()
-            _lib.check(L.mdd_create(C.byref(cfg), device_index, C.byref(h)))
+            _lib.check((L.mdd_create_ctc if self._ctc_only else L.mdd_create)(C.byref(cfg), device_index, C.byref(h)))
             self._handle = h
             self._dirty = True
         if not self._dirty:
@@ -190,6 +196,9 @@ class CTC_Model(nn.Module):
         if not self.add_cnn:
             print("error")          # model_ctc.py:224-225
             return None
+        if self.training and self._ctc_only:
+            raise NotImplementedError("CTC-only training is not built: the training step (mdd_train_*) covers the attention model; "
+                                      "call .eval() for the decode forward")
         _lib.require_gpu()
         if self.training:      # BatchNorm on batch statistics, Dropout(drop_out) behind each LayerCNN / BatchRNN; differentiable
             if visualize:
@@ -199,7 +208,7 @@ class CTC_Model(nn.Module):
         src_device = x.device
         dev = x.device if x.is_cuda else torch.device("cuda", torch.cuda.current_device())
         xd = x.to(dev, torch.float32).contiguous()
-        idd = x1.to(dev, torch.int64).contiguous()
+        idd = None if self._ctc_only else x1.to(dev, torch.int64).contiguous()   # (the CTC-only forward never reads x1: cnn_rnn.py:147)
         B, T, Fdim = xd.shape
         if Fdim != self.rnn_param["rnn_input_size"]:
             raise RuntimeError("expected feature size %d, got %d" % (self.rnn_param["rnn_input_size"], Fdim))
@@ -209,8 +218,8 @@ class CTC_Model(nn.Module):
                 _lib.check(_lib.lib().mdd_enable_taps(self._handle, 1))
             out = torch.empty((T // 2, B, self.num_class), dtype=torch.float32, device=dev)
             st = _lib.current_stream_ptr()
-            _lib.check(_lib.lib().mdd_forward(self._handle, C.c_void_p(xd.data_ptr()), B, T, C.c_void_p(idd.data_ptr()),
-                                              idd.shape[1], C.c_void_p(out.data_ptr()), st))
+            ids, L = (None, 0) if idd is None else (C.c_void_p(idd.data_ptr()), idd.shape[1])
+            _lib.check(_lib.lib().mdd_forward(self._handle, C.c_void_p(xd.data_ptr()), B, T, ids, L, C.c_void_p(out.data_ptr()), st))
             if self.strict_errors:
                 rc = _lib.lib().mdd_sync(self._handle, st)
                 if rc != 0:

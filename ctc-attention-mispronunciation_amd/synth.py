@@ -13,10 +13,14 @@ import numpy as np
 
 
 class Geometry(object):
-    """Shapes of one model instance (reference: AA/conf/ctc_config.0329.yaml:50-64)."""
+    """Shapes of one model instance (reference: AA/conf/ctc_config.0329.yaml:50-64).  ctc_only: the CTC-only baseline model
+    (CRC/models/cnn_rnn.py, CRC/conf/ctc_config.yaml: the same acoustic geometry) -- no embedding, so emb_rows = emb_dim = 0."""
 
     def __init__(self, feat=243, hidden=384, layers=4, num_class=45,
-                 channels=32, emb_rows=44, emb_dim=512):
+                 channels=32, emb_rows=44, emb_dim=512, ctc_only=False):
+        self.ctc_only = bool(ctc_only)
+        if self.ctc_only:
+            emb_rows = emb_dim = 0
         self.feat = feat            # stacked input width (81 * 3)
         self.hidden = hidden        # rnn_hidden_size
         self.layers = layers        # rnn_layers
@@ -67,7 +71,8 @@ def _bn(rng, sd, prefix, n):
 
 
 def synth_state_dict(geom, seed=1234, fc_gain=6.0, score_gain=1.0):
-    """Ordered dict key -> numpy array, keys/shapes as the reference state_dict."""
+    """Ordered dict key -> numpy array, keys/shapes as the reference state_dict.  A CTC-only geometry gets the keys of
+    CRC/models/cnn_rnn.py's CTC_Model: nothing of the attention branch is drawn, and fc.* is 2H wide (score_gain has no effect)."""
     rng = np.random.Generator(np.random.PCG64(seed))
     sd = OrderedDict()
     c, H = geom.channels, geom.hidden
@@ -86,6 +91,10 @@ def synth_state_dict(geom, seed=1234, fc_gain=6.0, score_gain=1.0):
         for sfx in ("", "_reverse"):
             sd["rnns.%d.rnn.weight_ih_l0%s" % (n, sfx)] = _uni(rng, (4 * H, isz), k)
             sd["rnns.%d.rnn.weight_hh_l0%s" % (n, sfx)] = _uni(rng, (4 * H, H), k)
+    if getattr(geom, "ctc_only", False):
+        _bn(rng, sd, "fc.0", 2 * H)
+        sd["fc.1.weight"] = _uni(rng, (geom.num_class, 2 * H), fc_gain / np.sqrt(2.0 * H))
+        return sd
     sd["embeds.weight"] = rng.standard_normal((geom.emb_rows, geom.emb_dim)).astype(np.float32)
     for sfx in ("", "_reverse"):
         sd["lstm_embeds.weight_ih_l0" + sfx] = _uni(rng, (4 * H, geom.emb_dim), k)
@@ -110,7 +119,7 @@ def synth_batch(geom, B, T, L, seed=1234, ragged=True):
     rng = np.random.Generator(np.random.PCG64(seed + 17))
     x = rng.standard_normal((B, T, geom.feat)).astype(np.float32)
     x1 = np.zeros((B, L), dtype=np.int64)
-    hi = min(geom.emb_rows, geom.num_class - 1)
+    hi = min(geom.emb_rows or geom.num_class - 1, geom.num_class - 1)   # (a CTC-only geometry has no embedding: canonical ids are class ids)
     frac = np.ones(B, dtype=np.float32)
     tlen = np.full(B, L, dtype=np.int64)
     for b in range(B):

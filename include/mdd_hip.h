@@ -6,6 +6,9 @@
  * layer: its seam is Python objects.  Each entry point below names the reference interface it
  * replaces; INTEGRATION.md shows the ctypes binding a maintainer of the reference would add.
  *
+ * The reference's CTC-only baseline recipe (egs/cnn-rnn-ctc = "CRC": the same acoustic model without the text encoder and the attention)
+ * runs through the same entry points on a handle of mdd_create_ctc; its eval-mode forward only.
+ *
  * Conventions
  *   - plain pointers and sizes only; no C++ or torch types cross the boundary
  *   - pointers named *_dev are device (HBM) addresses, everything else is host memory
@@ -69,10 +72,32 @@ int mdd_version(void);
 /* ---- model lifetime + weights: replaces CTC_Model(...) + load_state_dict (AA/infer.py:251-254) */
 int mdd_create(const mdd_config *cfg, int device, mdd_model **out);
 void mdd_destroy(mdd_model *m);
+/* ---- the CTC-only model: replaces CTC_Model(...) of CRC/models/cnn_rnn.py:70-145 + load_state_dict.  The handle runs the eval forward
+ * conv x 2 -> `layers` x BiLSTM -> BatchNorm1d(2H) + Linear(2H -> num_class, no bias) -> log-softmax (cnn_rnn.py:147-179) and is used
+ * through the same functions as an mdd_create handle.  Geometry (ctc_geometry_error, csrc/plan.h); any other returns MDD_ERR_ARG with
+ * mdd_last_error() naming the field:
+ *   feat, hidden, layers, num_class, channels as for mdd_config above (the same messages);  emb_rows = 0 and emb_dim = 0: the model has no
+ *   embedding.  The attention tail's room condition does not apply.
+ * Weights: the 12 + 4 layers + 4 (layers - 1) + 5 float entries of its state_dict (45 at 4 layers), fc.0.* [2H] and fc.1.weight [C, 2H].
+ *   mdd_load_weight checks each entry as it arrives and returns MDD_ERR_ARG naming the key for a key of the attention branch
+ *   (embeds.weight, lstm_embeds.*, score.weight), any other key the state_dict does not have, or a shape other than the geometry's;
+ *   mdd_finalize_weights returns MDD_ERR_STATE naming the first entry that never arrived.  No embedding, text table, score or 4H-wide
+ *   classifier operand is built.
+ * Forward: mdd_forward, mdd_forward_raw, mdd_forward_fused, mdd_forward_profile ignore x1_dev, L and canon_dev: the pointers may be NULL
+ *   and are never read, there is no id check and no limit on L, and no text-side buffer is allocated.  frames_dev of mdd_forward_fused
+ *   keeps its meaning (the reverse direction of every BiLSTM starts at the utterance's own batch length; rows t < frames_dev[b] are
+ *   bit-identical to mdd_forward on that batch alone).  The stage list is the acoustic stages of an mdd_create handle followed by
+ *   `ctc_tail` (csrc/ctc_tail.hip: fp32 in every mode; on the matrix cores where hidden is a multiple of 32 and num_class <= 48).
+ *   Modes 0, 1, 2, MDD_PRECISION and the fallbacks are those of mdd_set_precision below with emb_dim taking no part.
+ * Taps: "conv1" and "rnn<i>" as below; "text", "key" and "score" return NULL.
+ * The decoders, alignment, one-edit posteriors and the CTC loss take log-probs and do not care which handle made them.  There is no training
+ * step for this model (mdd_train_create builds the attention model only). */
+int mdd_create_ctc(const mdd_config *cfg, int device, mdd_model **out);
+int32_t mdd_is_ctc_only(mdd_model *m);   /* 1 for a handle of mdd_create_ctc, else 0 */
 /* Copy one state_dict entry (host fp32, contiguous, reference key name and shape) to the device.
  * `num_batches_tracked` entries are accepted and ignored. */
 int mdd_load_weight(mdd_model *m, const char *key, const float *data, const int64_t *shape, int32_t ndim);
-/* Check that all 55 float entries arrived, fold eval-mode BatchNorm into scale/shift vectors and
+/* Check that all 55 float entries arrived (mdd_create_ctc: 45), fold eval-mode BatchNorm into scale/shift vectors and
  * repack LSTM gate rows for the step kernel.  Synchronises the device. */
 int mdd_finalize_weights(mdd_model *m);
 
