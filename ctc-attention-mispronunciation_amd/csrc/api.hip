@@ -123,11 +123,12 @@ static std::vector<Stage> forward_stages(mdd_model *m, const ForwardCall &call) 
     const ForwardPlan p = m->plan;
     const float *x = call.x;
     const int B = call.B, T = call.T, L = call.L, Traw = call.Traw, Tp = T / 2, Lp = L;
+    const int Bt = call.K * B;   // rows of the text side: candidate set k's canonical of utterance b is text row k * B + b (K = 1: the utterances themselves)
     const int H = c.hidden, H2 = 2 * H, ch = c.channels, E = c.emb_dim, K0 = m->rnn_in(), nl = c.layers;
     const bool x3 = p.precision == 1, fused = p.conv != Conv::Separate;   // x3: the activations travel as split-bf16 planes
-    const size_t rows = (size_t)Tp * B, trows = (size_t)L * B;
+    const size_t rows = (size_t)Tp * B, trows = (size_t)L * Bt;
     const auto split = [x3](const DeviceBuf &b, size_t n) { return x3 ? split_view(b, n) : kNoSplit; };
-    const double step_flops = 2.0 * 2 * (double)B * H * 4 * H;   // one step of a BiLSTM layer
+    const double step_flops = 2.0 * 2 * (double)B * H * 4 * H, tstep_flops = step_flops * call.K;   // one step of a BiLSTM layer, of the text encoder
     std::vector<Stage> s;
 
     if (fused) {   // conv0 recomputed per output row (x1.5) + conv1 as implicit GEMM, one kernel
@@ -175,30 +176,33 @@ static std::vector<Stage> forward_stages(mdd_model *m, const ForwardCall &call) 
     const float *table = p.text_table ? w->text_table[p.proj == Gemm::F32x6] : nullptr;
     int *tidx = reinterpret_cast<int *>(m->tidx.p);
     s.push_back({"embed", 1, 0.0, [=](hipStream_t st) {
-        if (table) return launch_embed_index(c.emb_rows, call.x1, B, L, tidx, m->err_flag.p, st);
-        return launch_embed(w->emb, c.emb_rows, E, call.x1, B, L, x3 ? nullptr : m->embo.p, split(m->embo_s, trows * E), m->err_flag.p, st);
+        if (table) return launch_embed_index(c.emb_rows, call.x1, Bt, L, tidx, m->err_flag.p, st);
+        return launch_embed(w->emb, c.emb_rows, E, call.x1, Bt, L, x3 ? nullptr : m->embo.p, split(m->embo_s, trows * E), m->err_flag.p, st);
     }});
-    s.push_back({"gemm_text", 1, 2.0 * (double)L * B * 8 * H * E, [=](hipStream_t st) {
-        if (table) return launch_gather_rows(table, tidx, m->gx.p, L * B, 8 * H, st);
-        return project(m, ProjIn{m->embo.p, split(m->embo_s, trows * E), false}, L * B, E, *tw, w->t_bias, st);
+    s.push_back({"gemm_text", 1, 2.0 * (double)L * Bt * 8 * H * E, [=](hipStream_t st) {
+        if (table) return launch_gather_rows(table, tidx, m->gx.p, L * Bt, 8 * H, st);
+        return project(m, ProjIn{m->embo.p, split(m->embo_s, trows * E), false}, L * Bt, E, *tw, w->t_bias, st);
     }});
-    const LstmStepArgs ta = lstm_raw_out(L, B, call.llen, m->text.p, split(m->text_s, trows * H2));
-    s.push_back({"lstm_text", p.gated ? 1 : L, step_flops * L, [=](hipStream_t st) { return run_lstm(m, *tw, ta, st); }});
-    s.push_back({"gemm_key", 1, 2.0 * (double)L * B * H2 * H2, [=](hipStream_t st) {
+    const LstmStepArgs ta = lstm_raw_out(L, Bt, call.llen, m->text.p, split(m->text_s, trows * H2));
+    s.push_back({"lstm_text", p.gated ? 1 : L, tstep_flops * L, [=](hipStream_t st) { return run_lstm(m, *tw, ta, st); }});
+    s.push_back({"gemm_key", 1, 2.0 * (double)L * Bt * H2 * H2, [=](hipStream_t st) {
         if (x3) {
             const SplitPtr ks = split_view(m->key_s, trows * H2);
-            return launch_gemm_bf16x3({.p = split_view(m->text_s, trows * H2), .ld = H2}, {.p = w->w_score_s, .ld = H2}, nullptr, &ks, H2, L * B, H2, H2, st);
+            return launch_gemm_bf16x3({.p = split_view(m->text_s, trows * H2), .ld = H2}, {.p = w->w_score_s, .ld = H2}, nullptr, &ks, H2, L * Bt, H2, H2, st);
         }
-        return launch_gemm_nt({.p = m->text.p, .ld = H2}, {.p = w->w_score, .ld = H2}, m->key.p, H2, L * B, H2, H2, st);
+        return launch_gemm_nt({.p = m->text.p, .ld = H2}, {.p = w->w_score, .ld = H2}, m->key.p, H2, L * Bt, H2, H2, st);
     }});
-    s.push_back({"gemm_score", 1, 2.0 * (double)B * Tp * L * H2, [=](hipStream_t st) {   // scores S[b][t][l] = X[t,b,:] . key[l,b,:]   (:204)
-        const GemmOpts per_utt{.batch = B, .sC = (long)Tp * Lp};
-        if (x3) return launch_gemm_bf16x3({.p = split_view(m->x_s, rows * H2), .ld = B * H2, .stride = H2}, {.p = split_view(m->key_s, trows * H2), .ld = B * H2, .stride = H2},
-                                          m->S.p, nullptr, Lp, Tp, L, H2, st, per_utt);
-        return launch_gemm_nt({.p = m->xraw.p, .ld = B * H2, .stride = H2}, {.p = m->key.p, .ld = B * H2, .stride = H2}, m->S.p, Lp, Tp, L, H2, st, per_utt, m->sw.score_wide);
+    // scores S[j][t][l] = X[t, j % B, :] . key[l, j, :]   (:204): one product per text row; with candidates the X operand repeats with period B
+    const int xperiod = call.K > 1 ? B : 0;
+    s.push_back({"gemm_score", 1, 2.0 * (double)Bt * Tp * L * H2, [=](hipStream_t st) {
+        const GemmOpts per_row{.batch = Bt, .sC = (long)Tp * Lp};
+        if (x3) return launch_gemm_bf16x3({.p = split_view(m->x_s, rows * H2), .ld = B * H2, .stride = H2, .period = xperiod},
+                                          {.p = split_view(m->key_s, trows * H2), .ld = Bt * H2, .stride = H2}, m->S.p, nullptr, Lp, Tp, L, H2, st, per_row);
+        return launch_gemm_nt({.p = m->xraw.p, .ld = B * H2, .stride = H2, .period = xperiod}, {.p = m->key.p, .ld = Bt * H2, .stride = H2}, m->S.p, Lp, Tp, L, H2, st,
+                              per_row, m->sw.score_wide);
     }});
-    s.push_back({"attn_tail", 1, 2.0 * (double)B * Tp * ((double)L * H2 + 2.0 * H2 * c.num_class), [=](hipStream_t st) {
-        return launch_attn_tail(m->S.p, Lp, m->xraw.p, m->text.p, w->fscale, w->fshift, w->w_fc, w->w_fcp, call.logp, Tp, B, L, H2, c.num_class, st, call.llen);
+    s.push_back({"attn_tail", 1, 2.0 * (double)Bt * Tp * ((double)L * H2 + 2.0 * H2 * c.num_class), [=](hipStream_t st) {
+        return launch_attn_tail(m->S.p, Lp, m->xraw.p, m->text.p, w->fscale, w->fshift, w->w_fc, w->w_fcp, call.logp, Tp, Bt, L, H2, c.num_class, st, call.llen, B);
     }});
     return s;
 }
@@ -361,13 +365,17 @@ static int prepare(mdd_model *m, const ForwardCall &call) {
     if (!ctc && !call.x1) { set_error("mdd_forward: null pointer"); return MDD_ERR_ARG; }
     if (!m->finalized) { set_error("mdd_forward: call mdd_finalize_weights first"); return MDD_ERR_STATE; }
     if (B <= 0 || T < 2 || (!ctc && L <= 0)) { set_error("mdd_forward: bad shape B=%d T=%d L=%d", B, T, L); return MDD_ERR_ARG; }
+    if (call.K < 1 || (long long)call.K * B > (1 << 24)) { set_error("mdd_forward: bad candidate count K=%d (B=%d)", call.K, B); return MDD_ERR_ARG; }
     if (T % 2) { set_error("mdd_forward: T must be even (data_loader.py:140-142 pads to n_downsample)"); return MDD_ERR_ARG; }
     MDD_HIP_CHECK(hipSetDevice(m->device));
     std::lock_guard<std::mutex> prep_lock(g_prep_mu);
     const mdd_config &c = m->cfg;
-    const int H = c.hidden, Tp = T / 2, K0 = m->rnn_in(), Bpad = (B + 15) / 16 * 16;
-    const ForwardPlan p = plan_of(m, B);
-    const size_t rows = (size_t)Tp * B, trows = (size_t)L * B, mrows = rows > trows ? rows : trows;
+    // Candidates: the whole call runs under the plan of its K * B text rows, acoustic stages included.  Every condition plan_forward puts on the
+    // row count is an upper bound, so the B acoustic rows are valid under it, and they get the kernels they would get in the repeated batch.
+    const int Bt = call.K * B;
+    const int H = c.hidden, Tp = T / 2, K0 = m->rnn_in(), Bpad = (Bt + 15) / 16 * 16;
+    const ForwardPlan p = plan_of(m, Bt);
+    const size_t rows = (size_t)Tp * B, trows = (size_t)L * Bt, mrows = rows > trows ? rows : trows;
     const bool x3 = p.precision == 1, separate = p.conv == Conv::Separate;
     // f32x6: three bf16 planes of the largest projection operand = 1.5 x its fp32 size (in floats: 3/2)
     const size_t kmax = (size_t)(K0 > 2 * H ? K0 : 2 * H), emb = (size_t)c.emb_dim;
@@ -380,19 +388,19 @@ static int prepare(mdd_model *m, const ForwardCall &call) {
               grow(m->seq0, rows * K0) && grow(m->gx, mrows * 8 * H) && grow(m->act[0], rows * 2 * H) && grow(m->act[1], rows * 2 * H) &&
               grow(m->xraw, rows * 2 * H) && grow(m->hbuf, (size_t)4 * Bpad * H) && grow(m->cbuf, (size_t)2 * Bpad * H) &&
               (ctc || ((p.text_table ? grow(m->tidx, trows) : grow(m->embo, trows * emb)) && grow(m->text, trows * 2 * H) && grow(m->key, trows * 2 * H) &&
-                       grow(m->S, (size_t)B * Tp * L))) &&   // (a CTC-only handle has no text side)
+                       grow(m->S, (size_t)Bt * Tp * L))) &&   // (a CTC-only handle has no text side)
               (p.proj != Gemm::F32x6 || grow(m->p3, p3_floats)) &&
               (!p.hx_floats || grow(m->hx, p.hx_floats));   // the exchange buffer of the persistent layers + stamps
     if (ok && x3)
         ok = grow(m->seq0_s, rows * K0) && grow(m->act_s[0], rows * 2 * H) && grow(m->act_s[1], rows * 2 * H) && grow(m->x_s, rows * 2 * H) &&
-             (ctc || (grow(m->embo_s, trows * emb) && grow(m->text_s, trows * 2 * H) && grow(m->key_s, trows * 2 * H))) && grow(m->hsplit, (size_t)4 * B * H);
+             (ctc || (grow(m->embo_s, trows * emb) && grow(m->text_s, trows * 2 * H) && grow(m->key_s, trows * 2 * H))) && grow(m->hsplit, (size_t)4 * Bt * H);
     if (ok && m->taps) {
         m->tap_rnn.resize(c.layers);
         for (int n = 0; ok && n + 1 < c.layers; n++) ok = grow(m->tap_rnn[n], rows * 2 * H);
     }
     if (moved) m->graphs.clear();   // (the hipFree behind it synchronised the device, so no replay of an old graph is still running)
     if (rc) return rc;
-    m->lastB = B; m->lastT = T; m->lastL = L;
+    m->lastB = B; m->lastT = T; m->lastL = L; m->lastK = call.K;
     m->plan = p;
     return MDD_OK;
 }
@@ -445,6 +453,24 @@ extern "C" int mdd_forward_fused(mdd_model *m, const float *x_dev, int32_t B, in
     if (!m || !frames_dev || (!canon_dev && !m->ctc_only)) { set_error("mdd_forward_fused: null pointer"); return MDD_ERR_ARG; }
     ForwardCall call = plain_call(m, x_dev, B, T, x1_dev, L, logp_dev);
     call.tlen = frames_dev; call.llen = m->ctc_only ? nullptr : canon_dev;
+    return forward(m, call, (hipStream_t)stream);
+}
+
+// K canonical candidates per utterance on one acoustic pass (contract: include/mdd_hip.h).  The text stages run on K * B rows, the score GEMM and
+// the attention tail pair text row j with acoustic row j % B (forward_stages); everything that can be refused is refused here, by name.
+extern "C" int mdd_forward_candidates(mdd_model *m, const float *x_dev, int32_t B, int32_t T, const int64_t *x1_dev, int32_t K, int32_t L,
+                                      const int32_t *frames_dev, const int32_t *canon_dev, float *logp_dev, void *stream) {
+    const char *null_arg = !m ? "m" : !x_dev ? "x_dev" : !x1_dev ? "x1_dev" : !logp_dev ? "logp_dev" : nullptr;
+    if (null_arg) { set_error("mdd_forward_candidates: %s is NULL", null_arg); return MDD_ERR_ARG; }
+    if (m->ctc_only) { set_error("mdd_forward_candidates: a CTC-only handle has no canonical side (mdd_create_ctc); use mdd_forward"); return MDD_ERR_ARG; }
+    if (K < 1) { set_error("mdd_forward_candidates: K=%d, at least one candidate set is needed", K); return MDD_ERR_ARG; }
+    if (B < 1) { set_error("mdd_forward_candidates: B=%d must be at least 1", B); return MDD_ERR_ARG; }
+    if (T < 2 || T % 2) { set_error("mdd_forward_candidates: T=%d must be even and at least 2", T); return MDD_ERR_ARG; }
+    if (L < 1 || L > max_canonical_len(m->cfg)) {
+        set_error("mdd_forward_candidates: L=%d outside 1 .. %ld, the canonical length the attention tail holds", L, max_canonical_len(m->cfg)); return MDD_ERR_ARG;
+    }
+    ForwardCall call = plain_call(m, x_dev, B, T, x1_dev, L, logp_dev);
+    call.K = K; call.tlen = frames_dev; call.llen = canon_dev;
     return forward(m, call, (hipStream_t)stream);
 }
 
@@ -502,7 +528,7 @@ extern "C" int mdd_forward_profile(mdd_model *m, const float *x_dev, int32_t B, 
 
 extern "C" const float *mdd_tap(mdd_model *m, const char *name, int64_t *numel) {
     if (!m || !name || !m->lastB) return nullptr;
-    const int64_t B = m->lastB, rows = (int64_t)(m->lastT / 2) * B, trows = (int64_t)m->lastL * B, H2 = 2 * m->cfg.hidden;
+    const int64_t B = m->lastB, Bt = B * m->lastK, rows = (int64_t)(m->lastT / 2) * B, trows = (int64_t)m->lastL * Bt, H2 = 2 * m->cfg.hidden;
     const std::string n(name);
     const bool x3 = m->plan.precision == 1;
     float *p = nullptr;
@@ -511,7 +537,7 @@ extern "C" const float *mdd_tap(mdd_model *m, const char *name, int64_t *numel) 
     else if (m->ctc_only && (n == "text" || n == "key" || n == "score")) return nullptr;   // stages a CTC-only forward does not have
     else if (n == "text") { p = m->text.p; ne = trows * H2; }
     else if (n == "key") { p = m->key.p; ne = trows * H2; }
-    else if (n == "score") { p = m->S.p; ne = B * (m->lastT / 2) * m->lastL; }   // S[b][t][l]
+    else if (n == "score") { p = m->S.p; ne = Bt * (m->lastT / 2) * m->lastL; }   // S[b][t][l] (b over the text rows)
     else if (n == "lstm_dbg" && m->plan.gated) {   // diagnostic stamps of the last persistent layer launch (MDD_LSTM_DBG=1)
         p = m->hx.p + m->plan.stamps_at;
         ne = 256 * 6 * 2;

@@ -85,7 +85,7 @@ __global__ __launch_bounds__(256) void attn_tail_kernel(const float *__restrict_
                                                         const float *__restrict__ V, const float *__restrict__ fscale,
                                                         const float *__restrict__ fshift, const float *__restrict__ wfc,
                                                         float *__restrict__ logp, int Tp, int B, int Lmax, int H2, int C,
-                                                        const int *__restrict__ llen) {
+                                                        const int *__restrict__ llen, int Bx) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int L = llen ? min(max(llen[blockIdx.y], 1), Lmax) : Lmax;   // this utterance's own batch's canonical length (fused batches)
     float *attw = smem;                 // [TT][L]
@@ -93,6 +93,7 @@ __global__ __launch_bounds__(256) void attn_tail_kernel(const float *__restrict_
     float *lg = y + TT * 2 * H2;        // [TT][C]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int b = blockIdx.y, t0 = blockIdx.x * TT;
+    const int bx = b % Bx;              // the acoustic row of text row b (Bx == B: b itself)
     const int nt = min(TT, Tp - t0);
     const int D2 = 2 * H2;
 
@@ -123,7 +124,7 @@ __global__ __launch_bounds__(256) void attn_tail_kernel(const float *__restrict_
         const float sx = fscale[d], hx = fshift[d], sc = fscale[H2 + d], hc = fshift[H2 + d];
 #pragma unroll
         for (int r = 0; r < TT; r++) {
-            const float xv = r < nt ? X[((size_t)(t0 + r) * B + b) * H2 + d] : 0.f;
+            const float xv = r < nt ? X[((size_t)(t0 + r) * Bx + bx) * H2 + d] : 0.f;
             y[r * D2 + d] = xv * sx + hx;
             y[r * D2 + H2 + d] = acc[r] * sc + hc;
         }
@@ -156,7 +157,7 @@ __global__ __launch_bounds__(256) void attn_tail_kernel(const float *__restrict_
         for (int c = lane; c < C; c += 64) sum += expf(lg[r * C + c] - mx);
         for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
         const float lse = logf(sum);
-        float *orow = logp + ((size_t)(t0 + r) * B + b) * C;
+        float *orow = logp + (((size_t)(b / Bx) * Tp + t0 + r) * Bx + bx) * C;   // logp [B / Bx][Tp][Bx][C]
         for (int c = lane; c < C; c += 64) orow[c] = (lg[r * C + c] - mx) - lse;
     }
 }
@@ -177,7 +178,7 @@ __global__ __launch_bounds__(256, 2) void attn_tail_mfma_kernel(const float *__r
                                                              const float *__restrict__ V, const float *__restrict__ fscale,
                                                              const float *__restrict__ fshift, const float *__restrict__ wfcp,
                                                              float *__restrict__ logp, int Tp, int B, int Lmax, int H2, int C,
-                                                             const int *__restrict__ llen) {
+                                                             const int *__restrict__ llen, int Bx) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     // fused batches of different canonical lengths: this utterance attends over the l < llen[b] of its own batch (the same
     // arithmetic, in the same order, as a launch with L = llen[b]); the LDS tile is sized for Lmax
@@ -196,7 +197,7 @@ __global__ __launch_bounds__(256, 2) void attn_tail_mfma_kernel(const float *__r
     const float4 *wp = reinterpret_cast<const float4 *>(wfcp) + (size_t)wave * 3 * J * 64 + lane;
     const bool xhalf = wave < 2;         // this wave's K quarter [wave*D2/4, +D2/4) lies in the x half (H2 = 2 quarters)
     const int xrow = min(t0 + li, Tp - 1);
-    const float *xsrc = X + ((size_t)xrow * B + b) * H2 + wave * (D2 / 4) + 4 * kq;   // + 16 j
+    const float *xsrc = X + ((size_t)xrow * Bx + b % Bx) * H2 + wave * (D2 / 4) + 4 * kq;   // + 16 j; X has Bx rows per frame, text row b reads row b % Bx
     const float *scp = fscale + wave * (D2 / 4) + 4 * kq, *shp = fshift + wave * (D2 / 4) + 4 * kq;
 
     // 1. softmax over L (one wave per row); padded rows / columns are zero.  With L <= 64 (one element per lane) a wave's
@@ -349,18 +350,20 @@ __global__ __launch_bounds__(256, 2) void attn_tail_mfma_kernel(const float *__r
         float sum = lane < C ? expf(v - mx) : 0.f;
         for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
         const float lse = logf(sum);
-        if (lane < C) logp[((size_t)(t0 + r) * B + b) * C + lane] = (v - mx) - lse;
+        if (lane < C) logp[(((size_t)(b / Bx) * Tp + t0 + r) * Bx + b % Bx) * C + lane] = (v - mx) - lse;   // logp [B / Bx][Tp][Bx][C]
     }
 }
 
 int launch_attn_tail(const float *S, int Lp, const float *X, const float *V, const float *fscale, const float *fshift,
-                     const float *wfc, const float *wfcp, float *logp, int Tp, int B, int L, int H2, int C, hipStream_t st, const int *llen) {
+                     const float *wfc, const float *wfcp, float *logp, int Tp, int B, int L, int H2, int C, hipStream_t st, const int *llen, int Bx) {
+    if (Bx == 0) Bx = B;
+    if (Bx < 0 || B <= 0 || B % Bx) { set_error("attn_tail: B=%d text rows over Bx=%d acoustic rows (B a positive multiple of Bx)", B, Bx); return MDD_ERR_ARG; }
     if (wfcp && (2 * H2) % 256 == 0 && C <= 48) {
         const int LA = (L + 3) & ~3;
         size_t smem = sizeof(float) * ((size_t)16 * LA + (size_t)16 * (H2 + 4) + 4 * 16 * 48);
         if (smem > 160 * 1024) { set_error("attn_tail: L=%d too long for the LDS tile (%zu B)", L, smem); return MDD_ERR_ARG; }
         hipLaunchKernelGGL(attn_tail_mfma_kernel, dim3((Tp + 15) / 16, B), dim3(256), smem, st, S, Lp, X, V, fscale, fshift, wfcp,
-                           logp, Tp, B, L, H2, C, llen);
+                           logp, Tp, B, L, H2, C, llen, Bx);
         MDD_LAUNCH_CHECK();
         return MDD_OK;
     }
@@ -369,7 +372,7 @@ int launch_attn_tail(const float *S, int Lp, const float *X, const float *V, con
     if (smem > 160 * 1024) { set_error("attn_tail: L=%d too long for the LDS tile (%zu B)", L, smem); return MDD_ERR_ARG; }
     // y starts 16-byte aligned because TT*L*4 % 16 == 0 for TT = 16.
     dim3 grid((Tp + TT - 1) / TT, B), block(256);
-    hipLaunchKernelGGL(attn_tail_kernel, grid, block, smem, st, S, Lp, X, V, fscale, fshift, wfc, logp, Tp, B, L, H2, C, llen);
+    hipLaunchKernelGGL(attn_tail_kernel, grid, block, smem, st, S, Lp, X, V, fscale, fshift, wfc, logp, Tp, B, L, H2, C, llen, Bx);
     MDD_LAUNCH_CHECK();
     return MDD_OK;
 }

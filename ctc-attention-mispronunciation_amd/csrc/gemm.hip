@@ -68,7 +68,7 @@ template <bool ALIGNED, bool SEG, int BNT = BN>
 __global__ __launch_bounds__(256) void gemm_nt_f32_kernel(const float *__restrict__ A, const float *__restrict__ W,
                                                           const float *__restrict__ bias, float *__restrict__ C, int M,
                                                           int N, int K, int lda, int ldw, int ldc, long sA, long sW,
-                                                          long sC, int tiles_n) {
+                                                          long sC, int tiles_n, int pA, int pW) {
     constexpr int MT = BNT / 64, WR = 32 * MT;   // 32-row MFMA tiles per wave, rows per wave
     constexpr int WOFF = BM * LDS_LD;
     __shared__ float lds[2][(BM + BNT) * LDS_LD];  // [buffer][A rows | W rows][k]
@@ -81,7 +81,8 @@ __global__ __launch_bounds__(256) void gemm_nt_f32_kernel(const float *__restric
     int swz = (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + (bid >> 3);
     const int tm = swz / tiles_n, tn = swz % tiles_n;
     const int m0 = tm * BM, n0 = tn * BNT;
-    A += (size_t)blockIdx.z * sA; W += (size_t)blockIdx.z * sW; C += (size_t)blockIdx.z * sC;
+    // pA / pW (GemmOperand::period): product z reads matrix z % period of that operand
+    A += (size_t)(pA ? blockIdx.z % pA : blockIdx.z) * sA; W += (size_t)(pW ? blockIdx.z % pW : blockIdx.z) * sW; C += (size_t)blockIdx.z * sC;
 
     f32x16 acc[MT][2], tot[MT][2];
 #pragma unroll
@@ -156,13 +157,14 @@ int launch_gemm_nt(const GemmOperand &A, const GemmOperand &W, float *C, int ldc
         set_error("gemm_nt: row-major operands, no accumulate, no split-K (launch_gemm_f32 runs those)"); return MDD_ERR_ARG;
     }
     if (M <= 0 || N <= 0 || K <= 0 || o.batch <= 0) { set_error("gemm: bad shape %d %d %d x%d", M, N, K, o.batch); return MDD_ERR_ARG; }
+    if (A.period < 0 || W.period < 0) { set_error("gemm_nt: negative operand period %d %d", A.period, W.period); return MDD_ERR_ARG; }
     const bool narrow = N <= 64 && !wide;
     int tiles_m = (M + BM - 1) / BM, tiles_n = narrow ? 1 : (N + BN - 1) / BN;
     dim3 grid(tiles_m * tiles_n, 1, o.batch), block(256);
     bool aligned = (A.ld % 4 == 0) && (W.ld % 4 == 0) && (A.stride % 4 == 0) && (W.stride % 4 == 0) &&
                    ((uintptr_t)A.p % 16 == 0) && ((uintptr_t)W.p % 16 == 0);
     const bool seg = N <= 1024 && K > 64;
-#define GO(AL_, SEG_, BNT_) hipLaunchKernelGGL((gemm_nt_f32_kernel<AL_, SEG_, BNT_>), grid, block, 0, st, A.p, W.p, o.bias, C, M, N, K, A.ld, W.ld, ldc, A.stride, W.stride, o.sC, tiles_n)
+#define GO(AL_, SEG_, BNT_) hipLaunchKernelGGL((gemm_nt_f32_kernel<AL_, SEG_, BNT_>), grid, block, 0, st, A.p, W.p, o.bias, C, M, N, K, A.ld, W.ld, ldc, A.stride, W.stride, o.sC, tiles_n, A.period, W.period)
     if (narrow) {
         if (aligned && seg) GO(true, true, 64); else if (aligned) GO(true, false, 64); else if (seg) GO(false, true, 64); else GO(false, false, 64);
     } else if (aligned && seg) GO(true, true, BN);
@@ -282,6 +284,7 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const float *__restrict__
 
 int launch_gemm_f32(const GemmOperand &A, const GemmOperand &B, float *C, int ldc, int M, int N, int K, hipStream_t st, const GemmOpts &o) {
     if (M <= 0 || N <= 0 || K <= 0 || o.batch <= 0) { set_error("gemm_f32: bad shape %d %d %d x%d", M, N, K, o.batch); return MDD_ERR_ARG; }
+    if (A.period || B.period) { set_error("gemm_f32: no operand period (launch_gemm_nt runs it)"); return MDD_ERR_ARG; }
     const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
     const int batch = o.ksplit > 0 ? (K + o.ksplit - 1) / o.ksplit : o.batch;     // split-K: that many partial products, C + z*sC each
     dim3 grid(tiles_m * tiles_n, 1, batch), block(256);

@@ -65,7 +65,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16x3_glds_kernel(const unsigned
                                                                    const unsigned short *__restrict__ Wh, const unsigned short *__restrict__ Wl,
                                                                    const float *__restrict__ bias, float *__restrict__ C,
                                                                    unsigned short *__restrict__ Ch, unsigned short *__restrict__ Cl, int M, int N,
-                                                                   int K, int lda, int ldw, int ldc, long sA, long sW, long sC, int tiles_n) {
+                                                                   int K, int lda, int ldw, int ldc, long sA, long sW, long sC, int tiles_n, int pA, int pW) {
     // v_mfma_f32_16x16x32_bf16, per wave 64x64 = 4x4 tiles.  Same shape and product order as the 256x256 kernel, so an
     // output element is accumulated identically whichever kernel the problem size selects (results do not depend on
     // how many utterances share the batch, bit for bit).
@@ -78,8 +78,10 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16x3_glds_kernel(const unsigned
     int swz = (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + (bid >> 3);
     const int tm = swz / tiles_n, tn = swz % tiles_n;
     const int m0 = tm * XBM, n0 = tn * XBN;
-    Ah += (size_t)blockIdx.z * sA; Al += (size_t)blockIdx.z * sA;
-    Wh += (size_t)blockIdx.z * sW; Wl += (size_t)blockIdx.z * sW;
+    // pA / pW (SplitOperand::period): product z reads matrix z % period of that operand
+    const size_t za = pA ? blockIdx.z % pA : blockIdx.z, zw = pW ? blockIdx.z % pW : blockIdx.z;
+    Ah += za * sA; Al += za * sA;
+    Wh += zw * sW; Wl += zw * sW;
 
     f32x4 acc[4][4];
 #pragma unroll
@@ -402,6 +404,7 @@ static bool x3_args_ok(const SplitOperand &A, const SplitOperand &W, int M, int 
 int launch_gemm_bf16x3_256(X3Form form, const SplitOperand &A, const SplitOperand &W, float *C, int ldc, int M, int N, int K, hipStream_t st,
                            const float *bias, long long *stamps) {
     if (!x3_args_ok(A, W, M, N, K, 1)) return MDD_ERR_ARG;
+    if (A.period || W.period) { set_error("gemm_bf16x3_256: one product, no operand period (launch_gemm_bf16x3 runs it)"); return MDD_ERR_ARG; }
     const int tn = (N + 255) / 256;
     const dim3 grid(((M + 255) / 256) * tn), block(512);
     const size_t smem = 2 * 4 * 256 * XROW;
@@ -418,16 +421,18 @@ int launch_gemm_bf16x3(const SplitOperand &A, const SplitOperand &W, float *C, c
                        const GemmOpts &o, bool tile128) {
     if (o.accumulate || o.ksplit) { set_error("gemm_bf16x3: no accumulate, no split-K (a batch of partial products stands in for it)"); return MDD_ERR_ARG; }
     if (!x3_args_ok(A, W, M, N, K, o.batch)) return MDD_ERR_ARG;
+    if (A.period < 0 || W.period < 0) { set_error("gemm_bf16x3: negative operand period %d %d", A.period, W.period); return MDD_ERR_ARG; }
     // large projection: 256x256 tiles, the 8-phase kernel (the single-barrier kernel it is screened against: mdd_diag_gemm_ph8)
-    if (!Csplit && o.batch == 1 && M >= 1024 && N >= 512 && !tile128) return launch_gemm_bf16x3_256(X3Form::Phase8, A, W, C, ldc, M, N, K, st, o.bias);
+    if (!Csplit && o.batch == 1 && M >= 1024 && N >= 512 && !tile128)   // (one product: matrix 0 of either operand whatever its period)
+        return launch_gemm_bf16x3_256(X3Form::Phase8, {.p = A.p, .ld = A.ld}, {.p = W.p, .ld = W.ld}, C, ldc, M, N, K, st, o.bias);
     const int tm = (M + XBM - 1) / XBM, tn = (N + XBN - 1) / XBN;   // 128x128 tiles (also batched / split output)
     dim3 grid(tm * tn, 1, o.batch), block(256);
     if (Csplit)
         hipLaunchKernelGGL(gemm_bf16x3_glds_kernel<1>, grid, block, 0, st, A.p.hi, A.p.lo, W.p.hi, W.p.lo, o.bias, (float *)nullptr, Csplit->hi, Csplit->lo,
-                           M, N, K, A.ld, W.ld, ldc, A.stride, W.stride, o.sC, tn);
+                           M, N, K, A.ld, W.ld, ldc, A.stride, W.stride, o.sC, tn, A.period, W.period);
     else
         hipLaunchKernelGGL(gemm_bf16x3_glds_kernel<0>, grid, block, 0, st, A.p.hi, A.p.lo, W.p.hi, W.p.lo, o.bias, C, (unsigned short *)nullptr,
-                           (unsigned short *)nullptr, M, N, K, A.ld, W.ld, ldc, A.stride, W.stride, o.sC, tn);
+                           (unsigned short *)nullptr, M, N, K, A.ld, W.ld, ldc, A.stride, W.stride, o.sC, tn, A.period, W.period);
     MDD_LAUNCH_CHECK();
     return MDD_OK;
 }
@@ -439,6 +444,7 @@ int launch_gemm_bf16x3(const SplitOperand &A, const SplitOperand &W, float *C, c
 int gemm_bf16x3_ops(const GemmOperand &A, const GemmOperand &B, const float *bias, float *C, int ldc, int M, int N, int K, int S, DeviceBuf &xs_a,
                     DeviceBuf &xs_b, DeviceBuf &part, hipStream_t st) {
     if (S < 1 || (S > 1 && (bias || ldc != N))) { set_error("gemm_bf16x3_ops: %d chunks need ldc == N and no bias", S); return MDD_ERR_ARG; }
+    if (A.period || B.period) { set_error("gemm_bf16x3_ops: one product, no operand period"); return MDD_ERR_ARG; }
     const int Kc = ((K + S - 1) / S + 31) / 32 * 32, Kp = S * Kc;
     if (int rc = xs_a.need((size_t)M * Kp)) return rc;
     if (int rc = xs_b.need((size_t)N * Kp)) return rc;

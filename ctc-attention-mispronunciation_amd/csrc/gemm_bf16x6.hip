@@ -287,6 +287,7 @@ bool x6_ops_ok(const GemmOperand &A, const GemmOperand &B, const float *C, int l
 }
 int gemm_f32x6_ops(const GemmOperand &A, const GemmOperand &B, const float *bias, float *C, int ldc, int M, int N, int K, int S, DeviceBuf &xs_a,
                    DeviceBuf &xs_b, DeviceBuf &part, hipStream_t st) {
+    if (A.period || B.period) { set_error("gemm_f32x6_ops: one product, no operand period"); return MDD_ERR_ARG; }
     if (M <= 0 || N <= 0 || K <= 0 || S < 1 || ldc < N || !x6_ops_ok(A, B, C, ldc) || (S > 1 && bias)) {
         set_error("gemm_f32x6_ops: M=%d N=%d K=%d S=%d lda=%d ldb=%d ldc=%d", M, N, K, S, A.ld, B.ld, ldc); return MDD_ERR_ARG;
     }

@@ -60,6 +60,8 @@ struct GemmOperand {
     const float *p; int ld;    // op[r,k] = k_major ? p[k * ld + r] : p[r * ld + k]
     bool k_major = false;      // the operand is stored [K, rows]
     long stride = 0;           // elements from one matrix of a batch to the next
+    int period = 0;            // > 0: matrix z of the batch is the operand's matrix z % period (several products share one), 0: matrix z.  Only
+                               // launch_gemm_nt and launch_gemm_bf16x3 run it; every other launcher refuses a non-zero value
 };
 struct GemmOpts {
     const float *bias = nullptr;   // [N], added to every row
@@ -70,14 +72,14 @@ struct GemmOpts {
 // General fp32 GEMM (training step): C[m,n] (+)= sum_k opA[m,k] opB[n,k] (see gemm.hip).
 int launch_gemm_f32(const GemmOperand &A, const GemmOperand &B, float *C, int ldc, int M, int N, int K, hipStream_t st, const GemmOpts &o = GemmOpts());
 // The decode path's C[M,N] = A[M,K] . W[N,K]^T (+ bias[N]); fp32 MFMA (v_mfma_f32_32x32x2_f32), batched over o.batch.  Row-major operands
-// only: k_major, accumulate and ksplit are refused.  N <= 64: a 128x64 tile unless `wide`.
+// only: k_major, accumulate and ksplit are refused.  N <= 64: a 128x64 tile unless `wide`.  An operand's period is honoured on both tiles.
 int launch_gemm_nt(const GemmOperand &A, const GemmOperand &W, float *C, int ldc, int M, int N, int K, hipStream_t st, const GemmOpts &o = GemmOpts(),
                    bool wide = false);
 
 // C = A . W^T on the bf16 matrix cores with split-bf16 operands (see gemm_bf16x3.hip).  Output fp32 C, or a split-bf16 tensor when
 // Csplit != nullptr.  K % 32 == 0, ld and stride % 8 == 0; accumulate and ksplit are refused.  tile128: the 128x128 kernel also on a large
-// projection (timing aid).
-struct SplitOperand { SplitPtr p; int ld; long stride = 0; };
+// projection (timing aid).  An operand's period is honoured (the 128x128 kernel, which is what every batched product runs).
+struct SplitOperand { SplitPtr p; int ld; long stride = 0; int period = 0; };   // period: as GemmOperand's
 int launch_gemm_bf16x3(const SplitOperand &A, const SplitOperand &W, float *C, const SplitPtr *Csplit, int ldc, int M, int N, int K, hipStream_t st,
                        const GemmOpts &o = GemmOpts(), bool tile128 = false);
 // One product through one of the 256x256-tile kernels: the 8-phase kernel (what launch_gemm_bf16x3 takes for a large projection), the
@@ -175,7 +177,9 @@ int launch_gather_rows(const float *table, const int *idx, float *out, int M, in
 // softmax over L of S[b][t][:], ctx = A.V, y = BN(cat(X, ctx)), logits = y.Wfc^T, log-softmax
 int launch_attn_tail(const float *S, int Lp, const float *X, const float *V, const float *fscale, const float *fshift,
                      const float *wfc, const float *wfcp, float *logp, int Tp, int B, int L, int H2, int C, hipStream_t st,
-                     const int *llen = nullptr);   // llen[b]: canonical length of b's own batch (softmax / context over l < llen[b]); null = L
+                     const int *llen = nullptr,    // llen[b]: canonical length of b's own batch (softmax / context over l < llen[b]); null = L
+                     int Bx = 0);                  // > 0: X holds Bx acoustic rows per frame, text row b reads X row b % Bx and writes
+                                                   // logp [B / Bx][Tp][Bx][C] (the K = B / Bx candidate sets of mdd_forward_candidates); 0: Bx = B
 
 // The CTC-only model's tail (ctc_tail.hip): logp[r, :] = log_softmax((X[r, :] * fscale + fshift) . Wfc^T) over R rows of K = 2H values; wfcp: Wfc in
 // the matrix-core form's lane order (DecodeWeights::w_fcp), null where the geometry runs the scalar form

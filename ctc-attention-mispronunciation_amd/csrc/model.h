@@ -12,14 +12,16 @@ namespace mdd {
 // graphs (every member initialised and no padding, so it compares bytewise).
 struct ForwardCall {
     const float *x = nullptr;          // [B, T, feat] stacked frames; [B, Traw, feat / 3] unstacked ones where Traw > 0
-    const int64_t *x1 = nullptr;       // [B, L] canonical ids
-    float *logp = nullptr;             // [T / 2, B, num_class]
-    const int *tlen = nullptr, *llen = nullptr;   // mdd_forward_fused: per-row posterior frames / canonical length of the row's own batch (null: T / 2, L)
+    const int64_t *x1 = nullptr;       // [K, B, L] canonical ids
+    float *logp = nullptr;             // [K, T / 2, B, num_class]
+    const int *tlen = nullptr, *llen = nullptr;   // mdd_forward_fused: per-row posterior frames [B] / canonical length [K * B] of the row's own batch (null: T / 2, L)
     int B = 0, T = 0, L = 0;
     int Traw = 0;                      // mdd_forward_raw: the stack / skip is still to be applied to x
+    int K = 1;                         // mdd_forward_candidates: candidate sets -- K * B text rows (j = k * B + b) attend over the B acoustic rows (j % B)
+    int reserved = 0;                  // (keeps the struct free of padding)
     bool operator<(const ForwardCall &o) const { return memcmp(this, &o, sizeof(ForwardCall)) < 0; }
 };
-static_assert(sizeof(ForwardCall) == 5 * sizeof(void *) + 4 * sizeof(int), "ForwardCall is compared bytewise: no padding");
+static_assert(sizeof(ForwardCall) == 5 * sizeof(void *) + 6 * sizeof(int), "ForwardCall is compared bytewise: no padding");
 
 // Move-only owner of a HIP event / graph / executable graph, in the style of DeviceArray.
 template <class T, hipError_t (*Destroy)(T)> struct HipOwned {
@@ -98,8 +100,8 @@ struct mdd_model {
     mdd::DeviceArray<int> err_flag;
     mdd::DeviceArray<unsigned int> sync_words;
     hipStream_t cap_stream = nullptr;  // graphs are captured here (the legacy default stream cannot capture)
-    int lastB = 0, lastT = 0, lastL = 0;
-    mdd::ForwardPlan plan{};    // the kernels of the last prepared forward (shape lastB / lastT / lastL)
+    int lastB = 0, lastT = 0, lastL = 0, lastK = 1;
+    mdd::ForwardPlan plan{};    // the kernels of the last prepared forward (shape lastB / lastT / lastL, lastK candidate sets)
     std::map<mdd::ForwardCall, mdd::GraphExec> graphs;
     ~mdd_model() { graphs.clear(); if (cap_stream) (void)hipStreamDestroy(cap_stream); }
     int W1() const { return mdd::conv_out(cfg.feat); }

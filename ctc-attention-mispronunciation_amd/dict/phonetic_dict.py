@@ -7,6 +7,8 @@ reference ships as ``dict/cmudict.dict`` -- behind the same method names:
 
 * ``load_cmudict`` / ``cmu_dict(word)``  (AA/dict/phonetic_dict.py:133-145, 443-454): the pronunciation stored under the
   lower-cased key, ARPAbet with stress digits, ``None`` for an unknown word;
+* ``cmu_dict_all(word)`` (no reference counterpart): every pronunciation of the word, the alternates ``word(2)``, ``word(3)``, ... included,
+  for ``infer --pronunciations``;
 * ``api_word_phones_cmu(word)``: here the dictionary answer (the reference returns the phonemizer's);
 * ``phones_for_model(cmu_phones)``: the transformation ``infer.py`` applies before the ids go to the model
   (AA/infer.py:543-548): stress digits dropped except on ER0 / AH0 (separate classes of the 41-phone set), lower-cased.
@@ -40,6 +42,20 @@ class Phonetic(object):
         if to_ipa:      # IPA rendering (stress-mark placement, AA/dict/phonetic_dict.py:367-400) is display code outside the path
             raise NotImplementedError("to_ipa=True: IPA display is not part of the offline lookup")
         return " ".join(phones)
+
+    def cmu_dict_all(self, word):
+        """Every pronunciation the dictionary lists for the word, in dictionary order: the entry under the key itself, then the alternates
+        the CMU dictionary files as ``key(2)``, ``key(3)``, ... (up to the first number it lacks).  ``[]`` for an unknown word."""
+        self.load_cmudict()
+        key = word.lower()
+        found = []
+        n = 1
+        while True:
+            phones = self.cmudict_plain.get(key if n == 1 else "%s(%d)" % (key, n), None)
+            if not phones:
+                return found
+            found.append(" ".join(phones))
+            n += 1
 
     def api_word_phones_cmu(self, word):
         return self.cmu_dict(word.strip())

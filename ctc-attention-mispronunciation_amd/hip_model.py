@@ -81,6 +81,25 @@ class HipModel(object):
                          (C.c_void_p(x.data_ptr()), B, T) + self._ids(x1) +
                          (C.c_void_p(frames.data_ptr()), None if canon is None else C.c_void_p(canon.data_ptr())))
 
+    def forward_candidates(self, x, x1, frames=None, canon=None, out=None, sync_errors=False):
+        """K canonical candidates per utterance on one acoustic pass (mdd_forward_candidates): x [B,T,F] f32 cuda, x1 [K,B,L] i64 cuda, candidate
+        set k being the B utterances with the canonicals x1[k]; frames [B] int32 = T_g/2 as in forward_fused (None: T/2), canon [K*B] (or [K,B])
+        int32 = the padded canonical length of each set (None: L).  Returns logp [K,T/2,B,C]: entry k is what forward_fused gives rows k*B .. of
+        x repeated K times, bit for bit, and what forward(x, x1[k][:, :L_k]) gives wherever B and K*B rows run the same kernels
+        (include/mdd_hip.h)."""
+        assert x.is_cuda and x.dtype == torch.float32
+        assert x1.is_cuda and x1.dtype == torch.int64 and x1.dim() == 3 and x1.shape[1] == x.shape[0]
+        assert frames is None or (frames.is_cuda and frames.dtype == torch.int32 and frames.numel() == x.shape[0])
+        assert canon is None or (canon.is_cuda and canon.dtype == torch.int32 and canon.numel() == x1.shape[0] * x1.shape[1])
+        x, x1 = x.contiguous(), x1.contiguous()
+        frames, canon = (None if frames is None else frames.contiguous()), (None if canon is None else canon.contiguous())
+        B, T, _ = x.shape
+        K, _, L = x1.shape
+        if out is None:
+            out = torch.empty((K, T // 2, B, self.geom.num_class), dtype=torch.float32, device=x.device)
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())   # noqa: E731
+        return self._run(_lib.lib().mdd_forward_candidates, x, B, T, out, sync_errors, (ptr(x), B, T, ptr(x1), K, L, ptr(frames), ptr(canon)))
+
     def forward_raw(self, raw, x1=None, out=None, sync_errors=False):
         """raw [B,T_raw,F/3] f32 cuda (unstacked frames), x1 [B,L] i64 cuda -> logp, exactly as
         forward(stack_features(raw), x1): the stack/skip of data_loader.py:138-142 is applied on the fly."""

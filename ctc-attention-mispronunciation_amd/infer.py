@@ -2,7 +2,7 @@
 (AA/infer.py:435-598, ``main``), run as
 
     python -m ctc_attention_mispronunciation_amd.infer --conf CONF --wav_transcript_path DIR [-p cmudict] [-f cmu]
-        [--cmvn PATH] [--cmudict PATH] [--precision f32x6|f32|bf16x3] [--decode_seq PATH] [--timestamps] [--posteriors]
+        [--cmvn PATH] [--cmudict PATH] [--precision f32x6|f32|bf16x3] [--decode_seq PATH] [--timestamps] [--posteriors] [--pronunciations]
 
 The conf YAML is read as ``infer_init`` reads it (AA/infer.py:211-261): the checkpoint
 ``checkpoint_dir/exp_name/ctc_best_model.pkl``, ``vocab_file``, ``decode_type``, ``beam_width``, ``lm_path``, ``lm_alpha``,
@@ -55,6 +55,10 @@ def parse_args(argv=None):
     ap.add_argument("--posteriors", action="store_true",
                     help="add a 'post   :' line to each block: per canonical phoneme the probability that it was pronounced and the most "
                          "probable alternative (its deletion or a substitute), from the CTC likelihood of every one-edit variant")
+    ap.add_argument("--pronunciations", action="store_true",
+                    help="score every pronunciation the CMU dictionary lists for the word (word, word(2), ...) on one acoustic pass, report the "
+                         "utterance against the one with the highest CTC log-likelihood (not length-normalised; ties go to the earlier entry) "
+                         "and add a 'pron   :' line with every pronunciation's log-likelihood")
     return ap.parse_args(argv)
 
 
@@ -84,9 +88,11 @@ def load_model(opts, precision=None):
     return model
 
 
-def collect(folder, phonetic):
+def collect(folder, phonetic, pronunciations=False):
     """(items, word_dict, transcripts, total seconds) over the N.wav / N.txt pairs of `folder`, sorted by N as a string.
-    Each item is (utt, samples, phones, sample rate); lengths and seconds are counted at 16 kHz."""
+    Each item is (utt, samples, phones, sample rate); lengths and seconds are counted at 16 kHz.  ``pronunciations``: the item gets a fifth
+    entry, the model phones of every pronunciation ``phonetic.cmu_dict_all`` lists for the word (in dictionary order, the item's own first;
+    entries that give the same model phones as an earlier one are dropped), and word_dict[utt]['cmu_all'] their dictionary strings."""
     from .utils.fbank import read_wav, resample_len, quantize_pcm16, SAMPLE_RATE
     items, word_dict, transcripts, total = [], {}, {}, 0.0
     names = sorted(p for p in os.listdir(folder) if os.path.isfile(os.path.join(folder, p)) and p.endswith(".wav"))
@@ -120,6 +126,14 @@ def collect(folder, phonetic):
             continue
         items.append((utt, samples, phonetic.phones_for_model(cmu), rate))
         word_dict[utt] = {"ipa": cmu, "cmu_phns": cmu}
+        if pronunciations:
+            cmu_all, phones_all = [cmu], [items[-1][2]]
+            for alt in phonetic.cmu_dict_all(utterance.strip()):
+                if phonetic.phones_for_model(alt) not in phones_all:
+                    cmu_all.append(alt)
+                    phones_all.append(phonetic.phones_for_model(alt))
+            items[-1] += (phones_all,)
+            word_dict[utt]["cmu_all"] = cmu_all
         transcripts[utt] = utterance
         total += n16 / float(SAMPLE_RATE)
     return items, word_dict, transcripts, total
@@ -163,15 +177,17 @@ def main(argv=None):
         decoder = BeamDecoder(vocab.index2word, beam_width=opts.beam_width, blank_index=0, space_idx=-1, lm_path=opts.lm_path,
                               lm_alpha=opts.lm_alpha)
     t2 = time.time()
-    items, word_dict, transcripts, total_wav_time = collect(args.wav_transcript_path, phonetic)
+    if args.pronunciations and not hasattr(model, "embeds"):
+        refuse("--pronunciations: the CTC-only model's posteriors do not depend on the canonical phones; there is nothing to choose between")
+    items, word_dict, transcripts, total_wav_time = collect(args.wav_transcript_path, phonetic, args.pronunciations)
     cnt = len(items)
     t3 = time.time()
     cmvn = fbank.cmvn_scale_offset(fbank.read_cmvn_stats(args.cmvn))
     loader = WavBatchLoader(items, vocab, opts.batch_size, cmvn=cmvn, right_ctx=opts.right_ctx, n_skip_frame=opts.n_skip_frame,
-                            n_downsample=getattr(opts, "n_downsample", 2))
+                            n_downsample=getattr(opts, "n_downsample", 2), pronunciations=args.pronunciations)
     device = torch.device("cuda", torch.cuda.current_device())
     c1, c2, c3 = infer(phonetic, word_dict, loader, device, model, decoder, vocab, transcripts, False,
-                       decode_seq_path=args.decode_seq, timestamps=args.timestamps, posteriors=args.posteriors)
+                       decode_seq_path=args.decode_seq, timestamps=args.timestamps, posteriors=args.posteriors, pronunciations=args.pronunciations)
     print(c1, c2, c3)
     end = time.time()
     total = max(total_wav_time, 1e-9)

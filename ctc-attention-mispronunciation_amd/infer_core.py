@@ -216,8 +216,22 @@ def seconds_per_frame(test_loader, cnn_time_stride):
     return FRAME_SHIFT_SAMPLES / float(SAMPLE_RATE) * int(skip) * int(cnn_time_stride)
 
 
+def choose_pronunciation(loglik, count):
+    """Index of the highest of the first ``count`` log-likelihoods; ties go to the earlier dictionary entry."""
+    best = 0
+    for p in range(1, count):
+        if loglik[p] > loglik[best]:
+            best = p
+    return best
+
+
+def pronunciation_line(phones, loglik, chosen):
+    """The ``pron   :`` line of a block: every pronunciation with its CTC log-likelihood, the chosen one marked with '*'."""
+    return "pron   : " + " | ".join("%s%s [%.4f]" % ("*" if p == chosen else "", ph, ll) for p, (ph, ll) in enumerate(zip(phones, loglik)))
+
+
 def infer(phonetic, word_dict, test_loader, device, model, decoder, vocab, test_transcipt_dict, use_ipa, out=None,
-          decode_seq_path=None, timestamps=False, posteriors=False):
+          decode_seq_path=None, timestamps=False, posteriors=False, pronunciations=False):
     """AA/infer.py:282-372.  Per batch ``(inputs, input_sizes, _, _, trans, trans_sizes, utt_list)``: ``model(inputs, trans)``,
     frame counts ``(input_sizes * T').long()``, ``decoder.decode``, then per utterance the 'sil' strip, 'err' removal, ``wer``,
     alignment, fault lists and score (``diagnose``), printed as the reference's 13-line block to ``out`` (stdout by default).
@@ -234,9 +248,18 @@ def infer(phonetic, word_dict, test_loader, device, model, decoder, vocab, test_
 
     ``posteriors=True`` (no reference counterpart) adds one line, ``post   :`` (``diagnose_posterior`` / ``posterior_line``), before the
     closing empty line and after the ``timestamps`` lines if both are asked for: per canonical phoneme the probability that it was
-    pronounced and the most probable alternative, from one ``phoneme_posteriors`` call per batch.  Without it nothing changes."""
+    pronounced and the most probable alternative, from one ``phoneme_posteriors`` call per batch.  Without it nothing changes.
+
+    ``pronunciations=True`` (no reference counterpart) takes the loader's 8-tuples (``WavBatchLoader(pronunciations=True)``): the batch's K
+    candidate sets go through ``model.forward_candidates`` -- one acoustic pass, K conditioned posteriors -- and per utterance each distinct
+    pronunciation is scored by the CTC log-likelihood of its own ids under its own posteriors (``hip_model.ctc_variants``' base over the
+    utterance's frames; not length-normalised).  The highest wins, ties to the earlier dictionary entry, and the utterance's whole block --
+    dictionary line, decode, alignment, diagnosis, score and the ``time`` / ``gop`` / ``post`` lines -- is that candidate's; a
+    ``pron   :`` line (``pronunciation_line``) closes the block.  Without it nothing changes."""
     if posteriors:
         from .utils.ctcDecoder import phoneme_posteriors
+    if pronunciations:
+        from .hip_model import ctc_variants
     out = sys.stdout if out is None else out
     to_display = phonetic.cmu_to_ipa_wiki if use_ipa else None
     translate = getattr(phonetic, "api_word_translation", None)
@@ -245,31 +268,51 @@ def infer(phonetic, word_dict, test_loader, device, model, decoder, vocab, test_
     try:
         with torch.no_grad():
             for data in test_loader:
-                inputs, input_sizes, _, _, trans, trans_sizes, utt_list = data
+                inputs, input_sizes, _, _, trans, trans_sizes, utt_list = data[:7]
                 inputs = inputs.to(device)
-                trans = trans.to(device)
-                probs = model(inputs, trans)
-                lens = frames_from_fraction(input_sizes, probs.size(0))
-                if timestamps:
-                    from .utils.ctcDecoder import timed_spans
-                    frame_lens = lens.numpy().tolist()
-                    decoded, spans = decoder.decode_timed(probs, frame_lens)
-                    canon_spans = timed_spans(probs, frame_lens, trans, trans_sizes, decoder.blank_index)
-                    spf = seconds_per_frame(test_loader, inputs.size(1) // probs.size(0))
+                # one (posteriors, canonical ids, lengths) per candidate set; without --pronunciations the batch itself
+                if pronunciations:
+                    sets = [(t.to(device), s) for t, s in data[7]["sets"]]
+                    sets = [(p,) + ts for p, ts in zip(model.forward_candidates(inputs, [t for t, _ in sets]), sets)]
                 else:
-                    decoded = decoder.decode(probs, lens.numpy().tolist())
-                if posteriors:
-                    post = phoneme_posteriors(probs, lens.numpy().tolist(), trans, trans_sizes, decoder.blank_index)
-                trans, trans_sizes = trans.cpu().numpy(), trans_sizes.numpy()
-                for x in range(len(decoded)):
+                    trans = trans.to(device)
+                    sets = [(model(inputs, trans), trans, trans_sizes)]
+                lens = frames_from_fraction(input_sizes, sets[0][0].size(0))
+                frame_lens = lens.numpy().tolist()
+                per_set = []     # what the blocks need of each set
+                for probs, trans, trans_sizes in sets:
+                    r = {}
+                    if timestamps:
+                        from .utils.ctcDecoder import timed_spans
+                        r["decoded"], r["spans"] = decoder.decode_timed(probs, frame_lens)
+                        r["canon_spans"] = timed_spans(probs, frame_lens, trans, trans_sizes, decoder.blank_index)
+                        spf = seconds_per_frame(test_loader, inputs.size(1) // probs.size(0))
+                    else:
+                        r["decoded"] = decoder.decode(probs, frame_lens)
+                    if posteriors:
+                        r["post"] = phoneme_posteriors(probs, frame_lens, trans, trans_sizes, decoder.blank_index)
+                    if pronunciations:
+                        r["loglik"] = ctc_variants(probs, frame_lens, trans.to(torch.int32), trans_sizes.to(torch.int32), decoder.blank_index,
+                                                   want_ins=False).base.cpu().tolist()
+                    r["trans"], r["trans_sizes"] = trans.cpu().numpy(), trans_sizes.numpy()
+                    per_set.append(r)
+                for x in range(len(utt_list)):
+                    chosen = 0
+                    if pronunciations:
+                        count = data[7]["counts"][x]
+                        loglik = [per_set[p]["loglik"][x] for p in range(count)]
+                        chosen = choose_pronunciation(loglik, count)
+                    r = per_set[chosen]
+                    decoded, trans, trans_sizes = r["decoded"], r["trans"], r["trans_sizes"]
                     canonical = " ".join(vocab.index2word[num] for num in trans[x][:trans_sizes[x]])
                     utterance = test_transcipt_dict[utt_list[x]]
                     if timestamps:
-                        d = diagnose_timed(decoded[x], spans[x], canonical, canon_spans[x], decoder, spf, to_display)
+                        d = diagnose_timed(decoded[x], r["spans"][x], canonical, r["canon_spans"][x], decoder, spf, to_display)
                     else:
                         d = diagnose(decoded[x], canonical, decoder, to_display)
                     tmp1, tmp2, tmp3 = d["printed"]
-                    block = ["id     : " + utt_list[x], utt_list[x] + ": " + utterance, str(word_dict[utt_list[x]]["ipa"]),
+                    dict_line = word_dict[utt_list[x]]["cmu_all"][chosen] if pronunciations else word_dict[utt_list[x]]["ipa"]
+                    block = ["id     : " + utt_list[x], utt_list[x] + ": " + utterance, str(dict_line),
                              str(translate(utterance)) if translate is not None else "", tmp2, tmp3, tmp1,
                              "ins err: " + " ".join(d["insertions"]), "sub err: " + " ".join(d["substitutions"]),
                              "del err: " + " ".join(d["deletions"]),
@@ -278,9 +321,13 @@ def infer(phonetic, word_dict, test_loader, device, model, decoder, vocab, test_
                     if timestamps:
                         block[-1:-1] = timed_lines(d)
                     if posteriors:
+                        post = r["post"]
                         dp = diagnose_posterior(decoded[x], canonical, None if post[x] is None else post[x][0], decoder, vocab.index2word,
                                                 to_display)
                         block[-1:-1] = [posterior_line(dp)]
+                    if pronunciations:
+                        phones = [" ".join(vocab.index2word[num] for num in per_set[p]["trans"][x][:per_set[p]["trans_sizes"][x]]) for p in range(count)]
+                        block[-1:-1] = [pronunciation_line(phones, loglik, chosen)]
                     out.write("\n".join(block) + "\n")
                     total_correct_cnt += d["correct"]
                     total_cnt += d["correct"] + d["del_sub"]

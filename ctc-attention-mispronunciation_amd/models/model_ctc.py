@@ -232,6 +232,51 @@ class CTC_Model(nn.Module):
                 return res, [x, cnn.to(src_device), seq.to(src_device), res]
         return out if src_device == dev else out.to(src_device)
 
+    def forward_candidates(self, x, candidates):
+        """Several canonical candidates per utterance on one acoustic pass (no reference counterpart; mdd_forward_candidates).
+        x: [B, T, F] as ``forward`` takes it; candidates: a list of K LongTensors [B, L_k], host or device, each one a canonical batch as
+        ``forward``'s x1 (padded to its own longest, as the reference's collate pads a batch).  Returns a list of K tensors [T/2, B, num_class]
+        on x's device: entry k is what ``forward(x, candidates[k])`` returns -- bit for bit wherever B and K*B rows run the same kernels
+        (include/mdd_hip.h at mdd_forward_candidates: hidden 384 up to K*B = 1024, any geometry while K*B <= 128), within the parity tolerance
+        elsewhere.  The conv front end and the BiLSTM layers run once.  Eval mode only."""
+        if self._ctc_only:
+            raise NotImplementedError("forward_candidates: the CTC-only model has no canonical side -- its posteriors do not depend on the "
+                                      "canonical phones, so one forward serves every candidate")
+        if self.training:
+            raise NotImplementedError("forward_candidates is an eval-mode facility: call .eval() first")
+        if not self.add_cnn:
+            print("error")
+            return None
+        candidates = list(candidates)
+        if not candidates:
+            raise ValueError("forward_candidates: at least one candidate batch is needed")
+        _lib.require_gpu()
+        src_device = x.device
+        dev = x.device if x.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        xd = x.to(dev, torch.float32).contiguous()
+        B, T, Fdim = xd.shape
+        if Fdim != self.rnn_param["rnn_input_size"]:
+            raise RuntimeError("expected feature size %d, got %d" % (self.rnn_param["rnn_input_size"], Fdim))
+        K, L = len(candidates), max(int(c.shape[1]) for c in candidates)
+        ids = torch.zeros((K, B, L), dtype=torch.int64, device=dev)
+        for k, c in enumerate(candidates):
+            if c.dim() != 2 or c.shape[0] != B or c.shape[1] < 1:
+                raise ValueError("forward_candidates: candidate %d is %s, expected [%d, L >= 1]" % (k, tuple(c.shape), B))
+            ids[k, :, :c.shape[1]] = c.to(dev, torch.int64)
+        canon = torch.tensor([int(c.shape[1]) for c in candidates], dtype=torch.int32).repeat_interleave(B).to(dev)
+        with torch.cuda.device(dev):
+            self._sync_weights(dev.index if dev.index is not None else torch.cuda.current_device())
+            if getattr(self, "_taps", False):
+                _lib.check(_lib.lib().mdd_enable_taps(self._handle, 1))
+            out = torch.empty((K, T // 2, B, self.num_class), dtype=torch.float32, device=dev)
+            st = _lib.current_stream_ptr()
+            _lib.check(_lib.lib().mdd_forward_candidates(self._handle, C.c_void_p(xd.data_ptr()), B, T, C.c_void_p(ids.data_ptr()), K, L, None,
+                                                         C.c_void_p(canon.data_ptr()), C.c_void_p(out.data_ptr()), st))
+            if self.strict_errors:
+                if _lib.lib().mdd_sync(self._handle, st) != 0:
+                    raise IndexError(_lib.lib().mdd_last_error().decode())
+        return [out[k] if src_device == dev else out[k].to(src_device) for k in range(K)]
+
     def compute_wer(self, index, input_sizes, targets, target_sizes):
         """Greedy collapse + edit distance on host index arrays (model_ctc.py:227-244)."""
         errs = toks = 0

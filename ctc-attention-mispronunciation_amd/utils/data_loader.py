@@ -149,21 +149,45 @@ class WavBatchLoader(object):
     (inputs, input_sizes, labels, label_sizes, trans, trans_sizes, utt_list): ``inputs`` / ``input_sizes`` come from
     ``fbank.fbank_batch`` (one kernel launch, the features never pass through the host; a batch that holds any rate other than
     16 kHz is first resampled to 16 kHz PCM16 by ``fbank.resample_batch``, AA/infer.py:498-501, and its samples stay on the
-    device); trans ids are looked up as SpeechDataset does (unknown -> 'UNK') and padded as create_input pads them; the label pair repeats them (infer.py reads its canonical file as the labels too, :273-276)."""
+    device); trans ids are looked up as SpeechDataset does (unknown -> 'UNK') and padded as create_input pads them; the label pair repeats them (infer.py reads its canonical file as the labels too, :273-276).
 
-    def __init__(self, items, vocab, batch_size, cmvn=None, right_ctx=2, n_skip_frame=2, n_downsample=2):
+    ``pronunciations=True`` (no reference counterpart): an item may carry a fifth entry, the list of all pronunciations of its word (phone
+    strings; the first is the item's own), and every batch becomes an 8-tuple whose last entry is ``candidate_sets``' result for it: the
+    batch's K = (largest count in the batch) candidate sets for ``CTC_Model.forward_candidates`` and each utterance's count."""
+
+    def __init__(self, items, vocab, batch_size, cmvn=None, right_ctx=2, n_skip_frame=2, n_downsample=2, pronunciations=False):
         self.items = list(items)
         self.vocab = vocab
         self.batch_size = int(batch_size)
         self.cmvn = cmvn
         self.right_ctx, self.n_skip_frame, self.n_downsample = right_ctx, n_skip_frame, n_downsample
+        self.pronunciations = bool(pronunciations)
 
     def __len__(self):
         return (len(self.items) + self.batch_size - 1) // self.batch_size
 
+    def _collate_ids(self, phones):
+        """(trans, trans_sizes) of one batch of phone strings, padded to its own longest as create_input pads them."""
+        unk = self.vocab.word2index["UNK"]
+        ids = [[self.vocab.word2index.get(c, unk) for c in p.split()] for p in phones]
+        l_max = max(len(t) for t in ids)
+        trans = torch.zeros(len(ids), l_max)
+        trans_sizes = torch.zeros(len(ids))
+        for i, t in enumerate(ids):
+            trans[i, :len(t)] = torch.tensor(t, dtype=torch.float32)
+            trans_sizes[i] = len(t)
+        return trans.long(), trans_sizes.long()
+
+    def candidate_sets(self, chunk):
+        """The candidate sets of one batch of items: ``{"sets": [(trans_k, trans_sizes_k)] * K, "counts": [n_i]}``.  K is the largest number
+        of pronunciations an item of the batch carries; set k holds each word's k-th pronunciation, or its first where it has fewer, and is
+        padded to its own longest as the reference's collate would pad that batch.  Set 0 is the batch's ordinary ``trans``."""
+        prons = [list(it[4]) if len(it) > 4 and it[4] else [it[2]] for it in chunk]
+        K = max(len(p) for p in prons)
+        return {"sets": [self._collate_ids([p[k] if k < len(p) else p[0] for p in prons]) for k in range(K)], "counts": [len(p) for p in prons]}
+
     def __iter__(self):
         from .fbank import SAMPLE_RATE, fbank_batch, resample_batch
-        unk = self.vocab.word2index["UNK"]
         for start in range(0, len(self.items), self.batch_size):
             chunk = self.items[start:start + self.batch_size]
             rates = [int(it[3]) if len(it) > 3 else SAMPLE_RATE for it in chunk]
@@ -174,12 +198,6 @@ class WavBatchLoader(object):
                 wav, offsets = resample_batch([it[1] for it in chunk], rates)
                 inputs, input_sizes = fbank_batch(wav, cmvn=self.cmvn, right_ctx=self.right_ctx, n_skip_frame=self.n_skip_frame,
                                                   n_downsample=self.n_downsample, offsets=offsets)
-            ids = [[self.vocab.word2index.get(c, unk) for c in it[2].split()] for it in chunk]
-            l_max = max(len(t) for t in ids)
-            trans = torch.zeros(len(chunk), l_max)
-            trans_sizes = torch.zeros(len(chunk))
-            for i, t in enumerate(ids):
-                trans[i, :len(t)] = torch.tensor(t, dtype=torch.float32)
-                trans_sizes[i] = len(t)
-            trans, trans_sizes = trans.long(), trans_sizes.long()
-            yield inputs, input_sizes, trans.clone(), trans_sizes.clone(), trans, trans_sizes, [it[0] for it in chunk]
+            trans, trans_sizes = self._collate_ids([it[2] for it in chunk])
+            batch = (inputs, input_sizes, trans.clone(), trans_sizes.clone(), trans, trans_sizes, [it[0] for it in chunk])
+            yield batch + (self.candidate_sets(chunk),) if self.pronunciations else batch

@@ -158,6 +158,32 @@ int mdd_forward(mdd_model *m, const float *x_dev, int32_t B, int32_t T, const in
  * bit-identical to mdd_forward on its batch alone; rows beyond are undefined. */
 int mdd_forward_fused(mdd_model *m, const float *x_dev, int32_t B, int32_t T, const int64_t *x1_dev, int32_t L,
                       const int32_t *frames_dev, const int32_t *canon_dev, float *logp_dev, void *stream);
+/* ---- A2-A7 for K canonical candidates per utterance on ONE acoustic pass (no reference counterpart: the reference would run K forwards).
+ * The posteriors are conditioned on the canonical sequence, so scoring an utterance against several pronunciations of its word, several
+ * target words or a teacher's variant needs one posterior tensor per candidate; the conv front end and the BiLSTM layers (28 of the 30 ms
+ * of a pass) do not depend on the canonical and run once.  x_dev [B,T,F]; x1_dev [K,B,L] int64: candidate set k is one reference batch,
+ * the B utterances of x_dev with the canonicals x1_dev[k], 0-padded to the common L; logp_dev [K,T/2,B,C].
+ *   frames_dev [B] or NULL     frames_dev[b] = T_g / 2 of utterance b's batch, exactly as in mdd_forward_fused; NULL: T / 2 for all
+ *   canon_dev [K*B] or NULL    canon_dev[k*B + b] = the padded canonical length L_k of candidate set k, at least 1 and at most L (the
+ *                              reference pads each batch to its own longest canonical and masks nothing); NULL: L for all.  A device
+ *                              array: a value outside 1 .. L is clamped into it, as mdd_forward_fused does
+ * Rows t < frames_dev[b] of logp_dev[k] are what mdd_forward_fused gives row k*B + b of the batch made by repeating x_dev K times, with
+ * the same frames (repeated) and canon: bit for bit, in every arithmetic mode.  Rows beyond are undefined.
+ * Kernel choice: the whole call, acoustic stages included, runs under ONE plan, plan_forward(..., K*B) (csrc/plan.h).  Every condition
+ * that plan puts on the row count is an upper bound, so the B acoustic rows are valid under it, and it is what makes the equality above
+ * hold for every geometry.  The consequence: logp_dev[k] equals mdd_forward(x_dev, x1_dev[k]) bit for bit wherever plan_forward gives B and
+ * K*B rows the same kernels -- hidden = 384 up to K*B = 1024 rows, and any geometry while K*B <= 128 or the mode in effect is not 2;
+ * elsewhere (mode 2 at hidden = 256 with B <= 128 < K*B: the f32x6 recurrence against the exact-fp32 one; B <= 1024 < K*B: a persistent
+ * layer kernel against the per-step one) the two agree within the parity tolerance, 1e-4 on the log-probs.
+ * The text stages (embedding / text projection, text encoder, keys) run on K*B rows j = k*B + b; the scores and the attention tail pair
+ * text row j with acoustic row j % B.  The limit on L is mdd_forward's (max_canonical_len).  K*B > 1024 is legal and takes the per-step
+ * recurrences, as any such B does.
+ * MDD_ERR_ARG, with the argument named in mdd_last_error() and before anything is enqueued (logp_dev untouched, the handle usable): K < 1;
+ * m, x_dev, x1_dev or logp_dev NULL; a handle of mdd_create_ctc (no canonical side); B < 1; T odd or < 2; L < 1 or over the limit.  An id
+ * outside [0,emb_rows) is reported by the next mdd_sync(), as for mdd_forward. */
+int mdd_forward_candidates(mdd_model *m, const float *x_dev, int32_t B, int32_t T, const int64_t *x1_dev /* [K,B,L] */, int32_t K, int32_t L,
+                           const int32_t *frames_dev /* [B] or NULL */, const int32_t *canon_dev /* [K*B] or NULL */,
+                           float *logp_dev /* [K,T/2,B,C] */, void *stream);
 
 /* ---- A1 + A2..A7 in one call: raw_dev holds the unstacked frames [B, T_raw, feat/3] (make_context(.,0,2) + skip_feat(.,2)
  * + even padding are applied on the fly: AA/utils/tools.py:207-227, AA/utils/data_loader.py:138-142); logp_dev is
