@@ -19,7 +19,7 @@ EXPORTS = (
     "mdd_resample_len", "mdd_resample_filter", "mdd_resample_batch",
     "mdd_train_create", "mdd_train_destroy", "mdd_train_num_tensors", "mdd_train_tensor_info", "mdd_train_num_masks", "mdd_train_mask_bytes",
     "mdd_train_forward", "mdd_train_backward", "mdd_train_sync", "mdd_train_set_precision", "mdd_adam_step",
-    "mdd_diag_gemm_ph8", "mdd_diag_gates", "mdd_diag_gemm", "mdd_diag_gemm_ops", "mdd_diag_gemm_time", "mdd_diag_conv_time",
+    "mdd_diag_gemm_ph8", "mdd_diag_gates", "mdd_diag_gemm", "mdd_diag_gemm_ops", "mdd_diag_gemm_time", "mdd_diag_gemm_clock", "mdd_diag_conv_time",
 )
 
 

@@ -10,6 +10,15 @@
 
 namespace mdd {
 
+// The tile walk of an entry's f32x6 launches: MDD_GEMM_X6_RASTER as it stands at the call.  Unset: the default; a value that is neither rows
+// nor <rb>x<cb> is an error here (at create it would be the default, plan.h), so that no arm of a comparison runs under another's name.
+static int diag_raster(const char *entry, X6Raster *out) {
+    const char *e = getenv("MDD_GEMM_X6_RASTER");
+    *out = kX6DefaultRaster;
+    if (e && !x6_raster_parse(e, out)) { set_error("%s: MDD_GEMM_X6_RASTER=%s (rows, or <rb>x<cb> with rb * cb <= 32)", entry, e); return MDD_ERR_ARG; }
+    return MDD_OK;
+}
+
 // Pseudo-random fill: element i is value(hash(i, seed)).  The three formulas are the ones the figures under profiles/ were taken with.
 template <class T, class F> __global__ void diag_fill_kernel(T *p, size_t n, unsigned seed, F value) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
@@ -149,7 +158,8 @@ extern "C" int mdd_diag_gates(const float *x_dev, float *sig_dev, float *tanh_de
     return MDD_OK;
 }
 
-// One GEMM through a chosen arithmetic, fp32 operands and result on the device; synchronises.
+// One GEMM through a chosen arithmetic, fp32 operands and result on the device; synchronises.  The f32x6 launches of this entry and of the
+// two below take their tile walk from MDD_GEMM_X6_RASTER as it stands at the call (plan.h).
 //   mode 0: exact fp32 MFMA (gemm_nt_f32_kernel)   1: split-bf16 x3 (operands split here)   3: the f32x6 kernel (three planes, split here)
 extern "C" int mdd_diag_gemm(int mode, const float *A_dev, const float *W_dev, float *C_dev, int M, int N, int K, void *stream) {
     hipStream_t st = (hipStream_t)stream;
@@ -158,6 +168,8 @@ extern "C" int mdd_diag_gemm(int mode, const float *A_dev, const float *W_dev, f
     if (mode == 0) return launch_gemm_nt({.p = A_dev, .ld = K}, {.p = W_dev, .ld = K}, C_dev, N, M, N, K, st);
     const size_t na = (size_t)M * K, nw = (size_t)N * K;
     const int planes = mode == 1 ? 2 : 3;
+    X6Raster raster;
+    if (int rc = diag_raster("mdd_diag_gemm", &raster)) return rc;
     DeviceArray<unsigned short> pa, pw;     // freed on return, behind the synchronisation
     if (pa.need(planes * na) || pw.need(planes * nw)) { set_error("mdd_diag_gemm: out of memory"); return MDD_ERR_NOMEM; }
     int rc;
@@ -170,7 +182,7 @@ extern "C" int mdd_diag_gemm(int mode, const float *A_dev, const float *W_dev, f
         rc = init_once(attr, init_gemm_x6_attributes);
         if (!rc) rc = launch_split3(A_dev, M, K, K, pa.p, st);
         if (!rc) rc = launch_split3(W_dev, N, K, K, pw.p, st);
-        if (!rc) rc = launch_gemm_f32x6(pa.p, na, pw.p, nw, nullptr, C_dev, M, N, K, N, st, nullptr);
+        if (!rc) rc = launch_gemm_f32x6(pa.p, na, pw.p, nw, nullptr, C_dev, M, N, K, N, st, raster);
     }
     (void)hipStreamSynchronize(st);
     return rc;
@@ -184,10 +196,12 @@ extern "C" int mdd_diag_gemm_ops(int mode, int ta, int tb, const float *A_dev, i
     }
     if (mode != 0 && mode != 3) { set_error("mdd_diag_gemm_ops: mode %d (0 exact fp32, 3 f32x6)", mode); return MDD_ERR_ARG; }
     const GemmOperand A{A_dev, lda, ta != 0}, B{B_dev, ldb, tb != 0};
+    X6Raster raster;
+    if (int rc = diag_raster("mdd_diag_gemm_ops", &raster)) return rc;
     DeviceBuf xa, xb, part;     // freed on return, behind the synchronisation
     int rc;
     if (mode == 0) rc = launch_gemm_f32(A, B, C_dev, ldc, M, N, K, st);
-    else if (!(rc = init_gemm_x6_attributes())) rc = gemm_f32x6_ops(A, B, nullptr, C_dev, ldc, M, N, K, splits, xa, xb, part, st);
+    else if (!(rc = init_gemm_x6_attributes())) rc = gemm_f32x6_ops(A, B, nullptr, C_dev, ldc, M, N, K, splits, xa, xb, part, st, raster);
     if (hipStreamSynchronize(st) != hipSuccess && !rc) { set_error("mdd_diag_gemm_ops: the stream failed"); rc = MDD_ERR_HIP; }
     return rc;
 }
@@ -195,13 +209,24 @@ extern "C" int mdd_diag_gemm_ops(int mode, int ta, int tb, const float *A_dev, i
 // Timing aid: two warm and `reps` timed launches of one GEMM kernel (operands resident and pre-split; events on the null stream) -> mean ms.
 //   mode 0 exact fp32 MFMA, 1 split-bf16 x3, 3 f32x6
 // MDD_GEMM_STAMP (mode 3): one extra launch of the stamped instantiation; per-K-tile cycle means of the first 1024 workgroups are printed
-extern "C" int mdd_diag_gemm_time(int mode, int M, int N, int K, int reps, float *ms_out) {
-    if (M <= 0 || N <= 0 || K <= 0 || K % 32 || reps < 1 || !ms_out) { set_error("mdd_diag_gemm_time: bad arguments"); return MDD_ERR_ARG; }
-    if (mode != 0 && mode != 1 && mode != 3) { set_error("mdd_diag_gemm_time: mode %d", mode); return MDD_ERR_ARG; }
+// mhz_out (nullable, mode 3): the clock the chip held inside the kernel, from one launch of the stamped instantiation enqueued straight behind
+// the timed ones and ten more: the median over workgroups of shader-clock ticks / 100 MHz constant-clock ticks around the tile loop, x 100.
+// `reps` long enough (2 s) for the clock to have settled is the caller's business.
+static int gemm_time(const char *entry, int mode, int M, int N, int K, int reps, float *ms_out, float *mhz_out);
+extern "C" int mdd_diag_gemm_time(int mode, int M, int N, int K, int reps, float *ms_out) { return gemm_time("mdd_diag_gemm_time", mode, M, N, K, reps, ms_out, nullptr); }
+extern "C" int mdd_diag_gemm_clock(int M, int N, int K, int reps, float *ms_out, float *mhz_out) {
+    if (!mhz_out) { set_error("mdd_diag_gemm_clock: bad arguments"); return MDD_ERR_ARG; }
+    return gemm_time("mdd_diag_gemm_clock", 3, M, N, K, reps, ms_out, mhz_out);
+}
+static int gemm_time(const char *entry, int mode, int M, int N, int K, int reps, float *ms_out, float *mhz_out) {
+    if (M <= 0 || N <= 0 || K <= 0 || K % 32 || reps < 1 || !ms_out) { set_error("%s: bad arguments", entry); return MDD_ERR_ARG; }
+    if (mode != 0 && mode != 1 && mode != 3) { set_error("%s: mode %d", entry, mode); return MDD_ERR_ARG; }
+    X6Raster raster;
+    if (int rc = diag_raster(entry, &raster)) return rc;
     const size_t na = (size_t)M * K, nw = (size_t)N * K, nc = (size_t)M * N;
     DeviceBuf A, W, Cm;
     DeviceArray<unsigned short> pa, pw;
-    if (A.need(na) || W.need(nw) || Cm.need(nc) || pa.need(3 * na) || pw.need(3 * nw)) { set_error("mdd_diag_gemm_time: out of memory"); return MDD_ERR_NOMEM; }
+    if (A.need(na) || W.need(nw) || Cm.need(nc) || pa.need(3 * na) || pw.need(3 * nw)) { set_error("%s: out of memory", entry); return MDD_ERR_NOMEM; }
     if (int rc = fill(A.p, na, 1u, TwoScales())) return rc;
     if (int rc = fill(W.p, nw, 2u, TwoScales())) return rc;
     const SplitPtr a{pa.p, pa.p + na}, w{pw.p, pw.p + nw};
@@ -214,17 +239,34 @@ extern "C" int mdd_diag_gemm_time(int mode, int M, int N, int K, int reps, float
         if (int rc = launch_split3(A.p, M, K, K, pa.p, nullptr)) return rc;
         if (int rc = launch_split3(W.p, N, K, K, pw.p, nullptr)) return rc;
     }
-    const auto x6 = [&](long long *stamps) { return launch_gemm_f32x6(pa.p, na, pw.p, nw, nullptr, Cm.p, M, N, K, N, nullptr, stamps); };
+    const auto x6 = [&](long long *stamps) { return launch_gemm_f32x6(pa.p, na, pw.p, nw, nullptr, Cm.p, M, N, K, N, nullptr, raster, stamps); };
+    const size_t ns = X6_STAMP_WORDS;
+    DeviceArray<long long> sd;
+    if (mode == 3 && (mhz_out || getenv("MDD_GEMM_STAMP"))) {
+        if (int rc = sd.need(ns)) return rc;
+        MDD_HIP_CHECK(hipMemset(sd.p, 0, ns * 8));
+    }
     if (int rc = time_launches(2, reps, ms_out, [&] {
             if (mode == 0) return launch_gemm_nt({.p = A.p, .ld = K}, {.p = W.p, .ld = K}, Cm.p, N, M, N, K, nullptr);
             if (mode == 1) return launch_gemm_bf16x3({.p = a, .ld = K}, {.p = w, .ld = K}, Cm.p, nullptr, N, M, N, K, nullptr);
             return x6(nullptr);
         })) return rc;
-    if (mode == 3 && getenv("MDD_GEMM_STAMP")) {
-        const size_t ns = (size_t)1024 * 4 * 4;
-        DeviceArray<long long> sd;
+    if (mode == 3 && mhz_out) {
+        for (int r = 0; r < 10; r++) if (int rc = x6(nullptr)) return rc;
+        if (int rc = x6(sd.p)) return rc;
         std::vector<long long> h(ns);
-        if (int rc = sd.need(ns)) return rc;
+        MDD_HIP_CHECK(hipMemcpy(h.data(), sd.p, ns * 8, hipMemcpyDeviceToHost));
+        std::vector<double> mhz;
+        for (size_t g = 0; g < (size_t)X6_STAMP_WGS; g++) {
+            const long long clk = h[X6_STAMP_PHASE_WORDS + g * 2], rt = h[X6_STAMP_PHASE_WORDS + g * 2 + 1];
+            if (clk > 0 && rt > 0) mhz.push_back((double)clk / (double)rt * 100.0);
+        }
+        if (mhz.empty()) { set_error("%s: no workgroup stamped", entry); return MDD_ERR_STATE; }
+        std::nth_element(mhz.begin(), mhz.begin() + mhz.size() / 2, mhz.end());
+        *mhz_out = (float)mhz[mhz.size() / 2];
+    }
+    if (mode == 3 && getenv("MDD_GEMM_STAMP")) {
+        std::vector<long long> h(ns);
         MDD_HIP_CHECK(hipMemset(sd.p, 0, ns * 8));
         if (int rc = x6(sd.p)) return rc;
         MDD_HIP_CHECK(hipMemcpy(h.data(), sd.p, ns * 8, hipMemcpyDeviceToHost));

@@ -51,41 +51,49 @@ __device__ __forceinline__ bf16x8 x6_frag(const unsigned char *plane, int row, i
 // elements each and the workgroups walk chunks x tiles VIRTUAL tiles.  In K-tile-major planes chunk s is a contiguous slab of every plane,
 // (s * K / 32) * rows * 32 elements in, so a virtual tile is an ordinary tile on shifted plane pointers; it writes its M x N partial
 // product (ldc == N) behind the s - 1 before it, and a reduction pass sums them (no atomics: the sum has one fixed order).  tiles_c: output
-// tiles per chunk, which arrives in the `ldc` argument (the row stride of a partial product is N); ntiles counts the virtual tiles; K is
-// the chunk's length.  The instantiation with SPLITK false is the decode path's kernel, instruction for instruction what it was without
-// this parameter: every SPLITK expression below folds to the kernel argument it replaces.
+// tiles per chunk, which arrives in the `ldc` argument (the row stride of a partial product is N); walk.ntiles counts the virtual tiles, which
+// are always taken in the row walk (the launcher builds it as chunks x tiles_c and sets walk.tiles_n to the output's column tiles); K is the
+// chunk's length.  The instantiation with SPLITK false is the decode path's kernel: every SPLITK expression below folds to the plain
+// argument (Ap, Wp, C, ldc), and tile_of to one call of x6_tile_of per round looked at.
 template <bool STAMP, bool SPLITK = false>
 __global__ __launch_bounds__(256, 1) void gemm_f32x6_kernel(const unsigned short *__restrict__ Ap, const unsigned short *__restrict__ Wp, size_t a_plane, size_t w_plane,
-                                                            const float *__restrict__ bias, float *__restrict__ C, int M, int N, int K, int ldc, int tiles_n,
-                                                            int ntiles, long long *stamps) {
+                                                            const float *__restrict__ bias, float *__restrict__ C, int M, int N, int K, int ldc, X6Walk walk,
+                                                            long long *stamps) {
     // STAMP (diagnostic instantiation): per wave, cycles of the K loop in the MFMA stream / waiting for memory / at the barrier
-    // -> stamps[(workgroup * 4 + wave) * 4 + {0, 1, 2}] (tools/gemm_time.py)
-    long long sacc[4] = {0, 0, 0, 0}, stt = 0;
+    // -> stamps[(workgroup * 4 + wave) * 4 + {0, 1, 2}]; per workgroup, the shader clock's and the 100 MHz constant clock's ticks around
+    // the tile loop -> stamps[X6_STAMP_PHASE_WORDS + workgroup * 2 + {0, 1}]: their quotient is the clock the chip held (tools/gemm_time.py)
+    long long sacc[4] = {0, 0, 0, 0}, stt = 0, clk0 = 0, rt0 = 0;
 #define X6_T(i_) do { if (STAMP) { const long long n_ = (long long)__builtin_readcyclecounter(); sacc[i_] += n_ - stt; stt = n_; } } while (0)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem6[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    // PERSISTENT: a workgroup walks the tiles vb = blockIdx.x, + gridDim.x, ... (one workgroup per CU: no dispatch between tiles, and the next
-    // tile's first operands are requested before this tile's epilogue).  Tile of a virtual block index: an XCD (vb % 8) walks consecutive
-    // tiles, so that the A panel stays in its L2.
-    const int tq = ntiles >> 3, trem = ntiles & 7;
+    // PERSISTENT: a workgroup takes one tile per round of `walk` (one workgroup per CU: no dispatch between tiles, and the next tile's first
+    // operands are requested before this tile's epilogue).  Which tile, gemm_raster.h says: by default the 32 workgroups of an XCD
+    // (blockIdx.x % 8) share a block of 4 row panels x 8 column tiles per round, so that what the XCD streams through its L2 in the round
+    // is 4 A panels and a third of W (in the row walk, MDD_GEMM_X6_RASTER=rows: two or three A panels and the whole of W, twice the bytes).
+    // A workgroup with no tile in a round sits it out.  tile_of runs once per tile, on scalars.
     const unsigned short *Ab_ = Ap, *Wb_ = Wp;   // SPLITK: this tile's chunk of the planes and its partial product
     float *Cb_ = C;
 #define X6_AB (SPLITK ? Ab_ : Ap)
 #define X6_WB (SPLITK ? Wb_ : Wp)
 #define X6_LDC (SPLITK ? N : ldc)
-    auto tile_of = [&](int vb, int &m0_, int &n0_) {
-        const int xcd = vb & 7;
-        const int vt = (xcd < trem ? xcd * (tq + 1) : trem * (tq + 1) + (xcd - trem) * tq) + (vb >> 3);
-        const int tiles_c = ldc, s = SPLITK ? vt / tiles_c : 0;
-        const int swz = SPLITK ? vt - s * tiles_c : vt;
+    const int tiles_n = walk.tiles_n;
+    if (SPLITK) walk.tiles_n = ldc;   // the virtual tiles, always in the row walk: "row" = chunk s, "column" = the chunk's tile
+    // the first round from r_ on in which this workgroup has a tile (walk.rounds: none), and that tile
+    auto tile_of = [&](int r_, int &m0_, int &n0_) {
+        int tm = 0, tn = 0;
+        while (r_ < walk.rounds && !x6_tile_of(walk, (int)blockIdx.x, r_, tm, tn)) r_++;
+        if (r_ >= walk.rounds) return r_;
         if (SPLITK) {
+            const int s = tm, swz = tn;
             Ab_ = Ap + (size_t)s * (K / X6_BK) * M * 32; Wb_ = Wp + (size_t)s * (K / X6_BK) * N * 32; Cb_ = C + (size_t)s * M * N;
+            tm = swz / tiles_n; tn = swz % tiles_n;
         }
-        const int tm = swz / tiles_n, tn = swz % tiles_n;
         m0_ = tm * X6_BM + wave * (16 * X6_RT); n0_ = tn * X6_BN;  // this wave's first row; the workgroup's first column
+        return r_;
     };
-    int vb = blockIdx.x, m0, n0;
-    tile_of(vb, m0, n0);
+    int m0 = 0, n0 = 0;
+    int rnd = tile_of(0, m0, n0);
+    if (rnd >= walk.rounds) return;   // (the whole workgroup: nothing below has been reached)
     f32x4 hh[X6_RT][8], sm[X6_RT][8], tot[X6_RT][8];
     const int l16 = lane & 15, kq = lane >> 4;
     // A fragments straight from the K-tile-major planes: lane (row l16 of row tile i, k-slice kq) reads 16 bytes at ((kt * M + row) * 32 + kq * 8)
@@ -173,6 +181,7 @@ __global__ __launch_bounds__(256, 1) void gemm_f32x6_kernel(const unsigned short
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // ... everybody's pieces; and every wave is done reading this stage
         X6_T(2);
     };
+    if (STAMP) { clk0 = (long long)__builtin_amdgcn_s_memtime(); rt0 = (long long)__builtin_amdgcn_s_memrealtime(); }
     for (;;) {   // ---- one tile per iteration
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_waitcnt(0x0F70);
@@ -199,11 +208,11 @@ __global__ __launch_bounds__(256, 1) void gemm_f32x6_kernel(const unsigned short
     }
     // the next tile's first W stage and A fragments are requested before this tile's epilogue (stage 0 and faA are free: every wave has passed
     // the last K-tile's barrier)
-    const int m0c = m0, n0c = n0, vbn = vb + (int)gridDim.x;
+    const int m0c = m0, n0c = n0;
     float *const Cc = SPLITK ? Cb_ : C;
-    const bool more = vbn < ntiles;
+    rnd = tile_of(rnd + 1, m0, n0);
+    const bool more = rnd < walk.rounds;
     if (more) {
-        tile_of(vbn, m0, n0);
         set_tile();
 #pragma unroll
         for (int idx = 0; idx < X6_NPW; idx++) piece(idx, 0, 0u);
@@ -226,11 +235,14 @@ __global__ __launch_bounds__(256, 1) void gemm_f32x6_kernel(const unsigned short
         }
     }
     if (!more) break;
-    vb = vbn;
     }   // ---- tiles
 #undef X6_MFMA
-    if (STAMP && stamps && lane == 0 && blockIdx.x < 1024)
+    if (STAMP && stamps && lane == 0 && blockIdx.x < X6_STAMP_WGS)
         for (int i = 0; i < 4; i++) stamps[((size_t)blockIdx.x * 4 + wave) * 4 + i] = sacc[i];
+    if (STAMP && stamps && tid == 0 && blockIdx.x < X6_STAMP_WGS) {
+        stamps[X6_STAMP_PHASE_WORDS + (size_t)blockIdx.x * 2] = (long long)__builtin_amdgcn_s_memtime() - clk0;
+        stamps[X6_STAMP_PHASE_WORDS + (size_t)blockIdx.x * 2 + 1] = (long long)__builtin_amdgcn_s_memrealtime() - rt0;
+    }
 #undef X6_T
 #undef X6_AB
 #undef X6_WB
@@ -246,15 +258,15 @@ int init_gemm_x6_attributes() {
 
 // A3, W3: three consecutive K-tile-major bf16 planes (hi | mid | lo; launch_split3) of a_plane = M x K / w_plane = N x K elements each
 int launch_gemm_f32x6(const unsigned short *A3, size_t a_plane, const unsigned short *W3, size_t w_plane, const float *bias, float *C, int M, int N, int K,
-                      int ldc, hipStream_t st, long long *stamps) {
+                      int ldc, hipStream_t st, X6Raster raster, long long *stamps) {
     if (M <= 0 || N <= 0 || K <= 0 || K % X6_BK || ldc % 4 || a_plane != (size_t)M * K || w_plane != (size_t)N * K) {
         set_error("gemm_f32x6: bad shape M=%d N=%d K=%d ldc=%d", M, N, K, ldc);
         return MDD_ERR_ARG;
     }
-    const int tn = (N + X6_BN - 1) / X6_BN, ntiles = ((M + X6_BM - 1) / X6_BM) * tn;
-    const dim3 grid(ntiles < 256 ? ntiles : 256);   // one persistent workgroup per CU
-    if (stamps) hipLaunchKernelGGL(gemm_f32x6_kernel<true>, grid, dim3(256), X6_NS * X6_STAGE, st, A3, W3, a_plane, w_plane, bias, C, M, N, K, ldc, tn, ntiles, stamps);
-    else hipLaunchKernelGGL(gemm_f32x6_kernel<false>, grid, dim3(256), X6_NS * X6_STAGE, st, A3, W3, a_plane, w_plane, bias, C, M, N, K, ldc, tn, ntiles, (long long *)nullptr);
+    const X6Walk walk = x6_choose_walk((M + X6_BM - 1) / X6_BM, (N + X6_BN - 1) / X6_BN, raster);   // the block walk, or the row walk where the rule falls back
+    const dim3 grid(walk.grid);   // one persistent workgroup per CU
+    if (stamps) hipLaunchKernelGGL(gemm_f32x6_kernel<true>, grid, dim3(256), X6_NS * X6_STAGE, st, A3, W3, a_plane, w_plane, bias, C, M, N, K, ldc, walk, stamps);
+    else hipLaunchKernelGGL(gemm_f32x6_kernel<false>, grid, dim3(256), X6_NS * X6_STAGE, st, A3, W3, a_plane, w_plane, bias, C, M, N, K, ldc, walk, (long long *)nullptr);
     MDD_LAUNCH_CHECK();
     return MDD_OK;
 }
@@ -270,9 +282,10 @@ int launch_gemm_f32x6_splitk(const unsigned short *A3, size_t a_plane, const uns
     }
     const int tn = (N + X6_BN - 1) / X6_BN, tiles_c = ((M + X6_BM - 1) / X6_BM) * tn;
     if ((long long)tiles_c * S > (1 << 24)) { set_error("gemm_f32x6_splitk: %d x %d tiles", S, tiles_c); return MDD_ERR_ARG; }
-    const int nvt = tiles_c * S;
-    hipLaunchKernelGGL((gemm_f32x6_kernel<false, true>), dim3(nvt < 256 ? nvt : 256), dim3(256), X6_NS * X6_STAGE, st, A3, W3, a_plane, w_plane, (const float *)nullptr, part, M, N, Kc,
-                       /* ldc carries */ tiles_c, tn, nvt, (long long *)nullptr);
+    X6Walk walk = x6_choose_walk(S, tiles_c, kX6Rows);   // S x tiles_c virtual tiles, always in the row walk: their order is the step's own
+    walk.tiles_n = tn;
+    hipLaunchKernelGGL((gemm_f32x6_kernel<false, true>), dim3(walk.grid), dim3(256), X6_NS * X6_STAGE, st, A3, W3, a_plane, w_plane, (const float *)nullptr, part, M, N, Kc,
+                       /* ldc carries */ tiles_c, walk, (long long *)nullptr);
     MDD_LAUNCH_CHECK();
     return MDD_OK;
 }
@@ -280,13 +293,13 @@ int launch_gemm_f32x6_splitk(const unsigned short *A3, size_t a_plane, const uns
 // C[M,N] (row stride ldc) = opA . opB^T (+ bias[N]) as f32x6, for the training step: opA[m,k] = ta ? A[k*lda + m] : A[m*lda + k], opB[n,k]
 // likewise.  Both operands are written as three K-tile-major planes into xs_a / xs_b (transposed on the way when stored [K, *]) with the
 // contraction zero-padded to S chunks of whole K-tiles.  S == 1: one launch of the decode path's kernel.  S > 1 (no bias): the split-K
-// launch into `part` and launch_reduce_parts (into C itself when ldc == N, as the step calls it; else into one more slot of `part`, copied
+// launch (always in the row walk; `raster` is the one-launch form's) into `part` and launch_reduce_parts (into C itself when ldc == N, as the step calls it; else into one more slot of `part`, copied
 // out row by row).  The caller has checked x6_ops_ok.
 bool x6_ops_ok(const GemmOperand &A, const GemmOperand &B, const float *C, int ldc) {
     return A.ld % 4 == 0 && B.ld % 4 == 0 && ldc % 4 == 0 && (uintptr_t)A.p % 16 == 0 && (uintptr_t)B.p % 16 == 0 && (uintptr_t)C % 16 == 0;
 }
 int gemm_f32x6_ops(const GemmOperand &A, const GemmOperand &B, const float *bias, float *C, int ldc, int M, int N, int K, int S, DeviceBuf &xs_a,
-                   DeviceBuf &xs_b, DeviceBuf &part, hipStream_t st) {
+                   DeviceBuf &xs_b, DeviceBuf &part, hipStream_t st, X6Raster raster) {
     if (A.period || B.period) { set_error("gemm_f32x6_ops: one product, no operand period"); return MDD_ERR_ARG; }
     if (M <= 0 || N <= 0 || K <= 0 || S < 1 || ldc < N || !x6_ops_ok(A, B, C, ldc) || (S > 1 && bias)) {
         set_error("gemm_f32x6_ops: M=%d N=%d K=%d S=%d lda=%d ldb=%d ldc=%d", M, N, K, S, A.ld, B.ld, ldc); return MDD_ERR_ARG;
@@ -300,7 +313,7 @@ int gemm_f32x6_ops(const GemmOperand &A, const GemmOperand &B, const float *bias
     unsigned short *a3 = reinterpret_cast<unsigned short *>(xs_a.p), *w3 = reinterpret_cast<unsigned short *>(xs_b.p);
     if (int rc = A.k_major ? launch_transpose_split3(A.p, K, M, A.ld, Kp, a3, pa, st) : launch_split3_pad(A.p, M, K, A.ld, Kp, a3, pa, st)) return rc;
     if (int rc = B.k_major ? launch_transpose_split3(B.p, K, N, B.ld, Kp, w3, pw, st) : launch_split3_pad(B.p, N, K, B.ld, Kp, w3, pw, st)) return rc;
-    if (S == 1) return launch_gemm_f32x6(a3, pa, w3, pw, bias, C, M, N, Kp, ldc, st, nullptr);
+    if (S == 1) return launch_gemm_f32x6(a3, pa, w3, pw, bias, C, M, N, Kp, ldc, st, raster);
     const size_t mn = (size_t)M * N;
     auto partials = [&](float *p) { return launch_gemm_f32x6_splitk(a3, pa, w3, pw, p, M, N, Kc, S, st); };
     if (ldc == N) return sum_parts(part, S, mn, C, st, partials);

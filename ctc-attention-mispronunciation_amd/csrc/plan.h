@@ -36,6 +36,9 @@
 //   MDD_SCORE_TILE=128   modes 0 and 2: the attention scores on the 128-column tile   create    tests/test_score_tile.py
 //                        of gemm_nt_f32_kernel where L <= 64, instead of the
 //                        64-column one
+//   MDD_GEMM_X6_RASTER   gemm_f32x6_kernel's tile walk (gemm_raster.h): rows is the    create    tests/test_gemm_raster.py, tools/gemm_time.py
+//                        row walk in every launch, <rb>x<cb> blocks of that shape     (the mdd_diag_gemm* entries read it per call
+//                        instead of the default's                                      and refuse any other value)
 //   MDD_TRAIN_PRECISION  training handle: bf16x3|1 starts it in the split-bf16        create    train.py
 //                        variant (mdd_train_set_precision changes it later)
 //   MDD_TRAIN_PRECISION  training handle: f32x6|2 starts it with the large            create    train.py, tests/test_train_f32x6.py
@@ -43,14 +46,16 @@
 //   MDD_TRAIN_CONV1_IM2COL  training handle: conv1 as im2col + GEMM in the forward    create    tests/test_forward_call.py
 //                        and the backward, instead of the direct kernels
 //
-// The training handle takes MDD_LSTM=step (per-step recurrence in its split-bf16 variant too), its own two switches and nothing else
-// of this table: its persistent layer launches carry no diagnostics.
+// The training handle takes MDD_LSTM=step (per-step recurrence in its split-bf16 variant too), MDD_GEMM_X6_RASTER (its one-launch f32x6
+// products; the split-K ones are always in the row walk), its own two switches and nothing else of this table: its persistent layer
+// launches carry no diagnostics.
 #pragma once
 #include <stddef.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include "../../include/mdd_hip.h"
+#include "gemm_raster.h"
 
 namespace mdd {
 
@@ -68,6 +73,7 @@ struct Switches {
     bool x6_out_fp32 = false;   // MDD_X6_OUT=fp32
     bool text_gemm = false;     // MDD_TEXT_PROJ=gemm
     bool score_wide = false;    // MDD_SCORE_TILE=128
+    X6Raster x6_raster = kX6DefaultRaster;   // MDD_GEMM_X6_RASTER
     int train_precision = 0;    // MDD_TRAIN_PRECISION
     bool train_conv1_im2col = false;   // MDD_TRAIN_CONV1_IM2COL
 };
@@ -95,6 +101,7 @@ inline Switches read_switches() {
     s.x6_out_fp32 = is(getenv("MDD_X6_OUT"), "fp32");
     s.text_gemm = is(getenv("MDD_TEXT_PROJ"), "gemm");
     s.score_wide = is(getenv("MDD_SCORE_TILE"), "128");
+    s.x6_raster = x6_raster_from_env(getenv("MDD_GEMM_X6_RASTER"));
     e = getenv("MDD_TRAIN_PRECISION");
     if (is(e, "bf16x3") || is(e, "1")) s.train_precision = 1;
     if (is(e, "f32x6") || is(e, "2")) s.train_precision = 2;

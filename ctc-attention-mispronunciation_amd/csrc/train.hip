@@ -79,6 +79,7 @@ struct mdd_train_ws {
     int precision = 0;                 // mode of the NEXT forward.  0: exact fp32 MFMA everywhere (the reference trains in fp32); 1: the large contractions
                                        // as split-bf16 x3; 2: the large contractions as f32x6 (reference width), everything else as 0
     bool conv1_im2col = false;         // MDD_TRAIN_CONV1_IM2COL at create
+    mdd::X6Raster x6_raster = mdd::kX6DefaultRaster;   // MDD_GEMM_X6_RASTER at create: the tile walk of the one-launch f32x6 products
     mdd::DeviceArray<int> err_flag;    // set by the embedding gather on an id outside the table
     mdd::DeviceBuf masks, maskt;       // generated dropout masks (bytes); the conv sites' in channels-last order
     std::vector<const unsigned char *> mask_ptr;
@@ -159,7 +160,7 @@ static int gemm_big(mdd_train_ws *w, const GemmOperand &A, const GemmOperand &B,
     const size_t macs = (size_t)M * N * K;
     const bool may_split = !bias && ldc == N;
     if (mode == 2 && M >= 128 && N >= 128 && K >= 64 && macs >= ((size_t)1 << 27) && x6_ops_ok(A, B, C, ldc))
-        return gemm_f32x6_ops(A, B, bias, C, ldc, M, N, K, may_split ? split_chunks(Arith::X6, M, N, K) : 1, w->xs_a, w->xs_b, w->part, st);
+        return gemm_f32x6_ops(A, B, bias, C, ldc, M, N, K, may_split ? split_chunks(Arith::X6, M, N, K) : 1, w->xs_a, w->xs_b, w->part, st, w->x6_raster);
     if (mode == 1 && M >= 256 && N >= 256 && K >= 256 && ldc % 4 == 0 && macs >= ((size_t)1 << 30))
         return gemm_bf16x3_ops(A, B, bias, C, ldc, M, N, K, may_split ? split_chunks(Arith::X3, M, N, K) : 1, w->xs_a, w->xs_b, w->part, st);
     if (may_split && A.k_major && B.k_major) return gemm_f32_split(w, Arith::Exact, A, B, C, M, N, K, st);
@@ -220,6 +221,7 @@ extern "C" int mdd_train_create(const mdd_config *cfg, int device, mdd_train_ws 
     const Switches sw = read_switches();   // the environment at create (plan.h); the mode can change later, a backward follows its own forward (Saved)
     w->precision = sw.train_precision;
     w->conv1_im2col = sw.train_conv1_im2col;
+    w->x6_raster = sw.x6_raster;
     build_info(w.get());
     const int nl = cfg->layers + 1;
     w->xin.resize(nl); w->hraw.resize(nl); w->pd.resize(nl); w->gates.resize(nl); w->cst.resize(nl); w->wihp.resize(nl); w->whhp.resize(nl); w->whht.resize(nl);
