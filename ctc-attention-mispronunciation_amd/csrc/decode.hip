@@ -5,6 +5,7 @@
 // Both are serial scans over the posterior frames of one utterance; they are latency-bound, not
 // bandwidth- or flop-bound (180 B read per frame).  One workgroup per utterance.
 #include "mdd_internal.h"
+#include <type_traits>
 
 namespace mdd {
 
@@ -109,11 +110,16 @@ __global__ __launch_bounds__(256) void beam_prep_kernel(const float *__restrict_
 // ---- pass 2: one wave per utterance, serial over the live frames.  dynamic LDS layout (bytes):
 //   tot[beam*C] double | lmt[(C+1)*(C+1)] double (if it fits) | cl_v[beam*C] double | cl_o[beam*C] int |
 //   flags[Tcap] uint8 | prefix[2][beam][Tcap] uint8
+// NBEST selects the ending: false writes the winner alone (mdd_beam), true the `nbest` best final hypotheses (mdd_beam_nbest).
+// The last kernel argument is the stamp buffer of MDD_BEAM_DBG for the first and the count `nbest` for the second (which takes no
+// stamps), so the winner-only instantiations keep the argument block they always had.
+template <bool NBEST> using BeamTail = typename std::conditional<NBEST, int, long long *>::type;
+template <bool NBEST>
 __global__ __launch_bounds__(64) void beam_kernel(const double *__restrict__ lpw, const unsigned char *__restrict__ flags,
                                                   int T, int B, int C, const int32_t *__restrict__ len, int beam, int blank,
                                                   const double *__restrict__ lm, double alpha, int32_t *__restrict__ ids,
                                                   int32_t *__restrict__ nids, int32_t *__restrict__ status,
-                                                  double *__restrict__ score, int Tcap, int lm_in_lds, int skip, long long *dbg) {
+                                                  double *__restrict__ score, int Tcap, int lm_in_lds, int skip, BeamTail<NBEST> tail) {
     extern __shared__ __attribute__((aligned(16))) unsigned char sm[];
     const int C1 = C + 1;
     double *tot = reinterpret_cast<double *>(sm);
@@ -131,6 +137,10 @@ __global__ __launch_bounds__(64) void beam_kernel(const double *__restrict__ lpw
     __shared__ int sel_ord[MAXBEAM];
 
     const int b = blockIdx.x, lane = threadIdx.x;
+    long long *dbg = nullptr;
+    int nbest = 0;
+    if constexpr (NBEST) nbest = tail; else dbg = tail;
+    (void)nbest;
     int cur = 0, nb = 1, err = 0;
     long long ph[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, tstamp = 0;
 #define STAMP(i) do { if (dbg) { long long now_ = __builtin_readcyclecounter(); ph[i] += now_ - tstamp; tstamp = now_; } } while (0)
@@ -358,6 +368,54 @@ __global__ __launch_bounds__(64) void beam_kernel(const double *__restrict__ lpw
     }
     if (dbg && lane == 0) for (int i = 0; i < 10; i++) dbg[b * 10 + i] = ph[i];
     __syncthreads();
+    if constexpr (NBEST) {
+        // ---- final, N best: EOS LM term and length normalisation per entry (thread r = entry r of `BHat`), the first failing entry
+        // in entry order decides the status, then the reference's second sort() (:29-33,148) as a rank count through LDS --
+        // rank(r) = #{j : s_j > s_r or (s_j == s_r and j < r)}: descending, equal scores keep their entry order (Python's sort is
+        // stable and `curr` is filled in BHat order).  sel_v / sel_ord are dead after the frame loop.
+        const BeamMeta *last = meta[cur];
+        const bool act = lane < nb && !err;
+        int e = 0;
+        double s = -INFINITY;
+        if (act) {
+            const BeamMeta &y = last[lane];
+            if (y.len == 0) e = MDD_BEAM_INDEX_ERROR;                  // y[-1] on the empty tuple (:135)
+            else {
+                const double v = lmp[y.last * C1 + C];
+                if (v != v) e = MDD_BEAM_KEY_ERROR;
+                else {
+                    double pr = log_add_prob(LOG_ZERO, y.prTotal + v * alpha);
+                    pr = pr * (1.0 / (double)(y.len ? y.len : 1));
+                    s = pr;
+                }
+            }
+        }
+        const unsigned long long em = __ballot(e != 0);
+        if (em) err = __shfl(e, __ffsll((long long)em) - 1);
+        sel_v[lane] = s;                                                // entries >= nb: -inf
+        sel_ord[lane] = -1;
+        __syncthreads();
+        int rank = 0;
+        for (int j = 0; j < nb; j++) {
+            const double sj = sel_v[j];
+            rank += (sj > s || (sj == s && j < lane)) ? 1 : 0;
+        }
+        if (!err && lane < nb) sel_ord[rank] = lane;                    // a permutation of 0..nb-1
+        __syncthreads();
+        const unsigned char *rows = pref + (size_t)cur * beam * Tcap;
+        for (int n = 0; n < nbest; n++) {
+            const int r = (err || n >= nb) ? -1 : sel_ord[n];
+            const size_t o = (size_t)n * B + b;
+            int ln = 0;
+            if (r >= 0) {
+                ln = last[r].len;
+                const unsigned char *src = rows + (size_t)r * Tcap;
+                for (int j = lane; j < ln; j += 64) ids[o * T + j] = src[j];
+            }
+            if (lane == 0) { nids[o] = ln; score[o] = r >= 0 ? sel_v[r] : __builtin_nan(""); }
+        }
+        if (lane == 0) status[b] = err;
+    } else
     // ---- final: EOS LM term, length normalisation, first maximum (:130-148)
     if (lane == 0) {
         const BeamMeta *last = meta[cur];
@@ -422,14 +480,19 @@ __host__ __device__ inline size_t beam_fast_lm_bytes(int C) { return (sizeof(dou
 //     v_readfirstlane so that the control flow stays scalar;
 //   * per-beam values (copy-path scores, parent, merge slot) stay in the registers of lane == beam and move between
 //     lanes with v_readlane / ballots rather than through LDS.
-template <int NS, bool DBG>
+// NBEST selects the ending, as in beam_kernel.
+template <int NS, bool DBG, bool NBEST>
 __global__ __launch_bounds__(256) void beam_fast_kernel(const double *__restrict__ lpw, const unsigned char *__restrict__ flags,
                                                        int T, int B, int C, const int32_t *__restrict__ len, int beam, int blank,
                                                        const double *__restrict__ lm, double alpha, int32_t *__restrict__ ids,
                                                        int32_t *__restrict__ nids, int32_t *__restrict__ status,
-                                                       double *__restrict__ score, int Tcap, long long *__restrict__ dbg) {
+                                                       double *__restrict__ score, int Tcap, BeamTail<NBEST> tail) {
     extern __shared__ __attribute__((aligned(16))) unsigned char sm[];
     const int C1 = C + 1;
+    long long *__restrict__ dbg = nullptr;
+    int nbest = 0;
+    if constexpr (NBEST) nbest = tail; else dbg = tail;
+    (void)nbest; (void)dbg;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     double *lmt = reinterpret_cast<double *>(sm);                      // [C1*C1], shared by the waves
     unsigned char *mine = sm + beam_fast_lm_bytes(C) + (size_t)wave * ((beam_fast_wave_bytes(NS, beam, Tcap) + 15) & ~(size_t)15);
@@ -732,6 +795,43 @@ __global__ __launch_bounds__(256) void beam_fast_kernel(const double *__restrict
         FSTAMP(10);
     }
     BEAM_WAVE_SYNC();
+    if constexpr (NBEST) {
+        // final, N best (see beam_kernel): lane r speaks for entry r, its score stays in the lane; status and ranks come from
+        // ballots and v_readlane broadcasts, then the lanes of the wave stride each ranked prefix row, bytes to int32
+        err = __builtin_amdgcn_readfirstlane(err);
+        const int ylen = m_len[cur][li], ylast = m_last[cur][li];
+        const double mT = m_T[cur][li];
+        const double v = lmt[max(ylast, 0) * C1 + C];
+        const bool act = lane < nb && !err;
+        const int e = !act ? 0 : (ylen == 0 ? MDD_BEAM_INDEX_ERROR : (v != v ? MDD_BEAM_KEY_ERROR : 0));   // y[-1] on the empty tuple (:135)
+        double pr = log_add_prob(LOG_ZERO, mT + v * alpha);
+        pr = pr * (1.0 / (double)(ylen ? ylen : 1));
+        const double s = (act && !e) ? pr : -INFINITY;
+        const unsigned long long em = __ballot(e != 0);
+        if (em) err = __builtin_amdgcn_readlane(e, __ffsll((long long)em) - 1);   // the first failing entry in entry order
+        const int slo = __double2loint(s), shi = __double2hiint(s);
+        int rank = 0;
+        for (int j = 0; j < nb; j++) {
+            const double sj = __hiloint2double(__builtin_amdgcn_readlane(shi, j), __builtin_amdgcn_readlane(slo, j));
+            rank += (sj > s || (sj == s && j < lane)) ? 1 : 0;
+        }
+        const unsigned char *rows = pref + (size_t)cur * FB * Tcap;
+        for (int n = 0; n < nbest; n++) {
+            const unsigned long long hm = err ? 0ull : __ballot(lane < nb && rank == n);
+            const size_t o = (size_t)n * B + b;
+            int ln = 0;
+            double sc = __builtin_nan("");
+            if (hm) {
+                const int r = __ffsll((long long)hm) - 1;
+                ln = __builtin_amdgcn_readlane(ylen, r);
+                sc = __hiloint2double(__builtin_amdgcn_readlane(shi, r), __builtin_amdgcn_readlane(slo, r));
+                const unsigned char *src = rows + (size_t)r * Tcap;
+                for (int j = lane; j < ln; j += 64) ids[o * T + j] = src[j];
+            }
+            if (lane == 0) { nids[o] = ln; score[o] = sc; }
+        }
+        if (lane == 0) status[b] = err;
+    } else
     if (lane == 0) {   // final: EOS LM term, length normalisation, first maximum (:130-148)
         int best = -1;
         double bestv = 0.0;
@@ -773,13 +873,20 @@ extern "C" int mdd_greedy(const float *logp_dev, int32_t T, int32_t B, int32_t C
     return MDD_OK;
 }
 
-extern "C" int mdd_beam(const float *logp_dev, int32_t T, int32_t B, int32_t C, const int32_t *len_dev, int32_t beam,
-                        int32_t blank, const double *lm_dev, double lm_alpha, int32_t *ids_dev, int32_t *nids_dev,
-                        int32_t *status_dev, double *score_dev, void *stream) {
-    using namespace mdd;
+namespace mdd {
+// The checks, the frame pre-pass and the kernel dispatch of both beam entries.  nb false: mdd_beam (the winner alone, score_dev
+// optional, nbest unused); nb true: mdd_beam_nbest (outputs hypothesis-major, score_dev required).  Every refusal comes before any
+// device work.
+static int beam_dispatch(bool nb, const float *logp_dev, int32_t T, int32_t B, int32_t C, const int32_t *len_dev, int32_t beam,
+                         int32_t blank, const double *lm_dev, double lm_alpha, int32_t nbest, int32_t *ids_dev, int32_t *nids_dev,
+                         int32_t *status_dev, double *score_dev, void *stream) {
+    const char *who = nb ? "mdd_beam_nbest" : "mdd_beam";
     if (!logp_dev || !len_dev || !lm_dev || !ids_dev || !nids_dev || !status_dev || T <= 0 || B <= 0 || C <= 1 ||
         C > 256 || beam < 1 || beam > MAXBEAM || blank < 0 || blank >= C) {
-        set_error("mdd_beam: bad argument (need 1<=beam<=64, 2<=C<=256)"); return MDD_ERR_ARG;
+        set_error("%s: bad argument (need 1<=beam<=64, 2<=C<=256)", who); return MDD_ERR_ARG;
+    }
+    if (nb && (nbest < 1 || nbest > beam || !score_dev)) {
+        set_error("%s: bad argument (need 1<=nbest<=beam and score_dev)", who); return MDD_ERR_ARG;
     }
     hipStream_t st = (hipStream_t)stream;
     const int Tcap = (T + 1 + 3) & ~3;
@@ -787,10 +894,26 @@ extern "C" int mdd_beam(const float *logp_dev, int32_t T, int32_t B, int32_t C, 
     const size_t base = (sizeof(double) * 2 + sizeof(int)) * (size_t)beam * C + (size_t)(2 * beam + 1) * Tcap;
     const int lm_in_lds = (base + lm_bytes <= 96 * 1024) ? 1 : 0;
     const size_t smem = base + (lm_in_lds ? lm_bytes : 0);
-    if (smem > 140 * 1024) { set_error("mdd_beam: beam*C / T too large for LDS (%zu B)", smem); return MDD_ERR_ARG; }
+    if (smem > 140 * 1024) { set_error("%s: beam*C / T too large for LDS (%zu B)", who, smem); return MDD_ERR_ARG; }
+    const int nslots = beam * C;
+    const bool fast = beam <= FB && C <= 64 && nslots <= 1024 && !getenv("MDD_BEAM_GENERIC");
+    const int NS = nslots <= 512 ? 8 : 16;
+    const size_t lmb = beam_fast_lm_bytes(C);
+    const size_t pw = (beam_fast_wave_bytes(NS, beam, Tcap) + 15) & ~(size_t)15;
+    const size_t lds_max = 160 * 1024;
+    if (fast && lmb + pw > lds_max) { set_error("%s: T too long for LDS (%zu B)", who, lmb + pw); return MDD_ERR_ARG; }
+    // once: the LDS budgets of every instantiation.  The winner-only kernels are named first, in the order they always were, and the
+    // N-best ones after them: kernels are emitted in the order of their first use, so mdd_beam's keep their places in the code object
     static bool attr_set = false;
     if (!attr_set) {
-        MDD_HIP_CHECK(hipFuncSetAttribute((const void *)beam_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
+        MDD_HIP_CHECK(hipFuncSetAttribute((const void *)beam_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
+        MDD_HIP_CHECK(hipFuncSetAttribute((const void *)beam_fast_kernel<8, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
+        MDD_HIP_CHECK(hipFuncSetAttribute((const void *)beam_fast_kernel<16, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
+        MDD_HIP_CHECK(hipFuncSetAttribute((const void *)beam_fast_kernel<8, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
+        MDD_HIP_CHECK(hipFuncSetAttribute((const void *)beam_fast_kernel<16, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
+        MDD_HIP_CHECK(hipFuncSetAttribute((const void *)beam_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
+        MDD_HIP_CHECK(hipFuncSetAttribute((const void *)beam_fast_kernel<8, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
+        MDD_HIP_CHECK(hipFuncSetAttribute((const void *)beam_fast_kernel<16, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
         attr_set = true;
     }
     // stream-ordered scratch for the frame pre-pass: log-probabilities in fp64 + per-frame flags
@@ -802,21 +925,9 @@ extern "C" int mdd_beam(const float *logp_dev, int32_t T, int32_t B, int32_t C, 
     int grid = (int)((n + 255) / 256);
     if (grid > 2048) grid = 2048;
     hipLaunchKernelGGL(beam_prep_kernel, dim3(grid), dim3(256), 0, st, logp_dev, T, B, C, blank, lpw, flags);
-    const int nslots = beam * C;
-    if (beam <= FB && C <= 64 && nslots <= 1024 && !getenv("MDD_BEAM_GENERIC")) {
-        const int NS = nslots <= 512 ? 8 : 16;
-        const size_t lmb = beam_fast_lm_bytes(C);
-        const size_t pw = (beam_fast_wave_bytes(NS, beam, Tcap) + 15) & ~(size_t)15;
-        const size_t lds_max = 160 * 1024;
-        static bool fattr = false;
-        if (!fattr) {
-            MDD_HIP_CHECK(hipFuncSetAttribute((const void *)beam_fast_kernel<8, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
-            MDD_HIP_CHECK(hipFuncSetAttribute((const void *)beam_fast_kernel<16, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
-            MDD_HIP_CHECK(hipFuncSetAttribute((const void *)beam_fast_kernel<8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
-            MDD_HIP_CHECK(hipFuncSetAttribute((const void *)beam_fast_kernel<16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
-            fattr = true;
-        }
-        if (lmb + pw > lds_max) { (void)hipFreeAsync(lpw, st); set_error("mdd_beam: T too long for LDS (%zu B)", lmb + pw); return MDD_ERR_ARG; }
+    // MDD_BEAM_DBG (tools/beam_stamps.py): the stamps ride behind the B scores of mdd_beam; the N-best entry has no room for them
+    long long *dbg = (!nb && getenv("MDD_BEAM_DBG")) ? reinterpret_cast<long long *>(score_dev) + B : nullptr;
+    if (fast) {
         // waves per workgroup: as many as the LDS holds (<= 4); a small batch spreads out instead (one wave per CU is the
         // lowest latency when nothing else wants the CUs)
         int W = (int)((lds_max - lmb) / pw);
@@ -825,18 +936,36 @@ extern "C" int mdd_beam(const float *logp_dev, int32_t T, int32_t B, int32_t C, 
         if (const char *we = getenv("MDD_BEAM_W")) { const int w = atoi(we); if (w >= 1 && w <= W) W = w; }
         const size_t fs = lmb + (size_t)W * pw;
         const dim3 grid_f((B + W - 1) / W), block_f(64 * W);
-        long long *fdbg = getenv("MDD_BEAM_DBG") ? reinterpret_cast<long long *>(score_dev) + B : nullptr;   // tools/beam_stamps.py
-#define MDD_BEAM_FAST(NS_, DBG_) hipLaunchKernelGGL((beam_fast_kernel<NS_, DBG_>), grid_f, block_f, fs, st, lpw, flags, T, B, C, len_dev, beam, blank, \
-                                                  lm_dev, lm_alpha, ids_dev, nids_dev, status_dev, score_dev, Tcap, fdbg)
-        if (NS == 8) { if (fdbg) MDD_BEAM_FAST(8, true); else MDD_BEAM_FAST(8, false); }
-        else { if (fdbg) MDD_BEAM_FAST(16, true); else MDD_BEAM_FAST(16, false); }
+#define MDD_BEAM_FAST(NS_, DBG_, NB_, TAIL_) hipLaunchKernelGGL((beam_fast_kernel<NS_, DBG_, NB_>), grid_f, block_f, fs, st, lpw, flags, T, B, C, len_dev, beam, blank, \
+                                                       lm_dev, lm_alpha, ids_dev, nids_dev, status_dev, score_dev, Tcap, TAIL_)
+        if (nb) { if (NS == 8) MDD_BEAM_FAST(8, false, true, nbest); else MDD_BEAM_FAST(16, false, true, nbest); }
+        else if (NS == 8) { if (dbg) MDD_BEAM_FAST(8, true, false, dbg); else MDD_BEAM_FAST(8, false, false, dbg); }
+        else { if (dbg) MDD_BEAM_FAST(16, true, false, dbg); else MDD_BEAM_FAST(16, false, false, dbg); }
 #undef MDD_BEAM_FAST
-    } else
-    hipLaunchKernelGGL(beam_kernel, dim3(B), dim3(64), smem, st, lpw, flags, T, B, C, len_dev, beam, blank, lm_dev, lm_alpha,
-                       ids_dev, nids_dev, status_dev, score_dev, Tcap, lm_in_lds, getenv("MDD_BEAM_SKIP") ? atoi(getenv("MDD_BEAM_SKIP")) : 0,
-                       getenv("MDD_BEAM_DBG") ? reinterpret_cast<long long *>(score_dev) + B : nullptr);
+    } else {
+        const int skip = getenv("MDD_BEAM_SKIP") ? atoi(getenv("MDD_BEAM_SKIP")) : 0;
+#define MDD_BEAM_GEN(NB_, TAIL_) hipLaunchKernelGGL(beam_kernel<NB_>, dim3(B), dim3(64), smem, st, lpw, flags, T, B, C, len_dev, beam, blank, lm_dev, lm_alpha, \
+                                             ids_dev, nids_dev, status_dev, score_dev, Tcap, lm_in_lds, skip, TAIL_)
+        if (nb) MDD_BEAM_GEN(true, nbest); else MDD_BEAM_GEN(false, dbg);
+#undef MDD_BEAM_GEN
+    }
     hipError_t le = hipGetLastError();
     (void)hipFreeAsync(lpw, st);
     if (le != hipSuccess) { set_error("beam kernel launch failed: %s", hipGetErrorString(le)); return MDD_ERR_HIP; }
     return MDD_OK;
+}
+}  // namespace mdd
+
+extern "C" int mdd_beam(const float *logp_dev, int32_t T, int32_t B, int32_t C, const int32_t *len_dev, int32_t beam,
+                        int32_t blank, const double *lm_dev, double lm_alpha, int32_t *ids_dev, int32_t *nids_dev,
+                        int32_t *status_dev, double *score_dev, void *stream) {
+    return mdd::beam_dispatch(false, logp_dev, T, B, C, len_dev, beam, blank, lm_dev, lm_alpha, 0, ids_dev, nids_dev, status_dev,
+                              score_dev, stream);
+}
+
+extern "C" int mdd_beam_nbest(const float *logp_dev, int32_t T, int32_t B, int32_t C, const int32_t *len_dev, int32_t beam,
+                              int32_t blank, const double *lm_dev, double lm_alpha, int32_t nbest, int32_t *ids_dev,
+                              int32_t *nids_dev, int32_t *status_dev, double *score_dev, void *stream) {
+    return mdd::beam_dispatch(true, logp_dev, T, B, C, len_dev, beam, blank, lm_dev, lm_alpha, nbest, ids_dev, nids_dev,
+                              status_dev, score_dev, stream);
 }

@@ -2,7 +2,7 @@
 (AA/infer.py:435-598, ``main``), run as
 
     python -m ctc_attention_mispronunciation_amd.infer --conf CONF --wav_transcript_path DIR [-p cmudict] [-f cmu]
-        [--cmvn PATH] [--cmudict PATH] [--precision f32x6|f32|bf16x3] [--decode_seq PATH] [--timestamps] [--posteriors] [--pronunciations]
+        [--cmvn PATH] [--cmudict PATH] [--precision f32x6|f32|bf16x3] [--decode_seq PATH] [--timestamps] [--posteriors] [--pronunciations] [--nbest N]
 
 The conf YAML is read as ``infer_init`` reads it (AA/infer.py:211-261): the checkpoint
 ``checkpoint_dir/exp_name/ctc_best_model.pkl``, ``vocab_file``, ``decode_type``, ``beam_width``, ``lm_path``, ``lm_alpha``,
@@ -59,6 +59,10 @@ def parse_args(argv=None):
                     help="score every pronunciation the CMU dictionary lists for the word (word, word(2), ...) on one acoustic pass, report the "
                          "utterance against the one with the highest CTC log-likelihood (not length-normalised; ties go to the earlier entry) "
                          "and add a 'pron   :' line with every pronunciation's log-likelihood")
+    ap.add_argument("--nbest", type=int, default=None, metavar="N",
+                    help="add N 'nbest  :' lines to each block: the N best final hypotheses of the beam search with their beam score, exact CTC "
+                         "log-likelihood, share of probability among the N listed (not an absolute probability) and Comp.; needs "
+                         "decode_type Beam and 1 <= N <= beam_width")
     return ap.parse_args(argv)
 
 
@@ -158,6 +162,13 @@ def main(argv=None):
     opts = _Conf()
     for k, v in conf.items():
         setattr(opts, k, v)
+    if args.nbest is not None:
+        if opts.decode_type == "Greedy":
+            refuse("--nbest: the greedy decoder keeps one hypothesis; set decode_type to Beam")
+        if args.nbest < 1:
+            refuse("--nbest %d: N must be at least 1" % args.nbest)
+        if args.nbest > opts.beam_width:
+            refuse("--nbest %d: the search keeps beam_width = %d hypotheses; N cannot exceed it" % (args.nbest, opts.beam_width))
     if not os.path.exists(args.cmvn):
         refuse("CMVN stats not found at %s (pass --cmvn)" % args.cmvn)
     print(args.wav_transcript_path, False, args.phonetic)
@@ -187,7 +198,8 @@ def main(argv=None):
                             n_downsample=getattr(opts, "n_downsample", 2), pronunciations=args.pronunciations)
     device = torch.device("cuda", torch.cuda.current_device())
     c1, c2, c3 = infer(phonetic, word_dict, loader, device, model, decoder, vocab, transcripts, False,
-                       decode_seq_path=args.decode_seq, timestamps=args.timestamps, posteriors=args.posteriors, pronunciations=args.pronunciations)
+                       decode_seq_path=args.decode_seq, timestamps=args.timestamps, posteriors=args.posteriors, pronunciations=args.pronunciations,
+                       nbest=args.nbest or 0)
     print(c1, c2, c3)
     end = time.time()
     total = max(total_wav_time, 1e-9)

@@ -230,8 +230,26 @@ def pronunciation_line(phones, loglik, chosen):
     return "pron   : " + " | ".join("%s%s [%.4f]" % ("*" if p == chosen else "", ph, ll) for p, (ph, ll) in enumerate(zip(phones, loglik)))
 
 
+def nbest_lines(records, canonical, decoder, to_display=None):
+    """The ``nbest  :`` lines of a block, one per record ``(string, score, loglik, posterior)`` of ``BeamDecoder.decode_nbest``, best first:
+    ``nbest  : <rank> <*|space> <phones> | score <beam score> | loglik <CTC log-likelihood> | p <share> | Comp. <correct>/<total>``.
+    '*' marks rank 1, the hypothesis the block reports; score is the beam's length-normalised score, loglik the exact CTC log-likelihood
+    ('-inf' for a hypothesis that is no CTC path), p its share among the listed hypotheses ('-' when none of them is a CTC path) and
+    Comp. what ``diagnose`` counts for that hypothesis against the block's canonical ('-' where ``wer`` has nothing to align)."""
+    lines = []
+    for n, (hyp, score, loglik, share) in enumerate(records):
+        try:
+            d = diagnose(hyp, canonical, decoder, to_display)
+            comp = "%d/%d" % (d["correct"], d["correct"] + d["del_sub"])
+        except TypeError:                # an empty side after the 'sil' strip: Decoder.wer raises, as the reference's does
+            comp = "-"
+        lines.append("nbest  : %d %s %s | score %.4f | loglik %.4f | p %s | Comp. %s"
+                     % (n + 1, "*" if n == 0 else " ", hyp, score, loglik, "-" if share is None else "%.4f" % share, comp))
+    return lines
+
+
 def infer(phonetic, word_dict, test_loader, device, model, decoder, vocab, test_transcipt_dict, use_ipa, out=None,
-          decode_seq_path=None, timestamps=False, posteriors=False, pronunciations=False):
+          decode_seq_path=None, timestamps=False, posteriors=False, pronunciations=False, nbest=0):
     """AA/infer.py:282-372.  Per batch ``(inputs, input_sizes, _, _, trans, trans_sizes, utt_list)``: ``model(inputs, trans)``,
     frame counts ``(input_sizes * T').long()``, ``decoder.decode``, then per utterance the 'sil' strip, 'err' removal, ``wer``,
     alignment, fault lists and score (``diagnose``), printed as the reference's 13-line block to ``out`` (stdout by default).
@@ -255,7 +273,15 @@ def infer(phonetic, word_dict, test_loader, device, model, decoder, vocab, test_
     pronunciation is scored by the CTC log-likelihood of its own ids under its own posteriors (``hip_model.ctc_variants``' base over the
     utterance's frames; not length-normalised).  The highest wins, ties to the earlier dictionary entry, and the utterance's whole block --
     dictionary line, decode, alignment, diagnosis, score and the ``time`` / ``gop`` / ``post`` lines -- is that candidate's; a
-    ``pron   :`` line (``pronunciation_line``) closes the block.  Without it nothing changes."""
+    ``pron   :`` line (``pronunciation_line``) closes the block.  Without it nothing changes.
+
+    ``nbest=N`` (no reference counterpart; needs a ``BeamDecoder`` with ``beam_width >= N >= 1``) adds N ``nbest  :`` lines
+    (``nbest_lines``) before the closing empty line, after the ``time`` / ``gop`` / ``post`` lines and before ``pron``: the N best final
+    hypotheses of the beam search (``decode_nbest``: the reference computes this list and keeps its head), each with its beam score, its
+    exact CTC log-likelihood, its share of probability among the N and its ``Comp.`` against the block's canonical.  Rank 1 is the
+    block's decoded string.  With ``pronunciations`` the lines are the chosen candidate's.  With 0 nothing changes."""
+    if nbest and not (hasattr(decoder, "decode_nbest") and 1 <= nbest <= decoder.beam_width):
+        raise ValueError("nbest needs a BeamDecoder and 1 <= nbest <= beam_width")
     if posteriors:
         from .utils.ctcDecoder import phoneme_posteriors
     if pronunciations:
@@ -289,6 +315,8 @@ def infer(phonetic, word_dict, test_loader, device, model, decoder, vocab, test_
                         spf = seconds_per_frame(test_loader, inputs.size(1) // probs.size(0))
                     else:
                         r["decoded"] = decoder.decode(probs, frame_lens)
+                    if nbest:
+                        r["nbest"] = decoder.decode_nbest(probs, frame_lens, nbest)
                     if posteriors:
                         r["post"] = phoneme_posteriors(probs, frame_lens, trans, trans_sizes, decoder.blank_index)
                     if pronunciations:
@@ -325,6 +353,8 @@ def infer(phonetic, word_dict, test_loader, device, model, decoder, vocab, test_
                         dp = diagnose_posterior(decoded[x], canonical, None if post[x] is None else post[x][0], decoder, vocab.index2word,
                                                 to_display)
                         block[-1:-1] = [posterior_line(dp)]
+                    if nbest:
+                        block[-1:-1] = nbest_lines(r["nbest"][x], canonical, decoder, to_display)
                     if pronunciations:
                         phones = [" ".join(vocab.index2word[num] for num in per_set[p]["trans"][x][:per_set[p]["trans_sizes"][x]]) for p in range(count)]
                         block[-1:-1] = [pronunciation_line(phones, loglik, chosen)]

@@ -209,6 +209,19 @@ def phoneme_posteriors(prob_tensor, frame_seq_len, ids, nids, blank=0):
     return out
 
 
+def nbest_posteriors(loglik):
+    """Float64 softmax over one utterance's N log-likelihoods: the share of probability each listed hypothesis holds AMONG THE LISTED
+    ONES, not an absolute probability (what the list leaves out is not counted).  ``-inf`` entries get 0; ``None`` when every entry
+    is ``-inf`` (no listed hypothesis is a CTC path of the posteriors)."""
+    ll = np.asarray(loglik, dtype=np.float64).reshape(-1)
+    top = ll.max() if ll.size else -np.inf
+    if not top > -np.inf:
+        return None
+    with np.errstate(under="ignore"):
+        e = np.exp(ll - top)             # -inf entries: exactly 0
+    return e / e.sum()
+
+
 class GreedyDecoder(Decoder):
     """argmax per frame, collapse repeats, drop blanks (ctcDecoder.py:186-200)."""
 
@@ -293,8 +306,68 @@ class BeamDecoder(Decoder):
         strings = self._strings(ids, nids, status)
         return strings, timed_spans(lp, frame_seq_len, ids, nids, self.blank_index)
 
+    def decode_nbest_ids(self, prob_tensor, frame_seq_len=None, nbest=None):
+        """The ``nbest`` (default ``beam_width``) best final hypotheses of every utterance (mdd_beam_nbest), as device tensors
+        ``(ids [N,B,T], nids [N,B], status [B], score [N,B])``: slice n is ``decode_ids``' output for the hypothesis of rank n, slice 0
+        its output itself, bit for bit.  Ranks follow the reference's final sort: descending length-normalised score, equal scores in
+        the order of the final beam.  An utterance with an error status has nids 0 and score NaN in every slice.  Nothing synchronises."""
+        lp = _device_posteriors(prob_tensor)
+        T, B, Cn = lp.shape
+        N = self.beam_width if nbest is None else int(nbest)
+        if not 1 <= N <= self.beam_width:
+            raise ValueError("nbest must be in [1, beam_width = %d]" % self.beam_width)
+        lens = _lens_tensor(frame_seq_len, B, T, lp.device)
+        ids = torch.empty((N, B, T), dtype=torch.int32, device=lp.device)
+        nids = torch.empty((N, B), dtype=torch.int32, device=lp.device)
+        status = torch.empty((B,), dtype=torch.int32, device=lp.device)
+        score = torch.empty((N, B), dtype=torch.float64, device=lp.device)
+        lm = self._lm_table(Cn, lp.device)
+        with torch.cuda.device(lp.device):
+            _lib.check(_lib.lib().mdd_beam_nbest(C.c_void_p(lp.data_ptr()), T, B, Cn, C.c_void_p(lens.data_ptr()), self.beam_width,
+                                                 self.blank_index, C.c_void_p(lm.data_ptr()), float(self.lm_alpha), N,
+                                                 C.c_void_p(ids.data_ptr()), C.c_void_p(nids.data_ptr()),
+                                                 C.c_void_p(status.data_ptr()), C.c_void_p(score.data_ptr()),
+                                                 _lib.current_stream_ptr()))
+        return ids, nids, status, score
+
+    def nbest_loglik(self, prob_tensor, frame_seq_len, ids, nids, max_len=None):
+        """Exact CTC log-likelihood of every hypothesis of ``decode_nbest_ids``' ``ids [N,B,T]`` / ``nids [N,B]`` over its utterance's
+        frames, as a float64 numpy array [N,B]: one ``hip_model.ctc_loss`` call without gradient per slice (the fp32 nll of the training
+        lattice, negated), ``-inf`` where the lattice finds no path.  ``max_len`` bounds nids (default: the ids' row length); a tight
+        bound lets the lattice run in its one-wave form."""
+        from ..hip_model import ctc_loss
+        lp = _device_posteriors(prob_tensor)
+        T, B, _ = lp.shape
+        lens = _lens_tensor(frame_seq_len, B, T, lp.device).clamp(0, T)
+        width = ids.shape[2] if max_len is None else max(min(int(max_len), ids.shape[2]), 1)
+        nll = [ctc_loss(lp, ids[n, :, :width], lens, nids[n], blank=self.blank_index, want_grad=False)[0] for n in range(ids.shape[0])]
+        return -torch.stack(nll).double().cpu().numpy()
+
+    def decode_nbest(self, prob_tensor, frame_seq_len=None, nbest=None, rescore=True):
+        """Per utterance a list of N records ``(string, score, loglik, posterior)``, best first; record 0's string is ``decode``'s
+        string and the exceptions are ``decode``'s.  ``score`` is the beam's own length-normalised score, which is no CTC likelihood
+        (the search skips near-certain blank frames and applies its repeat rule to raw frames).  ``rescore`` adds ``loglik``, the exact
+        CTC log-likelihood of the hypothesis over the utterance's frames (``nbest_loglik``; ``-inf`` for a hypothesis that is no CTC path
+        of the posteriors), and ``posterior``, its share among the N listed hypotheses
+        (``nbest_posteriors``: relative to the list, not an absolute probability; ``None`` when no hypothesis of the list is a CTC
+        path).  With ``rescore=False`` both are ``None``."""
+        lp = _device_posteriors(prob_tensor)
+        T, B, _ = lp.shape
+        ids, nids, status, score = self.decode_nbest_ids(lp, frame_seq_len, nbest)
+        N = ids.shape[0]
+        nids_h = nids.cpu().numpy()
+        strings = [self._strings(ids[n], nids_h[n], status) for n in range(N)]      # raises decode's exception
+        loglik = self.nbest_loglik(lp, frame_seq_len, ids, nids, max_len=int(nids_h.max())) if rescore else None
+        score_h = score.cpu().numpy()
+        out = []
+        for b in range(B):
+            post = nbest_posteriors(loglik[:, b]) if rescore else None
+            out.append([(strings[n][b], float(score_h[n, b]), float(loglik[n, b]) if rescore else None,
+                         None if post is None else float(post[n])) for n in range(N)])
+        return out
+
     def _strings(self, ids, nids, status):
-        ids, nids, status = ids.cpu().numpy(), nids.cpu().numpy(), status.cpu().numpy()
+        ids, nids, status = ids.cpu().numpy(), torch.as_tensor(nids).cpu().numpy(), status.cpu().numpy()
         bad = np.nonzero(status)[0]
         if len(bad):   # the reference stops at the first utterance that raises
             err = _BEAM_ERRORS[int(status[bad[0]])]

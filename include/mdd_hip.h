@@ -239,6 +239,30 @@ int mdd_beam(const float *logp_dev, int32_t T, int32_t B, int32_t C, const int32
              int32_t blank, const double *lm_dev, double lm_alpha, int32_t *ids_dev, int32_t *nids_dev,
              int32_t *status_dev, double *score_dev, void *stream);
 
+/* ---- A9, N best: the same search, ending with the `nbest` best final hypotheses instead of the winner alone.  The reference builds this
+ * list and keeps its head (AA/utils/BeamSearch.py:130-148: the final state, EOS-scored and length-normalised, sorted, `[0]` taken).
+ * Inputs, argument ranges, kernels, LDS limits (the ending needs no LDS of its own: for C = 45 still T <= 3995 at beam 10, T <= 663 at
+ * beam 64) and the environment switches MDD_BEAM_GENERIC / MDD_BEAM_W are those of the winner-only entry above; plus 1 <= nbest <= beam,
+ * and score_dev is required.
+ * Outputs, hypothesis-major: ids_dev [nbest,B,T] (only the first nids[n,b] entries of a row are written), nids_dev [nbest,B],
+ * score_dev [nbest,B] (length-normalised beam score), status_dev [B].  Slice n of ids / nids / score has the winner-only entry's layout,
+ * so it chains into the CTC alignment, loss and variant entries with no conversion and no copy.
+ *   - Slice 0 and status are the winner-only entry's outputs bit for bit: ids, nids, status, score.
+ *   - Slices are in the order of the reference's final sort() (BeamSearch.py:29-33,148): descending score; equal scores keep the order of
+ *     the final beam (`BHat = last.sort()[0:beamWidth]`), as Python's stable sort leaves them.
+ *   - An utterance whose status is an error has nids = 0 and score NaN in every slice, and none of its ids are written.
+ *   - There is no count output: an utterance of status 0 always has exactly `beam` final hypotheses (every kept prefix re-enters the next
+ *     state as itself, so once the empty prefix has left the top `beam` the state never shrinks below `beam`; while it holds fewer, the
+ *     empty prefix is still among them and the ending raises IndexError), so every rank < nbest exists.
+ * The score is the beam's own and no CTC likelihood (the search skips near-certain blank frames and applies its repeat rule to raw
+ * frames); the loss entry on a slice gives the exact one.  A bad argument (those of the winner-only entry, nbest outside [1,beam], a NULL
+ * score_dev) or a shape over an LDS limit returns MDD_ERR_ARG with nothing enqueued and nothing written; the message starts with the
+ * entry's name.  MDD_BEAM_DBG is not read by this entry. */
+int mdd_beam_nbest(const float *logp_dev, int32_t T, int32_t B, int32_t C, const int32_t *len_dev, int32_t beam, int32_t blank,
+                   const double *lm_dev, double lm_alpha, int32_t nbest,
+                   int32_t *ids_dev    /* [nbest,B,T] */, int32_t *nids_dev /* [nbest,B] */,
+                   int32_t *status_dev /* [B] */,         double *score_dev /* [nbest,B], required */, void *stream);
+
 /* ---- A12: nn.CTCLoss(reduction='sum') pieces (AA/steps/train_ctc.py:72,186): alpha/beta lattice.
  * logp_dev [T,B,C], targets_dev [B,Lmax] int64 (padded), in_len_dev/tgt_len_dev [B] int64 ->
  * nll_dev [B] (per-utterance negative log-likelihood; the reference's loss is their sum; +inf for an utterance with no
