@@ -237,3 +237,45 @@ def ctc_variants(logp, lens, ids, nids, blank=0, max_len=None, want_ins=True):
                                                ptr(nids), Lmax, blank, ptr(base), C.c_void_p(sub.data_ptr() if stride else ws.data_ptr()),
                                                ptr(ins), ptr(status), ptr(ws), ws.numel() * 8, _lib.current_stream_ptr()))
     return VariantResult(base, sub, ins, status)
+
+
+ConfnetResult = collections.namedtuple("ConfnetResult", "total post status")
+
+
+def ctc_confnet_max_slots(num_class):
+    """The largest ``max_slots`` ``ctc_confnet`` accepts for ``num_class`` classes (mdd_ctc_confnet_max_slots: the kernel's LDS rows)."""
+    return int(_lib.lib().mdd_ctc_confnet_max_slots(int(num_class)))
+
+
+def ctc_confnet(logp, lens, w, nslots, blank=0, max_slots=None, want_post=True):
+    """CTC over an error network (mdd_ctc_confnet): every slot of an utterance offers C weighted entries, a reading picks one per slot.
+
+    logp [T,B,C] fp32 CUDA, lens [B] as ``ctc_variants`` takes them; w [B,stride,C] fp32 log-weights (entry k != blank: the slot emits
+    k; k == blank: it emits nothing; -inf: no such arc; rows need not be normalised), nslots [B] the slots in use; ``max_slots`` bounds
+    nslots (default: w.shape[1], so the call needs no sync).  Returns ``ConfnetResult(total [B] f64, post [B,stride,C] f64 | None,
+    status [B] i32)``, absolute log values: total over all readings (weights + CTC log-likelihood of the emitted labels), post[b,j,k]
+    over the readings that pick entry k in slot j -- exp(post - total) is the posterior; rows past nslots[b] are -inf up to
+    ``max_slots`` and not written beyond it.  Nothing synchronises."""
+    assert logp.is_cuda and logp.dtype == torch.float32
+    logp = logp.contiguous()
+    T, B, Cn = logp.shape
+    dev = logp.device
+    lens = torch.as_tensor(lens).to(dev, torch.int32).contiguous()
+    w = torch.as_tensor(w).to(dev, torch.float32).contiguous()
+    nslots = torch.as_tensor(nslots).to(dev, torch.int32).contiguous()
+    if w.dim() != 3 or w.shape[0] != B or w.shape[2] != Cn or lens.shape != (B,) or nslots.shape != (B,):
+        raise ValueError("ctc_confnet: lens [B], w [B, stride, C], nslots [B]")
+    stride = w.shape[1]
+    Jmax = stride if max_slots is None else int(max_slots)
+    total = torch.empty((B,), dtype=torch.float64, device=dev)
+    post = torch.empty((B, stride, Cn), dtype=torch.float64, device=dev) if want_post else None
+    status = torch.empty((B,), dtype=torch.int32, device=dev)
+    nws = _lib.lib().mdd_ctc_confnet_workspace_bytes(T, B, Cn, max(Jmax, 0), 1 if want_post else 0)
+    ws = torch.empty((max(nws, 16) + 7) // 8, dtype=torch.float64, device=dev)      # torch's caching allocator, as ctc_loss
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().mdd_ctc_confnet(ptr(logp), T, B, Cn, ptr(lens), C.c_void_p(w.data_ptr() if stride else ws.data_ptr()), stride,
+                                              ptr(nslots), Jmax, blank, ptr(total),
+                                              None if post is None else C.c_void_p(post.data_ptr() if stride else ws.data_ptr()),
+                                              ptr(status), ptr(ws), ws.numel() * 8, _lib.current_stream_ptr()))
+    return ConfnetResult(total, post, status)

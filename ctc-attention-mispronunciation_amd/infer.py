@@ -3,6 +3,7 @@
 
     python -m ctc_attention_mispronunciation_amd.infer --conf CONF --wav_transcript_path DIR [-p cmudict] [-f cmu]
         [--cmvn PATH] [--cmudict PATH] [--precision f32x6|f32|bf16x3] [--decode_seq PATH] [--timestamps] [--posteriors] [--pronunciations] [--nbest N]
+        [--joint_posteriors [--error_prior P]]
 
 The conf YAML is read as ``infer_init`` reads it (AA/infer.py:211-261): the checkpoint
 ``checkpoint_dir/exp_name/ctc_best_model.pkl``, ``vocab_file``, ``decode_type``, ``beam_width``, ``lm_path``, ``lm_alpha``,
@@ -63,6 +64,13 @@ def parse_args(argv=None):
                     help="add N 'nbest  :' lines to each block: the N best final hypotheses of the beam search with their beam score, exact CTC "
                          "log-likelihood, share of probability among the N listed (not an absolute probability) and Comp.; needs "
                          "decode_type Beam and 1 <= N <= beam_width")
+    ap.add_argument("--joint_posteriors", action="store_true",
+                    help="add a 'jpost  :' line to each block, in the format of 'post   :': the same per-phoneme figures as marginals over the "
+                         "error network of the canonical phones -- every phoneme kept, substituted or deleted and every gap empty or filled "
+                         "at once -- so two errors in one word no longer count against each other")
+    ap.add_argument("--error_prior", type=float, default=None, metavar="P",
+                    help="with --joint_posteriors: prior probability of an error per slot, 0 < P < 1 (a position keeps its phoneme with 1 - P "
+                         "and spreads P over the C - 1 other entries; a gap stays empty with 1 - P).  Default: every entry weighs the same")
     return ap.parse_args(argv)
 
 
@@ -152,6 +160,11 @@ def main(argv=None):
     if args.phonetic_format != "cmu":
         refuse("-f %s needs the IPA tables of phonemizer / espeak, which are not available offline; use -f cmu"
                % args.phonetic_format)
+    if args.error_prior is not None:
+        if not args.joint_posteriors:
+            refuse("--error_prior: only with --joint_posteriors")
+        if not 0.0 < args.error_prior < 1.0:
+            refuse("--error_prior %r: P must lie strictly between 0 and 1" % args.error_prior)
     t0 = time.time()
     import yaml
     try:
@@ -199,7 +212,7 @@ def main(argv=None):
     device = torch.device("cuda", torch.cuda.current_device())
     c1, c2, c3 = infer(phonetic, word_dict, loader, device, model, decoder, vocab, transcripts, False,
                        decode_seq_path=args.decode_seq, timestamps=args.timestamps, posteriors=args.posteriors, pronunciations=args.pronunciations,
-                       nbest=args.nbest or 0)
+                       nbest=args.nbest or 0, joint_posteriors=args.joint_posteriors, error_prior=args.error_prior)
     print(c1, c2, c3)
     end = time.time()
     total = max(total_wav_time, 1e-9)

@@ -188,10 +188,10 @@ def diagnose_posterior(decoded_phones, canonical_phones, positions, decoder, nam
     return dict(d, post=post)
 
 
-def posterior_line(d):
+def posterior_line(d, label="post   : "):
     """The extra line of a printed block: ``post   : ph[p_correct alt:p_alt] ...`` over the canonical row without its 'I' placeholders;
     alt is the most probable single alternative -- 'del' when that is the deletion of the phoneme, else the best substitute -- and '-'
-    stands for an unknown entry."""
+    stands for an unknown entry.  ``label`` is the line's head (``jpost  : `` for the joint marginals of ``joint_posteriors``)."""
     toks = []
     for p, q, op in zip(d["canonical"], d["post"], d["path"]):
         if op == "I":
@@ -201,7 +201,7 @@ def posterior_line(d):
         else:
             alt, pa = ("del", q[1]) if q[1] >= q[3] else (q[2], q[3])
             toks.append("%s[%.2f %s:%.2f]" % (p, q[0], alt, pa))
-    return "post   : " + " ".join(toks)
+    return label + " ".join(toks)
 
 
 def seconds_per_frame(test_loader, cnn_time_stride):
@@ -249,7 +249,7 @@ def nbest_lines(records, canonical, decoder, to_display=None):
 
 
 def infer(phonetic, word_dict, test_loader, device, model, decoder, vocab, test_transcipt_dict, use_ipa, out=None,
-          decode_seq_path=None, timestamps=False, posteriors=False, pronunciations=False, nbest=0):
+          decode_seq_path=None, timestamps=False, posteriors=False, pronunciations=False, nbest=0, joint_posteriors=False, error_prior=None):
     """AA/infer.py:282-372.  Per batch ``(inputs, input_sizes, _, _, trans, trans_sizes, utt_list)``: ``model(inputs, trans)``,
     frame counts ``(input_sizes * T').long()``, ``decoder.decode``, then per utterance the 'sil' strip, 'err' removal, ``wer``,
     alignment, fault lists and score (``diagnose``), printed as the reference's 13-line block to ``out`` (stdout by default).
@@ -279,11 +279,22 @@ def infer(phonetic, word_dict, test_loader, device, model, decoder, vocab, test_
     (``nbest_lines``) before the closing empty line, after the ``time`` / ``gop`` / ``post`` lines and before ``pron``: the N best final
     hypotheses of the beam search (``decode_nbest``: the reference computes this list and keeps its head), each with its beam score, its
     exact CTC log-likelihood, its share of probability among the N and its ``Comp.`` against the block's canonical.  Rank 1 is the
-    block's decoded string.  With ``pronunciations`` the lines are the chosen candidate's.  With 0 nothing changes."""
+    block's decoded string.  With ``pronunciations`` the lines are the chosen candidate's.  With 0 nothing changes.
+
+    ``joint_posteriors=True`` (no reference counterpart) adds one line, ``jpost  :``, in the format of ``post   :`` and directly behind it
+    (in front of ``nbest`` / ``pron``): the same per-phoneme figures as marginals over the whole error network of the canonical
+    sequence -- every position kept, substituted or deleted and every gap empty or filled AT ONCE, not one edit with the rest taken as
+    canonical (``ctcDecoder.joint_phoneme_posteriors``, one call per batch).  ``error_prior`` (0 < P < 1) is the prior probability of an
+    error per slot; ``None`` weights every entry of every slot alike.  It reads only the posteriors, so it serves both model classes;
+    with ``pronunciations`` the line is the chosen candidate's.  Without it nothing changes."""
+    if error_prior is not None and not (joint_posteriors and 0.0 < error_prior < 1.0):
+        raise ValueError("error_prior needs joint_posteriors and 0 < error_prior < 1")
     if nbest and not (hasattr(decoder, "decode_nbest") and 1 <= nbest <= decoder.beam_width):
         raise ValueError("nbest needs a BeamDecoder and 1 <= nbest <= beam_width")
     if posteriors:
         from .utils.ctcDecoder import phoneme_posteriors
+    if joint_posteriors:
+        from .utils.ctcDecoder import joint_phoneme_posteriors
     if pronunciations:
         from .hip_model import ctc_variants
     out = sys.stdout if out is None else out
@@ -319,6 +330,8 @@ def infer(phonetic, word_dict, test_loader, device, model, decoder, vocab, test_
                         r["nbest"] = decoder.decode_nbest(probs, frame_lens, nbest)
                     if posteriors:
                         r["post"] = phoneme_posteriors(probs, frame_lens, trans, trans_sizes, decoder.blank_index)
+                    if joint_posteriors:
+                        r["jpost"] = joint_phoneme_posteriors(probs, frame_lens, trans, trans_sizes, decoder.blank_index, error_prior)
                     if pronunciations:
                         r["loglik"] = ctc_variants(probs, frame_lens, trans.to(torch.int32), trans_sizes.to(torch.int32), decoder.blank_index,
                                                    want_ins=False).base.cpu().tolist()
@@ -353,6 +366,11 @@ def infer(phonetic, word_dict, test_loader, device, model, decoder, vocab, test_
                         dp = diagnose_posterior(decoded[x], canonical, None if post[x] is None else post[x][0], decoder, vocab.index2word,
                                                 to_display)
                         block[-1:-1] = [posterior_line(dp)]
+                    if joint_posteriors:
+                        post = r["jpost"]
+                        dp = diagnose_posterior(decoded[x], canonical, None if post[x] is None else post[x][0], decoder, vocab.index2word,
+                                                to_display)
+                        block[-1:-1] = [posterior_line(dp, "jpost  : ")]
                     if nbest:
                         block[-1:-1] = nbest_lines(r["nbest"][x], canonical, decoder, to_display)
                     if pronunciations:

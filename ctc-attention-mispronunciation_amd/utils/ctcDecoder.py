@@ -209,6 +209,80 @@ def phoneme_posteriors(prob_tensor, frame_seq_len, ids, nids, blank=0):
     return out
 
 
+def error_network(ids, nids, num_class, blank=0, error_prior=None):
+    """The error network of the canonical ``ids`` / ``nids`` ([B, stride] / [B]) for ``hip_model.ctc_confnet``: ``(w [B, 2 stride + 1,
+    C] float32, nslots = 2 nids + 1)``.  Slot 2g is the gap before position g (entry blank: nothing inserted, entry k: k inserted), slot
+    2i + 1 is position i (entry ids[i]: the phoneme itself, entry blank: deleted, entry k: substituted by k).  ``error_prior=None``: every
+    entry of every slot has log-weight 0 -- the uniform prior ``phoneme_posteriors`` implies, under which a gap offers C - 1 insertions
+    at the weight of "nothing".  ``error_prior=P`` (0 < P < 1): a position keeps its phoneme with log(1 - P) and every other entry gets
+    log(P / (C - 1)); a gap stays empty with log(1 - P) and every insertion gets log(P / (C - 1)).  Rows at or past 2 nids + 1 are
+    filled like gaps and never read."""
+    import math
+    ids = torch.as_tensor(ids)
+    nids = torch.as_tensor(nids)
+    if ids.dim() != 2 or nids.shape != (ids.shape[0],):
+        raise ValueError("error_network: ids [B, stride], nids [B]")
+    if error_prior is not None and not 0.0 < error_prior < 1.0:
+        raise ValueError("error_network: 0 < error_prior < 1")
+    if not 0 <= blank < num_class or num_class < 2:
+        raise ValueError("error_network: blank outside [0, num_class)")
+    B, stride = ids.shape
+    dev = ids.device
+    keep, err = (0.0, 0.0) if error_prior is None else (math.log1p(-error_prior), math.log(error_prior / (num_class - 1)))
+    w = torch.full((B, 2 * stride + 1, num_class), err, dtype=torch.float32, device=dev)
+    w[:, 0::2, blank] = keep
+    if stride:
+        own = ids.to(torch.int64).clamp(0, num_class - 1).unsqueeze(2)         # an id outside [0, C) is refused by nids / status, not here
+        w[:, 1::2, :].scatter_(2, own, keep)
+    return w, (2 * nids.to(torch.int32) + 1)
+
+
+def _posterior_tuples(post, total, status, ids_h, n, blank):
+    """``phoneme_posteriors``' result from the marginals of an error network: post [B, >= 2 n + 1, C], total [B] (log values)."""
+    out = []
+    for b in range(len(n)):
+        if status[b] != 0:
+            out.append(None)
+            continue
+        with np.errstate(under="ignore"):
+            p_all = np.exp(post[b] - total[b])         # -inf entries: exactly 0
+        positions, gaps = [], []
+        for i in range(int(n[b])):
+            p = p_all[2 * i + 1]
+            own = int(ids_h[b, i])
+            alt = p.copy()
+            alt[own] = alt[blank] = -1.0
+            k = int(alt.argmax())
+            positions.append((float(p[own]), float(p[blank]), k, float(p[k])))
+        for g in range(int(n[b]) + 1):
+            p = p_all[2 * g]
+            alt = p.copy()
+            alt[blank] = -1.0
+            k = int(alt.argmax())
+            gaps.append((k, float(p[k])))
+        out.append((positions, gaps))
+    return out
+
+
+def joint_phoneme_posteriors(prob_tensor, frame_seq_len, ids, nids, blank=0, error_prior=None):
+    """``phoneme_posteriors``' result -- per utterance ``None`` or ``(positions, gaps)`` with the same tuples -- where every number is a
+    marginal over the whole error network of ``ids`` (``error_network``, mdd_ctc_confnet): all positions may be kept, substituted or
+    deleted and all gaps filled in the same reading, each reading weighted by its entries' priors and the CTC likelihood of what it
+    emits.  ``None``: ids that are no valid targets, or a network without any alignment."""
+    from ..hip_model import ctc_confnet
+    lp = _device_posteriors(prob_tensor)
+    T, B, Cn = lp.shape
+    lens = _lens_tensor(frame_seq_len, B, T, lp.device)
+    ids_h, n = torch.as_tensor(ids).cpu().numpy(), torch.as_tensor(nids).cpu().numpy()
+    valid = [0 <= int(n[b]) <= ids_h.shape[1] and all(0 <= int(v) < Cn and int(v) != blank for v in ids_h[b, :max(int(n[b]), 0)])
+             for b in range(B)]
+    Lmax = min(max(int(n.max()), 0), ids_h.shape[1]) if B else 0           # no slots past the longest row
+    w, nslots = error_network(torch.as_tensor(ids)[:, :Lmax], torch.as_tensor(nids), Cn, blank, error_prior)
+    nslots = torch.where(torch.as_tensor(valid), nslots.cpu(), torch.full((B,), -1, dtype=torch.int32))       # not a target: BAD_TARGET
+    r = ctc_confnet(lp, lens, w, nslots, blank=blank)
+    return _posterior_tuples(r.post.cpu().numpy(), r.total.cpu().numpy(), r.status.cpu().numpy(), ids_h, n, blank)
+
+
 def nbest_posteriors(loglik):
     """Float64 softmax over one utterance's N log-likelihoods: the share of probability each listed hypothesis holds AMONG THE LISTED
     ONES, not an absolute probability (what the list leaves out is not counted).  ``-inf`` entries get 0; ``None`` when every entry

@@ -332,6 +332,39 @@ int mdd_ctc_variants(const float *logp_dev, int32_t T, int32_t B, int32_t C, con
                      double *base_dev, double *sub_dev, double *ins_dev, int32_t *status_dev,
                      void *workspace_dev, int64_t workspace_bytes, void *stream);
 
+/* ---- Joint per-phoneme posteriors (no reference counterpart): CTC over an error network, a confusion network whose every slot may
+ * emit one label or nothing (csrc/ctc_confnet.hip, DESIGN.md "Error network").  logp_dev / len_dev as mdd_ctc_variants.  Utterance b has
+ * nslots_dev[b] slots, 0 <= nslots <= Jmax <= slot_stride; slot j has the C fp32 log-weights w_dev[b, j, :]: entry k != blank "slot j emits
+ * label k", entry k == blank "slot j emits nothing", -inf "no such arc"; rows need not be normalised.  A reading picks one entry r_j per
+ * slot; its labels are the non-blank r_j in slot order, its score sum_j w[j, r_j] + log P_CTC(labels | logp, len).  Readings are counted
+ * as readings: two with the same labels both count.  The readings are weighted by the given priors -- with all-zero rows every entry
+ * counts alike, so a gap slot offers C - 1 insertions at the weight of "none".  Outputs, absolute log values in fp64:
+ *   total_dev [B]                 log-sum of the scores of all readings
+ *   post_dev [B,slot_stride,C]    (nullable) [j,k]: log-sum over the readings with r_j = k; exp(post - total) is the posterior and
+ *                                 logsumexp_k post[j,:] = total for every slot; rows nslots[b] <= j < Jmax are -inf, rows >= Jmax are not
+ *                                 written.  NULL: only the forward sweep runs, total has the same bits.
+ *   status_dev [B]                mdd_align_status
+ * The network of ids[0..L) is 2L+1 slots, slot 2g = gap g, slot 2i+1 = position i.  With gap rows "blank only, 0" and position rows "own
+ * label only, 0", total is mdd_ctc_variants' base; with one position (gap) row opened to all C entries at weight 0, its post row is that
+ * call's sub (ins) row, to rounding.  len = 0: only the all-empty reading has a path.
+ * MDD_ALIGN_INFEASIBLE: no reading has a path; total -inf, the written post rows -inf.  MDD_ALIGN_BAD_TARGET (nslots[b] outside [0,Jmax],
+ * a NaN or +inf weight in a slot in use): total and the rows below Jmax NaN; other utterances are unaffected.  Arithmetic: mdd_ctc_loss's
+ * (fp64 values, fp32 exp / log increments), no log-domain subtraction -- a reading that does not exist is exactly -inf; no atomics, the
+ * same bits on every call.
+ * mdd_ctc_confnet_max_slots(C): the largest Jmax accepted for C classes -- three [Jmax, C] fp64 rows of the lattice and a [16, C] one
+ *   live in 159 KB of LDS: (20344 - 16 (C + 1)) / (3 C + 6), 139 at C = 45, 20 at C = 256 -- or -1 for C outside 2..256.
+ * workspace_dev: caller-owned scratch of at least mdd_ctc_confnet_workspace_bytes(T,B,C,Jmax,want_post) bytes (16-byte aligned; with
+ *   want_post the forward's entry flow of every frame, 8 T B C Jmax bytes, else nothing), NULL = the library allocates stream-ordered
+ *   for the call.  Nothing synchronises.
+ * Bad host arguments (a required pointer NULL, T/B/C <= 0, C > 256, blank outside [0,C), Jmax < 0, > slot_stride or >
+ *   mdd_ctc_confnet_max_slots(C), a caller workspace that is too small) return MDD_ERR_ARG before any device work. */
+int32_t mdd_ctc_confnet_max_slots(int32_t C);
+int64_t mdd_ctc_confnet_workspace_bytes(int32_t T, int32_t B, int32_t C, int32_t Jmax, int32_t want_post);
+int mdd_ctc_confnet(const float *logp_dev, int32_t T, int32_t B, int32_t C, const int32_t *len_dev,
+                    const float *w_dev, int32_t slot_stride, const int32_t *nslots_dev, int32_t Jmax, int32_t blank,
+                    double *total_dev, double *post_dev, int32_t *status_dev,
+                    void *workspace_dev, int64_t workspace_bytes, void *stream);
+
 /* ---- A10: Decoder.wer core = _edit_distance + printChanges (AA/utils/ctcDecoder.py:118-184), host.
  * a = hypothesis tokens, b = canonical tokens; ops (capacity >= na+nb): 0 '-', 1 'S', 2 'I', 3 'D'.
  * Either side empty -> MDD_ERR_EMPTY (reference: TypeError). */
