@@ -31,10 +31,9 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include <mutex>
-
-#include "mdd_internal.h"
+#include "ctc_host.h"
 #include "ctc_lse.h"
+#include "ctc_wave.h"
 
 namespace mdd {
 
@@ -48,32 +47,6 @@ __device__ __forceinline__ double lse2(double a, double b) {
     if (b == -INFINITY) return a;
     double m = fmax(a, b);
     return m + log(exp(a - m) + exp(b - m));
-}
-
-// lane i <- lane i-1 (SHR) / lane i+1 (SHL) across the whole wave; the edge lane gets -inf
-template <int CTRL>
-__device__ __forceinline__ double wave_shift(double v) {
-    const int lo = __double2loint(v), hi = __double2hiint(v);
-    const int lo2 = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xf, 0xf, false);
-    const int hi2 = __builtin_amdgcn_update_dpp((int)0xfff00000, hi, CTRL, 0xf, 0xf, false);
-    return __hiloint2double(hi2, lo2);
-}
-static constexpr int DPP_WAVE_SHL1 = 0x130, DPP_WAVE_SHR1 = 0x138;
-
-// LDS traffic of ONE wave is processed in order; this only keeps the compiler from moving accesses across the point
-__device__ __forceinline__ void wave_lds_order() {
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
-__device__ __forceinline__ float wave_sum(float x) {   // every lane returns the sum over the 64 lanes
-    x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0xB1, 0xf, 0xf, true));    // quad_perm [1,0,3,2]
-    x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x4E, 0xf, 0xf, true));    // quad_perm [2,3,0,1]
-    x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x141, 0xf, 0xf, true));   // row_half_mirror
-    x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x140, 0xf, 0xf, true));   // row_mirror
-    const int xi = __builtin_bit_cast(int, x);
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(xi, 0)) + __builtin_bit_cast(float, __builtin_amdgcn_readlane(xi, 16)) +
-           __builtin_bit_cast(float, __builtin_amdgcn_readlane(xi, 32)) + __builtin_bit_cast(float, __builtin_amdgcn_readlane(xi, 48));
 }
 
 // I: the integer type of the labels and lengths -- int64_t for mdd_ctc_loss (torch's targets), int32_t for the lattice of
@@ -303,7 +276,7 @@ __global__ __launch_bounds__(512) void ctc_wave_kernel(CtcArgs<I> a) {
             }
             g[lane * NL + j] = go;
         }
-        const float gblank = wave_sum(ge);
+        const float gblank = wave_sum_dpp(ge);
         wave_lds_order();     // the walk below sees this frame's values
         for (int c = lane; c < C; c += 64) {
             float acc = c == blank ? gblank : 0.f;
@@ -438,29 +411,27 @@ int init_ctc_attributes() {
     return MDD_OK;
 }
 
-static int ensure_ctc_attributes() {   // kernel attributes, once per device
-    static std::mutex mu;
-    static bool done[64] = {false};
-    int dev = 0;
-    MDD_HIP_CHECK(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lock(mu);
-    if (!done[dev & 63]) { if (int rc = init_ctc_attributes()) return rc; done[dev & 63] = true; }
-    return MDD_OK;
+static int ensure_ctc_attributes() {
+    static OncePerDevice once;
+    return once_per_device(once, init_ctc_attributes);
 }
-
-static int ctc_nl(int Lmax) { return Lmax <= 63 ? 1 : (Lmax <= 127 ? 2 : 4); }
 
 static bool ctc_wave_form(int T, int C, int Lmax) {
-    return Lmax <= 255 && C <= 256 && wave_smem(T, C, ctc_nl(Lmax)) <= 128 * 1024 && !(getenv("MDD_CTC") && !strcmp(getenv("MDD_CTC"), "generic"));
+    return Lmax <= 255 && C <= 256 && wave_smem(T, C, ctc_labels_per_lane(Lmax)) <= 128 * 1024 && !(getenv("MDD_CTC") && !strcmp(getenv("MDD_CTC"), "generic"));
 }
 
-// One launch of the scan for either integer type.  ws: the wave form's [B][2][T][2 (Lmax + 1)] rows, or the general form's alpha rows
-// [B][T][2 Lmax + 1] followed, when want_beta, by its beta rows; null = no rows.  The caller checks the launch.
+bool ctc_lattice_fits(int T, int C, int Lmax) {    // the general form keeps 28 bytes of LDS per state
+    return ctc_wave_form(T, C, Lmax) || (size_t)28 * (2 * (size_t)Lmax + 1) <= 150 * 1024;
+}
+
+// One launch of the scan for either integer type, at shapes ctc_lattice_fits accepts.  ws: the wave form's [B][2][T][2 (Lmax + 1)] rows, or the
+// general form's alpha rows [B][T][2 Lmax + 1] followed, when want_beta, by its beta rows (ctc_rows_bytes); null = no rows.  The caller checks
+// the launch.
 template <typename I>
-static int launch_ctc(const float *logp, int T, int B, int C, const I *targets, int tgt_stride, int Lmax, const I *in_len, const I *tgt_len,
-                      int blank, float *nll, float *grad, double *ws, bool want_beta, const char *who, hipStream_t st) {
+static void launch_ctc(const float *logp, int T, int B, int C, const I *targets, int tgt_stride, int Lmax, const I *in_len, const I *tgt_len,
+                       int blank, float *nll, float *grad, double *ws, bool want_beta, hipStream_t st) {
     if (ctc_wave_form(T, C, Lmax)) {
-        const int NL = ctc_nl(Lmax);
+        const int NL = ctc_labels_per_lane(Lmax);
         CtcArgs<I> a;
         a.logp = logp; a.T = T; a.B = B; a.C = C; a.targets = targets; a.tgt_stride = tgt_stride; a.Lmax = Lmax; a.in_len = in_len; a.tgt_len = tgt_len;
         a.blank = blank; a.nll = nll; a.grad = grad; a.ws = ws; a.SP = 2 * (Lmax + 1);
@@ -471,21 +442,18 @@ static int launch_ctc(const float *logp, int T, int B, int C, const I *targets, 
     } else {
         const int Smax = 2 * Lmax + 1;
         const size_t smem = sizeof(double) * 3 * (size_t)Smax + sizeof(int) * (size_t)Smax;
-        if (smem > 150 * 1024) { set_error("%s: Lmax=%d too long for LDS", who, Lmax); return MDD_ERR_ARG; }
         hipLaunchKernelGGL(ctc_generic_kernel<I>, dim3(B), dim3(256), smem, st, logp, T, B, C, targets, tgt_stride, Lmax, in_len, tgt_len, blank,
                            nll, grad, ws, (ws && want_beta) ? ws + (size_t)B * T * Smax : nullptr, Smax);
     }
-    return MDD_OK;
 }
 
-bool ctc_lattice_fits(int T, int C, int Lmax) {    // the general form keeps 28 bytes of LDS per state
-    return ctc_wave_form(T, C, Lmax) || (size_t)28 * (2 * (size_t)Lmax + 1) <= 150 * 1024;
-}
-
-int64_t ctc_lattice_bytes(int T, int B, int C, int Lmax) {
+// bytes of the lattice rows launch_ctc keeps in ws
+static int64_t ctc_rows_bytes(int T, int B, int C, int Lmax, bool want_beta) {
     if (ctc_wave_form(T, C, Lmax)) return (int64_t)sizeof(double) * B * 2 * T * (2 * ((int64_t)Lmax + 1));
-    return (int64_t)sizeof(double) * 2 * B * T * (2 * (int64_t)Lmax + 1);
+    return (int64_t)sizeof(double) * (want_beta ? 2 : 1) * B * T * (2 * (int64_t)Lmax + 1);
 }
+
+int64_t ctc_lattice_bytes(int T, int B, int C, int Lmax) { return ctc_rows_bytes(T, B, C, Lmax, true); }
 
 int ctc_lattice(const float *logp, int T, int B, int C, const int32_t *len, const int32_t *ids, int ids_stride, const int32_t *nids, int Lmax,
                 int blank, double *ws, hipStream_t st, CtcLattice *out) {
@@ -497,7 +465,8 @@ int ctc_lattice(const float *logp, int T, int B, int C, const int32_t *len, cons
         const long long Smax = 2 * (long long)Lmax + 1;
         out->alpha = ws; out->beta = ws + (size_t)B * T * Smax; out->utt_stride = T * Smax; out->pitch = (int)Smax;
     }
-    return launch_ctc<int32_t>(logp, T, B, C, ids, ids_stride, Lmax, len, nids, blank, nullptr, nullptr, ws, true, "mdd_ctc_variants", st);
+    launch_ctc<int32_t>(logp, T, B, C, ids, ids_stride, Lmax, len, nids, blank, nullptr, nullptr, ws, true, st);
+    return MDD_OK;
 }
 
 }  // namespace mdd
@@ -505,33 +474,27 @@ int ctc_lattice(const float *logp, int T, int B, int C, const int32_t *len, cons
 // bytes of workspace mdd_ctc_loss needs for these shapes when a gradient is requested (0 without one)
 extern "C" int64_t mdd_ctc_workspace_bytes(int32_t T, int32_t B, int32_t C, int32_t Lmax, int32_t want_grad) {
     if (!want_grad || T <= 0 || B <= 0 || Lmax < 0) return 0;
-    if (mdd::ctc_wave_form(T, C, Lmax)) return (int64_t)sizeof(double) * B * 2 * T * (2 * ((int64_t)Lmax + 1));
-    return (int64_t)sizeof(double) * B * T * (2 * (int64_t)Lmax + 1);
+    return mdd::ctc_rows_bytes(T, B, C, Lmax, false);
 }
 
 extern "C" int mdd_ctc_loss(const float *logp_dev, int32_t T, int32_t B, int32_t C, const int64_t *targets_dev,
                             int32_t Lmax, const int64_t *in_len_dev, const int64_t *tgt_len_dev, int32_t blank,
                             float *nll_dev, float *grad_dev, void *workspace_dev, int64_t workspace_bytes, void *stream) {
     using namespace mdd;
-    if (!logp_dev || !targets_dev || !in_len_dev || !tgt_len_dev || !nll_dev || T <= 0 || B <= 0 || C <= 0 || Lmax < 0 ||
-        blank < 0 || blank >= C) {
-        set_error("mdd_ctc_loss: bad argument"); return MDD_ERR_ARG;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    if (int rc = ensure_ctc_attributes()) return rc;
+    const char *what = !logp_dev ? "logp_dev is NULL" : !targets_dev ? "targets_dev is NULL" : !in_len_dev ? "in_len_dev is NULL"
+                     : !tgt_len_dev ? "tgt_len_dev is NULL" : !nll_dev ? "nll_dev is NULL" : T <= 0 ? "T <= 0" : B <= 0 ? "B <= 0" : C <= 0 ? "C <= 0"
+                     : (blank < 0 || blank >= C) ? "blank outside [0, C)" : Lmax < 0 ? "Lmax < 0" : !ctc_lattice_fits(T, C, Lmax) ? "Lmax too long for LDS"
+                     : nullptr;
+    if (what) { set_error("mdd_ctc_loss: %s", what); return MDD_ERR_ARG; }
     const int64_t need = mdd_ctc_workspace_bytes(T, B, C, Lmax, grad_dev != nullptr);
-    double *ws = reinterpret_cast<double *>(workspace_dev);
-    bool own_ws = false;
-    if (need > 0 && (!ws || workspace_bytes < need)) {
-        if (ws) { set_error("mdd_ctc_loss: workspace of %lld bytes, need %lld (mdd_ctc_workspace_bytes)", (long long)workspace_bytes, (long long)need); return MDD_ERR_ARG; }
-        MDD_HIP_CHECK(hipMallocAsync((void **)&ws, (size_t)need, st));   // no caller workspace: stream-ordered allocation
-        own_ws = true;
-    }
-    const int rc = launch_ctc<int64_t>(logp_dev, T, B, C, targets_dev, Lmax, Lmax, in_len_dev, tgt_len_dev, blank, nll_dev, grad_dev,
-                                       grad_dev ? ws : nullptr, false, "mdd_ctc_loss", st);
-    if (rc) { if (own_ws) (void)hipFreeAsync(ws, st); return rc; }
-    hipError_t le = hipGetLastError();
-    if (own_ws) (void)hipFreeAsync(ws, st);
+    if (workspace_dev && workspace_bytes < need) return refuse_workspace("mdd_ctc_loss", "mdd_ctc_workspace_bytes", workspace_bytes, need);
+    if (int rc = ensure_ctc_attributes()) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    StreamWorkspace ws;
+    if (int rc = ws.acquire(workspace_dev, need, st)) return rc;
+    launch_ctc<int64_t>(logp_dev, T, B, C, targets_dev, Lmax, Lmax, in_len_dev, tgt_len_dev, blank, nll_dev, grad_dev,
+                        grad_dev ? ws.as<double>() : nullptr, false, st);
+    const hipError_t le = hipGetLastError();
     if (le != hipSuccess) { set_error("ctc kernel launch failed: %s", hipGetErrorString(le)); return MDD_ERR_HIP; }
     return MDD_OK;
 }

@@ -25,25 +25,12 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include <mutex>
-
-#include "mdd_internal.h"
+#include "ctc_host.h"
+#include "ctc_wave.h"
 
 namespace mdd {
 
-static constexpr int ALIGN_DPP_WAVE_SHR1 = 0x138;
 static constexpr size_t ALIGN_LDS_LIMIT = 150 * 1024;
-
-// lane i <- lane i-1 across the whole wave; lane 0 gets -inf
-__device__ __forceinline__ float align_shift_right(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp((int)0xff800000, __builtin_bit_cast(int, v), ALIGN_DPP_WAVE_SHR1, 0xf, 0xf, false));
-}
-
-// LDS traffic of ONE wave is processed in order; this only keeps the compiler from moving accesses across the point
-__device__ __forceinline__ void align_lds_order() {
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
 
 struct AlignArgs {
     const float *logp; int T, B, C;
@@ -181,7 +168,7 @@ __global__ __launch_bounds__(256) void ctc_align_wave_kernel(AlignArgs a) {
 #pragma unroll
                 for (int j = 0; j < NL; j++) nl[j] = row[lab[j]];
             }
-            const float from_left = align_shift_right(ao[NL - 1]);
+            const float from_left = wave_shift<DPP_WAVE_SHR1>(ao[NL - 1]);
             float ne[NL], no[NL];
             unsigned moves = 0;
 #pragma unroll
@@ -210,7 +197,7 @@ __global__ __launch_bounds__(256) void ctc_align_wave_kernel(AlignArgs a) {
             if (i == L) s_fin[0] = ae[j];
             if (i == L - 1) s_fin[1] = ao[j];
         }
-        align_lds_order();
+        wave_lds_order();
         if (lane == 0) {
             const float f0 = s_fin[0], f1 = L > 0 ? s_fin[1] : -INFINITY;
             const bool last_blank = L == 0 || f0 > f1;
@@ -323,11 +310,9 @@ __global__ __launch_bounds__(256) void ctc_align_generic_kernel(AlignArgs a) {
     align_outputs(a, b, Tb, s_ok != 0, path_w, edges, lp, lp_stride, lab, 2, 1);
 }
 
-static int align_nl(int Lmax) { return Lmax <= 63 ? 1 : (Lmax <= 127 ? 2 : 4); }
-
 static bool align_wave_form(int T, int C, int Lmax) {
     const char *e = getenv("MDD_CTC_ALIGN");
-    return Lmax <= 255 && C <= 256 && align_wave_smem(T, C, align_nl(Lmax)) <= ALIGN_LDS_LIMIT && !(e && !strcmp(e, "generic"));
+    return Lmax <= 255 && C <= 256 && align_wave_smem(T, C, ctc_labels_per_lane(Lmax)) <= ALIGN_LDS_LIMIT && !(e && !strcmp(e, "generic"));
 }
 
 static long long align_generic_ws_utt(int T, int Lmax) {
@@ -365,35 +350,22 @@ extern "C" int mdd_ctc_align(const float *logp_dev, int32_t T, int32_t B, int32_
                      : nullptr;
     if (what) { set_error("mdd_ctc_align: %s", what); return MDD_ERR_ARG; }
     const int64_t need = mdd_ctc_align_workspace_bytes(T, B, C, Lmax);
-    if (workspace_dev && workspace_bytes < need) {
-        set_error("mdd_ctc_align: workspace_bytes %lld, need %lld (mdd_ctc_align_workspace_bytes)", (long long)workspace_bytes, (long long)need);
-        return MDD_ERR_ARG;
-    }
+    if (workspace_dev && workspace_bytes < need) return refuse_workspace("mdd_ctc_align", "mdd_ctc_align_workspace_bytes", workspace_bytes, need);
     const bool wave_form = align_wave_form(T, C, Lmax);
     const int S4 = (2 * Lmax + 1 + 3) / 4;
     const size_t generic_smem = (size_t)48 * S4;
     if (!wave_form && generic_smem > ALIGN_LDS_LIMIT) { set_error("mdd_ctc_align: Lmax=%d too long for LDS", Lmax); return MDD_ERR_ARG; }
     hipStream_t st = (hipStream_t)stream;
-    {   // kernel attributes, once per device
-        static std::mutex mu;
-        static bool done[64] = {false};
-        int dev = 0;
-        MDD_HIP_CHECK(hipGetDevice(&dev));
-        std::lock_guard<std::mutex> lock(mu);
-        if (!done[dev & 63]) { if (int rc = init_align_attributes()) return rc; done[dev & 63] = true; }
-    }
-    unsigned char *ws = reinterpret_cast<unsigned char *>(workspace_dev);
-    bool own_ws = false;
-    if (need > 0 && !ws) {
-        MDD_HIP_CHECK(hipMallocAsync((void **)&ws, (size_t)need, st));   // no caller workspace: stream-ordered allocation
-        own_ws = true;
-    }
+    static OncePerDevice once;
+    if (int rc = once_per_device(once, init_align_attributes)) return rc;
+    StreamWorkspace ws;
+    if (int rc = ws.acquire(workspace_dev, need, st)) return rc;
     AlignArgs a;
     a.logp = logp_dev; a.T = T; a.B = B; a.C = C; a.len = len_dev; a.ids = ids_dev; a.ids_stride = ids_stride; a.nids = nids_dev;
     a.Lmax = Lmax; a.blank = blank; a.score = score_dev; a.status = status_dev; a.path = path_dev; a.seg = seg_dev; a.seg_logp = seg_logp_dev;
-    a.ws = ws; a.ws_utt = align_generic_ws_utt(T, Lmax); a.S4 = S4;
+    a.ws = ws.as<unsigned char>(); a.ws_utt = align_generic_ws_utt(T, Lmax); a.S4 = S4;
     if (wave_form) {
-        const int NL = align_nl(Lmax);
+        const int NL = ctc_labels_per_lane(Lmax);
         const size_t smem = align_wave_smem(T, C, NL);
         if (NL == 1) hipLaunchKernelGGL(ctc_align_wave_kernel<1>, dim3(B), dim3(256), smem, st, a);
         else if (NL == 2) hipLaunchKernelGGL(ctc_align_wave_kernel<2>, dim3(B), dim3(256), smem, st, a);
@@ -401,8 +373,7 @@ extern "C" int mdd_ctc_align(const float *logp_dev, int32_t T, int32_t B, int32_
     } else {
         hipLaunchKernelGGL(ctc_align_generic_kernel, dim3(B), dim3(256), generic_smem, st, a);
     }
-    hipError_t le = hipGetLastError();
-    if (own_ws) (void)hipFreeAsync(ws, st);
+    const hipError_t le = hipGetLastError();
     if (le != hipSuccess) { set_error("ctc align kernel launch failed: %s", hipGetErrorString(le)); return MDD_ERR_HIP; }
     return MDD_OK;
 }

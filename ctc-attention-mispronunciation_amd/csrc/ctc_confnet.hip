@@ -34,10 +34,10 @@
 // does not hold it.  The lane that holds the maximum sums the others against the second maximum when that lies far below (excl_all),
 // so every sum has a term near 1.  No atomics: the same bits on every call.
 #include <math.h>
-#include <mutex>
 
-#include "mdd_internal.h"
+#include "ctc_host.h"
 #include "ctc_lse.h"
+#include "ctc_wave.h"
 
 namespace mdd {
 
@@ -64,10 +64,6 @@ __device__ __forceinline__ float wave_maxf(float v) {
     for (int o = 32; o; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
     return v;
 }
-__device__ __forceinline__ float wave_sum(float v) {     // butterfly: every lane ends with the same bits
-    for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 // inc: the sum over the wave (the same bits in every lane); returns the sum over every lane but the own one.  At each level of the
 // butterfly a lane takes the sum of the sibling group, which does not hold it: an exclusive sum without a subtraction.
 __device__ __forceinline__ float wave_excl_sum(float &inc) {
@@ -88,7 +84,7 @@ template <int NP> __device__ __forceinline__ double lse_all(const double (&u)[NP
     const double mm = (m == -INFINITY) ? 0.0 : m;
     float s = 0.f;
     for (int p = 0; p < NP; p++) s += fexp((float)(u[p] - mm));
-    return mm + (double)flog(wave_sum(s));
+    return mm + (double)flog(wave_sum_butterfly(s));
 }
 
 // ex[p] = (+) over every value of the wave but the lane's own v[p]; all = (+) over every value.  The reference point m1 is the maximum
@@ -124,7 +120,7 @@ template <int NP> __device__ __forceinline__ void excl_all(const double (&v)[NP]
     if (mf - m2f > EXCL_FAR) {      // also m2 == -inf: the holder's sum is then empty
         float r = 0.f;
         for (int p = 0; p < NP; p++) if (!(p == ap && lane == al)) r += fexp((float)(v[p] - mm2));
-        const double far = mm2 + (double)flog(wave_sum(r));
+        const double far = mm2 + (double)flog(wave_sum_butterfly(r));
         for (int p = 0; p < NP; p++) if (p == ap && lane == al) ex[p] = far;
     }
 }
@@ -342,18 +338,10 @@ template <int NP> __global__ __launch_bounds__(64 * CN_WAVES) void ctc_confnet_k
     }
 }
 
-static int ensure_confnet_attributes() {   // kernel attributes, once per device
-    static std::mutex mu;
-    static bool done[64] = {false};
-    int dev = 0;
-    MDD_HIP_CHECK(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lock(mu);
-    if (!done[dev & 63]) {
-        const void *k[] = {(const void *)ctc_confnet_kernel<1>, (const void *)ctc_confnet_kernel<2>, (const void *)ctc_confnet_kernel<3>,
-                           (const void *)ctc_confnet_kernel<4>};
-        for (const void *f : k) MDD_HIP_CHECK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CN_LDS_LIMIT));
-        done[dev & 63] = true;
-    }
+static int init_confnet_attributes() {
+    const void *k[] = {(const void *)ctc_confnet_kernel<1>, (const void *)ctc_confnet_kernel<2>, (const void *)ctc_confnet_kernel<3>,
+                       (const void *)ctc_confnet_kernel<4>};
+    for (const void *f : k) MDD_HIP_CHECK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CN_LDS_LIMIT));
     return MDD_OK;
 }
 
@@ -380,21 +368,15 @@ extern "C" int mdd_ctc_confnet(const float *logp_dev, int32_t T, int32_t B, int3
                      : nullptr;
     if (what) { set_error("mdd_ctc_confnet: %s", what); return MDD_ERR_ARG; }
     const int64_t need = mdd_ctc_confnet_workspace_bytes(T, B, C, Jmax, post_dev != nullptr);
-    if (workspace_dev && workspace_bytes < need) {
-        set_error("mdd_ctc_confnet: workspace_bytes %lld, need %lld (mdd_ctc_confnet_workspace_bytes)", (long long)workspace_bytes, (long long)need);
-        return MDD_ERR_ARG;
-    }
-    if (int rc = ensure_confnet_attributes()) return rc;
+    if (workspace_dev && workspace_bytes < need) return refuse_workspace("mdd_ctc_confnet", "mdd_ctc_confnet_workspace_bytes", workspace_bytes, need);
+    static OncePerDevice once;
+    if (int rc = once_per_device(once, init_confnet_attributes)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    double *ws = reinterpret_cast<double *>(workspace_dev);
-    bool own_ws = false;
-    if (!ws && need > 0) {
-        MDD_HIP_CHECK(hipMallocAsync((void **)&ws, (size_t)need, st));   // no caller workspace: stream-ordered allocation
-        own_ws = true;
-    }
+    StreamWorkspace ws;
+    if (int rc = ws.acquire(workspace_dev, need, st)) return rc;
     ConfnetArgs a;
     a.logp = logp_dev; a.T = T; a.B = B; a.C = C; a.len = len_dev; a.w = w_dev; a.slot_stride = slot_stride; a.nslots = nslots_dev;
-    a.Jmax = Jmax; a.blank = blank; a.total = total_dev; a.post = post_dev; a.status = status_dev; a.ws = ws;
+    a.Jmax = Jmax; a.blank = blank; a.total = total_dev; a.post = post_dev; a.status = status_dev; a.ws = ws.as<double>();
     a.ws_utt = (size_t)T * C * Jmax;
     const size_t lds = confnet_lds_doubles(C, Jmax) * 8;
     const dim3 grid(B), block(64 * CN_WAVES);
@@ -405,7 +387,6 @@ extern "C" int mdd_ctc_confnet(const float *logp_dev, int32_t T, int32_t B, int3
         default: hipLaunchKernelGGL(ctc_confnet_kernel<4>, grid, block, lds, st, a); break;
     }
     const hipError_t le = hipGetLastError();
-    if (own_ws) (void)hipFreeAsync(ws, st);
     if (le != hipSuccess) { set_error("ctc confnet kernel launch failed: %s", hipGetErrorString(le)); return MDD_ERR_HIP; }
     return MDD_OK;
 }

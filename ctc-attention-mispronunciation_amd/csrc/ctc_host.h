@@ -1,0 +1,65 @@
+// The host shape of a CTC lattice entry (mdd_ctc_loss, mdd_ctc_align, mdd_ctc_variants, mdd_ctc_confnet, the beam entries), host code only:
+//   1. refuse    every bad argument by name, then a caller workspace that is too small (refuse_workspace) -- before any HIP call;
+//   2. attributes the kernels' LDS budgets, once per device (once_per_device);
+//   3. workspace the caller's, or one allocated on the stream for the call (StreamWorkspace);
+//   4. launch;
+//   5. check     hipGetLastError, with the workspace still in scope: its free is enqueued behind the last launch on every return path.
+#pragma once
+#include <mutex>
+
+#include "mdd_internal.h"
+
+namespace mdd {
+
+// init() runs once per device of the process (kernel attributes belong to the device that is current when they are set), under a lock;
+// an init that fails runs again on the next call.  One state per family of kernels, a static of the entry that launches them.
+struct OncePerDevice {
+    std::mutex mu;
+    bool done[64] = {false};
+};
+template <class Init> int once_per_device(OncePerDevice &s, Init init) {
+    int dev = 0;
+    MDD_HIP_CHECK(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lock(s.mu);
+    if (!s.done[dev & 63]) {
+        if (int rc = init()) return rc;
+        s.done[dev & 63] = true;
+    }
+    return MDD_OK;
+}
+
+// Scratch for one call: the caller's pointer when one is given, else `need` bytes allocated stream-ordered (none for need == 0) and freed
+// on the same stream by the destructor.  Declare it in front of the launches and let it live to the entry's return: the free then follows
+// the last launch whichever return is taken.
+class StreamWorkspace {
+public:
+    StreamWorkspace() = default;
+    StreamWorkspace(const StreamWorkspace &) = delete;
+    StreamWorkspace &operator=(const StreamWorkspace &) = delete;
+    StreamWorkspace(StreamWorkspace &&o) noexcept : p_(o.p_), owned_(o.owned_), st_(o.st_) { o.p_ = o.owned_ = nullptr; }
+    ~StreamWorkspace() { if (owned_) (void)hipFreeAsync(owned_, st_); }
+    int acquire(void *caller, int64_t need, hipStream_t st) {
+        p_ = caller;
+        if (caller || need <= 0) return MDD_OK;
+        MDD_HIP_CHECK(hipMallocAsync(&owned_, (size_t)need, st));
+        p_ = owned_;
+        st_ = st;
+        return MDD_OK;
+    }
+    template <class T> T *as() const { return static_cast<T *>(p_); }
+
+private:
+    void *p_ = nullptr, *owned_ = nullptr;
+    hipStream_t st_ = nullptr;
+};
+
+// The refusal of a caller workspace of `given` bytes where `bytes_fn` asks for `need`
+inline int refuse_workspace(const char *entry, const char *bytes_fn, int64_t given, int64_t need) {
+    set_error("%s: workspace_bytes %lld, need %lld (%s)", entry, (long long)given, (long long)need, bytes_fn);
+    return MDD_ERR_ARG;
+}
+
+// consecutive labels a lane owns in the wave forms of the lattice (ctc_wave_kernel, ctc_align_wave_kernel): 64 NL >= Lmax + 1 up to Lmax = 255
+inline int ctc_labels_per_lane(int Lmax) { return Lmax <= 63 ? 1 : (Lmax <= 127 ? 2 : 4); }
+
+}  // namespace mdd

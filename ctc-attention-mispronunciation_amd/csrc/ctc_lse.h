@@ -1,4 +1,4 @@
-// fp64 value, fp32 increment log-adds of the CTC lattices (ctc.hip's header comment; shared with ctc_variants.hip):
+// fp64 value, fp32 increment log-adds of the CTC lattices (ctc.hip's header comment; shared by ctc.hip, ctc_variants.hip and ctc_confnet.hip):
 //   m + log(sum exp(x - m)),  the differences and the exp / log in fp32 on the hardware transcendental units (v_exp_f32 / v_log_f32, 1 ulp).
 // The terms are <= 1 and the largest is exactly 1, so one log-add's absolute error is ~1e-7 whatever the magnitude of the values.
 // All-(-inf) operands give -inf, never NaN.

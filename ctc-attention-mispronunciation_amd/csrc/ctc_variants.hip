@@ -28,7 +28,7 @@
 #include <math.h>
 #include <stdlib.h>
 
-#include "mdd_internal.h"
+#include "ctc_host.h"
 #include "ctc_lse.h"
 
 namespace mdd {
@@ -179,10 +179,7 @@ extern "C" int mdd_ctc_variants(const float *logp_dev, int32_t T, int32_t B, int
                      : Lmax < 0 ? "Lmax < 0" : Lmax > ids_stride ? "Lmax > ids_stride" : !ctc_lattice_fits(T, C, Lmax) ? "Lmax too long for LDS" : nullptr;
     if (what) { set_error("mdd_ctc_variants: %s", what); return MDD_ERR_ARG; }
     const int64_t need = mdd_ctc_variants_workspace_bytes(T, B, C, Lmax);
-    if (workspace_dev && workspace_bytes < need) {
-        set_error("mdd_ctc_variants: workspace_bytes %lld, need %lld (mdd_ctc_variants_workspace_bytes)", (long long)workspace_bytes, (long long)need);
-        return MDD_ERR_ARG;
-    }
+    if (workspace_dev && workspace_bytes < need) return refuse_workspace("mdd_ctc_variants", "mdd_ctc_variants_workspace_bytes", workspace_bytes, need);
     VariantArgs a;
     a.nslots = Lmax + (ins_dev ? Lmax + 1 : 0);
     int waves = VAR_WAVES;
@@ -190,23 +187,17 @@ extern "C" int mdd_ctc_variants(const float *logp_dev, int32_t T, int32_t B, int
     a.nblk = (a.nslots + waves - 1) / waves;
     if ((int64_t)B * a.nblk > 0x7fffffffLL) { set_error("mdd_ctc_variants: B x Lmax too large for one launch"); return MDD_ERR_ARG; }
     hipStream_t st = (hipStream_t)stream;
-    double *ws = reinterpret_cast<double *>(workspace_dev);
-    bool own_ws = false;
-    if (!ws) {
-        MDD_HIP_CHECK(hipMallocAsync((void **)&ws, (size_t)need, st));   // no caller workspace: stream-ordered allocation
-        own_ws = true;
-    }
-    int rc = ctc_lattice(logp_dev, T, B, C, len_dev, ids_dev, ids_stride, nids_dev, Lmax, blank, ws, st, &a.lat);
-    hipError_t le = rc ? hipSuccess : hipGetLastError();
-    if (!rc && le == hipSuccess) {
+    StreamWorkspace ws;
+    if (int rc = ws.acquire(workspace_dev, need, st)) return rc;
+    if (int rc = ctc_lattice(logp_dev, T, B, C, len_dev, ids_dev, ids_stride, nids_dev, Lmax, blank, ws.as<double>(), st, &a.lat)) return rc;
+    hipError_t le = hipGetLastError();
+    if (le == hipSuccess) {
         a.logp = logp_dev; a.T = T; a.B = B; a.C = C; a.len = len_dev; a.ids = ids_dev; a.ids_stride = ids_stride; a.nids = nids_dev;
         a.Lmax = Lmax; a.blank = blank; a.base = base_dev; a.sub = sub_dev; a.ins = ins_dev; a.status = status_dev;
         hipLaunchKernelGGL(ctc_variants_head_kernel, dim3(B), dim3(64), 0, st, a);
         if (a.nslots > 0) hipLaunchKernelGGL(ctc_variants_kernel, dim3((unsigned)(B * a.nblk)), dim3(64 * waves), 0, st, a);
         le = hipGetLastError();
     }
-    if (own_ws) (void)hipFreeAsync(ws, st);
-    if (rc) return rc;
     if (le != hipSuccess) { set_error("ctc variants kernel launch failed: %s", hipGetErrorString(le)); return MDD_ERR_HIP; }
     return MDD_OK;
 }

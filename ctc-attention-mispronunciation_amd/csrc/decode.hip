@@ -4,7 +4,7 @@
 // BeamDecoder.decode -> ctcBeamSearch.decode (AA/utils/ctcDecoder.py:215-226, AA/utils/BeamSearch.py:73-153).
 // Both are serial scans over the posterior frames of one utterance; they are latency-bound, not
 // bandwidth- or flop-bound (180 B read per frame).  One workgroup per utterance.
-#include "mdd_internal.h"
+#include "ctc_host.h"
 #include <type_traits>
 
 namespace mdd {
@@ -902,10 +902,10 @@ static int beam_dispatch(bool nb, const float *logp_dev, int32_t T, int32_t B, i
     const size_t pw = (beam_fast_wave_bytes(NS, beam, Tcap) + 15) & ~(size_t)15;
     const size_t lds_max = 160 * 1024;
     if (fast && lmb + pw > lds_max) { set_error("%s: T too long for LDS (%zu B)", who, lmb + pw); return MDD_ERR_ARG; }
-    // once: the LDS budgets of every instantiation.  The winner-only kernels are named first, in the order they always were, and the
-    // N-best ones after them: kernels are emitted in the order of their first use, so mdd_beam's keep their places in the code object
-    static bool attr_set = false;
-    if (!attr_set) {
+    // once per device: the LDS budgets of every instantiation.  The winner-only kernels are named first, in the order they always were, and
+    // the N-best ones after them: kernels are emitted in the order of their first use, so mdd_beam's keep their places in the code object
+    static OncePerDevice once;
+    const int arc = once_per_device(once, []() -> int {
         MDD_HIP_CHECK(hipFuncSetAttribute((const void *)beam_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
         MDD_HIP_CHECK(hipFuncSetAttribute((const void *)beam_fast_kernel<8, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
         MDD_HIP_CHECK(hipFuncSetAttribute((const void *)beam_fast_kernel<16, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
@@ -914,14 +914,15 @@ static int beam_dispatch(bool nb, const float *logp_dev, int32_t T, int32_t B, i
         MDD_HIP_CHECK(hipFuncSetAttribute((const void *)beam_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024));
         MDD_HIP_CHECK(hipFuncSetAttribute((const void *)beam_fast_kernel<8, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
         MDD_HIP_CHECK(hipFuncSetAttribute((const void *)beam_fast_kernel<16, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
-        attr_set = true;
-    }
+        return MDD_OK;
+    });
+    if (arc) return arc;
     // stream-ordered scratch for the frame pre-pass: log-probabilities in fp64 + per-frame flags
-    double *lpw = nullptr;
-    unsigned char *flags = nullptr;
     const size_t n = (size_t)T * B * C;
-    MDD_HIP_CHECK(hipMallocAsync((void **)&lpw, n * sizeof(double) + (size_t)T * B, st));
-    flags = reinterpret_cast<unsigned char *>(lpw + n);
+    StreamWorkspace ws;
+    if (int rc = ws.acquire(nullptr, (int64_t)(n * sizeof(double) + (size_t)T * B), st)) return rc;
+    double *lpw = ws.as<double>();
+    unsigned char *flags = reinterpret_cast<unsigned char *>(lpw + n);
     int grid = (int)((n + 255) / 256);
     if (grid > 2048) grid = 2048;
     hipLaunchKernelGGL(beam_prep_kernel, dim3(grid), dim3(256), 0, st, logp_dev, T, B, C, blank, lpw, flags);
@@ -949,8 +950,7 @@ static int beam_dispatch(bool nb, const float *logp_dev, int32_t T, int32_t B, i
         if (nb) MDD_BEAM_GEN(true, nbest); else MDD_BEAM_GEN(false, dbg);
 #undef MDD_BEAM_GEN
     }
-    hipError_t le = hipGetLastError();
-    (void)hipFreeAsync(lpw, st);
+    const hipError_t le = hipGetLastError();
     if (le != hipSuccess) { set_error("beam kernel launch failed: %s", hipGetErrorString(le)); return MDD_ERR_HIP; }
     return MDD_OK;
 }

@@ -144,24 +144,45 @@ class HipModel(object):
             pass
 
 
+class _CtcCall(object):
+    """What the four CTC lattice functions share: ``logp`` contiguous fp32 [T,B,C] on its device, conversion of the other arrays to that
+    device, and one call of an entry that ends ``..., workspace_dev, workspace_bytes, stream``."""
+
+    def __init__(self, logp):
+        assert logp.is_cuda and logp.dtype == torch.float32
+        self.logp = logp.contiguous()
+        self.T, self.B, self.C = self.logp.shape
+        self.dev = self.logp.device
+        self.ws = None
+
+    def to(self, x, dtype):
+        return torch.as_tensor(x).to(self.dev, dtype).contiguous()
+
+    def empty(self, shape, dtype, want=True):
+        return torch.empty(shape, dtype=dtype, device=self.dev) if want else None
+
+    def workspace(self, bytes_fn, *shape):
+        """The call's scratch from torch's caching allocator (stream-ordered, no hipMalloc per call), sized by ``bytes_fn(T, B, C, *shape)``."""
+        nws = bytes_fn(self.T, self.B, self.C, *shape)
+        self.ws = torch.empty((max(nws, 16) + 7) // 8, dtype=torch.float64, device=self.dev)
+
+    def ptr(self, t, rows=1):
+        """Device address of ``t`` (None: NULL); an empty [B, 0] array (``rows`` = 0) passes the workspace's address in its place."""
+        return None if t is None else C.c_void_p(t.data_ptr() if rows else self.ws.data_ptr())
+
+    def __call__(self, entry, *args):
+        with torch.cuda.device(self.dev):
+            _lib.check(entry(self.ptr(self.logp), self.T, self.B, self.C, *args, self.ptr(self.ws), self.ws.numel() * 8, _lib.current_stream_ptr()))
+
+
 def ctc_loss(logp, targets, in_len, tgt_len, blank=0, want_grad=True):
     """nn.CTCLoss(reduction='sum') pieces on the GPU: returns (nll [B], grad [T,B,C] or None)."""
-    assert logp.is_cuda and logp.dtype == torch.float32
-    logp = logp.contiguous()
-    T, B, Cn = logp.shape
-    dev = logp.device
-    tg = targets.to(dev, torch.int64).contiguous()
-    il = in_len.to(dev, torch.int64).contiguous()
-    tl = tgt_len.to(dev, torch.int64).contiguous()
-    nll = torch.empty((B,), dtype=torch.float32, device=dev)
-    grad = torch.empty_like(logp) if want_grad else None
-    nws = _lib.lib().mdd_ctc_workspace_bytes(T, B, Cn, tg.shape[1], 1 if want_grad else 0)
-    ws = torch.empty((max(nws, 16) + 7) // 8, dtype=torch.float64, device=dev)      # torch's caching allocator: stream-ordered, no hipMalloc per call
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().mdd_ctc_loss(C.c_void_p(logp.data_ptr()), T, B, Cn, C.c_void_p(tg.data_ptr()), tg.shape[1],
-                                           C.c_void_p(il.data_ptr()), C.c_void_p(tl.data_ptr()), blank,
-                                           C.c_void_p(nll.data_ptr()), C.c_void_p(grad.data_ptr()) if want_grad else None,
-                                           C.c_void_p(ws.data_ptr()), ws.numel() * 8, _lib.current_stream_ptr()))
+    c = _CtcCall(logp)
+    tg, il, tl = c.to(targets, torch.int64), c.to(in_len, torch.int64), c.to(tgt_len, torch.int64)
+    nll = c.empty((c.B,), torch.float32)
+    grad = torch.empty_like(c.logp) if want_grad else None
+    c.workspace(_lib.lib().mdd_ctc_workspace_bytes, tg.shape[1], 1 if want_grad else 0)
+    c(_lib.lib().mdd_ctc_loss, c.ptr(tg), tg.shape[1], c.ptr(il), c.ptr(tl), blank, c.ptr(nll), c.ptr(grad))
     return nll, grad
 
 
@@ -177,29 +198,19 @@ def ctc_align(logp, lens, ids, nids, blank=0, max_len=None, want_path=True, want
     ``AlignResult(score [B] f32, status [B] i32, path [B,T] i32 | None, seg [B,stride,2] i32 | None, seg_logp [B,stride] f32 | None)``:
     path[b,t] is the position of the label frame t emits or -1, seg[b,i] the first and one-past-last frame of label i, seg_logp[b,i]
     the sum of its frames' log-posteriors.  Nothing synchronises."""
-    assert logp.is_cuda and logp.dtype == torch.float32
-    logp = logp.contiguous()
-    T, B, Cn = logp.shape
-    dev = logp.device
-    lens = torch.as_tensor(lens).to(dev, torch.int32).contiguous()
-    ids = torch.as_tensor(ids).to(dev, torch.int32).contiguous()
-    nids = torch.as_tensor(nids).to(dev, torch.int32).contiguous()
+    c = _CtcCall(logp)
+    B = c.B
+    lens, ids, nids = c.to(lens, torch.int32), c.to(ids, torch.int32), c.to(nids, torch.int32)
     if ids.dim() != 2 or ids.shape[0] != B or lens.shape != (B,) or nids.shape != (B,):
         raise ValueError("ctc_align: lens [B], ids [B, stride], nids [B]")
     stride = ids.shape[1]
     Lmax = stride if max_len is None else int(max_len)
-    score = torch.empty((B,), dtype=torch.float32, device=dev)
-    status = torch.empty((B,), dtype=torch.int32, device=dev)
-    path = torch.empty((B, T), dtype=torch.int32, device=dev) if want_path else None
-    seg = torch.empty((B, stride, 2), dtype=torch.int32, device=dev) if want_segments else None
-    seg_logp = torch.empty((B, stride), dtype=torch.float32, device=dev) if want_segments else None
-    nws = _lib.lib().mdd_ctc_align_workspace_bytes(T, B, Cn, max(Lmax, 0))
-    ws = torch.empty((max(nws, 16) + 7) // 8, dtype=torch.float64, device=dev)      # torch's caching allocator, as ctc_loss
-    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().mdd_ctc_align(ptr(logp), T, B, Cn, ptr(lens), C.c_void_p(ids.data_ptr() if stride else ws.data_ptr()), stride,
-                                            ptr(nids), Lmax, blank, ptr(score), ptr(status), ptr(path), ptr(seg), ptr(seg_logp),
-                                            ptr(ws), ws.numel() * 8, _lib.current_stream_ptr()))
+    score, status = c.empty((B,), torch.float32), c.empty((B,), torch.int32)
+    path = c.empty((B, c.T), torch.int32, want_path)
+    seg, seg_logp = c.empty((B, stride, 2), torch.int32, want_segments), c.empty((B, stride), torch.float32, want_segments)
+    c.workspace(_lib.lib().mdd_ctc_align_workspace_bytes, max(Lmax, 0))
+    c(_lib.lib().mdd_ctc_align, c.ptr(lens), c.ptr(ids, stride), stride, c.ptr(nids), Lmax, blank, c.ptr(score), c.ptr(status), c.ptr(path),
+      c.ptr(seg), c.ptr(seg_logp))
     return AlignResult(score, status, path, seg, seg_logp)
 
 
@@ -214,28 +225,19 @@ def ctc_variants(logp, lens, ids, nids, blank=0, max_len=None, want_ins=True):
     ``VariantResult(base [B] f64, sub [B,stride,C] f64, ins [B,stride+1,C] f64 | None, status [B] i32)``, absolute log-likelihoods:
     sub[b,i,k] with ids[i] replaced by k (k == blank: ids[i] deleted; k == ids[i]: base), ins[b,g,k] with k inserted before position g
     (k == blank: base); rows past nids[b] are -inf up to ``max_len`` and not written beyond it.  Nothing synchronises."""
-    assert logp.is_cuda and logp.dtype == torch.float32
-    logp = logp.contiguous()
-    T, B, Cn = logp.shape
-    dev = logp.device
-    lens = torch.as_tensor(lens).to(dev, torch.int32).contiguous()
-    ids = torch.as_tensor(ids).to(dev, torch.int32).contiguous()
-    nids = torch.as_tensor(nids).to(dev, torch.int32).contiguous()
+    c = _CtcCall(logp)
+    B = c.B
+    lens, ids, nids = c.to(lens, torch.int32), c.to(ids, torch.int32), c.to(nids, torch.int32)
     if ids.dim() != 2 or ids.shape[0] != B or lens.shape != (B,) or nids.shape != (B,):
         raise ValueError("ctc_variants: lens [B], ids [B, stride], nids [B]")
     stride = ids.shape[1]
     Lmax = stride if max_len is None else int(max_len)
-    base = torch.empty((B,), dtype=torch.float64, device=dev)
-    sub = torch.empty((B, stride, Cn), dtype=torch.float64, device=dev)
-    ins = torch.empty((B, stride + 1, Cn), dtype=torch.float64, device=dev) if want_ins else None
-    status = torch.empty((B,), dtype=torch.int32, device=dev)
-    nws = _lib.lib().mdd_ctc_variants_workspace_bytes(T, B, Cn, max(Lmax, 0))
-    ws = torch.empty((max(nws, 16) + 7) // 8, dtype=torch.float64, device=dev)      # torch's caching allocator, as ctc_loss
-    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().mdd_ctc_variants(ptr(logp), T, B, Cn, ptr(lens), C.c_void_p(ids.data_ptr() if stride else ws.data_ptr()), stride,
-                                               ptr(nids), Lmax, blank, ptr(base), C.c_void_p(sub.data_ptr() if stride else ws.data_ptr()),
-                                               ptr(ins), ptr(status), ptr(ws), ws.numel() * 8, _lib.current_stream_ptr()))
+    base, status = c.empty((B,), torch.float64), c.empty((B,), torch.int32)
+    sub = c.empty((B, stride, c.C), torch.float64)
+    ins = c.empty((B, stride + 1, c.C), torch.float64, want_ins)
+    c.workspace(_lib.lib().mdd_ctc_variants_workspace_bytes, max(Lmax, 0))
+    c(_lib.lib().mdd_ctc_variants, c.ptr(lens), c.ptr(ids, stride), stride, c.ptr(nids), Lmax, blank, c.ptr(base), c.ptr(sub, stride), c.ptr(ins),
+      c.ptr(status))
     return VariantResult(base, sub, ins, status)
 
 
@@ -256,26 +258,15 @@ def ctc_confnet(logp, lens, w, nslots, blank=0, max_slots=None, want_post=True):
     status [B] i32)``, absolute log values: total over all readings (weights + CTC log-likelihood of the emitted labels), post[b,j,k]
     over the readings that pick entry k in slot j -- exp(post - total) is the posterior; rows past nslots[b] are -inf up to
     ``max_slots`` and not written beyond it.  Nothing synchronises."""
-    assert logp.is_cuda and logp.dtype == torch.float32
-    logp = logp.contiguous()
-    T, B, Cn = logp.shape
-    dev = logp.device
-    lens = torch.as_tensor(lens).to(dev, torch.int32).contiguous()
-    w = torch.as_tensor(w).to(dev, torch.float32).contiguous()
-    nslots = torch.as_tensor(nslots).to(dev, torch.int32).contiguous()
-    if w.dim() != 3 or w.shape[0] != B or w.shape[2] != Cn or lens.shape != (B,) or nslots.shape != (B,):
+    c = _CtcCall(logp)
+    B = c.B
+    lens, w, nslots = c.to(lens, torch.int32), c.to(w, torch.float32), c.to(nslots, torch.int32)
+    if w.dim() != 3 or w.shape[0] != B or w.shape[2] != c.C or lens.shape != (B,) or nslots.shape != (B,):
         raise ValueError("ctc_confnet: lens [B], w [B, stride, C], nslots [B]")
     stride = w.shape[1]
     Jmax = stride if max_slots is None else int(max_slots)
-    total = torch.empty((B,), dtype=torch.float64, device=dev)
-    post = torch.empty((B, stride, Cn), dtype=torch.float64, device=dev) if want_post else None
-    status = torch.empty((B,), dtype=torch.int32, device=dev)
-    nws = _lib.lib().mdd_ctc_confnet_workspace_bytes(T, B, Cn, max(Jmax, 0), 1 if want_post else 0)
-    ws = torch.empty((max(nws, 16) + 7) // 8, dtype=torch.float64, device=dev)      # torch's caching allocator, as ctc_loss
-    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().mdd_ctc_confnet(ptr(logp), T, B, Cn, ptr(lens), C.c_void_p(w.data_ptr() if stride else ws.data_ptr()), stride,
-                                              ptr(nslots), Jmax, blank, ptr(total),
-                                              None if post is None else C.c_void_p(post.data_ptr() if stride else ws.data_ptr()),
-                                              ptr(status), ptr(ws), ws.numel() * 8, _lib.current_stream_ptr()))
+    total, status = c.empty((B,), torch.float64), c.empty((B,), torch.int32)
+    post = c.empty((B, stride, c.C), torch.float64, want_post)
+    c.workspace(_lib.lib().mdd_ctc_confnet_workspace_bytes, max(Jmax, 0), 1 if want_post else 0)
+    c(_lib.lib().mdd_ctc_confnet, c.ptr(lens), c.ptr(w, stride), stride, c.ptr(nslots), Jmax, blank, c.ptr(total), c.ptr(post, stride), c.ptr(status))
     return ConfnetResult(total, post, status)

@@ -146,14 +146,37 @@ def _lens_tensor(frame_seq_len, B, T, dev):
     return torch.tensor([int(v) for v in frame_seq_len], dtype=torch.int32, device=dev)
 
 
+def _posteriors_and_lens(prob_tensor, frame_seq_len):
+    """(lp, T, B, C, lens): the posteriors on their device and the int32 frame counts beside them."""
+    lp = _device_posteriors(prob_tensor)
+    T, B, Cn = lp.shape
+    return lp, T, B, Cn, _lens_tensor(frame_seq_len, B, T, lp.device)
+
+
+def _pick_tuples(pos_rows, gap_rows, own_ids, blank):
+    """``phoneme_posteriors``' ``(positions, gaps)`` from rows of probabilities: pos_rows[i] over the C entries of position i (own id,
+    blank = deleted, substitutes), gap_rows[g] over those of gap g (blank = nothing inserted, insertions)."""
+    positions, gaps = [], []
+    for p, own in zip(pos_rows, own_ids):
+        own = int(own)
+        alt = p.copy()
+        alt[own] = alt[blank] = -1.0
+        k = int(alt.argmax())
+        positions.append((float(p[own]), float(p[blank]), k, float(p[k])))
+    for p in gap_rows:
+        alt = p.copy()
+        alt[blank] = -1.0
+        k = int(alt.argmax())
+        gaps.append((k, float(p[k])))
+    return positions, gaps
+
+
 def timed_spans(prob_tensor, frame_seq_len, ids, nids, blank=0):
     """Forced alignment of ``ids`` / ``nids`` ([B, stride] / [B], as ``decode_ids`` returns them) to the posteriors (mdd_ctc_align):
     per utterance a list of ``(start_frame, end_frame, mean_logp)``, one per id -- the first frame, one past the last frame and the mean
     log-posterior of the id over its frames -- or ``None`` when the ids have no feasible alignment (or are no valid targets)."""
     from ..hip_model import ctc_align
-    lp = _device_posteriors(prob_tensor)
-    T, B, _ = lp.shape
-    lens = _lens_tensor(frame_seq_len, B, T, lp.device)
+    lp, T, B, _, lens = _posteriors_and_lens(prob_tensor, frame_seq_len)
     r = ctc_align(lp, lens, ids, nids, blank=blank, want_path=False)
     status, seg, seg_logp, n = r.status.cpu().numpy(), r.seg.cpu().numpy(), r.seg_logp.cpu().numpy(), torch.as_tensor(nids).cpu().numpy()
     out = []
@@ -172,11 +195,8 @@ def phoneme_posteriors(prob_tensor, frame_seq_len, ids, nids, blank=0):
     (the phoneme itself, its deletion, each substitute), alt_id the most probable substitute and p_alt its probability; gaps[g] =
     ``(ins_id, p_ins)`` for 0 <= g <= nids[b] -- the most probable insertion before position g in the softmax over ins[b, g, :], whose
     blank entry is "nothing inserted".  Variants without an alignment have probability 0."""
-    import numpy as np
     from ..hip_model import ctc_variants
-    lp = _device_posteriors(prob_tensor)
-    T, B, _ = lp.shape
-    lens = _lens_tensor(frame_seq_len, B, T, lp.device)
+    lp, T, B, _, lens = _posteriors_and_lens(prob_tensor, frame_seq_len)
     ids_h, n = torch.as_tensor(ids).cpu().numpy(), torch.as_tensor(nids).cpu().numpy()
     r = ctc_variants(lp, lens, ids, nids, blank=blank, max_len=min(max(int(n.max()), 0), ids_h.shape[1]))     # no slots past the longest row
     status, sub, ins = r.status.cpu().numpy(), r.sub.cpu().numpy(), r.ins.cpu().numpy()
@@ -191,21 +211,8 @@ def phoneme_posteriors(prob_tensor, frame_seq_len, ids, nids, blank=0):
         if status[b] != 0:
             out.append(None)
             continue
-        positions, gaps = [], []
-        for i in range(int(n[b])):
-            p = softmax(sub[b, i])
-            own = int(ids_h[b, i])
-            alt = p.copy()
-            alt[own] = alt[blank] = -1.0
-            k = int(alt.argmax())
-            positions.append((float(p[own]), float(p[blank]), k, float(p[k])))
-        for g in range(int(n[b]) + 1):
-            p = softmax(ins[b, g])
-            alt = p.copy()
-            alt[blank] = -1.0
-            k = int(alt.argmax())
-            gaps.append((k, float(p[k])))
-        out.append((positions, gaps))
+        L = int(n[b])
+        out.append(_pick_tuples([softmax(sub[b, i]) for i in range(L)], [softmax(ins[b, g]) for g in range(L + 1)], ids_h[b, :L], blank))
     return out
 
 
@@ -246,21 +253,8 @@ def _posterior_tuples(post, total, status, ids_h, n, blank):
             continue
         with np.errstate(under="ignore"):
             p_all = np.exp(post[b] - total[b])         # -inf entries: exactly 0
-        positions, gaps = [], []
-        for i in range(int(n[b])):
-            p = p_all[2 * i + 1]
-            own = int(ids_h[b, i])
-            alt = p.copy()
-            alt[own] = alt[blank] = -1.0
-            k = int(alt.argmax())
-            positions.append((float(p[own]), float(p[blank]), k, float(p[k])))
-        for g in range(int(n[b]) + 1):
-            p = p_all[2 * g]
-            alt = p.copy()
-            alt[blank] = -1.0
-            k = int(alt.argmax())
-            gaps.append((k, float(p[k])))
-        out.append((positions, gaps))
+        L = int(n[b])
+        out.append(_pick_tuples(p_all[1:2 * L:2], p_all[0:2 * L + 1:2], ids_h[b, :L], blank))
     return out
 
 
@@ -270,9 +264,7 @@ def joint_phoneme_posteriors(prob_tensor, frame_seq_len, ids, nids, blank=0, err
     deleted and all gaps filled in the same reading, each reading weighted by its entries' priors and the CTC likelihood of what it
     emits.  ``None``: ids that are no valid targets, or a network without any alignment."""
     from ..hip_model import ctc_confnet
-    lp = _device_posteriors(prob_tensor)
-    T, B, Cn = lp.shape
-    lens = _lens_tensor(frame_seq_len, B, T, lp.device)
+    lp, T, B, Cn, lens = _posteriors_and_lens(prob_tensor, frame_seq_len)
     ids_h, n = torch.as_tensor(ids).cpu().numpy(), torch.as_tensor(nids).cpu().numpy()
     valid = [0 <= int(n[b]) <= ids_h.shape[1] and all(0 <= int(v) < Cn and int(v) != blank for v in ids_h[b, :max(int(n[b]), 0)])
              for b in range(B)]
@@ -300,9 +292,7 @@ class GreedyDecoder(Decoder):
     """argmax per frame, collapse repeats, drop blanks (ctcDecoder.py:186-200)."""
 
     def decode_ids(self, prob_tensor, frame_seq_len=None):
-        lp = _device_posteriors(prob_tensor)
-        T, B, Cn = lp.shape
-        lens = _lens_tensor(frame_seq_len, B, T, lp.device)
+        lp, T, B, Cn, lens = _posteriors_and_lens(prob_tensor, frame_seq_len)
         ids = torch.empty((B, T), dtype=torch.int32, device=lp.device)
         nids = torch.empty((B,), dtype=torch.int32, device=lp.device)
         with torch.cuda.device(lp.device):
@@ -351,9 +341,7 @@ class BeamDecoder(Decoder):
         return self._tables[key]
 
     def decode_ids(self, prob_tensor, frame_seq_len=None):
-        lp = _device_posteriors(prob_tensor)
-        T, B, Cn = lp.shape
-        lens = _lens_tensor(frame_seq_len, B, T, lp.device)
+        lp, T, B, Cn, lens = _posteriors_and_lens(prob_tensor, frame_seq_len)
         ids = torch.empty((B, T), dtype=torch.int32, device=lp.device)
         nids = torch.empty((B,), dtype=torch.int32, device=lp.device)
         status = torch.empty((B,), dtype=torch.int32, device=lp.device)
@@ -385,12 +373,10 @@ class BeamDecoder(Decoder):
         ``(ids [N,B,T], nids [N,B], status [B], score [N,B])``: slice n is ``decode_ids``' output for the hypothesis of rank n, slice 0
         its output itself, bit for bit.  Ranks follow the reference's final sort: descending length-normalised score, equal scores in
         the order of the final beam.  An utterance with an error status has nids 0 and score NaN in every slice.  Nothing synchronises."""
-        lp = _device_posteriors(prob_tensor)
-        T, B, Cn = lp.shape
+        lp, T, B, Cn, lens = _posteriors_and_lens(prob_tensor, frame_seq_len)
         N = self.beam_width if nbest is None else int(nbest)
         if not 1 <= N <= self.beam_width:
             raise ValueError("nbest must be in [1, beam_width = %d]" % self.beam_width)
-        lens = _lens_tensor(frame_seq_len, B, T, lp.device)
         ids = torch.empty((N, B, T), dtype=torch.int32, device=lp.device)
         nids = torch.empty((N, B), dtype=torch.int32, device=lp.device)
         status = torch.empty((B,), dtype=torch.int32, device=lp.device)
@@ -410,9 +396,8 @@ class BeamDecoder(Decoder):
         lattice, negated), ``-inf`` where the lattice finds no path.  ``max_len`` bounds nids (default: the ids' row length); a tight
         bound lets the lattice run in its one-wave form."""
         from ..hip_model import ctc_loss
-        lp = _device_posteriors(prob_tensor)
-        T, B, _ = lp.shape
-        lens = _lens_tensor(frame_seq_len, B, T, lp.device).clamp(0, T)
+        lp, T, B, _, lens = _posteriors_and_lens(prob_tensor, frame_seq_len)
+        lens = lens.clamp(0, T)
         width = ids.shape[2] if max_len is None else max(min(int(max_len), ids.shape[2]), 1)
         nll = [ctc_loss(lp, ids[n, :, :width], lens, nids[n], blank=self.blank_index, want_grad=False)[0] for n in range(ids.shape[0])]
         return -torch.stack(nll).double().cpu().numpy()
@@ -425,13 +410,12 @@ class BeamDecoder(Decoder):
         of the posteriors), and ``posterior``, its share among the N listed hypotheses
         (``nbest_posteriors``: relative to the list, not an absolute probability; ``None`` when no hypothesis of the list is a CTC
         path).  With ``rescore=False`` both are ``None``."""
-        lp = _device_posteriors(prob_tensor)
-        T, B, _ = lp.shape
-        ids, nids, status, score = self.decode_nbest_ids(lp, frame_seq_len, nbest)
+        lp, T, B, _, lens = _posteriors_and_lens(prob_tensor, frame_seq_len)
+        ids, nids, status, score = self.decode_nbest_ids(lp, lens, nbest)
         N = ids.shape[0]
         nids_h = nids.cpu().numpy()
         strings = [self._strings(ids[n], nids_h[n], status) for n in range(N)]      # raises decode's exception
-        loglik = self.nbest_loglik(lp, frame_seq_len, ids, nids, max_len=int(nids_h.max())) if rescore else None
+        loglik = self.nbest_loglik(lp, lens, ids, nids, max_len=int(nids_h.max())) if rescore else None
         score_h = score.cpu().numpy()
         out = []
         for b in range(B):

@@ -270,7 +270,10 @@ int mdd_beam_nbest(const float *logp_dev, int32_t T, int32_t B, int32_t C, const
  * on the log-probs: [T,B,C] (zero on frames >= in_len).  A target label outside [0,C) makes that utterance's nll NaN
  * and its gradient rows zero (ATen would index past the row).
  * workspace_dev: caller-owned scratch of at least mdd_ctc_workspace_bytes(T,B,C,Lmax, grad_dev != NULL) bytes (16-byte
- * aligned; the alpha/beta rows of the backward sweep); NULL = the library allocates stream-ordered for the call. */
+ * aligned; the alpha/beta rows of the backward sweep); NULL = the library allocates stream-ordered for the call.
+ * Bad host arguments (a required pointer NULL, T/B/C <= 0, blank outside [0,C), Lmax < 0, an Lmax past 255 whose 2 Lmax + 1
+ *   lattice states do not fit the general kernel's LDS rows (Lmax > 2742), a caller workspace that is too small) return
+ *   MDD_ERR_ARG before any device work. */
 int64_t mdd_ctc_workspace_bytes(int32_t T, int32_t B, int32_t C, int32_t Lmax, int32_t want_grad);
 int mdd_ctc_loss(const float *logp_dev, int32_t T, int32_t B, int32_t C, const int64_t *targets_dev, int32_t Lmax,
                  const int64_t *in_len_dev, const int64_t *tgt_len_dev, int32_t blank, float *nll_dev,

@@ -225,6 +225,27 @@ def test_variants_rejects_bad_arguments_before_device_work():
         assert name in L_.mdd_last_error().decode(), (change, L_.mdd_last_error().decode())
 
 
+def test_ctc_loss_rejects_bad_arguments_before_device_work():
+    """mdd_ctc_loss refuses as the entries built on its lattice do: MDD_ERR_ARG, the argument named, a caller workspace one byte short
+    refused too; host addresses stand in for device buffers, none is used and no HIP call is reached (this runs without a GPU)."""
+    L_ = _lib()
+    host = np.zeros(64, np.float32)
+    buf = C.c_void_p(host.ctypes.data)
+    good = dict(logp=buf, T=10, B=2, C=5, targets=buf, Lmax=8, in_len=buf, tgt_len=buf, blank=0, nll=buf, grad=buf, ws=None, ws_bytes=0)
+    order = ["logp", "T", "B", "C", "targets", "Lmax", "in_len", "tgt_len", "blank", "nll", "grad", "ws", "ws_bytes"]
+    need = L_.mdd_ctc_workspace_bytes(10, 2, 5, 8, 1)
+    assert need >= 8 * 2 * 10 * 17
+    cases = [(dict(logp=None), "logp_dev"), (dict(targets=None), "targets_dev"), (dict(in_len=None), "in_len_dev"),
+             (dict(tgt_len=None), "tgt_len_dev"), (dict(nll=None), "nll_dev"), (dict(T=0), "T <= 0"), (dict(B=0), "B <= 0"),
+             (dict(C=0), "C <= 0"), (dict(T=-3), "T <= 0"), (dict(B=-1), "B <= 0"), (dict(C=-2), "C <= 0"), (dict(Lmax=-1), "Lmax < 0"),
+             (dict(blank=-1), "blank outside"), (dict(blank=5), "blank outside"), (dict(ws=buf, ws_bytes=need - 1), "workspace")]
+    for change, name in cases:
+        a = dict(good, **change)
+        assert L_.mdd_ctc_loss(*[a[k] for k in order], None) == -1, change
+        msg = L_.mdd_last_error().decode()
+        assert msg.startswith("mdd_ctc_loss: ") and name in msg, (change, msg)
+
+
 def _decoder():
     from ctc_attention_mispronunciation_amd.utils.ctcDecoder import Decoder
     return Decoder({0: "blank"}, space_idx=-1, blank_index=0)
