@@ -12,14 +12,17 @@
 //   MDD_LSTM=step        the per-step recurrence in every mode: no persistent layer   create    test_persistent_f32_lstm_batch_sizes_match_step_kernels,
 //                        launch, no device gate (a second process on the device)                test_persistent_f32_lstm_full_length_and_poisoned_input,
 //                                                                                               test_bench_two_ranks_rehearsal, test_bench_exchange_runs_beside_the_next_forward,
-//                                                                                               tools/lstm_bcheck.py
+//                                                                                               test_forward_tiles_against_float64[*-f32-step],
+//                                                                                               test_variant_forward_is_the_persistent_layer_kernel, tools/lstm_bcheck.py
 //   MDD_LSTM=x3          mode 1: lstm_step_x3_kernel, the LDS-tiled split-bf16 step;  create    test_persistent_lstm_equals_step_kernels_bitwise,
 //                        modes 0 and 2: the packed step kernel                                  test_persistent_lstm_batch_sizes_match_step_kernels,
 //                                                                                               test_fused_batches_of_different_lengths_equal_their_own_runs[*-bf16x3-x3],
-//                                                                                               test_fused_batches_straddling_64_equal_their_own_runs[*-bf16x3-x3]
+//                                                                                               test_fused_batches_straddling_64_equal_their_own_runs[*-bf16x3-x3],
+//                                                                                               test_forward_tiles_against_float64[*-bf16x3-x3]
 //   MDD_LSTM_X6=0        mode 2: the exact-fp32 layer kernel instead of the f32x6 one create    test_persistent_x6_lstm_tracks_exact_fp32_recurrence,
 //                                                                                               test_persistent_x6_lstm_full_length_and_poisoned_input, tools/lstm_kernel_choice.py
-//   MDD_LSTM_X6=force    mode 2: the f32x6 layer kernel wherever it can run           create    test_persistent_x6_lstm_tracks_exact_fp32_recurrence
+//   MDD_LSTM_X6=force    mode 2: the f32x6 layer kernel wherever it can run           create    test_persistent_x6_lstm_tracks_exact_fp32_recurrence,
+//                                                                                               test_forward_tiles_against_float64[H256-*-f32x6-x6force]
 //   MDD_CONV=rowwise     mode 2: the row-at-a-time conv_fused_kernel<3>               create    tests/test_conv_multirow.py, tests/test_conv_pipeline.py
 //   MDD_LSTM_DBG         persistent layer launches with T' > 100 write phase stamps   create    test_persistent_lstm_stale_panel_redo_path, tools/lstm_stamps.py,
 //                        behind their exchange buffer (mdd_tap "lstm_dbg")                      tools/lstm_f32_stamps.py
