@@ -4,8 +4,11 @@
 // algorithm is its published one (feat/feature-window.cc, feat/mel-computations.cc, feat/feature-fbank.cc,
 // transform/cmvn.cc) for: 16 kHz, 25 ms / 10 ms frames, snip-edges, no dither, remove-dc-offset, raw log-energy in
 // column 0, preemphasis 0.97, hamming window, 512-point FFT, power spectrum, 80 triangular mel bins from 20 Hz to
-// Nyquist, log.  PARITY UNPINNED (no Kaldi output to compare with here): tests check it against oracle/oracle.py's
-// numpy restatement of the same text.
+// Nyquist, log.  PARITY UNPINNED (no Kaldi output to compare with here): tests check it against restatements of the same
+// text.  tests/test_fbank.py holds every output element of both kernels, with and without CMVN, to the float64 restatement
+// of tests/fbank_reference.py under its per-element conditioning model (noise, impulses, tones, Nyquist, DC, the floor,
+// frame-count edges, recorded words; the batched kernel's stacking against float64 rows, not against fbank_kernel);
+// tests/test_fbank_reference.py pins that restatement to oracle/oracle.py's and shows what the bound catches.
 //
 // One wave per frame, four frames per workgroup.  A frame is 400 samples = 1.6 KB: the work is a 512-point FFT in LDS
 // (9 radix-2 stages, 4 butterflies per lane and stage, wave-synchronous), 80 short dot products and a row store --
@@ -180,8 +183,12 @@ static int fbank_tables(int dev, FbankTables *out) {
         for (int i = 0; i < FB_N; i++) window[i] = (float)(0.54 - 0.46 * cos(2.0 * M_PI * i / (FB_N - 1)));
         std::vector<float2> tw(FB_HALF);
         for (int k = 0; k < FB_HALF; k++) tw[k] = make_float2((float)cos(-2.0 * M_PI * k / FB_P), (float)sin(-2.0 * M_PI * k / FB_P));
-        // MelBanks (no VTLN): triangles in the mel domain, evaluated at the centre frequencies of FFT bins 0..255
-        auto mel = [](float fr) { return 1127.0f * logf(1.0f + fr / 700.0f); };
+        // MelBanks (no VTLN): triangles in the mel domain, evaluated at the centre frequencies of FFT bins 0..255.
+        // A weight is a difference of mel values near 2000 over a spacing of 35, so one ulp of the mel scale is up to 1e-4 of a
+        // weight: with the C library's logf the table followed the build host (glibc's and numpy's float32 log differ in 31 of
+        // these 256 values, which moved log-mel outputs by up to 12 units of tests/fbank_reference.py's model).  The scale is
+        // therefore the correctly rounded one -- the double log of the float argument, rounded to float -- on every host.
+        auto mel = [](float fr) { return 1127.0f * (float)log((double)(1.0f + fr / 700.0f)); };
         const float bin_width = 16000.0f / FB_P, mel_low = mel(20.0f), mel_high = mel(8000.0f);
         const float delta = (mel_high - mel_low) / (FB_BINS + 1);
         std::vector<int> first(FB_BINS), count(FB_BINS), woff(FB_BINS);

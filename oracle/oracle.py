@@ -283,7 +283,9 @@ def mel_banks(num_bins=80, nfft=512, samp_freq=16000.0, low_freq=20.0, high_freq
     nyquist = 0.5 * samp_freq
     if high_freq <= 0.0:
         high_freq += nyquist
-    mel = lambda f: f32(1127.0) * np.log(f32(1.0) + f32(f) / f32(700.0), dtype=f32)  # noqa: E731
+    # logf correctly rounded (float64 log, rounded to float32): numpy's own float32 log is an ulp off in 31 of the 256 mel values,
+    # and an ulp of the mel scale is up to 1e-4 of a triangle weight (csrc/fbank.hip builds its table the same way)
+    mel = lambda f: f32(1127.0) * f32(np.log(np.float64(f32(1.0) + f32(f) / f32(700.0))))  # noqa: E731
     bin_width = f32(samp_freq / nfft)
     mel_low, mel_high = mel(low_freq), mel(high_freq)
     delta = f32((mel_high - mel_low) / f32(num_bins + 1))
