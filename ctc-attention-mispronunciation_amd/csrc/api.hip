@@ -261,7 +261,7 @@ static int create_handle(const char *what, bool ctc_only, const mdd_config *cfg,
     m->ctc_only = ctc_only;
     m->sw = read_switches();
     m->precision = m->sw.precision;
-    for (auto init : {init_kernel_attributes, init_lstm_attributes, init_granule_attributes, init_lstm_f32_attributes, init_lstm_x6_attributes,
+    for (auto init : {init_kernel_attributes, init_lstm_attributes, init_granule_attributes, init_lstm_bwd_attributes, init_lstm_f32_attributes, init_lstm_x6_attributes,
                       init_conv_attributes, init_gemm_attributes, init_gemm_x6_attributes})
         if (int rc = init()) return rc;
     const int n_cu = prop.multiProcessorCount;   // (where a grid does not fit: per-step kernels, e.g. smaller partitions, other gfx950 SKUs)

@@ -1,32 +1,13 @@
 // The host shape of a CTC lattice entry (mdd_ctc_loss, mdd_ctc_align, mdd_ctc_variants, mdd_ctc_confnet, the beam entries), host code only:
 //   1. refuse    every bad argument by name, then a caller workspace that is too small (refuse_workspace) -- before any HIP call;
-//   2. attributes the kernels' LDS budgets, once per device (once_per_device);
+//   2. attributes the kernels' LDS budgets, once per device (once_per_device, mdd_internal.h);
 //   3. workspace the caller's, or one allocated on the stream for the call (StreamWorkspace);
 //   4. launch;
 //   5. check     hipGetLastError, with the workspace still in scope: its free is enqueued behind the last launch on every return path.
 #pragma once
-#include <mutex>
-
 #include "mdd_internal.h"
 
 namespace mdd {
-
-// init() runs once per device of the process (kernel attributes belong to the device that is current when they are set), under a lock;
-// an init that fails runs again on the next call.  One state per family of kernels, a static of the entry that launches them.
-struct OncePerDevice {
-    std::mutex mu;
-    bool done[64] = {false};
-};
-template <class Init> int once_per_device(OncePerDevice &s, Init init) {
-    int dev = 0;
-    MDD_HIP_CHECK(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lock(s.mu);
-    if (!s.done[dev & 63]) {
-        if (int rc = init()) return rc;
-        s.done[dev & 63] = true;
-    }
-    return MDD_OK;
-}
 
 // Scratch for one call: the caller's pointer when one is given, else `need` bytes allocated stream-ordered (none for need == 0) and freed
 // on the same stream by the destructor.  Declare it in front of the launches and let it live to the entry's return: the free then follows

@@ -83,13 +83,6 @@ template <class F, class B, class A> static int time_each(int reps, float *mean,
 }
 static int nothing(int) { return MDD_OK; }
 
-static int init_once(bool &done, int (*init)()) {
-    if (done) return MDD_OK;
-    if (int rc = init()) return rc;
-    done = true;
-    return MDD_OK;
-}
-
 }  // namespace mdd
 
 using namespace mdd;
@@ -102,8 +95,8 @@ using namespace mdd;
 // workgroups per CU) on the same problem.
 extern "C" int mdd_diag_gemm_ph8(int M, int N, int K, int reps, unsigned seed, unsigned *mismatches_out, float *ms_out) {
     if (M <= 0 || N <= 0 || K < 32 || K % 32 || !mismatches_out || reps < 1) { set_error("mdd_diag_gemm_ph8: bad shape"); return MDD_ERR_ARG; }
-    static bool attr = false;
-    if (int rc = init_once(attr, init_gemm_attributes)) return rc;
+    static OncePerDevice attr;
+    if (int rc = once_per_device(attr, init_gemm_attributes)) return rc;
     const size_t na = (size_t)M * K, nw = (size_t)N * K, nc = (size_t)M * N;
     DeviceArray<unsigned short> Ap, Wp;
     DeviceBuf C1, C2;
@@ -178,8 +171,8 @@ extern "C" int mdd_diag_gemm(int mode, const float *A_dev, const float *W_dev, f
         if (!(rc = launch_split(A_dev, na, a, st)) && !(rc = launch_split(W_dev, nw, w, st)))
             rc = launch_gemm_bf16x3({.p = a, .ld = K}, {.p = w, .ld = K}, C_dev, nullptr, N, M, N, K, st);
     } else {
-        static bool attr = false;
-        rc = init_once(attr, init_gemm_x6_attributes);
+        static OncePerDevice attr;
+        rc = once_per_device(attr, init_gemm_x6_attributes);
         if (!rc) rc = launch_split3(A_dev, M, K, K, pa.p, st);
         if (!rc) rc = launch_split3(W_dev, N, K, K, pw.p, st);
         if (!rc) rc = launch_gemm_f32x6(pa.p, na, pw.p, nw, nullptr, C_dev, M, N, K, N, st, raster);

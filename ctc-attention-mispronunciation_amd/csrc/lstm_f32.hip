@@ -2,7 +2,7 @@
 // launch with every product an exact fp32 MFMA (v_mfma_f32_16x16x4_f32), as torch.nn.LSTM computes it in the reference
 // (AA/models/model_ctc.py:27-29 builds the nn.LSTM, :36-49 BatchRNN.forward runs it; text encoder :150,198).
 //
-// It repeats lstm_step_packed_kernel (lstm.hip) BIT FOR BIT -- the same two accumulators per gate tile (even / odd float4
+// It repeats lstm_step_packed_kernel (lstm_step.hip) BIT FOR BIT -- the same two accumulators per gate tile (even / odd float4
 // components of the packed W_hh'), the same k-groups per MFMA ({16j + 4q + m : q = 0..3}) in the same order (j ascending, m
 // ascending), the same (a0 + a1) + gx combine, the same gate functions (lstm_persist.h) -- but the per-step launches re-read W_hh (4.7 MB) from
 // L2 on every one of the 250 steps and pay a kernel boundary each; here a workgroup keeps its gate rows of W_hh' in
@@ -25,7 +25,7 @@
 // product loop (4 VALU per 3 MFMAs) and let the compiler copy AGPR-resident weights to VGPRs (v_accvgpr_read), ran its
 // MFMAs at 50 cycles apiece instead of 32 (profiles/round3_lstm_f32_stamps.txt).  Hence: the product loop contains nothing but
 // MFMAs, the operand reads (ds_read_b128 of a chunk = four k-groups' worth of B) and the LDS-DMA requests; weights living in the
-// accumulation file feed the MFMA from there (inline asm, as in lstm.hip); the tag bits are cleared once per panel, in LDS, by
+// accumulation file feed the MFMA from there (inline asm, as in lstm_granule.h); the tag bits are cleared once per panel, in LDS, by
 // the thread that fetched the chunk, in the same pass that checks them; the gate nonlinearities are the short forms of
 // lstm_persist.h.
 // A tile phase is 96 * RTW MFMAs = 3.8 us at H = 384 against ~3 us of hand-off latency: with two or more tiles the next tile's
@@ -33,7 +33,7 @@
 // the previous phase's stores were acknowledged microseconds ago), and checked + cleaned by the wave that fetched each piece
 // BEFORE the cell update; a stale piece (a member's h had not landed) is simply requested again after the publish.  Nothing is
 // consumed unchecked, so the product loop has no redo path.
-#include "lstm_persist.h"
+#include "lstm_host.h"
 
 namespace mdd {
 
@@ -59,9 +59,8 @@ __global__ __launch_bounds__(256, 1) void lstm_layer_f32_kernel(PersistArgs a) {
     __shared__ int s_fail;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 15, kq = lane >> 4;
-    const int w = blockIdx.x, xl = w & 7, jw = w >> 3;
-    const int team = xl * 4 + (jw >> 3), member = jw & 7;           // 8 members share blockIdx % 8 (one XCD under round-robin; speed only)
-    const int d = team >> 4, g = team & 15;
+    const Team8 tm = team8_of_block();
+    const int team = tm.team, member = tm.member, d = tm.d, g = tm.g;
     const int B = a.B, T = a.T;
     if (tid == 0) s_fail = 0;
 
@@ -100,31 +99,19 @@ __global__ __launch_bounds__(256, 1) void lstm_layer_f32_kernel(PersistArgs a) {
     constexpr int RQJ = J - NLD - MDD_F32_RQ_TAIL;                   // first k-group of the in-loop sweep request: ALL NLD pieces are issued inside the loop
     static_assert(RQJ >= RTW && RQJ + NLD <= J, "the sweep pieces follow the gx pieces and fit the loop");
     u64 *hxg = reinterpret_cast<u64 *>(a.hx);
-    unsigned int *abortf = a.sync + 16;
+    unsigned int *abortf = a.sync + kPersistAbortWord;
     long long ph[6] = {0, 0, 0, 0, 0, 0}, tst = DBG ? (long long)__builtin_readcyclecounter() : 0;
 
     // gate pre-activations of (tile bt, time tt): lane (row li, unit kq) of piece rt fetches the 16 bytes (i, f, g, o of its unit and
     // row) it consumes itself in the cell update of row tile rt -- nothing crosses lanes, no barrier between transfer and use
-    const unsigned gvoff = (unsigned)(d * 4 * H + (member * UW + wave * RTW * 4 + kq) * 4) * 4u;
-    const unsigned wave_lds = __builtin_amdgcn_readfirstlane((unsigned)wave * 1024u);
-    const unsigned wave_gx = __builtin_amdgcn_readfirstlane((unsigned)wave * (unsigned)(RTW * 1024));
+    const unsigned gvoff = (unsigned)(d * 4 * H + (member * UW + wave * RTW * 4 + kq) * 4) * 4u;   // byte offset of row tile 0's unit in a gx row
+    const unsigned wave_lds = __builtin_amdgcn_readfirstlane((unsigned)wave * 1024u);   // a wave's 1 KB slot inside a 4 KB LDS-DMA pass
+    const unsigned wave_gx = __builtin_amdgcn_readfirstlane((unsigned)wave * (unsigned)(RTW * 1024));   // a wave's RTW row tiles inside a slab
     const unsigned gx_lds = (unsigned)(unsigned long long)(lds_void_t *)Gx, rw_lds = (unsigned)(unsigned long long)(lds_void_t *)Rw;
-    auto load_gx = [&](int bt, int par, int tt, int i0 = 0, int i1 = 99) {
-        i1 = i1 > RTW ? RTW : i1;
-        const float *gbase = a.gx + (size_t)tt * B * 2 * 4 * H;
-        const int b = min(g * a.BGr + min(bt * 16 + li, a.BGr - 1), B - 1);           // rows past the batch read a valid row (never used)
-        const unsigned rowoff = (unsigned)b * (unsigned)(2 * 4 * H * 4) + gvoff;
-#pragma unroll
-        for (int i = i0; i < i1; i++)
-            lds_dma16_s<false>(gbase, rowoff + (unsigned)(i * 64), gx_lds + (unsigned)(((bt * 2 + par) * GXT + i * 256) * 4) + wave_gx);
-    };
+    const Team8Dma q = {hxg, pgran, B, g, li, team, tid, gvoff, wave_lds, wave_gx, gx_lds, rw_lds};
+    auto load_gx = [&](int bt, int par, int tt, int i0 = 0, int i1 = 99) { team8_load_gx<H>(a, q, bt, par, tt, i0, i1); };
     // sweep of (tile bt, state of step sp) into panel buffer pb: NLD pieces per wave, piece i = bytes [i * 4 KB + tid * 16, +16)
-    auto request_sweep = [&](int bt, int sp, int pb, int i0 = 0, int i1 = 99) {
-        i1 = i1 > NLD ? NLD : i1;
-        const unsigned char *srcp = reinterpret_cast<const unsigned char *>(hxg + (size_t)((sp & 1) * 32 + team) * pgran + bt * tgran);
-#pragma unroll
-        for (int i = i0; i < i1; i++) lds_dma16_s<true>(srcp + (size_t)i * NTH * 16, (unsigned)tid * 16u, rw_lds + (unsigned)(pb * PANB + i * NTH * 16) + wave_lds);
-    };
+    auto request_sweep = [&](int bt, int sp, int pb, int i0 = 0, int i1 = 99) { team8_request_sweep<H>(q, bt, sp & 1, pb, i0, i1); };
     // This thread's own pieces of panel buffer pb against the tag of step sp (wave-uniform verdict); fresh pieces are written back
     // with the tag bits cleared, i.e. as the plain fp32 operands the product loop reads
     auto pieces_stale = [&](int pb, int sp) -> bool {
@@ -285,7 +272,7 @@ __global__ __launch_bounds__(256, 1) void lstm_layer_f32_kernel(PersistArgs a) {
                     if ((++polls & 63) == 0) {
                         int ab = 0;
                         if (t0 == 0) t0 = wall_clock64();
-                        if (lane == 0) ab = (__hip_atomic_load(abortf, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) || (wall_clock64() - t0 > 200000000ll);
+                        if (lane == 0) ab = (__hip_atomic_load(abortf, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) || (wall_clock64() - t0 > kPersistStallTicks);
                         if (__any(ab)) {
                             if (lane == 0) { __hip_atomic_store(abortf, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); atomicExch(a.err_flag, 2); s_fail = 1; }
                             break;
@@ -304,46 +291,26 @@ __global__ __launch_bounds__(256, 1) void lstm_layer_f32_kernel(PersistArgs a) {
     if (DBG && tid == 0) for (int i = 0; i < 6; i++) a.dbg[blockIdx.x * 6 + i] = ph[i];
 }
 
-template <int H, int NBT, bool DBG = false>
-static int launch_f32_t(PersistArgs a, hipStream_t st) {
-    if (int rc = launch_zero_fill(a.sync, 32 * sizeof(unsigned int), st)) return rc;
-    if (int rc = launch_zero_fill(a.hx, team8_hx_live_bytes(H, NBT * 16), st)) return rc;   // tags must start at 0 on every launch (by a kernel: lstm.hip)
-    hipLaunchKernelGGL((lstm_layer_f32_kernel<H, NBT, DBG>), dim3(kPersistGrid), dim3(256), team8_lds_bytes(H, NBT), st, a);
-    MDD_LAUNCH_CHECK();
-    return MDD_OK;
-}
+struct F32Family : PersistFamily {   // the instantiations: {384, 256} x 1..4 tiles per team; H = 384 also stamped (MDD_LSTM_DBG)
+    using List = InstList<Inst<384, 1, true>, Inst<384, 2, true>, Inst<384, 3, true>, Inst<384, 4, true>, Inst<256, 1>, Inst<256, 2>, Inst<256, 3>, Inst<256, 4>>;
+    template <int H, int N, bool DBG> static auto kernel() { return lstm_layer_f32_kernel<H, N, DBG>; }
+    static constexpr size_t lds(int H, int N) { return team8_lds_bytes(H, N); }
+};
 
 int launch_lstm_layer_f32(const LstmStepArgs &s, unsigned short *hx, unsigned int *sync, int *err_flag, hipStream_t st, long long *stamps) {
-    PersistArgs a;
-    a.gx = s.gx; a.whh = {nullptr, nullptr}; a.whh_f32 = s.whh; a.hx = hx; a.sync = sync; a.err_flag = err_flag;
-    a.out = s.out; a.out_raw = s.out_raw; a.out_split = {nullptr, nullptr}; a.oscale = s.oscale; a.oshift = s.oscale ? s.oshift : nullptr;
-    a.T = s.T; a.B = s.B; a.BGr = (s.B + 15) / 16; a.BG = granule_bg(s.B); a.seqlen = s.seqlen;
-    a.dbg = stamps;
-    a.early = 0; a.gates_save = nullptr; a.c_save = nullptr;
+    PersistArgs a = persist_args(s, hx, sync, err_flag, s.H == 384 ? stamps : nullptr);
+    a.whh_f32 = s.whh;
     if (!s.packed || s.out_split.hi || s.gates_save) { set_error("persistent fp32 lstm: packed W_hh layout, fp32 outputs, inference only"); return MDD_ERR_ARG; }
     if (!a.out && !a.out_raw) { set_error("persistent fp32 lstm: no output"); return MDD_ERR_ARG; }
-    const int nbt = a.BG / 16;
-    if (nbt < 1 || nbt > 4) { set_error("persistent fp32 lstm: B=%d needs %d row tiles per team (max 4)", s.B, nbt); return MDD_ERR_ARG; }
-    if (a.dbg && s.H == 384) return nbt == 1 ? launch_f32_t<384, 1, true>(a, st) : nbt == 2 ? launch_f32_t<384, 2, true>(a, st) : nbt == 3 ? launch_f32_t<384, 3, true>(a, st) : launch_f32_t<384, 4, true>(a, st);
-    a.dbg = nullptr;
-    if (s.H == 384) return nbt == 1 ? launch_f32_t<384, 1>(a, st) : nbt == 2 ? launch_f32_t<384, 2>(a, st) : nbt == 3 ? launch_f32_t<384, 3>(a, st) : launch_f32_t<384, 4>(a, st);
-    if (s.H == 256) return nbt == 1 ? launch_f32_t<256, 1>(a, st) : nbt == 2 ? launch_f32_t<256, 2>(a, st) : nbt == 3 ? launch_f32_t<256, 3>(a, st) : launch_f32_t<256, 4>(a, st);
-    set_error("persistent fp32 lstm: unsupported H=%d", s.H);
-    return MDD_ERR_ARG;
+    const int nbt = team8_tiles(s.B);
+    if (nbt < 1 || nbt > kTeam8MaxTiles) { set_error("persistent fp32 lstm: B=%d needs %d row tiles per team (max %d)", s.B, nbt, kTeam8MaxTiles); return MDD_ERR_ARG; }
+    const int rc = launch_instantiation<F32Family>(s.H, nbt, a.dbg != nullptr, a, hx, team8_hx_live_bytes(s.H, nbt * 16), sync, st);
+    if (rc == kNoInstantiation) { set_error("persistent fp32 lstm: unsupported H=%d", s.H); return MDD_ERR_ARG; }
+    return rc;
 }
 
-int init_lstm_f32_attributes() {
-#define FATTR(H, N) MDD_HIP_CHECK(hipFuncSetAttribute((const void *)lstm_layer_f32_kernel<H, N>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024))
-    FATTR(384, 1); FATTR(384, 2); FATTR(384, 3); FATTR(384, 4); FATTR(256, 1); FATTR(256, 2); FATTR(256, 3); FATTR(256, 4);
-#undef FATTR
-#define FATTR(H, N) MDD_HIP_CHECK(hipFuncSetAttribute((const void *)lstm_layer_f32_kernel<H, N, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024))
-    FATTR(384, 1); FATTR(384, 2); FATTR(384, 3); FATTR(384, 4);
-#undef FATTR
-    return MDD_OK;
-}
+int init_lstm_f32_attributes() { return init_persistent_attributes<F32Family>(); }
 
-int persistent_f32_grid_fits(int n_cu) {
-    return persist_grid_fits(n_cu, (const void *)lstm_layer_f32_kernel<384, 4>, team8_lds_bytes(384, 4));
-}
+int persistent_f32_grid_fits(int n_cu) { return persist_grid_fits(n_cu, (const void *)F32Family::kernel<384, 4, false>(), F32Family::lds(384, 4)); }
 
 }  // namespace mdd

@@ -25,13 +25,9 @@
 // One wave per SIMD issues one instruction every four cycles at best and stalls on every dependency, so the kernel is written for
 // few instructions per phase: one assembly block per sweep (an immediate offset moves the global and the LDS address together), one
 // 16-byte publish store per owner, one barrier per phase, counted waits that skip the stores' acknowledgements.
-#include "lstm_persist.h"
-#include <type_traits>
-#include <utility>
+#include "lstm_host.h"
 
 namespace mdd {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 #define XSTAMP(i) do { if (DBG) { long long n_ = __builtin_readcyclecounter(); ph[i] += n_ - tst; tst = n_; } } while (0)
 
@@ -131,7 +127,7 @@ __global__ __launch_bounds__(256, 1) void lstm_layer_x6_kernel(X6Args a) {
     constexpr size_t tbytes = PANB;                                  // bytes per (parity, team, tile)
     const size_t pbytes = (size_t)NBT * tbytes;                      // bytes per (parity, team)
     unsigned char *hxb = reinterpret_cast<unsigned char *>(a.hx);
-    unsigned int *abortf = a.sync + 16;
+    unsigned int *abortf = a.sync + kPersistAbortWord;
     long long ph[6] = {0, 0, 0, 0, 0, 0}, tst = DBG ? (long long)__builtin_readcyclecounter() : 0;
 
     // gate pre-activations of (tile bt, time tt): lane (row li, unit kq) of piece r fetches the 16 bytes (i, f, g, o of its unit and row)
@@ -217,7 +213,7 @@ __global__ __launch_bounds__(256, 1) void lstm_layer_x6_kernel(X6Args a) {
             if ((++polls & 63) == 0) {
                 bool giveup = false;
                 if (t0 == 0) t0 = wall_clock64();
-                if (tid == 0 && ((__hip_atomic_load(abortf, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) || (wall_clock64() - t0 > 200000000ll))) {
+                if (tid == 0 && ((__hip_atomic_load(abortf, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) || (wall_clock64() - t0 > kPersistStallTicks))) {
                     __hip_atomic_store(abortf, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); atomicExch(a.err_flag, 2); giveup = true;
                 }
                 if (wg_any(giveup)) { ok = false; break; }
@@ -562,79 +558,47 @@ __global__ __launch_bounds__(256, 1) void lstm_layer_x6_kernel(X6Args a) {
         for (int i = 0; i < 6; i++) a.dbg[blockIdx.x * 6 + i] = ph[i];
 }
 
-static size_t x6_smem(int H, int NBT) {
+static constexpr size_t x6_smem(int H, int NBT) {
     const int UW = H / 16;
     return (size_t)2 * 16 * UW * 4 * 2 + (size_t)3 * 3 * 16 * 8 * 2 + (size_t)NBT * (NBT == 1 ? 2 : 1) * 16 * UW * 16 + (size_t)2 * 3 * (H / 8) * 256 + (size_t)2 * 6 * 2 * 1024;
 }
 
-template <int H, int NBT, bool DBG = false>
-static int launch_x6_t(const X6Args &a, hipStream_t st) {
-    if (int rc = launch_zero_fill(a.sync, 32 * sizeof(unsigned int), st)) return rc;
-    if (int rc = launch_zero_fill(a.hx, lstm_x6_hx_bytes(H, a.B), st)) return rc;   // tags must start at 0 on every launch (by a kernel: lstm.hip)
-    hipLaunchKernelGGL((lstm_layer_x6_kernel<H, NBT, DBG>), dim3(kPersistGrid), dim3(256), x6_smem(H, NBT), st, a);
-    MDD_LAUNCH_CHECK();
-    return MDD_OK;
-}
-
-// MDD_X6_DEV (development builds): only the instantiations under study are compiled (a full build of this file takes minutes)
-template <int H, int N>
-static constexpr bool x6_built() {
+// The instantiations: {384, 256} x 1..8 tiles per team; H = 384 also stamped (MDD_LSTM_DBG).  MDD_X6_DEV (development builds): only the
+// instantiations under study, H = 384 up to four tiles, are compiled (a full build of this file takes minutes)
+struct X6Family : PersistFamily {
+    using List = InstList<Inst<384, 1, true>, Inst<384, 2, true>, Inst<384, 3, true>, Inst<384, 4, true>, Inst<384, 5, true>, Inst<384, 6, true>, Inst<384, 7, true>, Inst<384, 8, true>,
+                          Inst<256, 1>, Inst<256, 2>, Inst<256, 3>, Inst<256, 4>, Inst<256, 5>, Inst<256, 6>, Inst<256, 7>, Inst<256, 8>>;
 #ifdef MDD_X6_DEV
-    return H == 384 && N <= 4;
-#else
-    return true;
+    static constexpr bool built(int H, int N) { return H == 384 && N <= 4; }
 #endif
-}
-template <int H, int N>
-static int launch_x6_pick(const X6Args &a, hipStream_t st) {
-    if constexpr (!x6_built<H, N>()) { set_error("persistent x6 lstm: H=%d with %d tiles per team is not in this development build", H, N); return MDD_ERR_ARG; }
-    else {
-        if constexpr (H == 384) { if (a.dbg) return launch_x6_t<H, N, true>(a, st); }
-        return launch_x6_t<H, N>(a, st);
-    }
-}
+    template <int H, int N, bool DBG> static auto kernel() { return lstm_layer_x6_kernel<H, N, DBG>; }
+    static constexpr size_t lds(int H, int N) { return x6_smem(H, N); }
+};
 
 int launch_lstm_layer_x6(const LstmStepArgs &s, const unsigned short *whh3, unsigned short *hx, unsigned int *sync, int *err_flag, hipStream_t st,
                          long long *stamps, int force_mask) {
     X6Args a;
     a.gx = s.gx; a.whh3 = whh3; a.hx = hx; a.sync = sync; a.err_flag = err_flag;
     a.out = s.out; a.out_raw = s.out_raw; a.oscale = s.oscale; a.oshift = s.oscale ? s.oshift : nullptr;
-    a.T = s.T; a.B = s.B; a.BGr = (s.B + 7) / 8; a.seqlen = s.seqlen;
-    a.force_mask = force_mask;
-    const int nbt = (a.BGr + 15) / 16;
-    a.dbg = stamps;
+    a.T = s.T; a.B = s.B; a.BGr = (s.B + 7) / 8; a.seqlen = s.seqlen; a.force_mask = force_mask; a.dbg = stamps;
+    const int nbt = x6_tiles(s.B);
     a.planes = s.out_planes; a.plane_stride = s.out_planes_stride; a.rows = s.T * s.B;
     if (a.planes && (double)a.rows * (2 * s.H) * 2 >= 4294967296.0) { set_error("persistent x6 lstm: a plane of %d x %d elements is beyond the 32-bit store offsets", a.rows, 2 * s.H); return MDD_ERR_ARG; }
     if (s.out_split.hi || s.gates_save || (!a.out && !a.out_raw && !a.planes) || !whh3) { set_error("persistent x6 lstm: fp32 outputs, inference only"); return MDD_ERR_ARG; }
-    if (nbt < 1 || nbt > 8) { set_error("persistent x6 lstm: B=%d needs %d row tiles per team (max 8)", s.B, nbt); return MDD_ERR_ARG; }
-#define X6_CASE(H_, N_) case N_: return launch_x6_pick<H_, N_>(a, st)
-    if (s.H == 384) switch (nbt) { X6_CASE(384, 1); X6_CASE(384, 2); X6_CASE(384, 3); X6_CASE(384, 4); X6_CASE(384, 5); X6_CASE(384, 6); X6_CASE(384, 7); X6_CASE(384, 8); }
-    if (s.H == 256) switch (nbt) { X6_CASE(256, 1); X6_CASE(256, 2); X6_CASE(256, 3); X6_CASE(256, 4); X6_CASE(256, 5); X6_CASE(256, 6); X6_CASE(256, 7); X6_CASE(256, 8); }
-#undef X6_CASE
-    set_error("persistent x6 lstm: unsupported H=%d", s.H);
+    if (nbt < 1 || nbt > kX6MaxTiles) { set_error("persistent x6 lstm: B=%d needs %d row tiles per team (max %d)", s.B, nbt, kX6MaxTiles); return MDD_ERR_ARG; }
+    const int rc = launch_instantiation<X6Family>(s.H, nbt, a.dbg != nullptr, a, hx, lstm_x6_hx_bytes(s.H, s.B), sync, st);
+    if (rc != kNoInstantiation) return rc;
+    if (!X6Family::built(s.H, nbt) && (s.H == 384 || s.H == 256))   // (a pair of the list that the development build's filter left out: no such pair in a full build)
+        set_error("persistent x6 lstm: H=%d with %d tiles per team is not in this development build", s.H, nbt);
+    else set_error("persistent x6 lstm: unsupported H=%d", s.H);
     return MDD_ERR_ARG;
 }
 
-template <int H, int N>
-static int x6_attr() {
-    if constexpr (x6_built<H, N>()) {
-        MDD_HIP_CHECK(hipFuncSetAttribute((const void *)lstm_layer_x6_kernel<H, N>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
-        if constexpr (H == 384) MDD_HIP_CHECK(hipFuncSetAttribute((const void *)lstm_layer_x6_kernel<H, N, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
-    }
-    return MDD_OK;
-}
-
-int init_lstm_x6_attributes() {
-#define XATTR(H, N) if (int rc = x6_attr<H, N>()) return rc
-    XATTR(384, 1); XATTR(384, 2); XATTR(384, 3); XATTR(384, 4); XATTR(384, 5); XATTR(384, 6); XATTR(384, 7); XATTR(384, 8);
-    XATTR(256, 1); XATTR(256, 2); XATTR(256, 3); XATTR(256, 4); XATTR(256, 5); XATTR(256, 6); XATTR(256, 7); XATTR(256, 8);
-#undef XATTR
-    return MDD_OK;
-}
+int init_lstm_x6_attributes() { return init_persistent_attributes<X6Family>(); }
 
 int persistent_x6_grid_fits(int n_cu) {
-    constexpr int N = x6_built<384, 8>() ? 8 : 4;
-    return persist_grid_fits(n_cu, (const void *)lstm_layer_x6_kernel<384, N>, x6_smem(384, N));
+    constexpr int N = X6Family::built(384, kX6MaxTiles) ? kX6MaxTiles : 4;
+    return persist_grid_fits(n_cu, (const void *)X6Family::kernel<384, N, false>(), X6Family::lds(384, N));
 }
 
 }  // namespace mdd

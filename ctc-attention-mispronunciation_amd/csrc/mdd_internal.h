@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include <map>
+#include <mutex>
 #include <string>
 #include <utility>
 #include <vector>
@@ -25,6 +26,23 @@ void set_error(const char *fmt, ...);
     } while (0)
 
 #define MDD_LAUNCH_CHECK() MDD_HIP_CHECK(hipGetLastError())
+
+// init() runs once per device of the process (kernel attributes belong to the device that is current when they are set), under a lock;
+// an init that fails runs again on the next call.  One state per family of kernels, a static of the entry that launches them.
+struct OncePerDevice {
+    std::mutex mu;
+    bool done[64] = {false};
+};
+template <class Init> int once_per_device(OncePerDevice &s, Init init) {
+    int dev = 0;
+    MDD_HIP_CHECK(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lock(s.mu);
+    if (!s.done[dev & 63]) {
+        if (int rc = init()) return rc;
+        s.done[dev & 63] = true;
+    }
+    return MDD_OK;
+}
 
 // A device array with exactly one owner: move-only, freed by its destructor.  need(n) grows it to at least n elements by freeing
 // and allocating afresh (the contents are not kept).
@@ -199,30 +217,32 @@ int64_t ctc_lattice_bytes(int T, int B, int C, int Lmax);
 bool ctc_lattice_fits(int T, int C, int Lmax);   // false: Lmax is past what either form of the scan holds in LDS
 int ctc_lattice(const float *logp, int T, int B, int C, const int32_t *len, const int32_t *ids, int ids_stride, const int32_t *nids, int Lmax,
                 int blank, double *ws, hipStream_t st, CtcLattice *out);
+// ---- lstm_step.hip: one launch per time step (launch_lstm_layer above; launch_lstm_layer_train: train.h)
 int init_lstm_attributes();
-// One launch for the whole layer (256 co-resident workgroups in 8-workgroup teams, data-tagged hand-off; see lstm.hip).
-int init_granule_attributes();
-int persistent_grid_fits(int n_cu);   // 1 when all 256 workgroups of a persistent layer launch can be resident at once
-// data-tagged variant (8-workgroup teams, no counter): hx = team8_hx_alloc_floats(H, B) floats (+ stamps; plan.h), sync: 32 uints.
+// ---- lstm_persist.hip: zero fill by a kernel (n a multiple of 16, p 16-byte aligned; see its definition for why not hipMemsetAsync)
+int launch_zero_fill(void *p, size_t n, hipStream_t st);
+// ---- lstm_granule.hip: one launch for the whole layer (256 co-resident workgroups in 8-workgroup teams, data-tagged hand-off, no counter),
+// split-bf16 arithmetic.  hx = team8_hx_alloc_floats(H, B) floats (+ stamps; plan.h), sync: 32 uints.
 // Diagnostics: stamps (nullable) receive per-workgroup phase cycle sums; early requests the next panel too early (redo path).
 int launch_lstm_layer_granule(const LstmStepArgs &s, unsigned short *hx, unsigned int *sync, int *err_flag, hipStream_t st,
                               long long *stamps = nullptr, bool early = false);
-// Exact-fp32 persistent layer (lstm_f32.hip): same teams / exchange buffer; W_hh in the packed layout (LstmStepArgs::packed), fp32 outputs
-// zero fill by a kernel (n a multiple of 16, p 16-byte aligned; see its definition in lstm.hip for why not hipMemsetAsync)
-int launch_zero_fill(void *p, size_t n, hipStream_t st);
+int init_granule_attributes();        // the forward and training-forward instantiations
+int persistent_grid_fits(int n_cu);   // 1 when all 256 workgroups of a persistent layer launch can be resident at once
+// ---- lstm_bwd.hip: the backward recurrence of a layer in one launch (split-bf16 training variant, B <= 256, H in {256, 384}); hx: lstm_bwd_granule_hx_bytes(H)
+size_t lstm_bwd_granule_hx_bytes(int H);
+int launch_lstm_bwd_granule(const float *dout, const float *gates, const float *cst, SplitPtr whhT, float *dg, int T, int B, int H, unsigned short *hx,
+                            unsigned int *sync, int *err_flag, hipStream_t st);
+__attribute__((visibility("hidden"))) int init_lstm_bwd_attributes();   // (hidden: the exported symbols stay as they were)
+// ---- lstm_f32.hip: exact-fp32 persistent layer, same teams / exchange buffer; W_hh in the packed layout (LstmStepArgs::packed), fp32 outputs
 int launch_lstm_layer_f32(const LstmStepArgs &s, unsigned short *hx, unsigned int *sync, int *err_flag, hipStream_t st, long long *stamps);
 int init_lstm_f32_attributes();
 int persistent_f32_grid_fits(int n_cu);
-// f32x6 persistent layer (lstm_x6.hip): teams of 16, W_hh' as three row-major bf16 planes [3][2][4H][H], h exchanged as three bf16 planes
+// ---- lstm_x6.hip: f32x6 persistent layer, teams of 16, W_hh' as three row-major bf16 planes [3][2][4H][H], h exchanged as three bf16 planes
 // (lstm_x6_hx_bytes); fp32 outputs.  force_mask >= 0: every (force_mask + 1)-th phase is declared stale (refetch branch).
 int launch_lstm_layer_x6(const LstmStepArgs &s, const unsigned short *whh3, unsigned short *hx, unsigned int *sync, int *err_flag, hipStream_t st,
                          long long *stamps, int force_mask);
 int init_lstm_x6_attributes();
 int persistent_x6_grid_fits(int n_cu);
-// The backward recurrence of a layer in one launch (split-bf16 training variant, B <= 256, H in {256, 384}); hx: lstm_bwd_granule_hx_bytes(H)
-size_t lstm_bwd_granule_hx_bytes(int H);
-int launch_lstm_bwd_granule(const float *dout, const float *gates, const float *cst, SplitPtr whhT, float *dg, int T, int B, int H, unsigned short *hx,
-                            unsigned int *sync, int *err_flag, hipStream_t st);
 // Per-device ticket around work that contains persistent launches (api.hip): launches of different handles / streams of one device run
 // one after another on the GPU (event dependency; the host does not block).  enter locks, leave records the event and unlocks.
 int device_gate_enter(int device, hipStream_t st, bool *held);

@@ -175,10 +175,16 @@ inline const char *ctc_geometry_error(const mdd_config &c) {
 // geometry runs its scalar form.  launch_ctc_tail checks the same sums per call.
 inline bool mfma_ctc_tail(const mdd_config &c) { return (2 * c.hidden) % 64 == 0 && c.num_class <= 48; }
 
-// Exchange buffers of the persistent layer kernels: batch rows per group of the 8-workgroup teams (lstm.hip, lstm_f32.hip; 16 groups,
-// padded to whole 16-row tiles), and the bytes of the 16-workgroup teams' buffer (lstm_x6.hip).  Both cover at most 1024 rows.
-inline int granule_bg(int B) { const int r = (B + 15) / 16; return (r + 15) / 16 * 16; }
-inline size_t lstm_x6_hx_bytes(int H, int B) { const int bgr = (B + 7) / 8, nbt = (bgr + 15) / 16; return (size_t)2 * 16 * nbt * 3 * (H / 8) * 256; }
+// 16-row tiles per team of the persistent layer kernels, which is the template instantiation a launcher picks: the 8-workgroup teams
+// (lstm_granule.hip, lstm_f32.hip, lstm_bwd.hip) split the batch over 16 groups, the 16-workgroup teams (lstm_x6.hip) over 8.  What each family
+// is built for: the split-bf16 and exact-fp32 layers, the training forward, the f32x6 layer, the backward layer.
+inline int team8_tiles(int B) { return ((B + 15) / 16 + 15) / 16; }
+inline int x6_tiles(int B) { return ((B + 7) / 8 + 15) / 16; }
+static constexpr int kTeam8MaxTiles = 4, kTrainMaxTiles = 2, kX6MaxTiles = 8, kBwdMaxTiles = 1;
+// Exchange buffers of the persistent layer kernels: batch rows per group of the 8-workgroup teams (padded to whole 16-row tiles), and the
+// bytes of the 16-workgroup teams' buffer.  Both cover at most 1024 rows.
+inline int granule_bg(int B) { return team8_tiles(B) * 16; }
+inline size_t lstm_x6_hx_bytes(int H, int B) { return (size_t)2 * 16 * x6_tiles(B) * 3 * (H / 8) * 256; }
 // The 8-workgroup teams' buffer, two sizes on purpose.  What the owners ALLOCATE, in floats: 2 parities x 32 teams x granule_bg(B) rows x H
 // u64 granules.  What the launchers zero before every launch and the kernels use, in bytes: 2 x 32 x BG rows x H tagged 4-byte words, half of
 // the allocation (the 2x slack is kept: the allocation's value is pinned by tests/test_host.py and the stamps sit behind it).

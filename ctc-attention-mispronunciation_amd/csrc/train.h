@@ -56,7 +56,7 @@ int launch_pack_gates(const float *w_fwd, const float *w_rev, float *packed, int
 int launch_unpack_gates(const float *packed, float *out_fwd, float *out_rev, int H, int K, hipStream_t st);
 int launch_transpose_whh(const float *w, float *wt, int H, hipStream_t st);
 int launch_lstm_bwd(const LstmBwdArgs &a, hipStream_t st);
-int launch_lstm_layer_train(const LstmStepArgs &a, hipStream_t st);   // lstm.hip: generic step kernels, saving gates and cell states
+int launch_lstm_layer_train(const LstmStepArgs &a, hipStream_t st);   // lstm_step.hip: generic step kernels, saving gates and cell states
 int launch_adam_multi(float *const *p, float *const *g, float *const *m, float *const *v, const int64_t *numel, int n, float lr, float b1, float b2, float eps,
                       float wd, int step, hipStream_t st);
 int launch_adam(float *p, const float *g, float *m, float *v, size_t n, float lr, float b1, float b2, float eps, float wd, int step, hipStream_t st);

@@ -228,7 +228,7 @@ extern "C" int mdd_train_create(const mdd_config *cfg, int device, mdd_train_ws 
     if (w->dacc.need(2 * 8192) || w->err_flag.need(2) || hipMemset(w->err_flag.p, 0, 2 * sizeof(int)) != hipSuccess || w->sync_words.need(32)) {
         set_error("mdd_train_create: out of memory"); return MDD_ERR_NOMEM;
     }
-    TRY(init_gemm_attributes()); TRY(init_gemm_x6_attributes()); TRY(init_granule_attributes()); TRY(init_conv1_attributes());
+    TRY(init_gemm_attributes()); TRY(init_gemm_x6_attributes()); TRY(init_granule_attributes()); TRY(init_lstm_bwd_attributes()); TRY(init_conv1_attributes());
     { int n_cu = 0; w->persist_ok = hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && persistent_grid_fits(n_cu) && !sw.lstm_step; }
     static_assert(2 * 8192 >= 2 * 8 * kMaxHidden, "dacc holds the two column sums of 8H features up to the largest hidden size (plan.h)");
     *out = w.release();

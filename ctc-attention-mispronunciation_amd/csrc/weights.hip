@@ -66,7 +66,7 @@ static bool bn_fold(mdd_model *m, const std::string &prefix, int n, std::vector<
     return true;
 }
 
-// rows n = g*H + u  ->  n' = u*4 + g (see lstm.hip); concatenates the two directions
+// rows n = g*H + u  ->  n' = u*4 + g (see lstm_step.hip); concatenates the two directions
 static bool pack_gate_rows(mdd_model *m, const std::string &base, const char *what, int H, int K, std::vector<float> &out) {
     out.assign((size_t)2 * 4 * H * K, 0.f);
     for (int d = 0; d < 2; d++) {
@@ -79,7 +79,7 @@ static bool pack_gate_rows(mdd_model *m, const std::string &base, const char *wh
     return true;
 }
 
-// Whh' [2][4H][H] (gate-permuted rows) -> Wp[d][ut][j][lane][m] (see lstm.hip)
+// Whh' [2][4H][H] (gate-permuted rows) -> Wp[d][ut][j][lane][m] (see lstm_step.hip)
 static void pack_whh(const std::vector<float> &w, int H, std::vector<float> &out) {
     const int NUT = H / 4, J = H / 16;
     out.resize(w.size());

@@ -1,11 +1,11 @@
 """The batch-tile geometries of the persistent BiLSTM layer kernels, shared by tests/test_batch_tiles.py (decode forward, GPU),
 tests/test_train_batch_tiles.py (training step, GPU) and tests/test_batch_tiles_reference.py (the CPU side of both).  No tests in here.
 
-The three layer kernels pick a template instantiation from the batch size (csrc/plan.h, lstm.hip, lstm_f32.hip, lstm_x6.hip):
+The three layer kernels pick a template instantiation from the batch size (csrc/plan.h, lstm_granule.hip, lstm_f32.hip, lstm_x6.hip):
 
     lstm_layer_x6_kernel<H, NBT>            128 rows per tile   NBT = ceil(ceil(B / 8) / 16) = 1..8    (NBT >= 3: the skewed schedule)
-    lstm_layer_f32_kernel<H, NBT>           256 rows per tile   NBT = granule_bg(B) / 16     = 1..4
-    lstm_layer_granule_kernel<H, NBT, RTW>  256 rows per tile   NBT = granule_bg(B) / 16     = 1..4
+    lstm_layer_f32_kernel<H, NBT>           256 rows per tile   NBT = team8_tiles(B)          = 1..4
+    lstm_layer_granule_kernel<H, NBT, RTW>  256 rows per tile   NBT = team8_tiles(B)          = 1..4
 
 TILE_B holds the first batch of each x6 instantiation NBT = 2..8 (one row into a new tile) and the full B = 1024; NBT is written down by
 hand from the formulas and compared with plan.h by tests/test_batch_tiles_reference.py.  B = 17 (one tile, held to float64 by

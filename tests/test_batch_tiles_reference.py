@@ -21,7 +21,7 @@ _DRIVER = r'''
 #include "plan.h"
 using namespace mdd;
 // stdin, one case per line: hidden mode B force        (reference geometry otherwise; force: MDD_LSTM_X6=force)
-// stdout: granule_bg(B) / 16, the x6 teams' tiles (from the size of their exchange buffer), the recurrence plan_forward picks, gated
+// stdout: team8_tiles(B), x6_tiles(B), the recurrence plan_forward picks, gated, the mode, kPersistMaxB, the two families' largest tile counts
 int main() {
     const DeviceFit fit{true, true, true};              // a whole MI355X holds every persistent grid
     for (std::string line; std::getline(std::cin, line);) {
@@ -35,9 +35,8 @@ int main() {
         sw.x6_force = force != 0;
         const ForwardPlan p = plan_forward(c, mode, sw, fit, B);
         const char *lstm = p.lstm == Lstm::X6 ? "x6" : p.lstm == Lstm::F32 ? "f32" : p.lstm == Lstm::Granule ? "granule" : "step";
-        const size_t per_tile = (size_t)2 * 16 * 3 * (c.hidden / 8) * 256;
-        std::cout << granule_bg(B) / 16 << ' ' << lstm_x6_hx_bytes(c.hidden, B) / per_tile << ' ' << lstm << ' ' << (p.gated ? 1 : 0) << ' '
-                  << p.precision << ' ' << kPersistMaxB << '\n';
+        std::cout << team8_tiles(B) << ' ' << x6_tiles(B) << ' ' << lstm << ' ' << (p.gated ? 1 : 0) << ' ' << p.precision << ' ' << kPersistMaxB << ' '
+                  << kTeam8MaxTiles << ' ' << kX6MaxTiles << '\n';
     }
 }
 '''
@@ -61,7 +60,7 @@ def tile_driver(tmp_path_factory):
 
 
 def test_nbt_table_follows_plan_h(tile_driver):
-    """The hand-made NBT table is granule_bg(B) / 16 and ceil(ceil(B / 8) / 16) of csrc/plan.h; the layer kernel each (H, precision) is
+    """The hand-made NBT table is team8_tiles(B) and x6_tiles(B) of csrc/plan.h (ceil(ceil(B / 16) / 16) and ceil(ceil(B / 8) / 16)); the layer kernel each (H, precision) is
     expected to run at the TILE_B batches is plan_forward's choice, MDD_LSTM_X6=force gives the f32x6 teams at H = 256, and B = 1025 gets no
     layer kernel in any mode.  Every instantiation NBT = 1..8 (x6) and 1..4 (granule, f32) occurs for both hidden sizes."""
     assert bt.TILE_B == (129, 257, 385, 513, 641, 769, 897, 1024) and bt.PAST_B == 1025 and bt.LONG[1] == 300
@@ -70,8 +69,8 @@ def test_nbt_table_follows_plan_h(tile_driver):
     for H in bt.HIDDEN:
         for p in bt.PRECISIONS:
             got = tile_driver([(H, _MODE[p], B, 0) for B in batches])
-            for B, (team8, x6, lstm, gated, prec, max_b) in zip(batches, got):
-                assert int(max_b) == 1024 and int(prec) == _MODE[p]
+            for B, (team8, x6, lstm, gated, prec, max_b, max_team8, max_x6) in zip(batches, got):
+                assert int(max_b) == 1024 and int(prec) == _MODE[p] and (int(max_team8), int(max_x6)) == (4, 8)
                 want_x6, want_team8 = bt.NBT[B]
                 if B > 1024:
                     assert (want_x6, want_team8) == (None, None) and (lstm, gated) == ("step", "0"), (H, p, B, lstm)
@@ -85,6 +84,11 @@ def test_nbt_table_follows_plan_h(tile_driver):
                     assert lstm == ("x6" if p == "f32x6" else bt.LAYER_KERNEL[H, p]), (H, p, B, lstm)
         forced = tile_driver([(H, _MODE["f32x6"], B, 1) for B in bt.TILE_B])
         assert [f[2] for f in forced] == ["x6"] * len(bt.TILE_B), (H, forced)
+    # every batch up to kPersistMaxB stays within both families' largest instantiation, and kPersistMaxB is the largest that does
+    every = tile_driver([(384, _MODE["f32x6"], B, 0) for B in range(1, 1026)])
+    for B, (team8, x6, _, _, _, max_b, max_team8, max_x6) in zip(range(1, 1026), every):
+        assert (1 <= int(team8) <= int(max_team8) and 1 <= int(x6) <= int(max_x6)) == (B <= int(max_b)), (B, team8, x6)
+    assert int(every[-1][0]) > 4 and int(every[-1][1]) > 8
     # which instantiations the batches reach (B = 17: tests/test_geometry.py; 300: the long case; the rest: TILE_B)
     on = [B for B in batches if B <= 1024]
     assert sorted({bt.NBT[B][0] for B in on}) == list(range(1, 9))

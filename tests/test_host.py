@@ -369,17 +369,20 @@ def test_asm_mfma_hazards(tmp_path):
         pytest.skip("no hipcc on this machine")
     csrc = os.path.join(ROOT, "ctc-attention-mispronunciation_amd", "csrc")
     procs = []
-    for unit, pat in (("lstm", ["granule"]), ("lstm_f32", ["layer_f32"]), ("gemm_bf16x6", ["f32x6"])):
+    # every translation unit with asm MFMAs, and how many kernels the screen must find in each (None: at least one): the 8 + 4 forward and
+    # training-forward instantiations, the 2 backward ones, the 8 + 4 stamped exact-fp32 ones -- a kernel cannot silently drop out of the screen
+    for unit, pat, count in (("lstm_granule", ["granule"], 12), ("lstm_bwd", ["granule"], 2), ("lstm_f32", ["layer_f32"], 12), ("gemm_bf16x6", ["f32x6"], None)):
         out = str(tmp_path / (unit + ".s"))
-        procs.append((unit, pat, out, subprocess.Popen([hipcc, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off", "-Wno-unused-result",
+        procs.append((unit, pat, count, out, subprocess.Popen([hipcc, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off", "-Wno-unused-result",
                                                         "-Wno-inline-asm", "--offload-device-only", "-S", "-o", out, os.path.join(csrc, unit + ".hip")],
                                                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))
-    for unit, pat, out, pr in procs:
+    for unit, pat, count, out, pr in procs:
         log = pr.communicate(timeout=900)[0]
         assert pr.returncode == 0, log[-2000:]
         r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "check_mfma_hazards.py"), out] + pat, capture_output=True, text=True)
         assert r.returncode == 0 and " 0 finding(s)" in r.stdout, unit + ":\n" + r.stdout[:3000]
         assert not r.stdout.startswith("0 kernel(s)"), unit
+        assert count is None or r.stdout.startswith("%d kernel(s) scanned" % count), unit + ": " + r.stdout[:100]
 
 
 _PLAN_DRIVER = r'''
