@@ -1,6 +1,6 @@
 // Persistent BPTT layer kernel.
 // The backward recurrence of one bidirectional layer in ONE launch (the split-bf16 training variant; the exact mode keeps one launch
-// per step, train_kernels.hip).  Same grid and teams as the forward layer kernel (lstm_granule.hip: 256 workgroups = 2 directions x 16 batch groups
+// per step, lstm_step.hip).  Same grid and teams as the forward layer kernel (lstm_granule.hip: 256 workgroups = 2 directions x 16 batch groups
 // x 8 members, one 16-row batch tile per team: B <= 256), the same data-tagged hand-off, the roles transposed:
 //   dh[b, k] = dout[t, b, k] + sum_n DG_prev[b, n] * Whh'[n][k]            (n over the 4H gate rows, k over the H units)
 // A member owns UW = H/8 units k.  Its rows of Whh'^T ([UW][4H], bf16 hi/lo) stay in registers for the whole launch, the

@@ -16,7 +16,10 @@
 //
 // The launch boundary is the step-to-step dependency (all-to-all over hidden units): per the
 // MI355X price list a dependent kernel boundary (~1.5 us) is cheaper than any in-launch grid sync.
+// The exact-fp32 training step's part of the family is here too (train.h): the gate-row packing and W_hh transpose of its weight
+// layouts and the per-step backward, lstm_bwd_step_kernel.  Every per-step kernel, forward or backward, goes through launch_steps().
 #include "lstm_persist.h"
+#include "train.h"
 
 namespace mdd {
 
@@ -80,7 +83,7 @@ __global__ __launch_bounds__(256) void lstm_step_kernel(LstmStepArgs a, int s) {
         const float hn = hold ? 0.f : og * tanhf(cn);
         a.cbuf[ci] = cn;
         hnext[(size_t)b * H + u] = hn;
-        if (a.gates_save) {   // train mode: what the backward sweep needs (train_kernels.hip)
+        if (a.gates_save) {   // train mode: what the backward sweep needs (lstm_bwd_step_kernel below, lstm_bwd.hip)
             const size_t si = (((size_t)t * B + b) * 2 + d) * H + u;
             *reinterpret_cast<float4 *>(a.gates_save + si * 4) = make_float4(ig, fg, gg, og);
             a.c_save[si] = cn;
@@ -283,14 +286,133 @@ __global__ __launch_bounds__(256, 1) void lstm_step_x3_kernel(LstmStepArgs a, in
     }
 }
 
-// One launch per time step of a per-step kernel, grid (grid_x, 2 directions, 64-row batch blocks); the caller checks the launches
-static void launch_steps(void (*kernel)(LstmStepArgs, int), int grid_x, size_t smem, const LstmStepArgs &a, hipStream_t st) {
-    for (int s = 0; s < a.T; s++) hipLaunchKernelGGL(kernel, dim3(grid_x, 2, (a.B + 63) / 64), dim3(256), smem, st, a, s);
+// ------------------------------------------------------------------------------------------------ LSTM weight layouts
+// reference W [4H, K] per direction (gate-major rows g*H + u)  <->  packed W' [2][4H][K] with rows u*4 + g
+__global__ void pack_gates_kernel(const float *__restrict__ w_fwd, const float *__restrict__ w_rev, float *__restrict__ packed, int H, int K, int to_packed,
+                                  float *__restrict__ out_fwd, float *__restrict__ out_rev) {
+    const size_t n = (size_t)2 * 4 * H * K;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const int k = (int)(i % K);
+        const size_t row = i / K;                      // d*4H + u*4 + g
+        const int d = (int)(row / (4 * H)), rr = (int)(row % (4 * H)), u = rr >> 2, g = rr & 3;
+        const size_t j = ((size_t)g * H + u) * K + k;  // index inside the direction's reference tensor
+        if (to_packed) packed[i] = (d ? w_rev : w_fwd)[j];
+        else (d ? out_rev : out_fwd)[j] = packed[i];
+    }
 }
+int launch_pack_gates(const float *w_fwd, const float *w_rev, float *packed, int H, int K, hipStream_t st) {
+    hipLaunchKernelGGL(pack_gates_kernel, dim3(2048), dim3(256), 0, st, w_fwd, w_rev, packed, H, K, 1, (float *)nullptr, (float *)nullptr);
+    MDD_LAUNCH_CHECK(); return MDD_OK;
+}
+int launch_unpack_gates(const float *packed, float *out_fwd, float *out_rev, int H, int K, hipStream_t st) {
+    hipLaunchKernelGGL(pack_gates_kernel, dim3(2048), dim3(256), 0, st, (const float *)nullptr, (const float *)nullptr, const_cast<float *>(packed), H, K, 0, out_fwd, out_rev);
+    MDD_LAUNCH_CHECK(); return MDD_OK;
+}
+// Whh' [2][4H][H] -> WhhT [2][H][4H]  (the backward step reads Whh' down its columns)
+__global__ void transpose_whh_kernel(const float *__restrict__ w, float *__restrict__ wt, int H) {
+    const size_t n = (size_t)2 * 4 * H * H;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const int k = (int)(i % H);
+        const size_t row = i / H;
+        const int d = (int)(row / (4 * H)), nrow = (int)(row % (4 * H));
+        wt[((size_t)d * H + k) * 4 * H + nrow] = w[i];
+    }
+}
+int launch_transpose_whh(const float *w, float *wt, int H, hipStream_t st) {
+    hipLaunchKernelGGL(transpose_whh_kernel, dim3(2048), dim3(256), 0, st, w, wt, H);
+    MDD_LAUNCH_CHECK(); return MDD_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ LSTM backward (BPTT), one launch per step
+// Backward order s = 0..T-1 visits time t_s = T-1-s (forward direction) / s (reverse direction).  Launch s, for its 16 hidden
+// units k and 16 batch rows b:
+//   dh[b,k]   = dout[t_s, b, d, k] + sum_n DG[t_prev][b, d, n] * Whh'[d][n][k]         (t_prev = the time visited by launch s-1)
+//   then the cell backward of (t_s, b, k): with the saved gates i,f,g,o, c_t and c_{t-1},
+//     do = dh * tanh(c_t) * o(1-o);   dc = dh * o * (1 - tanh(c_t)^2) + dc_carry
+//     di = dc * g * i(1-i);  df = dc * c_{t-1} * f(1-f);  dg = dc * i * (1-g^2);  dc_carry = dc * f
+//   DG[t_s][b, d, k*4 + {i,f,g,o}] = pre-activation gradients (what the weight-gradient GEMMs and the next launch read).
+// The contraction over n = 4H is split over the four waves of the workgroup (one quarter each, v_mfma_f32_16x16x4_f32 with the
+// units on the MFMA row axis) and combined through LDS; the launch boundary is the step-to-step dependency.
+// NQ4 > 0: H is a compile-time multiple of 16 and a lane's share of the contraction is NQ4 float4 steps (24 at H = 384, 16 at
+// H = 256): ALL of its loads are issued before the first MFMA, so a step pays one L2 round trip instead of one per unrolled group.
+template <int NQ4>
+__global__ __launch_bounds__(256, 1) void lstm_bwd_step_kernel(LstmBwdArgs a, int s) {
+    __shared__ float red[4][16 * 16];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int kt = blockIdx.x, d = blockIdx.y, b0 = blockIdx.z * 16;
+    const int H = a.H, B = a.B, T = a.T, G = 4 * H;
+    const int t = d ? s : (T - 1 - s);
+    const int tprev = d ? s - 1 : (T - s);                 // time visited by the previous launch
+    const int li = lane & 15, kq = lane >> 4;
+    // the cell backward's operands (saved gates, cell states, the carried cell gradient, the upstream gradient) do not depend on the
+    // product: every thread requests those of its (unit, batch) element before the contraction, one memory round trip per step
+    const int ul = tid >> 4, bl = tid & 15;
+    const int u = kt * 16 + ul, b = b0 + bl;
+    const bool live = u < H && b < B;
+    const int uc = min(u, H - 1), bcl = min(b, B - 1);
+    const size_t si = (((size_t)t * B + bcl) * 2 + d) * H + uc;
+    const float4 gt = *reinterpret_cast<const float4 *>(a.gates + si * 4);
+    const float ct = a.cst[si];
+    const int tp = d ? t + 1 : t - 1;                       // the forward pass's previous time of this direction
+    const float cprev = (tp >= 0 && tp < T) ? a.cst[(((size_t)tp * B + bcl) * 2 + d) * H + uc] : 0.f;
+    const size_t ci = ((size_t)d * B + bcl) * H + uc;
+    const float dc_in = s > 0 ? a.dc[ci] : 0.f;
+    const float dout_v = a.dout[((size_t)t * B + bcl) * 2 * H + d * H + uc];
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    if (s > 0) {
+        // wave w contracts n in [w*G/4, (w+1)*G/4); inside the wave the four 16-lane groups take contiguous quarters of that range
+        const int nq = G / 16, n0 = wave * (G / 4) + kq * nq;
+        const int bb = min(b0 + li, B - 1);
+        const float *wp = a.whhT + ((size_t)d * H + min(kt * 16 + li, H - 1)) * G + n0;               // A[row = unit li][n]
+        const float *gp = a.dg + (((size_t)tprev * B + bb) * 2 + d) * G + n0;                        // B[n][col = batch li]
+        if (NQ4 > 0) {
+            float4 w4[NQ4 > 0 ? NQ4 : 1], g4[NQ4 > 0 ? NQ4 : 1];
+#pragma unroll
+            for (int n = 0; n < NQ4; n++) { w4[n] = *reinterpret_cast<const float4 *>(wp + 4 * n); g4[n] = *reinterpret_cast<const float4 *>(gp + 4 * n); }
+            __builtin_amdgcn_sched_barrier(0);
+            f32x4 a1 = acc, a2 = acc, a3 = acc;           // four chains: the dependent-issue latency of the fp32 MFMA exceeds its issue time
+#pragma unroll
+            for (int n = 0; n < NQ4; n++) {
+                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w4[n].x, g4[n].x, acc, 0, 0, 0);
+                a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w4[n].y, g4[n].y, a1, 0, 0, 0);
+                a2 = __builtin_amdgcn_mfma_f32_16x16x4f32(w4[n].z, g4[n].z, a2, 0, 0, 0);
+                a3 = __builtin_amdgcn_mfma_f32_16x16x4f32(w4[n].w, g4[n].w, a3, 0, 0, 0);
+            }
+#pragma unroll
+            for (int r = 0; r < 4; r++) acc[r] = (acc[r] + a1[r]) + (a2[r] + a3[r]);
+        } else {
+            for (int n = 0; n < nq; n++) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wp[n], gp[n], acc, 0, 0, 0);
+        }
+    }
+    // D layout: col = lane&15 (batch), row = 4*(lane>>4) + r (unit within the tile)
+#pragma unroll
+    for (int r = 0; r < 4; r++) red[wave][(4 * kq + r) * 16 + li] = acc[r];
+    __syncthreads();
+    // one thread per (unit, batch) of the tile
+    if (!live) return;
+    const float dh_rec = (red[0][ul * 16 + bl] + red[1][ul * 16 + bl]) + (red[2][ul * 16 + bl] + red[3][ul * 16 + bl]);
+    const float dh = dout_v + dh_rec;
+    const float th = tanhf(ct);
+    const float d_o = dh * th * gt.w * (1.f - gt.w);
+    const float dcell = dh * gt.w * (1.f - th * th) + dc_in;
+    const float d_i = dcell * gt.z * gt.x * (1.f - gt.x);
+    const float d_f = dcell * cprev * gt.y * (1.f - gt.y);
+    const float d_g = dcell * gt.x * (1.f - gt.z * gt.z);
+    a.dc[ci] = dcell * gt.y;
+    *reinterpret_cast<float4 *>(a.dg + (((size_t)t * B + b) * 2 + d) * G + u * 4) = make_float4(d_i, d_f, d_g, d_o);
+}
+
+// One launch per time step of a per-step kernel (forward: LstmStepArgs, backward: LstmBwdArgs); the caller checks the launches
+template <class Args>
+static void launch_steps(void (*kernel)(Args, int), dim3 grid, size_t smem, const Args &a, hipStream_t st) {
+    for (int s = 0; s < a.T; s++) hipLaunchKernelGGL(kernel, grid, dim3(256), smem, st, a, s);
+}
+// grid of the forward kernels: (grid_x, 2 directions, 64-row batch blocks)
+static dim3 fwd_grid(int grid_x, const LstmStepArgs &a) { return dim3(grid_x, 2, (a.B + 63) / 64); }
 template <int RT, int H>
 static void launch_x3_steps(const LstmStepArgs &a, hipStream_t st) {
     constexpr int ROWB = H * 2 + 16;
-    launch_steps(lstm_step_x3_kernel<RT, H>, 4 * H / (RT * 16), (size_t)2 * (RT * 16 + 64) * ROWB, a, st);
+    launch_steps(lstm_step_x3_kernel<RT, H>, fwd_grid(4 * H / (RT * 16), a), (size_t)2 * (RT * 16 + 64) * ROWB, a, st);
 }
 
 int init_lstm_attributes() {
@@ -301,7 +423,7 @@ int init_lstm_attributes() {
 
 int launch_lstm_layer_train(const LstmStepArgs &a, hipStream_t st) {
     if (a.H % 4 != 0 || a.T <= 0 || a.B <= 0 || a.packed || a.hsplit) { set_error("lstm (train): bad arguments T=%d B=%d H=%d", a.T, a.B, a.H); return MDD_ERR_ARG; }
-    launch_steps(a.H == 384 ? lstm_step_kernel<24> : a.H == 256 ? lstm_step_kernel<16> : a.H % 16 == 0 ? lstm_step_kernel<1> : lstm_step_kernel<0>, a.H / 4, 0, a, st);
+    launch_steps(a.H == 384 ? lstm_step_kernel<24> : a.H == 256 ? lstm_step_kernel<16> : a.H % 16 == 0 ? lstm_step_kernel<1> : lstm_step_kernel<0>, fwd_grid(a.H / 4, a), 0, a, st);
     MDD_LAUNCH_CHECK();
     return MDD_OK;
 }
@@ -311,7 +433,15 @@ int launch_lstm_layer(const LstmStepArgs &a, hipStream_t st) {
     if (a.hsplit && a.H != 384 && a.H != 256) { set_error("lstm: split-bf16 step built for H in {256,384}"); return MDD_ERR_ARG; }
     if (!a.hsplit && a.packed && a.H != 384 && a.H != 256) { set_error("lstm: packed layout built for H in {256,384}"); return MDD_ERR_ARG; }
     if (a.hsplit) a.H == 384 ? launch_x3_steps<2, 384>(a, st) : launch_x3_steps<2, 256>(a, st);
-    else launch_steps(!a.packed ? lstm_step_kernel<0> : a.H == 384 ? lstm_step_packed_kernel<24> : lstm_step_packed_kernel<16>, a.H / 4, 0, a, st);
+    else launch_steps(!a.packed ? lstm_step_kernel<0> : a.H == 384 ? lstm_step_packed_kernel<24> : lstm_step_packed_kernel<16>, fwd_grid(a.H / 4, a), 0, a, st);
+    MDD_LAUNCH_CHECK();
+    return MDD_OK;
+}
+
+int launch_lstm_bwd(const LstmBwdArgs &a, hipStream_t st) {
+    if (a.H % 4) { set_error("lstm backward: H must be a multiple of 4"); return MDD_ERR_ARG; }
+    launch_steps(a.H == 384 ? lstm_bwd_step_kernel<24> : a.H == 256 ? lstm_bwd_step_kernel<16> : lstm_bwd_step_kernel<0>,
+                 dim3((a.H + 15) / 16, 2, (a.B + 15) / 16), 0, a, st);
     MDD_LAUNCH_CHECK();
     return MDD_OK;
 }

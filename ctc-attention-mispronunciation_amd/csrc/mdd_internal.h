@@ -135,6 +135,7 @@ int launch_transpose_split3(const float *x, int K, int rows, int ld, int Kp, uns
 int launch_gemm_f32x6_splitk(const unsigned short *A3, size_t a_plane, const unsigned short *W3, size_t w_plane, float *part, int M, int N, int Kc, int S,
                              hipStream_t st);
 
+// ---- conv_f32.hip: input stacking and the exact-fp32 convs (mode 0, the tiny geometries)
 int launch_stack_skip(const float *raw, int B, int T_raw, int D, int right, int skip, int n_down, float *out,
                       hipStream_t st);
 // conv0: x [B,T,F] -> y0 [B,ch,T,W1]; conv1: y0 -> seq [T/2,B,ch*W2] (BN+ReLU folded; scale/shift per channel)
@@ -142,7 +143,14 @@ int launch_conv0(const float *x, const float *w, const float *scale, const float
                  int ch, hipStream_t st);
 int launch_conv1(const float *y0, const float *w_t, const float *scale, const float *shift, float *seq, SplitPtr seq_split, int B,
                  int T, int W1, int ch, hipStream_t st);  // seq (fp32) and/or seq_split may be null
+// The channel counts the exact-fp32 conv kernels (decode and training) are built for: f(integral_constant<int, ch>), false for any other count
+template <class F> bool with_conv_channels(int ch, F f) {
+    if (ch == 32) f(std::integral_constant<int, 32>{});
+    else if (ch == 4) f(std::integral_constant<int, 4>{});
+    return ch == 32 || ch == 4;
+}
 
+// ---- conv_fused.hip (row at a time), conv_multirow.hip (launch_conv_fused3's default); what they share: conv_fused.h
 // conv0 -> conv1 fused on the bf16 matrix cores (feat 243, 32 channels): x [B,T,243] -> split-bf16 rows [T/2*B, 1952]
 // (w1: conv1 weights as [co][kh][kw][ci] hi/lo planes).  out_f32 optional (taps).
 int launch_conv_fused(const float *x, const float *w0, const float *sc0, const float *sh0, SplitPtr w1, const float *sc1,
@@ -152,7 +160,7 @@ int launch_conv_fused3(const float *x, const float *w0, const float *sc0, const 
                        bool rowwise = false,    // f32x6 form: three K-tile-major planes out (rowwise: the row-at-a-time kernel, MDD_CONV=rowwise)
                        long long *stamps = nullptr);   // stamps (diagnostic, default kernel only): the stamped instantiation's phase cycle sums
 int init_conv_attributes();
-constexpr int CM_NPH = 10;  // stamped phases per wave of the default fused3 kernel (frontend.hip)
+constexpr int CM_NPH = 10;  // stamped phases per wave of the default fused3 kernel (conv_multirow.hip)
 
 // C = opA . opB^T (+ bias) as f32x6 in the training step's operand forms (ta / tb: stored [K, rows]); S > 1: split-K into `part` and a sum.
 // x6_ops_ok: the alignment half of the rule (leading dimensions multiples of 4, 16-byte aligned pointers).
