@@ -20,6 +20,7 @@ EXPORTS = (
     "mdd_train_create", "mdd_train_destroy", "mdd_train_num_tensors", "mdd_train_tensor_info", "mdd_train_num_masks", "mdd_train_mask_bytes",
     "mdd_train_forward", "mdd_train_backward", "mdd_train_sync", "mdd_train_set_precision", "mdd_adam_step",
     "mdd_diag_gemm_ph8", "mdd_diag_gates", "mdd_diag_gemm", "mdd_diag_gemm_ops", "mdd_diag_gemm_time", "mdd_diag_gemm_clock", "mdd_diag_conv_time",
+    "mdd_diag_beam_stamps",
 )
 
 
@@ -77,6 +78,8 @@ def lib():
     L.mdd_sync.argtypes = [vp, vp]
     L.mdd_greedy.argtypes = [vp, i32, i32, i32, vp, i32, vp, vp, vp]
     L.mdd_beam.argtypes = [vp, i32, i32, i32, vp, i32, i32, vp, C.c_double, vp, vp, vp, vp, vp]
+    if hasattr(L, "mdd_diag_beam_stamps"):   # a diagnostic entry: a build of an earlier commit under MDD_LIB_PATH (timing comparisons) lacks it
+        L.mdd_diag_beam_stamps.argtypes = [vp, i32, i32, i32, vp, i32, i32, vp, C.c_double, vp, vp, vp, vp, vp, vp]
     L.mdd_beam_nbest.argtypes = [vp, i32, i32, i32, vp, i32, i32, vp, C.c_double, i32, vp, vp, vp, vp, vp]
     L.mdd_ctc_loss.argtypes = [vp, i32, i32, i32, vp, i32, vp, vp, i32, vp, vp, vp, C.c_int64, vp]
     L.mdd_ctc_workspace_bytes.argtypes = [i32, i32, i32, i32, i32]

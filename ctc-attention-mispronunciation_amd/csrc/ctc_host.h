@@ -19,7 +19,7 @@ public:
     StreamWorkspace &operator=(const StreamWorkspace &) = delete;
     StreamWorkspace(StreamWorkspace &&o) noexcept : p_(o.p_), owned_(o.owned_), st_(o.st_) { o.p_ = o.owned_ = nullptr; }
     ~StreamWorkspace() { if (owned_) (void)hipFreeAsync(owned_, st_); }
-    int acquire(void *caller, int64_t need, hipStream_t st) {
+    __attribute__((visibility("hidden"))) int acquire(void *caller, int64_t need, hipStream_t st) {   // (hidden: where it is not inlined it is no new export)
         p_ = caller;
         if (caller || need <= 0) return MDD_OK;
         MDD_HIP_CHECK(hipMallocAsync(&owned_, (size_t)need, st));

@@ -52,6 +52,9 @@
 // The training handle takes MDD_LSTM=step (per-step recurrence in its split-bf16 variant too), MDD_GEMM_X6_RASTER (its one-launch f32x6
 // products; the split-K ones are always in the row walk), its own two switches and nothing else of this table: its persistent layer
 // launches carry no diagnostics.
+//
+// The beam entries take no handle: their two switches (MDD_BEAM_GENERIC, MDD_BEAM_W) are read at every call by read_beam_switches(), and
+// beam_plan() below is their selection, the same kind of pure function.
 #pragma once
 #include <stddef.h>
 #include <stdlib.h>
@@ -241,6 +244,79 @@ inline ForwardPlan plan_forward(const mdd_config &c, int precision, const Switch
         const size_t granules = team8_hx_alloc_floats(H, B), planes = lstm_x6_hx_bytes(H, B) / 4;
         p.stamps_at = lx6 ? planes : granules;
         p.hx_floats = (lx6 && planes > granules ? planes : granules) + kHxTailFloats;
+    }
+    return p;
+}
+
+// ---- The beam entries (beam.hip): everything mdd_beam / mdd_beam_nbest decide from numbers -- the LDS needs of the two search kernels, the
+// route, the waves per workgroup, and which limit a shape is over.  tests/test_beam_plan_host.py walks it against the expressions written out.
+#if defined(__HIPCC__)
+#define MDD_PLAN_HD __host__ __device__
+#else
+#define MDD_PLAN_HD
+#endif
+
+constexpr int kBeamMax = 64;       // beams of the generic kernel (beam.h: MAXBEAM)
+constexpr int kBeamFastMax = 16;   // beams of the single-wave kernel (beam.h: FB)
+
+// LDS bytes of one wave's private state in beam_fast_kernel (NS*64 slots, beam prefixes of up to Tcap ids), and of the LM table its waves share.
+// The kernel lays its LDS out by these two, the plan budgets it by them.
+MDD_PLAN_HD inline size_t beam_fast_wave_bytes(int NS, int beam, int Tcap) {
+    constexpr int FB = kBeamFastMax;
+    return sizeof(double) * ((size_t)2 * NS * 64 + 64 + 6 * FB + 4 * FB) + sizeof(unsigned long long) * 4 * FB +
+           sizeof(int) * ((size_t)2 * NS * 64 + 4 * FB + 2 * FB) + (size_t)(2 * FB + 1) * Tcap;   // FB prefix rows whatever the beam: no row guards
+}
+MDD_PLAN_HD inline size_t beam_fast_lm_bytes(int C) { return (sizeof(double) * (size_t)(C + 1) * (C + 1) + 15) & ~(size_t)15; }
+
+// The switches of the beam entries, read at every call (include/mdd_hip.h promises it; tests/test_decoders.py sets them per test).
+struct BeamSwitches {
+    bool generic = false;   // MDD_BEAM_GENERIC (any value): every shape to the generic kernel
+    int w = 0;              // MDD_BEAM_W = w: utterances per workgroup of the single-wave kernel (0: unset; honoured where 1 <= w <= W and B > 64)
+};
+static inline BeamSwitches read_beam_switches() {   // (static, and beam_plan: no symbol of the library, the exports stay as they were)
+    BeamSwitches s;
+    s.generic = getenv("MDD_BEAM_GENERIC") != nullptr;
+    if (const char *e = getenv("MDD_BEAM_W")) s.w = atoi(e);
+    return s;
+}
+
+constexpr size_t kBeamGenericLdsMax = 140 * 1024, kBeamLmInLdsMax = 96 * 1024, kBeamFastLdsMax = 160 * 1024;
+enum class BeamLimit { Ok, GenericLds, FastLds };   // "beam*C / T too large for LDS" | "T too long for LDS"
+struct BeamPlan {
+    BeamLimit over;      // Ok, or the first limit the shape is over, in the order the entries refuse; the fields behind it are then not filled in
+    size_t over_bytes;   // the LDS need its message prints
+    bool nbest;          // the ending: mdd_beam_nbest's ranked list, or the winner alone
+    int Tcap;            // a prefix row: T ids + 1, in whole words
+    size_t smem;         // generic kernel: dynamic LDS,
+    int lm_in_lds;       //   with the LM table in it
+    bool fast;           // the route: beam_fast_kernel, or beam_kernel
+    int NS;              // fast kernel: slots per lane (the instantiation),
+    size_t lmb, pw;      //   LDS of the shared LM table and of one wave, each rounded up to 16 bytes,
+    int W;               //   waves (utterances) per workgroup; 0 on the generic route
+};
+static inline BeamPlan beam_plan(int T, int B, int C, int beam, bool nbest_entry, const BeamSwitches &sw) {
+    BeamPlan p{};
+    p.nbest = nbest_entry;
+    p.Tcap = (T + 1 + 3) & ~3;
+    const size_t lm_bytes = sizeof(double) * (size_t)(C + 1) * (C + 1);
+    const size_t base = (sizeof(double) * 2 + sizeof(int)) * (size_t)beam * C + (size_t)(2 * beam + 1) * p.Tcap;
+    p.lm_in_lds = (base + lm_bytes <= kBeamLmInLdsMax) ? 1 : 0;
+    p.smem = base + (p.lm_in_lds ? lm_bytes : 0);
+    if (p.smem > kBeamGenericLdsMax) { p.over = BeamLimit::GenericLds; p.over_bytes = p.smem; return p; }
+    const int nslots = beam * C;
+    p.fast = beam <= kBeamFastMax && C <= 64 && nslots <= 1024 && !sw.generic;
+    p.NS = nslots <= 512 ? 8 : 16;
+    p.lmb = beam_fast_lm_bytes(C);
+    p.pw = (beam_fast_wave_bytes(p.NS, beam, p.Tcap) + 15) & ~(size_t)15;
+    if (p.fast && p.lmb + p.pw > kBeamFastLdsMax) { p.over = BeamLimit::FastLds; p.over_bytes = p.lmb + p.pw; return p; }
+    if (p.fast) {
+        // waves per workgroup: as many as the LDS holds (<= 4); a small batch spreads out instead (one wave per CU is the
+        // lowest latency when nothing else wants the CUs)
+        int W = (int)((kBeamFastLdsMax - p.lmb) / p.pw);
+        W = W > 4 ? 4 : W;                                              // one wave per SIMD: the kernel is built for the 512-VGPR budget
+        if (B <= 64) W = 1;
+        if (sw.w >= 1 && sw.w <= W) W = sw.w;
+        p.W = W;
     }
     return p;
 }

@@ -2,7 +2,7 @@
 
 ``GreedyDecoder`` / ``BeamDecoder`` keep the reference's constructor arguments and
 ``decode(prob_tensor, frame_seq_len) -> list[str]`` contract (same strings, same exception types);
-the scans run in gfx950 kernels (mdd_greedy / mdd_beam, csrc/decode.hip).  ``Decoder.wer`` keeps the
+the scans run in gfx950 kernels (mdd_greedy / mdd_beam, csrc/greedy.hip and csrc/beam.hip).  ``Decoder.wer`` keeps the
 ``(distance, op-path)`` return and runs the integer DP + backtrace natively on the host (mdd_align).
 Posteriors may live on the GPU (no copy) or on the CPU as the reference passes them (copied in).
 """

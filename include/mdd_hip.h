@@ -232,9 +232,11 @@ int mdd_greedy(const float *logp_dev, int32_t T, int32_t B, int32_t C, const int
  *     global memory beyond that.
  *   The generic bound is checked for every shape, so the single-wave kernel obeys both.  For C = 45: T <= 3995 at beam 10,
  *   T <= 663 at beam 64.  A shape over a limit returns MDD_ERR_ARG (mdd_last_error names the LDS need) and writes nothing.
+ *   These sums, the route and the waves per workgroup are one host function, beam_plan in csrc/plan.h (tests/test_beam_plan_host.py).
  * Environment, read at every call (diagnostics and tests): MDD_BEAM_GENERIC (any value) sends every shape to the generic kernel;
  * MDD_BEAM_W = w sets the utterances per workgroup of the single-wave kernel when B > 64 and 1 <= w <= W, W = min(4, what the LDS
- * holds); any other value is ignored, and so is the variable when B <= 64 (one utterance per workgroup). */
+ * holds); any other value is ignored, and so is the variable when B <= 64 (one utterance per workgroup).  The entry reads nothing else
+ * and writes only its outputs; the phase stamps of the single-wave kernel are mdd_diag_beam_stamps's (Diagnostics, below). */
 int mdd_beam(const float *logp_dev, int32_t T, int32_t B, int32_t C, const int32_t *len_dev, int32_t beam,
              int32_t blank, const double *lm_dev, double lm_alpha, int32_t *ids_dev, int32_t *nids_dev,
              int32_t *status_dev, double *score_dev, void *stream);
@@ -257,7 +259,7 @@ int mdd_beam(const float *logp_dev, int32_t T, int32_t B, int32_t C, const int32
  * The score is the beam's own and no CTC likelihood (the search skips near-certain blank frames and applies its repeat rule to raw
  * frames); the loss entry on a slice gives the exact one.  A bad argument (those of the winner-only entry, nbest outside [1,beam], a NULL
  * score_dev) or a shape over an LDS limit returns MDD_ERR_ARG with nothing enqueued and nothing written; the message starts with the
- * entry's name.  MDD_BEAM_DBG is not read by this entry. */
+ * entry's name. */
 int mdd_beam_nbest(const float *logp_dev, int32_t T, int32_t B, int32_t C, const int32_t *len_dev, int32_t beam, int32_t blank,
                    const double *lm_dev, double lm_alpha, int32_t nbest,
                    int32_t *ids_dev    /* [nbest,B,T] */, int32_t *nids_dev /* [nbest,B] */,
@@ -512,6 +514,14 @@ int mdd_diag_gemm_clock(int M, int N, int K, int reps, float *ms_out, float *mhz
    wave in each phase, from one launch of the stamped instantiation of the default kernel.  mismatch (nullable): the number of output
    words in which the two kernels differ. */
 int mdd_diag_conv_time(int B, int T, int reps, int which, float *ms_out, double *phases, long long *mismatch);
+/* mdd_diag_beam_stamps: mdd_beam (same arguments, outputs and refusals; the outputs are mdd_beam's bits) through the stamped instantiation of
+   the single-wave kernel.  stamps_dev [B,12], the caller's own buffer: per utterance the cycles its wave spent in each of the eleven phases
+   of the frame loop, summed over the live frames (tools/beam_stamps.py names them), and in word 11 the sum of the candidate-list lengths.
+   Returns MDD_ERR_ARG with nothing enqueued and nothing written when stamps_dev is NULL or the shape is not routed to the single-wave
+   kernel (beam > 16, C > 64, beam*C > 1024, or MDD_BEAM_GENERIC set): the generic kernel has no stamps. */
+int mdd_diag_beam_stamps(const float *logp_dev, int32_t T, int32_t B, int32_t C, const int32_t *len_dev, int32_t beam,
+                         int32_t blank, const double *lm_dev, double lm_alpha, int32_t *ids_dev, int32_t *nids_dev,
+                         int32_t *status_dev, double *score_dev, long long *stamps_dev /* [B,12] */, void *stream);
 int mdd_diag_gates(const float *x_dev, float *sig_dev, float *tanh_dev, int64_t n, void *stream);
 
 #ifdef __cplusplus

@@ -1,4 +1,4 @@
-"""Every kernel path of csrc/decode.hip against the CPU oracle (oracle/mdd_oracle.c: orc_beam / orc_greedy), through the C ABI.
+"""Every kernel path of csrc/greedy.hip and csrc/beam*.hip against the CPU oracle (oracle/mdd_oracle.c: orc_beam / orc_greedy), through the C ABI.
 
 The three search kernels and the host dispatch are driven with any class count, beam width, blank index and batch size: several waves
 per workgroup (B > 64, MDD_BEAM_W), both fast-kernel instantiations and their slot-count edges, the same shapes through the generic
@@ -18,7 +18,10 @@ Known blind spots.  Which of the two slots a merged entry occupies (`q < a` in t
 the symmetric ties of the tied and uniform families both placements sort alike, so only the hand-built `mergetie` family (a merged
 entry that ties a non-mate at the cut of the beam) tells them apart.  The environment switches cannot be observed through the ABI: if
 the library stopped reading MDD_BEAM_W or MDD_BEAM_GENERIC, the routes would run one kernel and still pass.  The prefix-verify loop
-matters only on a hash collision, which nothing here injects."""
+matters only on a hash collision, which nothing here injects.
+
+The LDS limits restated below in Python are csrc/plan.h's beam_plan, which tests/test_beam_plan_host.py walks on the CPU; the stamped
+instantiations of the single-wave kernel run through mdd_diag_beam_stamps at the end of the beam section."""
 import ctypes as C
 import functools
 from typing import NamedTuple, Optional, Tuple
@@ -456,7 +459,7 @@ def _record(route, rel):
 
 
 def check_beam(case, route, monkeypatch):
-    for var in ("MDD_BEAM_GENERIC", "MDD_BEAM_W", "MDD_BEAM_DBG", "MDD_BEAM_SKIP"):
+    for var in ("MDD_BEAM_GENERIC", "MDD_BEAM_W"):
         monkeypatch.delenv(var, raising=False)
     if route == "generic":
         monkeypatch.setenv("MDD_BEAM_GENERIC", "1")
@@ -506,6 +509,76 @@ def test_beam_T_limit(beam, Cn, monkeypatch):
     assert msg.startswith("mdd_beam") and "LDS" in msg, msg
     assert (ids == SENT_I).all() and (nids == SENT_I).all() and (st == SENT_I).all() and (sc == SENT_F).all()
     check_beam(CASE_BY_NAME["fast_flat_b16_C45_blank0"], "auto", monkeypatch)
+
+
+# --------------------------------------------------------------------------------- mdd_diag_beam_stamps (the stamped instantiation)
+STAMP_WORDS = 12
+SENT_S = -(1 << 40)        # no cycle count and no list length is negative
+STAMP_SHAPES = {"ns8": (5, 3), "ns16": (64, 16)}      # (C, beam): beam*C <= 512 is the 8-slot instantiation, 1024 the 16-slot one
+
+
+def _stamp_case(Cn, beam):
+    return Case("stamps_b%d_C%d" % (beam, Cn), "flat", Cn, beam, 0, 0.2, 12, 3, 900 + beam + Cn, lens=(12, 9, 5))
+
+
+def gpu_beam_stamps(logp, lens, lm, beam, blank, alpha, null_stamps=False):
+    """One mdd_diag_beam_stamps call on sentinel-filled outputs: (rc, ids, nids, status, score, stamps [B,12], guard [12]) as numpy.  The
+    stamp buffer is the caller's own [B,12] words; the 12 words allocated behind it are the guard that must come back untouched."""
+    T, B, Cn = logp.shape
+    d_lp, d_len, d_lm = _dev(logp), _dev(np.asarray(lens, dtype=np.int32)), _dev(np.asarray(lm, dtype=np.float64))
+    ids = torch.full((B, T), SENT_I, dtype=torch.int32, device="cuda")
+    nids = torch.full((B,), SENT_I, dtype=torch.int32, device="cuda")
+    st = torch.full((B,), SENT_I, dtype=torch.int32, device="cuda")
+    sc = torch.full((B,), SENT_F, dtype=torch.float64, device="cuda")
+    stamps = torch.full((B + 1, STAMP_WORDS), SENT_S, dtype=torch.int64, device="cuda")
+    torch.cuda.synchronize()
+    rc = _L().mdd_diag_beam_stamps(_ptr(d_lp), T, B, Cn, _ptr(d_len), beam, blank, _ptr(d_lm), C.c_double(alpha), _ptr(ids), _ptr(nids),
+                                   _ptr(st), _ptr(sc), None if null_stamps else _ptr(stamps), None)
+    torch.cuda.synchronize()
+    stamps = stamps.cpu().numpy()
+    return rc, ids.cpu().numpy(), nids.cpu().numpy(), st.cpu().numpy(), sc.cpu().numpy(), stamps[:B], stamps[B]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape", sorted(STAMP_SHAPES))
+def test_beam_stamps_entry_decodes_like_mdd_beam(shape, monkeypatch):
+    """Both stamped instantiations: ids, nids, status and score are mdd_beam's on the same input, bit for bit; every word of stamps[B,12]
+    was written, the eleven cycle sums are not negative; the 12 words behind the buffer are untouched."""
+    for var in ("MDD_BEAM_GENERIC", "MDD_BEAM_W"):
+        monkeypatch.delenv(var, raising=False)
+    Cn, beam = STAMP_SHAPES[shape]
+    case = _stamp_case(Cn, beam)
+    assert fast_eligible(beam, Cn) and (beam * Cn <= 512) == (shape == "ns8")
+    logp, lens, lm = inputs(case)
+    rc0, ids0, nids0, st0, sc0 = gpu_beam(logp, lens, lm, beam, case.blank, case.alpha)
+    assert rc0 == MDD_OK, _L().mdd_last_error().decode()
+    rc, ids, nids, st, sc, stamps, guard = gpu_beam_stamps(logp, lens, lm, beam, case.blank, case.alpha)
+    assert rc == MDD_OK, _L().mdd_last_error().decode()
+    assert (nids0 != SENT_I).all() and (nids0 > 0).any(), "the input must decode"
+    for name, a, b in (("ids", ids, ids0), ("nids", nids, nids0), ("status", st, st0), ("score", sc, sc0)):
+        assert a.tobytes() == b.tobytes(), name
+    print("%s: stamps of utterance 0: %s" % (case.name, stamps[0].tolist()))
+    assert (stamps != SENT_S).all(), "a stamp word was not written"
+    assert (stamps[:, :11] >= 0).all()
+    assert (guard == SENT_S).all(), "words behind the stamp buffer were written"
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("why", ["generic_only_beam17", "null_stamps"])
+def test_beam_stamps_entry_refuses_without_writing(why, monkeypatch):
+    """A shape the plan does not send to the single-wave kernel, or no stamp buffer: MDD_ERR_ARG, nothing enqueued, every output's
+    sentinels intact."""
+    for var in ("MDD_BEAM_GENERIC", "MDD_BEAM_W"):
+        monkeypatch.delenv(var, raising=False)
+    Cn, beam = (5, 17) if why == "generic_only_beam17" else (5, 3)
+    case = _stamp_case(Cn, beam)
+    assert fast_eligible(beam, Cn) == (why == "null_stamps")
+    logp, lens, lm = inputs(case)
+    rc, ids, nids, st, sc, stamps, guard = gpu_beam_stamps(logp, lens, lm, beam, case.blank, case.alpha, null_stamps=why == "null_stamps")
+    assert rc == MDD_ERR_ARG
+    assert _L().mdd_last_error().decode().startswith("mdd_diag_beam_stamps"), _L().mdd_last_error().decode()
+    assert (ids == SENT_I).all() and (nids == SENT_I).all() and (st == SENT_I).all() and (sc == SENT_F).all()
+    assert (stamps == SENT_S).all() and (guard == SENT_S).all()
 
 
 # ------------------------------------------------------------------------------------------------------------- greedy

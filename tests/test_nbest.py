@@ -1,4 +1,4 @@
-"""mdd_beam_nbest on every kernel path of csrc/decode.hip, BeamDecoder.decode_nbest on top of it (GPU).
+"""mdd_beam_nbest on every kernel path of csrc/beam*.hip, BeamDecoder.decode_nbest on top of it (GPU).
 
 Every (case, route) of tests/test_decoders.py runs at nbest = beam, 1 and min(3, beam) on sentinel-filled outputs.  Asserted: the
 status is the oracle's; slice 0 (ids, nids, score) and the status are bit-identical to an mdd_beam call on the same inputs, for every
@@ -49,7 +49,7 @@ def gpu_nbest(logp, lens, lm, beam, blank, alpha, nbest):
 
 
 def _set_route(route, monkeypatch):
-    for var in ("MDD_BEAM_GENERIC", "MDD_BEAM_W", "MDD_BEAM_DBG", "MDD_BEAM_SKIP"):
+    for var in ("MDD_BEAM_GENERIC", "MDD_BEAM_W"):
         monkeypatch.delenv(var, raising=False)
     if route == "generic":
         monkeypatch.setenv("MDD_BEAM_GENERIC", "1")

@@ -1,8 +1,7 @@
-"""Diagnostic: per-phase cycle shares of beam_fast_kernel (MDD_BEAM_DBG; stamps go to a side buffer behind the scores)."""
+"""Diagnostic: per-phase cycle shares of beam_fast_kernel (mdd_diag_beam_stamps; the stamps go to a [B,12] buffer of their own)."""
 import os, sys, ctypes as C
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-os.environ['MDD_BEAM_DBG'] = '1'
 import torch, numpy as np
 from ctc_attention_mispronunciation_amd import synth, _lib
 from ctc_attention_mispronunciation_amd.utils.NgramLM import LanguageModel
@@ -12,12 +11,14 @@ lp = torch.log_softmax(torch.from_numpy(z), -1).cuda()
 lm = torch.from_numpy(LanguageModel(os.path.join(ROOT, 'tests/golden/lm_synth45.arpa')).dense_table(synth.phone_table_41(), Cn)).cuda()
 lens = torch.full((B,), T, dtype=torch.int32, device='cuda')
 ids = torch.empty((B, T), dtype=torch.int32, device='cuda'); nids = torch.empty(B, dtype=torch.int32, device='cuda'); st = torch.empty(B, dtype=torch.int32, device='cuda')
-score = torch.zeros(B + B * 12, dtype=torch.float64, device='cuda')   # [B scores | B x 12 int64 stamps]
+score = torch.zeros(B, dtype=torch.float64, device='cuda')
+stamps = torch.zeros((B, 12), dtype=torch.int64, device='cuda')
 for _ in range(2):
-    _lib.check(_lib.lib().mdd_beam(C.c_void_p(lp.data_ptr()), T, B, Cn, C.c_void_p(lens.data_ptr()), 10, 0, C.c_void_p(lm.data_ptr()), 0.0,
-               C.c_void_p(ids.data_ptr()), C.c_void_p(nids.data_ptr()), C.c_void_p(st.data_ptr()), C.c_void_p(score.data_ptr()), None))
+    _lib.check(_lib.lib().mdd_diag_beam_stamps(C.c_void_p(lp.data_ptr()), T, B, Cn, C.c_void_p(lens.data_ptr()), 10, 0, C.c_void_p(lm.data_ptr()), 0.0,
+               C.c_void_p(ids.data_ptr()), C.c_void_p(nids.data_ptr()), C.c_void_p(st.data_ptr()), C.c_void_p(score.data_ptr()),
+               C.c_void_p(stamps.data_ptr()), None))
 torch.cuda.synchronize()
-ph = score[B:].view(torch.int64).view(B, 12).cpu().numpy().astype(np.float64)
+ph = stamps.cpu().numpy().astype(np.float64)
 names = ['load/prefetch', 'candidates', 'copy+parent', 'verify', 'err', 'merge', 'lmax+lane-rank+theta', 'compact', 'rank', 'materialise', 'prefix copy', '(list len sum)']
 tot = ph[:, :11].sum(1).mean()
 for i, n in enumerate(names):
