@@ -107,7 +107,7 @@ static int project(mdd_model *m, const ProjIn &in, int rows, int K, const LstmWe
     if (m->plan.proj == Gemm::F32x6) {   // fp32-grade arithmetic at 6/16 of the fp32 MFMA's cost (gemm_bf16x6.hip)
         if (!in.planes_written)
             if (int rc = launch_split3(in.f32, rows, K, K, as_u16(m->p3), st)) return rc;
-        return launch_gemm_f32x6(as_u16(m->p3), (size_t)rows * K, lw.wih_3, (size_t)G2 * K, bias, m->gx.p, rows, G2, K, G2, st, m->sw.x6_raster);
+        return launch_gemm_f32x6(as_u16(m->p3), (size_t)rows * K, lw.wih_3, (size_t)G2 * K, bias, m->gx.p, rows, G2, K, G2, st, m->sw.x6_raster, nullptr, m->sw.x6_rt);
     }
     return launch_gemm_nt({.p = in.f32, .ld = K}, {.p = lw.wih, .ld = K}, m->gx.p, G2, rows, G2, K, st, {.bias = bias});
 }

@@ -18,6 +18,13 @@ static int diag_raster(const char *entry, X6Raster *out) {
     if (e && !x6_raster_parse(e, out)) { set_error("%s: MDD_GEMM_X6_RASTER=%s (rows, or <rb>x<cb> with rb * cb <= 32)", entry, e); return MDD_ERR_ARG; }
     return MDD_OK;
 }
+// Likewise the tile, MDD_GEMM_X6_RT: unset, the launcher's rule (kX6RtRule; `unset` where an entry's default is another); 3 or 4; anything else is an error.
+static int diag_rt(const char *entry, int *out, int unset = kX6RtRule) {
+    const char *e = getenv("MDD_GEMM_X6_RT");
+    *out = unset;
+    if (e && !x6_rt_parse(e, out)) { set_error("%s: MDD_GEMM_X6_RT=%s (3 or 4)", entry, e); return MDD_ERR_ARG; }
+    return MDD_OK;
+}
 
 // Pseudo-random fill: element i is value(hash(i, seed)).  The three formulas are the ones the figures under profiles/ were taken with.
 template <class T, class F> __global__ void diag_fill_kernel(T *p, size_t n, unsigned seed, F value) {
@@ -152,7 +159,7 @@ extern "C" int mdd_diag_gates(const float *x_dev, float *sig_dev, float *tanh_de
 }
 
 // One GEMM through a chosen arithmetic, fp32 operands and result on the device; synchronises.  The f32x6 launches of this entry and of the
-// two below take their tile walk from MDD_GEMM_X6_RASTER as it stands at the call (plan.h).
+// two below take their tile walk from MDD_GEMM_X6_RASTER and their tile from MDD_GEMM_X6_RT as they stand at the call (plan.h).
 //   mode 0: exact fp32 MFMA (gemm_nt_f32_kernel)   1: split-bf16 x3 (operands split here)   3: the f32x6 kernel (three planes, split here)
 extern "C" int mdd_diag_gemm(int mode, const float *A_dev, const float *W_dev, float *C_dev, int M, int N, int K, void *stream) {
     hipStream_t st = (hipStream_t)stream;
@@ -163,6 +170,8 @@ extern "C" int mdd_diag_gemm(int mode, const float *A_dev, const float *W_dev, f
     const int planes = mode == 1 ? 2 : 3;
     X6Raster raster;
     if (int rc = diag_raster("mdd_diag_gemm", &raster)) return rc;
+    int rt;
+    if (int rc = diag_rt("mdd_diag_gemm", &rt)) return rc;
     DeviceArray<unsigned short> pa, pw;     // freed on return, behind the synchronisation
     if (pa.need(planes * na) || pw.need(planes * nw)) { set_error("mdd_diag_gemm: out of memory"); return MDD_ERR_NOMEM; }
     int rc;
@@ -175,7 +184,7 @@ extern "C" int mdd_diag_gemm(int mode, const float *A_dev, const float *W_dev, f
         rc = once_per_device(attr, init_gemm_x6_attributes);
         if (!rc) rc = launch_split3(A_dev, M, K, K, pa.p, st);
         if (!rc) rc = launch_split3(W_dev, N, K, K, pw.p, st);
-        if (!rc) rc = launch_gemm_f32x6(pa.p, na, pw.p, nw, nullptr, C_dev, M, N, K, N, st, raster);
+        if (!rc) rc = launch_gemm_f32x6(pa.p, na, pw.p, nw, nullptr, C_dev, M, N, K, N, st, raster, nullptr, rt);
     }
     (void)hipStreamSynchronize(st);
     return rc;
@@ -191,10 +200,12 @@ extern "C" int mdd_diag_gemm_ops(int mode, int ta, int tb, const float *A_dev, i
     const GemmOperand A{A_dev, lda, ta != 0}, B{B_dev, ldb, tb != 0};
     X6Raster raster;
     if (int rc = diag_raster("mdd_diag_gemm_ops", &raster)) return rc;
+    int rt;
+    if (int rc = diag_rt("mdd_diag_gemm_ops", &rt, 3)) return rc;   // unset: the training step's tile
     DeviceBuf xa, xb, part;     // freed on return, behind the synchronisation
     int rc;
     if (mode == 0) rc = launch_gemm_f32(A, B, C_dev, ldc, M, N, K, st);
-    else if (!(rc = init_gemm_x6_attributes())) rc = gemm_f32x6_ops(A, B, nullptr, C_dev, ldc, M, N, K, splits, xa, xb, part, st, raster);
+    else if (!(rc = init_gemm_x6_attributes())) rc = gemm_f32x6_ops(A, B, nullptr, C_dev, ldc, M, N, K, splits, xa, xb, part, st, raster, rt);
     if (hipStreamSynchronize(st) != hipSuccess && !rc) { set_error("mdd_diag_gemm_ops: the stream failed"); rc = MDD_ERR_HIP; }
     return rc;
 }
@@ -216,6 +227,8 @@ static int gemm_time(const char *entry, int mode, int M, int N, int K, int reps,
     if (mode != 0 && mode != 1 && mode != 3) { set_error("%s: mode %d", entry, mode); return MDD_ERR_ARG; }
     X6Raster raster;
     if (int rc = diag_raster(entry, &raster)) return rc;
+    int rt;
+    if (int rc = diag_rt(entry, &rt)) return rc;
     const size_t na = (size_t)M * K, nw = (size_t)N * K, nc = (size_t)M * N;
     DeviceBuf A, W, Cm;
     DeviceArray<unsigned short> pa, pw;
@@ -232,7 +245,7 @@ static int gemm_time(const char *entry, int mode, int M, int N, int K, int reps,
         if (int rc = launch_split3(A.p, M, K, K, pa.p, nullptr)) return rc;
         if (int rc = launch_split3(W.p, N, K, K, pw.p, nullptr)) return rc;
     }
-    const auto x6 = [&](long long *stamps) { return launch_gemm_f32x6(pa.p, na, pw.p, nw, nullptr, Cm.p, M, N, K, N, nullptr, raster, stamps); };
+    const auto x6 = [&](long long *stamps) { return launch_gemm_f32x6(pa.p, na, pw.p, nw, nullptr, Cm.p, M, N, K, N, nullptr, raster, stamps, rt); };
     const size_t ns = X6_STAMP_WORDS;
     DeviceArray<long long> sd;
     if (mode == 3 && (mhz_out || getenv("MDD_GEMM_STAMP"))) {
@@ -267,7 +280,7 @@ static int gemm_time(const char *entry, int mode, int M, int N, int K, int reps,
         for (size_t w_ = 0; w_ < 1024 * 4; w_++) if (h[w_ * 4 + 0] > 0) { for (int i = 0; i < 4; i++) sum[i] += (double)h[w_ * 4 + i]; cnt++; }
         const double d = (double)cnt * (K / 32);
         if (cnt) printf("  f32x6 stamps, cycles per K-tile and wave: MFMA stream %.0f (ideal %d), memory wait %.0f, barrier %.0f\n",
-                        sum[0] / d, X6_RT * 8 * 6 * 16, sum[1] / d, sum[2] / d);
+                        sum[0] / d, x6_choose_tile(M, x6_ceil_div(N, 128), raster, rt).rt * 8 * 6 * 16, sum[1] / d, sum[2] / d);
         fflush(stdout);
     }
     return MDD_OK;

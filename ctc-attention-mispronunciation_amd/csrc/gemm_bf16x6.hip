@@ -16,12 +16,19 @@
 
 namespace mdd {
 
-// ---- the kernel: 192 x 128 tile of C per workgroup, FOUR waves (one per SIMD, 512 registers each), K-tile 32.
-// A wave owns 48 rows x all 128 columns: 3 x 8 MFMA tiles x THREE accumulator sets -- hh (hi.hi), sm (the five small products), tot (hh
+// ---- the kernel: a (64 RT) x 128 tile of C per workgroup, FOUR waves (one per SIMD, 512 registers each), K-tile 32; RT = 3 or 4 (template
+// parameter; which launch takes which: x6_choose_tile, gemm_raster.h).
+// A wave owns 16 RT rows x all 128 columns: RT x 8 MFMA tiles x THREE accumulator sets -- hh (hi.hi), sm (the five small products), tot (hh
 // flushed into it every X6_FLUSH K-tiles: at K = 1952 one chain of 61 roundings was measured at 1.3x ATen's error, segments of 8
-// are below it) = 288 accumulator registers, which is what the one-wave-per-SIMD shape is for.
+// are below it).  RT = 3: 288 accumulator registers, which is what the one-wave-per-SIMD shape is for.  RT = 4 (256 x 128, the large
+// projections' tile): hh and sm alone are the 256 registers of the accumulation file, and `tot`, which is idle but for one addition per
+// segment, lives in the 112 KB of LDS the stages leave (28 of a lane's 32 chunks, X6_TOT below; 4 in registers): the per-K-tile cost that
+// does not grow with the rows -- the W pieces and fragment reads, the wait and the barrier -- is spread over a third more MFMAs, and per
+// MFMA a quarter fewer W bytes come through LDS and from beyond L2.  The arithmetic of a C element is the same in both: tot = 0, then
+// tot = tot + hh per segment, then (tot + sm) + bias.  What it gave (1 - 2.5 % of kernel time: the flush now costs LDS bandwidth of all
+// four waves at once) is in profiles/gemm_rt4_notes.txt.  RT = 3 is the training step's split-K instantiation and every small launch.
 // Operand paths (what the first forms of this kernel taught, profiles/round3_gemm_f32x6_notes.txt):
-//  * A: a wave's rows are nobody else's, so its A fragments never touch LDS: nine 16-byte-per-lane global loads per K-tile straight into
+//  * A: a wave's rows are nobody else's, so its A fragments never touch LDS: 3 RT (nine, twelve) 16-byte-per-lane global loads per K-tile straight into
 //    registers, issued a whole K-tile ahead.  The planes are K-tile-major (launch_split3), so one load instruction is 1 KB of
 //    contiguous memory in fragment order.
 //  * W: shared by the four waves, streamed HBM/L2 -> LDS by LDS-DMA (24 KB per K-tile, six pieces per wave, XOR-swizzled on the
@@ -36,12 +43,19 @@ namespace mdd {
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) void lds_void6;
-constexpr int X6_BM = 4 * 16 * X6_RT, X6_BN = 128, X6_BK = 32, X6_ROW = 64;   // X6_RT (mdd_internal.h): 16-row MFMA tiles per wave; X6_ROW: bytes per LDS row (32 bf16)
+constexpr int X6_BN = 128, X6_BK = 32, X6_ROW = 64;                   // X6_ROW: bytes per LDS row (32 bf16); a tile's rows: x6_bm(RT) (gemm_raster.h)
 constexpr int X6_PW = X6_BN * X6_ROW;                                 // bytes per W plane of a stage (8 KB)
 constexpr int X6_STAGE = 3 * X6_PW;                                   // 24 KB
 constexpr int X6_NS = 2;                                              // stages
 constexpr int X6_NPW = 3 * (X6_BN / 16) / 4;                          // LDS-DMA pieces per wave and K-tile (6)
 constexpr int X6_FLUSH = 8;
+// RT = 4: where a lane's `tot` lives.  Chunk c = i * 8 + j (row tile i, column tile j; one f32x4) of thread t is at X6_TOT + (c * 256 + t) * 16 bytes
+// behind the two W stages -- chunk-major, so a wave's 16-byte reads and writes are 1 KB of consecutive LDS (conflict-free) and a lane only
+// ever meets its own data: no barrier, only the wave's own lgkmcnt.  As many chunks as the CU's 160 KB hold beside the stages (28 of the
+// 32); the rest stay in registers.  Never an LDS-DMA target.
+constexpr int X6_TOT = X6_NS * X6_STAGE, X6_LDS_CU = 160 * 1024;
+constexpr int x6_tot_lds(int rt) { return rt < 4 ? 0 : (X6_LDS_CU - X6_TOT) / (256 * 16) < rt * 8 ? (X6_LDS_CU - X6_TOT) / (256 * 16) : rt * 8; }
+constexpr int x6_lds_bytes(int rt) { return X6_TOT + x6_tot_lds(rt) * 256 * 16; }
 
 __device__ __forceinline__ bf16x8 x6_frag(const unsigned char *plane, int row, int kbyte) {
     return *reinterpret_cast<const bf16x8 *>(plane + row * X6_ROW + ((((kbyte >> 4) ^ ((row >> 2) & 3))) << 4));
@@ -55,17 +69,20 @@ __device__ __forceinline__ bf16x8 x6_frag(const unsigned char *plane, int row, i
 // are always taken in the row walk (the launcher builds it as chunks x tiles_c and sets walk.tiles_n to the output's column tiles); K is the
 // chunk's length.  The instantiation with SPLITK false is the decode path's kernel: every SPLITK expression below folds to the plain
 // argument (Ap, Wp, C, ldc), and tile_of to one call of x6_tile_of per round looked at.
-template <bool STAMP, bool SPLITK = false>
+template <int RT, bool STAMP, bool SPLITK = false>
 __global__ __launch_bounds__(256, 1) void gemm_f32x6_kernel(const unsigned short *__restrict__ Ap, const unsigned short *__restrict__ Wp, size_t a_plane, size_t w_plane,
                                                             const float *__restrict__ bias, float *__restrict__ C, int M, int N, int K, int ldc, X6Walk walk,
                                                             long long *stamps) {
     // STAMP (diagnostic instantiation): per wave, cycles of the K loop in the MFMA stream / waiting for memory / at the barrier
     // -> stamps[(workgroup * 4 + wave) * 4 + {0, 1, 2}]; per workgroup, the shader clock's and the 100 MHz constant clock's ticks around
     // the tile loop -> stamps[X6_STAMP_PHASE_WORDS + workgroup * 2 + {0, 1}]: their quotient is the clock the chip held (tools/gemm_time.py)
+    constexpr int X6_RT = RT, X6_BM = x6_bm(RT);
+    constexpr int NL = x6_tot_lds(RT);   // chunks of `tot` in LDS (RT = 3: none, `tot` is registers and every NL branch below folds away)
     long long sacc[4] = {0, 0, 0, 0}, stt = 0, clk0 = 0, rt0 = 0;
 #define X6_T(i_) do { if (STAMP) { const long long n_ = (long long)__builtin_readcyclecounter(); sacc[i_] += n_ - stt; stt = n_; } } while (0)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem6[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    f32x4 *const totl = reinterpret_cast<f32x4 *>(smem6 + X6_TOT) + tid;   // chunk c of this lane: totl[c * 256]
     // PERSISTENT: a workgroup takes one tile per round of `walk` (one workgroup per CU: no dispatch between tiles, and the next tile's first
     // operands are requested before this tile's epilogue).  Which tile, gemm_raster.h says: by default the 32 workgroups of an XCD
     // (blockIdx.x % 8) share a block of 4 row panels x 8 column tiles per round, so that what the XCD streams through its L2 in the round
@@ -134,7 +151,7 @@ __global__ __launch_bounds__(256, 1) void gemm_f32x6_kernel(const unsigned short
     load_a(faA, 0);
 #define X6_MFMA(acc_, w_, a_) asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc_) : "v"(w_), "v"(a_))
     // One K-tile: fac holds its A fragments, fan receives the next K-tile's.  Column tiles in pairs (jp): the pair's six W fragments are read
-    // from LDS one pair ahead; per pair 3 rows x 2 columns x 6 products = 36 MFMAs, product-major (six different accumulators in a row),
+    // from LDS one pair ahead; per pair RT rows x 2 columns x 6 products = 36 (48) MFMAs, product-major (six different accumulators in a row),
     // smallest products first, hi.hi last and into its own accumulator.
     auto ktile = [&](int kt, bf16x8 (&fac)[X6_RT][3], bf16x8 (&fan)[X6_RT][3]) {
         const unsigned char *st = smem6 + (kt % X6_NS) * X6_STAGE;
@@ -155,11 +172,12 @@ __global__ __launch_bounds__(256, 1) void gemm_f32x6_kernel(const unsigned short
 #pragma unroll
                     for (int jj = 0; jj < 2; jj++) fw[(jp + 1) & 1][p][jj] = x6_frag(st + p * X6_PW, ((jp + 1) * 2 + jj) * 16 + l16, kq16);
             }
-            // memory instructions of the next K-tile, one per product group: 9 A fragment loads (pairs 0, 1), 6 W pieces (pairs 1, 2)
+            // memory instructions of the next K-tile, one per product group: the 3 * RT A fragment loads (9: pairs 0, 1; 12: pairs 0, 1), then the
+            // 6 W pieces (pairs 1, 2; at RT = 4 pairs 2, 3)
 #define X6_MEM(g_) do { const int s_ = jp * 6 + (g_); \
-                if (s_ < 9) { const int p_ = s_ / X6_RT, i_ = s_ % X6_RT; \
+                if (s_ < 3 * X6_RT) { const int p_ = s_ / X6_RT, i_ = s_ % X6_RT; \
                     asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(fan[i_][p_]) : "v"(aoff[i_]), "s"(X6_AB + (size_t)p_ * a_plane + (size_t)ktn * M * 32) : "memory"); } \
-                else if (s_ < 9 + X6_NPW) piece(s_ - 9, ktn, nst); } while (0)
+                else if (s_ < 3 * X6_RT + X6_NPW) piece(s_ - 3 * X6_RT, ktn, nst); } while (0)
 #define X6_GROUP(acc_, wp_, ap_) _Pragma("unroll") for (int i = 0; i < X6_RT; i++) { _Pragma("unroll") for (int jj = 0; jj < 2; jj++) X6_MFMA(acc_[i][jp * 2 + jj], fw[jp & 1][wp_][jj], fac[i][ap_]); }
             X6_MEM(0); X6_GROUP(sm, 1, 1)      // mid . mid
             X6_MEM(1); X6_GROUP(sm, 2, 0)      // W lo . A hi
@@ -189,7 +207,10 @@ __global__ __launch_bounds__(256, 1) void gemm_f32x6_kernel(const unsigned short
 #pragma unroll
     for (int i = 0; i < X6_RT; i++)
 #pragma unroll
-        for (int j = 0; j < 8; j++) { hh[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f}; sm[i][j] = hh[i][j]; tot[i][j] = hh[i][j]; }
+        for (int j = 0; j < 8; j++) {
+            hh[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f}; sm[i][j] = hh[i][j];
+            if (i * 8 + j < NL) totl[(i * 8 + j) * 256] = hh[i][j]; else tot[i][j] = hh[i][j];
+        }
     if (STAMP) stt = (long long)__builtin_readcyclecounter();
     // Segments of X6_FLUSH K-tiles with the flush of hh into tot BETWEEN them; K-tiles in pairs, so that the two A fragment sets swap roles
     // without a register copy.
@@ -204,7 +225,11 @@ __global__ __launch_bounds__(256, 1) void gemm_f32x6_kernel(const unsigned short
 #pragma unroll
         for (int i = 0; i < X6_RT; i++)
 #pragma unroll
-            for (int j = 0; j < 8; j++) { tot[i][j] += hh[i][j]; hh[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
+            for (int j = 0; j < 8; j++) {
+                if (i * 8 + j < NL) { f32x4 t = totl[(i * 8 + j) * 256]; t += hh[i][j]; totl[(i * 8 + j) * 256] = t; }
+                else tot[i][j] += hh[i][j];
+                hh[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            }
     }
     // the next tile's first W stage and A fragments are requested before this tile's epilogue (stage 0 and faA are free: every wave has passed
     // the last K-tile's barrier)
@@ -227,7 +252,7 @@ __global__ __launch_bounds__(256, 1) void gemm_f32x6_kernel(const unsigned short
         for (int j = 0; j < 8; j++) {
             const int col = n0c + j * 16 + q4;
             if (row >= M || col >= N) continue;
-            f32x4 v = tot[i][j] + sm[i][j];
+            f32x4 v = (i * 8 + j < NL ? totl[(i * 8 + j) * 256] : tot[i][j]) + sm[i][j];
             if (bias) { v[0] += bias[col]; if (col + 1 < N) v[1] += bias[col + 1]; if (col + 2 < N) v[2] += bias[col + 2]; if (col + 3 < N) v[3] += bias[col + 3]; }
             float *dst = Cc + (size_t)row * X6_LDC + col;
             if (col + 3 < N) *reinterpret_cast<f32x4 *>(dst) = v;
@@ -250,23 +275,34 @@ __global__ __launch_bounds__(256, 1) void gemm_f32x6_kernel(const unsigned short
 }
 
 int init_gemm_x6_attributes() {
-    MDD_HIP_CHECK(hipFuncSetAttribute((const void *)gemm_f32x6_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, X6_NS * X6_STAGE));
-    MDD_HIP_CHECK(hipFuncSetAttribute((const void *)gemm_f32x6_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, X6_NS * X6_STAGE));
-    MDD_HIP_CHECK(hipFuncSetAttribute((const void *)gemm_f32x6_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, X6_NS * X6_STAGE));
+    static_assert(x6_lds_bytes(3) == X6_NS * X6_STAGE && x6_lds_bytes(4) <= X6_LDS_CU && x6_tot_lds(4) >= 1, "the RT = 4 tile's tot region fits the CU's LDS");
+    MDD_HIP_CHECK(hipFuncSetAttribute((const void *)gemm_f32x6_kernel<3, false>, hipFuncAttributeMaxDynamicSharedMemorySize, x6_lds_bytes(3)));
+    MDD_HIP_CHECK(hipFuncSetAttribute((const void *)gemm_f32x6_kernel<3, true>, hipFuncAttributeMaxDynamicSharedMemorySize, x6_lds_bytes(3)));
+    MDD_HIP_CHECK(hipFuncSetAttribute((const void *)gemm_f32x6_kernel<3, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, x6_lds_bytes(3)));
+    MDD_HIP_CHECK(hipFuncSetAttribute((const void *)gemm_f32x6_kernel<4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, x6_lds_bytes(4)));
+    MDD_HIP_CHECK(hipFuncSetAttribute((const void *)gemm_f32x6_kernel<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, x6_lds_bytes(4)));
     return MDD_OK;
+}
+
+template <int RT> static void x6_launch(const X6Walk &walk, hipStream_t st, const unsigned short *A3, const unsigned short *W3, size_t a_plane, size_t w_plane,
+                                        const float *bias, float *C, int M, int N, int K, int ldc, long long *stamps) {
+    const dim3 grid(walk.grid);   // one persistent workgroup per CU
+    if (stamps) hipLaunchKernelGGL((gemm_f32x6_kernel<RT, true>), grid, dim3(256), x6_lds_bytes(RT), st, A3, W3, a_plane, w_plane, bias, C, M, N, K, ldc, walk, stamps);
+    else hipLaunchKernelGGL((gemm_f32x6_kernel<RT, false>), grid, dim3(256), x6_lds_bytes(RT), st, A3, W3, a_plane, w_plane, bias, C, M, N, K, ldc, walk, (long long *)nullptr);
 }
 
 // A3, W3: three consecutive K-tile-major bf16 planes (hi | mid | lo; launch_split3) of a_plane = M x K / w_plane = N x K elements each
 int launch_gemm_f32x6(const unsigned short *A3, size_t a_plane, const unsigned short *W3, size_t w_plane, const float *bias, float *C, int M, int N, int K,
-                      int ldc, hipStream_t st, X6Raster raster, long long *stamps) {
-    if (M <= 0 || N <= 0 || K <= 0 || K % X6_BK || ldc % 4 || a_plane != (size_t)M * K || w_plane != (size_t)N * K) {
-        set_error("gemm_f32x6: bad shape M=%d N=%d K=%d ldc=%d", M, N, K, ldc);
+                      int ldc, hipStream_t st, X6Raster raster, long long *stamps, int rt) {
+    if (M <= 0 || N <= 0 || K <= 0 || K % X6_BK || ldc % 4 || a_plane != (size_t)M * K || w_plane != (size_t)N * K || (rt != kX6RtRule && rt != 3 && rt != 4)) {
+        set_error("gemm_f32x6: bad shape M=%d N=%d K=%d ldc=%d (row tiles %d)", M, N, K, ldc, rt);
         return MDD_ERR_ARG;
     }
-    const X6Walk walk = x6_choose_walk((M + X6_BM - 1) / X6_BM, (N + X6_BN - 1) / X6_BN, raster);   // the block walk, or the row walk where the rule falls back
-    const dim3 grid(walk.grid);   // one persistent workgroup per CU
-    if (stamps) hipLaunchKernelGGL(gemm_f32x6_kernel<true>, grid, dim3(256), X6_NS * X6_STAGE, st, A3, W3, a_plane, w_plane, bias, C, M, N, K, ldc, walk, stamps);
-    else hipLaunchKernelGGL(gemm_f32x6_kernel<false>, grid, dim3(256), X6_NS * X6_STAGE, st, A3, W3, a_plane, w_plane, bias, C, M, N, K, ldc, walk, (long long *)nullptr);
+    // the tile (x6_choose_tile: RT = 4 where its rounds are no more MFMA time than RT = 3's, or what `rt` forces) and its walk (the block
+    // walk, or the row walk where x6_choose_walk falls back)
+    const X6Tile tile = x6_choose_tile(M, (N + X6_BN - 1) / X6_BN, raster, rt);
+    if (tile.rt == 4) x6_launch<4>(tile.walk, st, A3, W3, a_plane, w_plane, bias, C, M, N, K, ldc, stamps);
+    else x6_launch<3>(tile.walk, st, A3, W3, a_plane, w_plane, bias, C, M, N, K, ldc, stamps);
     MDD_LAUNCH_CHECK();
     return MDD_OK;
 }
@@ -280,11 +316,11 @@ int launch_gemm_f32x6_splitk(const unsigned short *A3, size_t a_plane, const uns
         set_error("gemm_f32x6_splitk: bad shape M=%d N=%d Kc=%d S=%d", M, N, Kc, S);
         return MDD_ERR_ARG;
     }
-    const int tn = (N + X6_BN - 1) / X6_BN, tiles_c = ((M + X6_BM - 1) / X6_BM) * tn;
+    const int tn = (N + X6_BN - 1) / X6_BN, tiles_c = x6_ceil_div(M, x6_bm(3)) * tn;   // the split-K instantiation stays on the 192-row tile
     if ((long long)tiles_c * S > (1 << 24)) { set_error("gemm_f32x6_splitk: %d x %d tiles", S, tiles_c); return MDD_ERR_ARG; }
     X6Walk walk = x6_choose_walk(S, tiles_c, kX6Rows);   // S x tiles_c virtual tiles, always in the row walk: their order is the step's own
     walk.tiles_n = tn;
-    hipLaunchKernelGGL((gemm_f32x6_kernel<false, true>), dim3(walk.grid), dim3(256), X6_NS * X6_STAGE, st, A3, W3, a_plane, w_plane, (const float *)nullptr, part, M, N, Kc,
+    hipLaunchKernelGGL((gemm_f32x6_kernel<3, false, true>), dim3(walk.grid), dim3(256), x6_lds_bytes(3), st, A3, W3, a_plane, w_plane, (const float *)nullptr, part, M, N, Kc,
                        /* ldc carries */ tiles_c, walk, (long long *)nullptr);
     MDD_LAUNCH_CHECK();
     return MDD_OK;
@@ -293,13 +329,13 @@ int launch_gemm_f32x6_splitk(const unsigned short *A3, size_t a_plane, const uns
 // C[M,N] (row stride ldc) = opA . opB^T (+ bias[N]) as f32x6, for the training step: opA[m,k] = ta ? A[k*lda + m] : A[m*lda + k], opB[n,k]
 // likewise.  Both operands are written as three K-tile-major planes into xs_a / xs_b (transposed on the way when stored [K, *]) with the
 // contraction zero-padded to S chunks of whole K-tiles.  S == 1: one launch of the decode path's kernel.  S > 1 (no bias): the split-K
-// launch (always in the row walk; `raster` is the one-launch form's) into `part` and launch_reduce_parts (into C itself when ldc == N, as the step calls it; else into one more slot of `part`, copied
+// launch (always in the row walk and on the 192-row tile; `raster` and `rt` are the one-launch form's) into `part` and launch_reduce_parts (into C itself when ldc == N, as the step calls it; else into one more slot of `part`, copied
 // out row by row).  The caller has checked x6_ops_ok.
 bool x6_ops_ok(const GemmOperand &A, const GemmOperand &B, const float *C, int ldc) {
     return A.ld % 4 == 0 && B.ld % 4 == 0 && ldc % 4 == 0 && (uintptr_t)A.p % 16 == 0 && (uintptr_t)B.p % 16 == 0 && (uintptr_t)C % 16 == 0;
 }
 int gemm_f32x6_ops(const GemmOperand &A, const GemmOperand &B, const float *bias, float *C, int ldc, int M, int N, int K, int S, DeviceBuf &xs_a,
-                   DeviceBuf &xs_b, DeviceBuf &part, hipStream_t st, X6Raster raster) {
+                   DeviceBuf &xs_b, DeviceBuf &part, hipStream_t st, X6Raster raster, int rt) {
     if (A.period || B.period) { set_error("gemm_f32x6_ops: one product, no operand period"); return MDD_ERR_ARG; }
     if (M <= 0 || N <= 0 || K <= 0 || S < 1 || ldc < N || !x6_ops_ok(A, B, C, ldc) || (S > 1 && bias)) {
         set_error("gemm_f32x6_ops: M=%d N=%d K=%d S=%d lda=%d ldb=%d ldc=%d", M, N, K, S, A.ld, B.ld, ldc); return MDD_ERR_ARG;
@@ -313,7 +349,7 @@ int gemm_f32x6_ops(const GemmOperand &A, const GemmOperand &B, const float *bias
     unsigned short *a3 = reinterpret_cast<unsigned short *>(xs_a.p), *w3 = reinterpret_cast<unsigned short *>(xs_b.p);
     if (int rc = A.k_major ? launch_transpose_split3(A.p, K, M, A.ld, Kp, a3, pa, st) : launch_split3_pad(A.p, M, K, A.ld, Kp, a3, pa, st)) return rc;
     if (int rc = B.k_major ? launch_transpose_split3(B.p, K, N, B.ld, Kp, w3, pw, st) : launch_split3_pad(B.p, N, K, B.ld, Kp, w3, pw, st)) return rc;
-    if (S == 1) return launch_gemm_f32x6(a3, pa, w3, pw, bias, C, M, N, Kp, ldc, st, raster);
+    if (S == 1) return launch_gemm_f32x6(a3, pa, w3, pw, bias, C, M, N, Kp, ldc, st, raster, nullptr, rt);
     const size_t mn = (size_t)M * N;
     auto partials = [&](float *p) { return launch_gemm_f32x6_splitk(a3, pa, w3, pw, p, M, N, Kc, S, st); };
     if (ldc == N) return sum_parts(part, S, mn, C, st, partials);

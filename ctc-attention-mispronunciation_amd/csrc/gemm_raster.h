@@ -1,5 +1,6 @@
-// The order in which the persistent workgroups of gemm_f32x6_kernel (gemm_bf16x6.hip) take the 192 x 128 tiles of C: one function from
-// (workgroup, round) to a tile, and the host-side rule that chooses between the two walks.  Host only, like plan.h: no HIP type, no device
+// The order in which the persistent workgroups of gemm_f32x6_kernel (gemm_bf16x6.hip) take the tiles of C -- 256 x 128 (four 16-row MFMA
+// tiles per wave, RT = 4) or 192 x 128 (RT = 3) -- : one function from (workgroup, round) to a tile, and the host-side rules that choose
+// between the two walks and between the two tiles.  Host only, like plan.h: no HIP type, no device
 // code of its own (tests/test_gemm_raster_host.py builds it with the host compiler and walks every shape); the kernel calls x6_tile_of
 // once per tile, in scalar code.
 //
@@ -11,9 +12,10 @@
 //   block walk  tiles in blocks of rb row panels x cb column tiles (smaller at the right and bottom edge), the blocks row-major and
 //               dealt to the XCDs in turn: block r * 8 + xcd is the XCD's round r, its workgroup j takes the block's tile j (row-major
 //               in the block), and a workgroup whose j is past a short block's size sits that round out.  Per round the XCD pulls
-//               cb column tiles of W and rb A panels: rb * cb = 32 minimises 192 rb + 128 cb near 4 x 8.  Needs a grid of 8 x 32.
+//               cb column tiles of W and rb A panels: rb * cb = 32 minimises 256 rb + 128 cb (RT = 3: 192 rb + 128 cb) near 4 x 8.  Needs a
+//               grid of 8 x 32.
 // Either walk gives a tile to exactly one (workgroup, round), and a C element's own K order does not depend on the walk: the outputs
-// are the same bits.
+// are the same bits.  Nor does it depend on the tile: RT = 4 performs RT = 3's arithmetic on every element.
 #pragma once
 #include <stdlib.h>
 #include <string.h>
@@ -31,7 +33,24 @@ constexpr int kX6Xcds = 8, kX6WgPerXcd = 32, kX6Grid = kX6Xcds * kX6WgPerXcd;   
 // rb == 0: the row walk.  Otherwise rb x cb blocks, rb * cb <= 32.
 struct X6Raster { int rb, cb; };
 constexpr X6Raster kX6Rows = {0, 0};
-constexpr X6Raster kX6DefaultRaster = {4, 8};   // profiles/gemm_raster_notes.txt
+constexpr X6Raster kX6DefaultRaster = {4, 8};   // profiles/gemm_raster_notes.txt, profiles/gemm_rt4_notes.txt
+
+// Rows of C per workgroup tile: four waves of RT 16-row MFMA tiles each.
+constexpr int x6_bm(int rt) { return 4 * 16 * rt; }
+// MDD_GEMM_X6_RT: "3" or "4" is that tile in every launch that takes the switch; unset, x6_choose_tile's rule decides per launch (kX6RtRule).
+// x6_rt_parse: false for any other value (the mdd_diag_gemm* entries refuse it, as they refuse a mistyped walk); x6_rt_from_env: a handle's
+// reading at create, where any other value is the default.
+constexpr int kX6RtRule = 0;
+inline bool x6_rt_parse(const char *e, int *out) {
+    if (!e || (strcmp(e, "3") && strcmp(e, "4"))) return false;
+    *out = e[0] - '0';
+    return true;
+}
+inline int x6_rt_from_env(const char *e) {
+    int rt = kX6RtRule;
+    if (e) x6_rt_parse(e, &rt);
+    return rt;
+}
 
 // MDD_GEMM_X6_RASTER: "rows" is the row walk everywhere; "<rb>x<cb>" (2x16, 4x8, 8x4: the timing aid's arms) those blocks, rb * cb <= 32.
 // x6_raster_parse: false for any other value (the mdd_diag_gemm* entries refuse it: a mistyped arm of an A/B must not run as the default
@@ -75,6 +94,19 @@ inline X6Walk x6_choose_walk(int tiles_m, int tiles_n, X6Raster want) {
     const int rounds = x6_ceil_div(x6_ceil_div(tiles_m, want.rb) * x6_ceil_div(tiles_n, want.cb), kX6Xcds);
     if (rounds > row_rounds) return rows;
     return {ntiles, tiles_n, want.rb, want.cb, kX6Grid, rounds};
+}
+
+// Which tile a launch of M rows x tiles_n column tiles takes, and its walk.  A round costs MFMA time in proportion to RT (every workgroup
+// of it multiplies RT x 8 MFMA tiles per K-tile), so RT = 4 is taken where its rounds are no more MFMA time than RT = 3's:
+// 4 x rounds(RT = 4) <= 3 x rounds(RT = 3), each counted in the walk that tile would get.  There the larger tile only saves: a quarter of
+// the W fragment reads, LDS-DMA bytes and W bytes from beyond L2 per MFMA, and the per-K-tile fixed cost spread over a third more MFMAs
+// (profiles/gemm_rt4_notes.txt).  A launch that RT = 3 finishes in one round (the text table's 44 rows, a short utterance's projections)
+// therefore stays on RT = 3, where more workgroups share its rows.  rt == 3 or 4 (MDD_GEMM_X6_RT): that tile whatever the counts.
+struct X6Tile { int rt; X6Walk walk; };
+inline X6Tile x6_choose_tile(int M, int tiles_n, X6Raster want, int rt = kX6RtRule) {
+    const X6Walk w3 = x6_choose_walk(x6_ceil_div(M, x6_bm(3)), tiles_n, want), w4 = x6_choose_walk(x6_ceil_div(M, x6_bm(4)), tiles_n, want);
+    if (rt == kX6RtRule) rt = 4 * w4.rounds <= 3 * w3.rounds ? 4 : 3;
+    return rt == 4 ? X6Tile{4, w4} : X6Tile{3, w3};
 }
 
 // Tile (tm, tn) of workgroup wg in round r; false: the workgroup has no tile in that round.  (In the row walk a workgroup's tiles

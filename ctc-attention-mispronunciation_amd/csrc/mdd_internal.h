@@ -122,10 +122,10 @@ int launch_split3_rowmajor(const float *w, int n, unsigned short *planes, hipStr
 // C = A . W^T with fp32-grade arithmetic on the bf16 matrix cores: operands as three K-tile-major bf16 planes each (gemm_bf16x6.hip)
 // raster: the tile walk asked for (gemm_raster.h; a handle's Switches::x6_raster); the launcher falls back to the row walk per shape.
 // stamps (diagnostic): the stamped instantiation's X6_STAMP_WORDS words
+// rt: 16-row MFMA tiles per wave, 3 or 4 (a 192- or 256-row tile; the same bits), or kX6RtRule: x6_choose_tile decides (a handle's Switches::x6_rt)
 int launch_gemm_f32x6(const unsigned short *A3, size_t a_plane, const unsigned short *W3, size_t w_plane, const float *bias, float *C, int M, int N, int K,
-                      int ldc, hipStream_t st, X6Raster raster = kX6DefaultRaster, long long *stamps = nullptr);
+                      int ldc, hipStream_t st, X6Raster raster = kX6DefaultRaster, long long *stamps = nullptr, int rt = kX6RtRule);
 int init_gemm_x6_attributes();
-constexpr int X6_RT = 3;    // 16-row MFMA tiles per wave of the f32x6 kernel
 constexpr int X6_STAMP_WGS = 1024, X6_STAMP_PHASE_WORDS = X6_STAMP_WGS * 4 * 4, X6_STAMP_WORDS = X6_STAMP_PHASE_WORDS + X6_STAMP_WGS * 2;
 // The same planes for the training step's operands: the contraction zero-padded from K to Kp (a multiple of 32), planes plane_elems apart.
 // launch_split3_pad: x [rows][ld], K leading columns; launch_transpose_split3: x stored [K][ld], operand row r = column r of x.
@@ -166,7 +166,7 @@ constexpr int CM_NPH = 10;  // stamped phases per wave of the default fused3 ker
 // x6_ops_ok: the alignment half of the rule (leading dimensions multiples of 4, 16-byte aligned pointers).
 bool x6_ops_ok(const GemmOperand &A, const GemmOperand &B, const float *C, int ldc);
 int gemm_f32x6_ops(const GemmOperand &A, const GemmOperand &B, const float *bias, float *C, int ldc, int M, int N, int K, int S, DeviceBuf &xs_a,
-                   DeviceBuf &xs_b, DeviceBuf &part, hipStream_t st, X6Raster raster = kX6DefaultRaster);
+                   DeviceBuf &xs_b, DeviceBuf &part, hipStream_t st, X6Raster raster = kX6DefaultRaster, int rt = 3);   // rt: the one-launch form's tile
 // The same for the split-bf16 x3 GEMM (gemm_bf16x3.hip): operands as hi/lo planes with the contraction along their rows, zero-padded to S chunks
 // of whole K-tiles; S > 1 (no bias, ldc == N): the chunks as a batch of partial products into `part` and a sum.
 int gemm_bf16x3_ops(const GemmOperand &A, const GemmOperand &B, const float *bias, float *C, int ldc, int M, int N, int K, int S, DeviceBuf &xs_a,

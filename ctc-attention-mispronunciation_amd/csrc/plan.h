@@ -42,6 +42,10 @@
 //   MDD_GEMM_X6_RASTER   gemm_f32x6_kernel's tile walk (gemm_raster.h): rows is the    create    tests/test_gemm_raster.py, tools/gemm_time.py
 //                        row walk in every launch, <rb>x<cb> blocks of that shape     (the mdd_diag_gemm* entries read it per call
 //                        instead of the default's                                      and refuse any other value)
+//   MDD_GEMM_X6_RT=3|4   gemm_f32x6_kernel's tile in every projection and the text     create    tests/test_gemm_x6_rt4.py, tools/gemm_time.py
+//                        table's product: 192 x 128 (3) or 256 x 128 with the hi.hi   (the mdd_diag_gemm* entries read it per call
+//                        total in LDS (4), instead of x6_choose_tile's rule per        and refuse any other value)
+//                        launch (gemm_raster.h); the same bits either way
 //   MDD_TRAIN_PRECISION  training handle: bf16x3|1 starts it in the split-bf16        create    train.py
 //                        variant (mdd_train_set_precision changes it later)
 //   MDD_TRAIN_PRECISION  training handle: f32x6|2 starts it with the large            create    train.py, tests/test_train_f32x6.py
@@ -51,7 +55,7 @@
 //
 // The training handle takes MDD_LSTM=step (per-step recurrence in its split-bf16 variant too), MDD_GEMM_X6_RASTER (its one-launch f32x6
 // products; the split-K ones are always in the row walk), its own two switches and nothing else of this table: its persistent layer
-// launches carry no diagnostics.
+// launches carry no diagnostics, and its f32x6 products stay on the 192-row tile.
 //
 // The beam entries take no handle: their two switches (MDD_BEAM_GENERIC, MDD_BEAM_W) are read at every call by read_beam_switches(), and
 // beam_plan() below is their selection, the same kind of pure function.
@@ -80,6 +84,7 @@ struct Switches {
     bool text_gemm = false;     // MDD_TEXT_PROJ=gemm
     bool score_wide = false;    // MDD_SCORE_TILE=128
     X6Raster x6_raster = kX6DefaultRaster;   // MDD_GEMM_X6_RASTER
+    int x6_rt = kX6RtRule;      // MDD_GEMM_X6_RT=3|4
     int train_precision = 0;    // MDD_TRAIN_PRECISION
     bool train_conv1_im2col = false;   // MDD_TRAIN_CONV1_IM2COL
 };
@@ -108,6 +113,7 @@ inline Switches read_switches() {
     s.text_gemm = is(getenv("MDD_TEXT_PROJ"), "gemm");
     s.score_wide = is(getenv("MDD_SCORE_TILE"), "128");
     s.x6_raster = x6_raster_from_env(getenv("MDD_GEMM_X6_RASTER"));
+    s.x6_rt = x6_rt_from_env(getenv("MDD_GEMM_X6_RT"));
     e = getenv("MDD_TRAIN_PRECISION");
     if (is(e, "bf16x3") || is(e, "1")) s.train_precision = 1;
     if (is(e, "f32x6") || is(e, "2")) s.train_precision = 2;

@@ -204,7 +204,7 @@ int build_weights(mdd_model *m, DecodeWeights &w) {
             unsigned short *planes = nullptr;   // (kept with the set: the GEMM below reads it after this function has returned)
             if ((rc = w.alloc(&planes, (size_t)3 * V * E)) || (rc = w.alloc(&w.text_table[1], (size_t)V * G2))) return rc;
             if ((rc = launch_split3(w.emb, V, E, E, planes, nullptr))) return rc;
-            if ((rc = launch_gemm_f32x6(planes, (size_t)V * E, tw.wih_3, (size_t)G2 * E, w.t_bias, w.text_table[1], V, G2, E, G2, nullptr, m->sw.x6_raster))) return rc;
+            if ((rc = launch_gemm_f32x6(planes, (size_t)V * E, tw.wih_3, (size_t)G2 * E, w.t_bias, w.text_table[1], V, G2, E, G2, nullptr, m->sw.x6_raster, nullptr, m->sw.x6_rt))) return rc;
         }
     }
     if (ctc) {   // the classifier on the last layer's 2H outputs (CRC/models/cnn_rnn.py:140-142): no score, no 4H operands

@@ -506,8 +506,9 @@ int mdd_diag_gemm_time(int mode, int M, int N, int K, int reps, float *ms_out);
 /* mdd_diag_gemm_clock: mdd_diag_gemm_time of the f32x6 kernel (mode 3), and the clock the chip held inside it straight behind those
    launches, in MHz: the median over workgroups of shader-clock ticks per tick of the 100 MHz constant clock, stamped once around the
    tile loop of the diagnostic instantiation.  The f32x6 launches of the mdd_diag_gemm* entries take their tile walk from
-   MDD_GEMM_X6_RASTER as it stands at the call (rows, or <rb>x<cb> blocks; csrc/gemm_raster.h) and return MDD_ERR_ARG for any other
-   value of it. */
+   MDD_GEMM_X6_RASTER as it stands at the call (rows, or <rb>x<cb> blocks; csrc/gemm_raster.h) and their tile from MDD_GEMM_X6_RT
+   (3: 192 x 128, 4: 256 x 128; unset: the launcher's rule, in mdd_diag_gemm_ops the training step's 3), and return MDD_ERR_ARG for
+   any other value of either. */
 int mdd_diag_gemm_clock(int M, int N, int K, int reps, float *ms_out, float *mhz_out);
 /* mdd_diag_conv_time: mean milliseconds of `reps` launches of the f32x6 conv front end on pseudo-random features [B, T, 243] and weights.
    which: 0 the default kernel, 1 the row-at-a-time kernel.  phases (nullable; 8 waves x 10 phases): mean cycles per workgroup of each
