@@ -7,6 +7,8 @@ imported from here.)
 import ctypes as C
 import os
 
+import numpy as np
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MDD_LIB_PATH") or os.path.join(_HERE, "libmdd_hip.so")   # (MDD_LIB_PATH: a diagnostic build of the same library, tests only)
 
@@ -140,3 +142,47 @@ def require_gpu():
     import torch
     if not torch.cuda.is_available():
         raise MddError("no HIP device visible: the MI355X path has no CPU fallback")
+
+
+# Python objects -> C arguments: nowhere else in the package.  PRECISIONS: the modes of mdd_set_precision and mdd_train_set_precision
+# (exact fp32 MFMA | flagged split-bf16 x3 | fp32-grade on the bf16 matrix cores, the reference's width)
+PRECISIONS = {"f32": 0, "bf16x3": 1, "f32x6": 2}
+
+
+def ptr(t):
+    """Address of a tensor's or numpy array's own memory (None: NULL); no copy, so a ``.contiguous()`` result must outlive the call."""
+    if t is None:
+        return None
+    if isinstance(t, np.ndarray):
+        return C.c_void_p(t.ctypes.data)
+    if hasattr(t, "data_ptr"):
+        return C.c_void_p(t.data_ptr())
+    raise TypeError("ptr: a torch tensor, a numpy array or None, not %s" % type(t).__name__)
+
+
+def ptr_array(tensors):
+    """void* [n] of the tensors' addresses (None entries: NULL)."""
+    arr = (C.c_void_p * len(tensors))()
+    for i, t in enumerate(tensors):
+        arr[i] = t.data_ptr() if t is not None else None
+    return arr
+
+
+def new_handle(create, cfg, device_index):
+    """The handle ``create`` (mdd_create, mdd_create_ctc, mdd_train_create) makes of an MddConfig on a device."""
+    h = C.c_void_p()
+    check(create(C.byref(cfg), device_index, C.byref(h)))
+    return h
+
+
+def to_gpu(t, dtype):
+    """``t`` contiguous in ``dtype`` on its own device, or on the current one when it is a host tensor."""
+    import torch
+    dev = t.device if t.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    return t.to(dev, dtype).contiguous()
+
+
+def raise_device_error(sync_entry, handle):
+    """Wait for the current stream (mdd_sync, mdd_train_sync) and raise what a kernel flagged, as nn.Embedding would: IndexError."""
+    if sync_entry(handle, current_stream_ptr()) != 0:
+        raise IndexError(lib().mdd_last_error().decode())

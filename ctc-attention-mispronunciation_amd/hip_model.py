@@ -1,6 +1,6 @@
 """Thin object over the C ABI for callers that hold a state_dict of numpy arrays / tensors and want
 ``forward`` without constructing torch modules (bench.py, tests, the sharded driver).  The
-reference-shaped drop-in class is ``models.model_ctc.CTC_Model``; both call the same entry points."""
+reference-shaped drop-in class is ``models.model_ctc.CTC_Model``, which drives a ``HipModel`` of its own configuration."""
 import collections
 import ctypes as C
 
@@ -11,46 +11,62 @@ from . import _lib
 
 
 class HipModel(object):
+    """The one owner of a decode handle (mdd_model): made of a synth.Geometry and a state_dict, or of an MddConfig alone (from_config)."""
+
     def __init__(self, geom, state_dict, device=0, taps=False, precision=None):
-        _lib.require_gpu()
-        self.geom = geom
-        self.device = torch.device("cuda", device)
-        self.handle = C.c_void_p()
         cfg = _lib.MddConfig(feat=geom.feat, hidden=geom.hidden, layers=geom.layers, num_class=geom.num_class,
                              channels=geom.channels, emb_rows=geom.emb_rows, emb_dim=geom.emb_dim, bn_eps=1e-5)
         # a CTC-only geometry (synth.Geometry(ctc_only=True): the reference's cnn-rnn-ctc model) gets the handle without a text side
-        create = _lib.lib().mdd_create_ctc if getattr(geom, "ctc_only", False) else _lib.lib().mdd_create
-        _lib.check(create(C.byref(cfg), device, C.byref(self.handle)))
-        if precision is not None:      # 'f32x6' (fp32-grade on the bf16 matrix cores: the default), 'f32' (exact fp32 MFMA) or 'bf16x3' (flagged variant)
-            _lib.check(_lib.lib().mdd_set_precision(self.handle, {'f32': 0, 'bf16x3': 1, 'f32x6': 2}[precision]))
+        self._open(geom, cfg, getattr(geom, "ctc_only", False), device, precision)
         self.load_state_dict(state_dict)
-        if taps:
-            _lib.check(_lib.lib().mdd_enable_taps(self.handle, 1))
+        self.enable_taps(taps)
+
+    @classmethod
+    def from_config(cls, cfg, ctc_only, device, precision=None):
+        """A handle of ``cfg`` (an MddConfig) on cuda:``device`` with no weights loaded: ``load_state_dict`` before the first forward."""
+        self = cls.__new__(cls)
+        self._open(None, cfg, ctc_only, device, precision)
+        return self
+
+    def _open(self, geom, cfg, ctc_only, device, precision):
+        _lib.require_gpu()
+        self.geom, self.feat, self.num_class, self._taps = geom, cfg.feat, cfg.num_class, False
+        self.device = torch.device("cuda", device)
+        self.handle = _lib.new_handle(_lib.lib().mdd_create_ctc if ctc_only else _lib.lib().mdd_create, cfg, device)
+        if precision is not None:      # 'f32x6' (fp32-grade on the bf16 matrix cores: the default), 'f32' (exact fp32 MFMA) or 'bf16x3' (flagged variant)
+            _lib.check(_lib.lib().mdd_set_precision(self.handle, _lib.PRECISIONS[precision]))
 
     @property
     def precision(self):
-        return {0: 'f32', 1: 'bf16x3', 2: 'f32x6'}[_lib.lib().mdd_get_precision(self.handle)]
+        return {mode: name for name, mode in _lib.PRECISIONS.items()}[_lib.lib().mdd_get_precision(self.handle)]
 
     def load_state_dict(self, state_dict):
+        """Every float entry (numpy array or tensor of any float dtype, converted to fp32 on the host), then mdd_finalize_weights."""
         L = _lib.lib()
         for key, val in state_dict.items():
-            a = val.detach().cpu().numpy() if torch.is_tensor(val) else np.asarray(val)
+            if torch.is_tensor(val):     # (bf16 has no numpy form)
+                val = val.detach().to("cpu", torch.float32 if val.is_floating_point() else val.dtype).numpy()
+            a = np.asarray(val)
             if a.dtype.kind != "f":
                 continue
             a = np.ascontiguousarray(a, dtype=np.float32)
             shape = (C.c_int64 * max(1, a.ndim))(*a.shape)
-            _lib.check(L.mdd_load_weight(self.handle, key.encode(), a.ctypes.data_as(C.c_void_p), shape, a.ndim))
+            _lib.check(L.mdd_load_weight(self.handle, key.encode(), _lib.ptr(a), shape, a.ndim))
         _lib.check(L.mdd_finalize_weights(self.handle))
+
+    def enable_taps(self, on=True):
+        """Keep the stage outputs of a forward for ``tap``.  Called only on a change of state: mdd_enable_taps drops the captured graphs."""
+        if bool(on) != self._taps:
+            _lib.check(_lib.lib().mdd_enable_taps(self.handle, int(bool(on))))
+            self._taps = bool(on)
 
     def _run(self, entry, like, B, T, out, sync_errors, args):
         """Allocate logp [T/2,B,C] unless given, enqueue ``entry(handle, *args, out, stream)`` and, on request, wait and raise device-side errors."""
         if out is None:
-            out = torch.empty((T // 2, B, self.geom.num_class), dtype=torch.float32, device=like.device)
-        st = _lib.current_stream_ptr()
-        _lib.check(entry(self.handle, *args, C.c_void_p(out.data_ptr()), st))
+            out = torch.empty((T // 2, B, self.num_class), dtype=torch.float32, device=like.device)
+        _lib.check(entry(self.handle, *args, _lib.ptr(out), _lib.current_stream_ptr()))
         if sync_errors:
-            if _lib.lib().mdd_sync(self.handle, st) != 0:
-                raise IndexError(_lib.lib().mdd_last_error().decode())
+            _lib.raise_device_error(_lib.lib().mdd_sync, self.handle)
         return out
 
     @staticmethod
@@ -59,14 +75,14 @@ class HipModel(object):
         if x1 is None:
             return None, 0
         assert x1.is_cuda and x1.dtype == torch.int64 and x1.is_contiguous()
-        return C.c_void_p(x1.data_ptr()), x1.shape[1]
+        return _lib.ptr(x1), x1.shape[1]
 
     def forward(self, x, x1=None, out=None, sync_errors=False):
         """x [B,T,F] f32 cuda, x1 [B,L] i64 cuda (None for a CTC-only model) -> logp [T/2,B,C] (enqueued on the current stream)."""
         assert x.is_cuda and x.dtype == torch.float32
         x, x1 = x.contiguous(), (None if x1 is None else x1.contiguous())
         B, T, _ = x.shape
-        return self._run(_lib.lib().mdd_forward, x, B, T, out, sync_errors, (C.c_void_p(x.data_ptr()), B, T) + self._ids(x1))
+        return self._run(_lib.lib().mdd_forward, x, B, T, out, sync_errors, (_lib.ptr(x), B, T) + self._ids(x1))
 
     def forward_fused(self, x, x1, frames, canon=None, out=None, sync_errors=False):
         """Several reference batches of different padded lengths in one launch sequence (mdd_forward_fused): x [B,T,F] with every
@@ -78,8 +94,7 @@ class HipModel(object):
         x1, canon = (None if x1 is None else x1.contiguous()), (None if canon is None else canon.contiguous())
         B, T, _ = x.shape
         return self._run(_lib.lib().mdd_forward_fused, x, B, T, out, sync_errors,
-                         (C.c_void_p(x.data_ptr()), B, T) + self._ids(x1) +
-                         (C.c_void_p(frames.data_ptr()), None if canon is None else C.c_void_p(canon.data_ptr())))
+                         (_lib.ptr(x), B, T) + self._ids(x1) + (_lib.ptr(frames), _lib.ptr(canon)))
 
     def forward_candidates(self, x, x1, frames=None, canon=None, out=None, sync_errors=False):
         """K canonical candidates per utterance on one acoustic pass (mdd_forward_candidates): x [B,T,F] f32 cuda, x1 [K,B,L] i64 cuda, candidate
@@ -96,9 +111,9 @@ class HipModel(object):
         B, T, _ = x.shape
         K, _, L = x1.shape
         if out is None:
-            out = torch.empty((K, T // 2, B, self.geom.num_class), dtype=torch.float32, device=x.device)
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())   # noqa: E731
-        return self._run(_lib.lib().mdd_forward_candidates, x, B, T, out, sync_errors, (ptr(x), B, T, ptr(x1), K, L, ptr(frames), ptr(canon)))
+            out = torch.empty((K, T // 2, B, self.num_class), dtype=torch.float32, device=x.device)
+        p = _lib.ptr
+        return self._run(_lib.lib().mdd_forward_candidates, x, B, T, out, sync_errors, (p(x), B, T, p(x1), K, L, p(frames), p(canon)))
 
     def forward_raw(self, raw, x1=None, out=None, sync_errors=False):
         """raw [B,T_raw,F/3] f32 cuda (unstacked frames), x1 [B,L] i64 cuda -> logp, exactly as
@@ -106,36 +121,35 @@ class HipModel(object):
         assert raw.is_cuda and raw.dtype == torch.float32
         raw, x1 = raw.contiguous(), (None if x1 is None else x1.contiguous())
         B, T_raw, D = raw.shape
-        assert 3 * D == self.geom.feat
+        assert 3 * D == self.feat
         return self._run(_lib.lib().mdd_forward_raw, raw, B, _lib.lib().mdd_stack_len(T_raw, 2, 2), out, sync_errors,
-                         (C.c_void_p(raw.data_ptr()), B, T_raw) + self._ids(x1))
+                         (_lib.ptr(raw), B, T_raw) + self._ids(x1))
 
     def profile(self, x, x1=None):
         """Per-stage (name, ms, launches, flops) of one forward replayed stage by stage between HIP events."""
         B, T, _ = x.shape
         x1p, L = self._ids(x1)
-        out = torch.empty((T // 2, B, self.geom.num_class), dtype=torch.float32, device=x.device)
+        out = torch.empty((T // 2, B, self.num_class), dtype=torch.float32, device=x.device)
         n = _lib.lib().mdd_forward_num_stages(self.handle)
         names = C.create_string_buffer(64 * n)
         ms, launches, flops = (C.c_float * n)(), (C.c_int32 * n)(), (C.c_double * n)()
-        _lib.check(_lib.lib().mdd_forward_profile(self.handle, C.c_void_p(x.data_ptr()), B, T, x1p,
-                                                  L, C.c_void_p(out.data_ptr()), _lib.current_stream_ptr(),
+        _lib.check(_lib.lib().mdd_forward_profile(self.handle, _lib.ptr(x), B, T, x1p, L, _lib.ptr(out), _lib.current_stream_ptr(),
                                                   names, 64 * n, ms, launches, flops, n))
         return list(zip(names.value.decode().split(","), list(ms), list(launches), list(flops)))
 
     def tap(self, name):
+        """Stage output of the last forward as a torch tensor (copy): conv1, rnn<i>, text, key."""
         n = C.c_int64(0)
         if not _lib.lib().mdd_tap(self.handle, name.encode(), C.byref(n)):
             raise KeyError(name)
         out = torch.empty(n.value, dtype=torch.float32, device=self.device)
-        _lib.check(_lib.lib().mdd_tap_copy(self.handle, name.encode(), C.c_void_p(out.data_ptr()), n.value,
-                                           _lib.current_stream_ptr()))
+        _lib.check(_lib.lib().mdd_tap_copy(self.handle, name.encode(), _lib.ptr(out), n.value, _lib.current_stream_ptr()))
         return out
 
     def close(self):
         if self.handle:
             _lib.lib().mdd_destroy(self.handle)
-            self.handle = C.c_void_p()
+            self.handle = None
 
     def __del__(self):
         try:
@@ -168,7 +182,7 @@ class _CtcCall(object):
 
     def ptr(self, t, rows=1):
         """Device address of ``t`` (None: NULL); an empty [B, 0] array (``rows`` = 0) passes the workspace's address in its place."""
-        return None if t is None else C.c_void_p(t.data_ptr() if rows else self.ws.data_ptr())
+        return _lib.ptr(t if rows or t is None else self.ws)
 
     def __call__(self, entry, *args):
         with torch.cuda.device(self.dev):

@@ -11,16 +11,15 @@ statistics, dropout, differentiable w.r.t. every parameter) through mdd_train_fo
 AA/infer.py also relies on this module re-exporting ``math`` (infer.py:342) -- kept, together with
 the other names the reference module exposes through ``import *``.
 """
-import ctypes as C
 import math  # noqa: F401  (re-exported on purpose)
 from collections import OrderedDict
 
-import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F  # noqa: F401
 
 from .. import _lib
+from ..hip_model import HipModel
 
 
 class _EditDistance(object):
@@ -111,8 +110,9 @@ class CTC_Model(nn.Module):
         else:
             self.fc = nn.Linear(fc_in, num_class, bias=False)
         self.log_softmax = nn.LogSoftmax(dim=-1)
-        self._handle = None
-        self._dirty = True
+        self._hip = None            # the decode handle (hip_model.HipModel), on the device of the last eval forward's inputs
+        self._dirty = True          # the module's weights are not the handle's
+        self._taps = False
         self.strict_errors = True   # raise IndexError for bad canonical ids synchronously, like nn.Embedding
         self._dropout_masks = None  # tests: the reference's own dropout masks (one uint8 tensor per site, mdd_hip.h); None = drawn
         self.train_precision = None  # train mode: None = library default (exact fp32, or MDD_TRAIN_PRECISION), "f32", "bf16x3" (flagged variant) or "f32x6" (reference width on the bf16 matrix cores)
@@ -135,25 +135,29 @@ class CTC_Model(nn.Module):
                               emb_rows=0 if self._ctc_only else self.embeds.num_embeddings,
                               emb_dim=0 if self._ctc_only else self.embeds.embedding_dim, bn_eps=self.fc[0].eps)
 
-    def _sync_weights(self, device_index):
-        L = _lib.lib()
-        if self._handle is None:
+    def _sync_weights(self, index):
+        """The handle on cuda:``index`` with the module's weights as they are now; inputs on another device get a new handle there."""
+        if self._hip is None or self._hip.device.index != index:
             self._check_supported()
-            h = C.c_void_p()
-            cfg = self._config()
-            _lib.check((L.mdd_create_ctc if self._ctc_only else L.mdd_create)(C.byref(cfg), device_index, C.byref(h)))
-            self._handle = h
+            if self._hip is not None:
+                self._hip.close()
+            self._hip = HipModel.from_config(self._config(), self._ctc_only, index)
             self._dirty = True
-        if not self._dirty:
-            return
-        for key, t in self.state_dict().items():
-            if not t.is_floating_point():
-                continue
-            a = np.ascontiguousarray(t.detach().to("cpu", torch.float32).numpy())
-            shape = (C.c_int64 * max(1, a.ndim))(*a.shape)
-            _lib.check(L.mdd_load_weight(self._handle, key.encode(), a.ctypes.data_as(C.c_void_p), shape, a.ndim))
-        _lib.check(L.mdd_finalize_weights(self._handle))
-        self._dirty = False
+        if self._dirty:
+            self._hip.load_state_dict(self.state_dict())
+            self._dirty = False
+
+    def _on_device(self, x, taps):
+        """x as the kernels take it (host features: on the current device), that device's handle up to date and, on request, its taps on."""
+        xd = _lib.to_gpu(x, torch.float32)
+        B, T, Fdim = xd.shape
+        if Fdim != self.rnn_param["rnn_input_size"]:
+            raise RuntimeError("expected feature size %d, got %d" % (self.rnn_param["rnn_input_size"], Fdim))
+        with torch.cuda.device(xd.device):
+            self._sync_weights(xd.device.index)
+        if taps:
+            self._hip.enable_taps(True)
+        return xd
 
     def load_state_dict(self, *args, **kwargs):
         self._dirty = True
@@ -167,27 +171,17 @@ class CTC_Model(nn.Module):
         """Call after editing parameters in place."""
         self._dirty = True
 
-    def __del__(self):
-        try:
-            if self._handle is not None:
-                _lib.lib().mdd_destroy(self._handle)
-        except Exception:  # noqa: BLE001  (interpreter shutdown)
-            pass
-
     def enable_taps(self, on=True):
         self._taps = bool(on)
-        if self._handle is not None:
-            _lib.check(_lib.lib().mdd_enable_taps(self._handle, int(on)))
+        if self._hip is not None:
+            self._hip.enable_taps(on)
 
     def tap(self, name):
-        """Stage output of the last forward as a torch tensor (copy): conv1, rnn<i>, text, key."""
-        n = C.c_int64(0)
-        if not _lib.lib().mdd_tap(self._handle, name.encode(), C.byref(n)):
+        """Stage output of the last forward as a torch tensor (copy) on the handle's device: conv1, rnn<i>, text, key."""
+        if self._hip is None:
             raise KeyError(name)
-        out = torch.empty(n.value, dtype=torch.float32, device="cuda")
-        _lib.check(_lib.lib().mdd_tap_copy(self._handle, name.encode(), C.c_void_p(out.data_ptr()), n.value,
-                                           _lib.current_stream_ptr()))
-        return out
+        with torch.cuda.device(self._hip.device):
+            return self._hip.tap(name)
 
     # ------------------------------------------------------------------ the reference API
     def forward(self, x, x1, visualize=False):
@@ -205,32 +199,16 @@ class CTC_Model(nn.Module):
                 raise NotImplementedError("visualize=True is an eval-mode facility here")
             from ..train import model_forward_train
             return model_forward_train(self, x, x1, masks=getattr(self, "_dropout_masks", None))
-        src_device = x.device
-        dev = x.device if x.is_cuda else torch.device("cuda", torch.cuda.current_device())
-        xd = x.to(dev, torch.float32).contiguous()
-        idd = None if self._ctc_only else x1.to(dev, torch.int64).contiguous()   # (the CTC-only forward never reads x1: cnn_rnn.py:147)
-        B, T, Fdim = xd.shape
-        if Fdim != self.rnn_param["rnn_input_size"]:
-            raise RuntimeError("expected feature size %d, got %d" % (self.rnn_param["rnn_input_size"], Fdim))
-        with torch.cuda.device(dev):
-            self._sync_weights(dev.index if dev.index is not None else torch.cuda.current_device())
-            if getattr(self, "_taps", False) or visualize:
-                _lib.check(_lib.lib().mdd_enable_taps(self._handle, 1))
-            out = torch.empty((T // 2, B, self.num_class), dtype=torch.float32, device=dev)
-            st = _lib.current_stream_ptr()
-            ids, L = (None, 0) if idd is None else (C.c_void_p(idd.data_ptr()), idd.shape[1])
-            _lib.check(_lib.lib().mdd_forward(self._handle, C.c_void_p(xd.data_ptr()), B, T, ids, L, C.c_void_p(out.data_ptr()), st))
-            if self.strict_errors:
-                rc = _lib.lib().mdd_sync(self._handle, st)
-                if rc != 0:
-                    raise IndexError(_lib.lib().mdd_last_error().decode())
+        xd = self._on_device(x, self._taps or visualize)
+        idd = None if self._ctc_only else x1.to(xd.device, torch.int64).contiguous()   # (the CTC-only forward never reads x1: cnn_rnn.py:147)
+        with torch.cuda.device(xd.device):
+            out = self._hip.forward(xd, idd, sync_errors=self.strict_errors).to(x.device)
             if visualize:
-                ch = self.cnn_param["layer"][-1][0][1]
-                seq = self.tap("conv1").view(T // 2, B, -1)
+                B, T, ch = xd.shape[0], xd.shape[1], self.cnn_param["layer"][-1][0][1]
+                seq = self._hip.tap("conv1").view(T // 2, B, -1)
                 cnn = seq.view(T // 2, B, ch, -1).permute(1, 2, 0, 3).contiguous()
-                res = out.to(src_device)
-                return res, [x, cnn.to(src_device), seq.to(src_device), res]
-        return out if src_device == dev else out.to(src_device)
+                return out, [x, cnn.to(x.device), seq.to(x.device), out]
+        return out
 
     def forward_candidates(self, x, candidates):
         """Several canonical candidates per utterance on one acoustic pass (no reference counterpart; mdd_forward_candidates).
@@ -251,12 +229,8 @@ class CTC_Model(nn.Module):
         if not candidates:
             raise ValueError("forward_candidates: at least one candidate batch is needed")
         _lib.require_gpu()
-        src_device = x.device
-        dev = x.device if x.is_cuda else torch.device("cuda", torch.cuda.current_device())
-        xd = x.to(dev, torch.float32).contiguous()
-        B, T, Fdim = xd.shape
-        if Fdim != self.rnn_param["rnn_input_size"]:
-            raise RuntimeError("expected feature size %d, got %d" % (self.rnn_param["rnn_input_size"], Fdim))
+        xd = self._on_device(x, self._taps)
+        B, dev = xd.shape[0], xd.device
         K, L = len(candidates), max(int(c.shape[1]) for c in candidates)
         ids = torch.zeros((K, B, L), dtype=torch.int64, device=dev)
         for k, c in enumerate(candidates):
@@ -265,17 +239,8 @@ class CTC_Model(nn.Module):
             ids[k, :, :c.shape[1]] = c.to(dev, torch.int64)
         canon = torch.tensor([int(c.shape[1]) for c in candidates], dtype=torch.int32).repeat_interleave(B).to(dev)
         with torch.cuda.device(dev):
-            self._sync_weights(dev.index if dev.index is not None else torch.cuda.current_device())
-            if getattr(self, "_taps", False):
-                _lib.check(_lib.lib().mdd_enable_taps(self._handle, 1))
-            out = torch.empty((K, T // 2, B, self.num_class), dtype=torch.float32, device=dev)
-            st = _lib.current_stream_ptr()
-            _lib.check(_lib.lib().mdd_forward_candidates(self._handle, C.c_void_p(xd.data_ptr()), B, T, C.c_void_p(ids.data_ptr()), K, L, None,
-                                                         C.c_void_p(canon.data_ptr()), C.c_void_p(out.data_ptr()), st))
-            if self.strict_errors:
-                if _lib.lib().mdd_sync(self._handle, st) != 0:
-                    raise IndexError(_lib.lib().mdd_last_error().decode())
-        return [out[k] if src_device == dev else out[k].to(src_device) for k in range(K)]
+            out = self._hip.forward_candidates(xd, ids, canon=canon, sync_errors=self.strict_errors)
+        return [out[k].to(x.device) for k in range(K)]
 
     def compute_wer(self, index, input_sizes, targets, target_sizes):
         """Greedy collapse + edit distance on host index arrays (model_ctc.py:227-244)."""

@@ -19,10 +19,9 @@ from . import _lib
 class TrainHandle(object):
     def __init__(self, cfg, device_index):
         _lib.require_gpu()
-        self.handle = C.c_void_p()
-        self.device_index = device_index
-        _lib.check(_lib.lib().mdd_train_create(C.byref(cfg), device_index, C.byref(self.handle)))
         L = _lib.lib()
+        self.device_index = device_index
+        self.handle = _lib.new_handle(L.mdd_train_create, cfg, device_index)
         n = L.mdd_train_num_tensors(self.handle)
         self.keys, self.numel, self.is_buffer = [], [], []
         buf = C.create_string_buffer(128)
@@ -35,50 +34,37 @@ class TrainHandle(object):
     def mask_shapes(self, geom_channels, hidden, B, T, W1, W2):
         return [(B, geom_channels, T, W1), (B, geom_channels, T // 2, W2)] + [(T // 2, B, 2 * hidden)] * (self.n_masks - 2)
 
-    @staticmethod
-    def _ptr_array(tensors):
-        arr = (C.c_void_p * len(tensors))()
-        for i, t in enumerate(tensors):
-            arr[i] = t.data_ptr() if t is not None else None
-        return arr
+    _ptr_array = staticmethod(_lib.ptr_array)
 
     def forward(self, tensors, x, x1, masks, seed, p_drop):
         B, T, _ = x.shape
         out = torch.empty((T // 2, B, self._num_class(tensors)), dtype=torch.float32, device=x.device)
-        marr = None
-        if masks is not None:
-            assert len(masks) == self.n_masks
-            marr = self._ptr_array(masks)
-        _lib.check(_lib.lib().mdd_train_forward(self.handle, self._ptr_array(tensors), C.c_void_p(x.data_ptr()), B, T, C.c_void_p(x1.data_ptr()),
-                                                x1.shape[1], marr, C.c_uint64(seed), C.c_float(p_drop), C.c_void_p(out.data_ptr()),
-                                                _lib.current_stream_ptr()))
+        assert masks is None or len(masks) == self.n_masks
+        marr = None if masks is None else _lib.ptr_array(masks)
+        _lib.check(_lib.lib().mdd_train_forward(self.handle, _lib.ptr_array(tensors), _lib.ptr(x), B, T, _lib.ptr(x1), x1.shape[1], marr,
+                                                C.c_uint64(seed), C.c_float(p_drop), _lib.ptr(out), _lib.current_stream_ptr()))
         return out
 
     def _num_class(self, tensors):
         return tensors[self.keys.index("fc.1.weight")].shape[0]
 
     def backward(self, tensors, dlogp, grads):
-        _lib.check(_lib.lib().mdd_train_backward(self.handle, self._ptr_array(tensors), C.c_void_p(dlogp.data_ptr()), self._ptr_array(grads),
+        _lib.check(_lib.lib().mdd_train_backward(self.handle, _lib.ptr_array(tensors), _lib.ptr(dlogp), _lib.ptr_array(grads),
                                                  _lib.current_stream_ptr()))
 
     def sync(self):
-        if _lib.lib().mdd_train_sync(self.handle, _lib.current_stream_ptr()) != 0:
-            raise IndexError(_lib.lib().mdd_last_error().decode())
+        _lib.raise_device_error(_lib.lib().mdd_train_sync, self.handle)
 
     def close(self):
         if self.handle:
             _lib.lib().mdd_train_destroy(self.handle)
-            self.handle = C.c_void_p()
+            self.handle = None
 
     def __del__(self):
         try:
             self.close()
         except Exception:  # noqa: BLE001
             pass
-
-
-# model.train_precision -> mdd_train_set_precision: exact fp32 | flagged split-bf16 x3 | the large contractions as f32x6 (reference width)
-TRAIN_PRECISIONS = {"f32": 0, "bf16x3": 1, "f32x6": 2}
 
 
 class _TrainForward(torch.autograd.Function):
@@ -105,19 +91,18 @@ class _TrainForward(torch.autograd.Function):
 
 def model_forward_train(model, x, x1, masks=None, seed=None):
     """Train-mode forward of the drop-in CTC_Model through libmdd_hip (called by CTC_Model.forward when model.training)."""
-    dev = x.device if x.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    xd = x.to(dev, torch.float32).contiguous()
+    xd = _lib.to_gpu(x, torch.float32)
+    dev, index = xd.device, xd.device.index
     idd = x1.to(dev, torch.int64).contiguous()
-    index = dev.index if dev.index is not None else torch.cuda.current_device()
     h = getattr(model, "_train_handle", None)
     if h is None or h.device_index != index:
         h = TrainHandle(model._config(), index)
         model._train_handle = h
     want = getattr(model, "train_precision", None)          # None: the library default (exact fp32, or MDD_TRAIN_PRECISION)
     if want is not None and want != getattr(h, "precision", None):
-        if want not in TRAIN_PRECISIONS:
-            raise ValueError("train_precision %r: expected one of %s" % (want, ", ".join(repr(k) for k in TRAIN_PRECISIONS)))
-        _lib.check(_lib.lib().mdd_train_set_precision(h.handle, TRAIN_PRECISIONS[want]))
+        if want not in _lib.PRECISIONS:
+            raise ValueError("train_precision %r: expected one of %s" % (want, ", ".join(repr(k) for k in _lib.PRECISIONS)))
+        _lib.check(_lib.lib().mdd_train_set_precision(h.handle, _lib.PRECISIONS[want]))    # the large contractions: exact fp32 | flagged split-bf16 x3 | f32x6
         h.precision = want
     sd = dict(model.named_parameters())
     sd.update(dict(model.named_buffers()))
@@ -139,7 +124,7 @@ def model_forward_train(model, x, x1, masks=None, seed=None):
             buf += 1
     if getattr(model, "strict_errors", True):
         h.sync()
-    model._dirty = True                                            # the eval path's packed weight copies are stale now
+    model.mark_weights_changed()                                   # the eval path's packed weight copies are stale now
     return out if x.device == dev else out.to(x.device)
 
 
@@ -223,7 +208,7 @@ class Adam(torch.optim.Optimizer):
                     if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() and p.grad.is_contiguous()):
                         raise RuntimeError("mdd Adam: parameters and gradients must be contiguous float32 CUDA tensors")
                 n = len(grp)
-                arr = lambda ts: TrainHandle._ptr_array(ts)           # noqa: E731
+                arr = _lib.ptr_array
                 numel = (C.c_int64 * n)(*[p.numel() for p in grp])
                 with torch.cuda.device(grp[0].device):
                     _lib.check(L.mdd_adam_step(arr(grp), arr([p.grad for p in grp]), arr([self.state[p]["exp_avg"] for p in grp]),

@@ -108,8 +108,7 @@ def align_ids(pair):
     b = np.ascontiguousarray(pair[1], dtype=np.int32)
     ops = np.zeros(len(a) + len(b) + 1, dtype=np.uint8)
     dist, nops = C.c_int32(0), C.c_int32(0)
-    _lib.check(_lib.lib().mdd_align(a.ctypes.data_as(C.c_void_p), len(a), b.ctypes.data_as(C.c_void_p), len(b),
-                                    C.byref(dist), ops.ctypes.data_as(C.c_void_p), C.byref(nops)))
+    _lib.check(_lib.lib().mdd_align(_lib.ptr(a), len(a), _lib.ptr(b), len(b), C.byref(dist), _lib.ptr(ops), C.byref(nops)))
     return dist.value, [_OPS[o] for o in ops[:nops.value]]
 
 
@@ -125,7 +124,7 @@ def align_ids_batch(a, a_len, b, b_len):
     n, stride = a.shape[0], a.shape[1] + b.shape[1]
     dist, nops = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
     ops = np.zeros((n, max(stride, 1)), dtype=np.uint8)
-    p = lambda v: v.ctypes.data_as(C.c_void_p)
+    p = _lib.ptr
     _lib.check(_lib.lib().mdd_align_batch(p(a), p(a_len), a.shape[1], p(b), p(b_len), b.shape[1], n, p(dist), p(ops), ops.shape[1], p(nops)))
     return dist, ops, nops
 
@@ -134,8 +133,7 @@ def _device_posteriors(prob_tensor):
     _lib.require_gpu()
     if prob_tensor.dim() != 3:
         raise ValueError("prob_tensor must be [T, B, C]")
-    dev = prob_tensor.device if prob_tensor.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    return prob_tensor.to(dev, torch.float32).contiguous()
+    return _lib.to_gpu(prob_tensor, torch.float32)
 
 
 def _lens_tensor(frame_seq_len, B, T, dev):
@@ -295,10 +293,9 @@ class GreedyDecoder(Decoder):
         lp, T, B, Cn, lens = _posteriors_and_lens(prob_tensor, frame_seq_len)
         ids = torch.empty((B, T), dtype=torch.int32, device=lp.device)
         nids = torch.empty((B,), dtype=torch.int32, device=lp.device)
+        p = _lib.ptr
         with torch.cuda.device(lp.device):
-            _lib.check(_lib.lib().mdd_greedy(C.c_void_p(lp.data_ptr()), T, B, Cn, C.c_void_p(lens.data_ptr()),
-                                             self.blank_index, C.c_void_p(ids.data_ptr()), C.c_void_p(nids.data_ptr()),
-                                             _lib.current_stream_ptr()))
+            _lib.check(_lib.lib().mdd_greedy(p(lp), T, B, Cn, p(lens), self.blank_index, p(ids), p(nids), _lib.current_stream_ptr()))
         return ids, nids
 
     def decode(self, prob_tensor, frame_seq_len):
@@ -340,20 +337,22 @@ class BeamDecoder(Decoder):
             self._tables[key] = torch.from_numpy(self.lm.dense_table(self.int_to_char, num_class)).to(dev)
         return self._tables[key]
 
-    def decode_ids(self, prob_tensor, frame_seq_len=None):
+    def _search(self, entry, prob_tensor, frame_seq_len, N, *nbest):
+        """mdd_beam (``nbest`` empty, N = 1) or mdd_beam_nbest (``nbest`` = (N,)): (ids [N,B,T], nids [N,B], status [B], score [N,B])."""
         lp, T, B, Cn, lens = _posteriors_and_lens(prob_tensor, frame_seq_len)
-        ids = torch.empty((B, T), dtype=torch.int32, device=lp.device)
-        nids = torch.empty((B,), dtype=torch.int32, device=lp.device)
+        ids = torch.empty((N, B, T), dtype=torch.int32, device=lp.device)
+        nids = torch.empty((N, B), dtype=torch.int32, device=lp.device)
         status = torch.empty((B,), dtype=torch.int32, device=lp.device)
-        score = torch.empty((B,), dtype=torch.float64, device=lp.device)
-        lm = self._lm_table(Cn, lp.device)
+        score = torch.empty((N, B), dtype=torch.float64, device=lp.device)
+        lm, p = self._lm_table(Cn, lp.device), _lib.ptr
         with torch.cuda.device(lp.device):
-            _lib.check(_lib.lib().mdd_beam(C.c_void_p(lp.data_ptr()), T, B, Cn, C.c_void_p(lens.data_ptr()), self.beam_width,
-                                           self.blank_index, C.c_void_p(lm.data_ptr()), float(self.lm_alpha),
-                                           C.c_void_p(ids.data_ptr()), C.c_void_p(nids.data_ptr()),
-                                           C.c_void_p(status.data_ptr()), C.c_void_p(score.data_ptr()),
-                                           _lib.current_stream_ptr()))
+            _lib.check(entry(p(lp), T, B, Cn, p(lens), self.beam_width, self.blank_index, p(lm), float(self.lm_alpha), *nbest,
+                             p(ids), p(nids), p(status), p(score), _lib.current_stream_ptr()))
         return ids, nids, status, score
+
+    def decode_ids(self, prob_tensor, frame_seq_len=None):
+        ids, nids, status, score = self._search(_lib.lib().mdd_beam, prob_tensor, frame_seq_len, 1)
+        return ids[0], nids[0], status, score[0]
 
     def decode(self, prob_tensor, frame_seq_len=None):
         ids, nids, status, _ = self.decode_ids(prob_tensor, frame_seq_len)
@@ -373,22 +372,10 @@ class BeamDecoder(Decoder):
         ``(ids [N,B,T], nids [N,B], status [B], score [N,B])``: slice n is ``decode_ids``' output for the hypothesis of rank n, slice 0
         its output itself, bit for bit.  Ranks follow the reference's final sort: descending length-normalised score, equal scores in
         the order of the final beam.  An utterance with an error status has nids 0 and score NaN in every slice.  Nothing synchronises."""
-        lp, T, B, Cn, lens = _posteriors_and_lens(prob_tensor, frame_seq_len)
         N = self.beam_width if nbest is None else int(nbest)
         if not 1 <= N <= self.beam_width:
             raise ValueError("nbest must be in [1, beam_width = %d]" % self.beam_width)
-        ids = torch.empty((N, B, T), dtype=torch.int32, device=lp.device)
-        nids = torch.empty((N, B), dtype=torch.int32, device=lp.device)
-        status = torch.empty((B,), dtype=torch.int32, device=lp.device)
-        score = torch.empty((N, B), dtype=torch.float64, device=lp.device)
-        lm = self._lm_table(Cn, lp.device)
-        with torch.cuda.device(lp.device):
-            _lib.check(_lib.lib().mdd_beam_nbest(C.c_void_p(lp.data_ptr()), T, B, Cn, C.c_void_p(lens.data_ptr()), self.beam_width,
-                                                 self.blank_index, C.c_void_p(lm.data_ptr()), float(self.lm_alpha), N,
-                                                 C.c_void_p(ids.data_ptr()), C.c_void_p(nids.data_ptr()),
-                                                 C.c_void_p(status.data_ptr()), C.c_void_p(score.data_ptr()),
-                                                 _lib.current_stream_ptr()))
-        return ids, nids, status, score
+        return self._search(_lib.lib().mdd_beam_nbest, prob_tensor, frame_seq_len, N, N)
 
     def nbest_loglik(self, prob_tensor, frame_seq_len, ids, nids, max_len=None):
         """Exact CTC log-likelihood of every hypothesis of ``decode_nbest_ids``' ``ids [N,B,T]`` / ``nids [N,B]`` over its utterance's

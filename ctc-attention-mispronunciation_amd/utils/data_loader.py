@@ -4,8 +4,6 @@ blank = 0, UNK = 1; :13-52), the context-stack / frame-skip / even-pad of one ut
 done on the GPU by mdd_stack_skip) and the zero-padding collate with its float32 length fractions
 (``create_input``, :151-181).  Reading Kaldi ark files is upstream of the path.
 """
-import ctypes as C
-
 import numpy as np
 import torch
 from torch.utils.data import DataLoader, Dataset
@@ -55,8 +53,8 @@ def stack_features(raw, right_ctx=2, n_skip_frame=2, n_downsample=2, out=None):
     if out is None:
         out = torch.empty((B, T, (right_ctx + 1) * D), dtype=torch.float32, device=r.device)
     assert out.is_contiguous() and out.numel() == B * T * (right_ctx + 1) * D
-    _lib.check(_lib.lib().mdd_stack_skip(C.c_void_p(r.data_ptr()), B, T_raw, D, right_ctx, n_skip_frame, n_downsample,
-                                         C.c_void_p(out.data_ptr()), _lib.current_stream_ptr()))
+    _lib.check(_lib.lib().mdd_stack_skip(_lib.ptr(r), B, T_raw, D, right_ctx, n_skip_frame, n_downsample, _lib.ptr(out),
+                                         _lib.current_stream_ptr()))
     return out.view(T, -1) if single else out.view(B, T, -1)
 
 

@@ -119,9 +119,7 @@ def compute_fbank_feats(samples, sample_rate=SAMPLE_RATE, cmvn=None, device=None
         if sc.numel() != NUM_COLS or of.numel() != NUM_COLS:
             raise ValueError("cmvn vectors must have %d entries" % NUM_COLS)
     with torch.cuda.device(dev):
-        _lib.check(_lib.lib().mdd_fbank(C.c_void_p(x.data_ptr()), x.numel(), C.c_void_p(sc.data_ptr()) if sc is not None else None,
-                                        C.c_void_p(of.data_ptr()) if of is not None else None, C.c_void_p(out.data_ptr()),
-                                        _lib.current_stream_ptr()))
+        _lib.check(_lib.lib().mdd_fbank(_lib.ptr(x), x.numel(), _lib.ptr(sc), _lib.ptr(of), _lib.ptr(out), _lib.current_stream_ptr()))
     return out
 
 
@@ -226,10 +224,8 @@ def fbank_batch(wavs, cmvn=None, right_ctx=2, n_skip_frame=2, n_downsample=2, ou
         of = torch.as_tensor(cmvn[1]).to(dev, torch.float32).contiguous()
         if sc.numel() != NUM_COLS or of.numel() != NUM_COLS:
             raise ValueError("cmvn vectors must have %d entries" % NUM_COLS)
-    _lib.check(L.mdd_fbank_batch(C.c_void_p(wav.data_ptr()), C.c_void_p(off.data_ptr()), B, t_out,
-                                 C.c_void_p(sc.data_ptr()) if sc is not None else None,
-                                 C.c_void_p(of.data_ptr()) if of is not None else None,
-                                 right_ctx, n_skip_frame, n_downsample, C.c_void_p(out.data_ptr()), _lib.current_stream_ptr()))
+    _lib.check(L.mdd_fbank_batch(_lib.ptr(wav), _lib.ptr(off), B, t_out, _lib.ptr(sc), _lib.ptr(of), right_ctx, n_skip_frame, n_downsample,
+                                 _lib.ptr(out), _lib.current_stream_ptr()))
     lens = [L.mdd_stack_len(L.mdd_fbank_num_frames(int(k)), n_skip_frame, n_downsample) for k in n]
     sizes = torch.zeros(B)
     for b in range(B):
@@ -252,8 +248,7 @@ def resample_len(n, rate):
 def resample_filter(rate):
     """The library's kaiser_best table for ``rate`` (mdd_resample_filter): (win, delta), float64 [32769] each."""
     win, delta = np.zeros(RESAMPLE_TABLE), np.zeros(RESAMPLE_TABLE)
-    _lib.check(_lib.lib().mdd_resample_filter(int(rate), C.c_void_p(win.ctypes.data), C.c_void_p(delta.ctypes.data),
-                                              RESAMPLE_TABLE))
+    _lib.check(_lib.lib().mdd_resample_filter(int(rate), _lib.ptr(win), _lib.ptr(delta), RESAMPLE_TABLE))
     return win, delta
 
 
@@ -278,7 +273,6 @@ def resample_batch(wavs, rates):
     wav = torch.from_numpy(np.concatenate(host)).to(dev)
     d_in, d_out, d_rates = (torch.from_numpy(a).to(dev) for a in (in_off, out_off, r))
     out = torch.empty(int(out_off[-1]), dtype=torch.float32, device=dev)
-    _lib.check(_lib.lib().mdd_resample_batch(C.c_void_p(wav.data_ptr()), C.c_void_p(d_in.data_ptr()),
-                                             C.c_void_p(d_rates.data_ptr()), len(host), C.c_void_p(d_out.data_ptr()),
-                                             C.c_void_p(out.data_ptr()), _lib.current_stream_ptr()))
+    _lib.check(_lib.lib().mdd_resample_batch(_lib.ptr(wav), _lib.ptr(d_in), _lib.ptr(d_rates), len(host), _lib.ptr(d_out), _lib.ptr(out),
+                                             _lib.current_stream_ptr()))
     return out, torch.from_numpy(out_off)

@@ -90,7 +90,7 @@ def test_ctc_model_mark_weights_changed_gives_fresh_model_bits():
     model = make(sd_a)
     with torch.no_grad():
         out_a = model(x, x1).clone()
-    assert _lib.lib().mdd_get_precision(model._handle) == 2
+    assert _lib.lib().mdd_get_precision(model._hip.handle) == 2
     unrelated = torch.empty(48 << 20, dtype=torch.uint8, device="cuda")
     with torch.no_grad():
         for k, t in model.state_dict().items():
