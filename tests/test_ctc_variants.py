@@ -399,6 +399,20 @@ def lane_case(L):
                 entries=[sampled_entries(L, Cn, blank, rs), sampled_entries(L // 2, Cn, blank, rs, 100)])
 
 
+def lds_case():
+    """T = 713, C = 45, L = 12: the general lattice kernel reached through the LDS rule of csrc/ctc.hip (713 frames of 45 log-probs beside the
+    wave kernel's lists are 12 bytes past its 128 KB; T = 712 is the last wave shape), not through the label count as L = 300 does.  Held to
+    BOUND as it stands and kept out of ``all_cases``, which BOUND was measured over; measured on an MI355X: 1.24e-6 over 171 finite entries
+    (the error grows with the frame count: 8.2e-7 was the worst at T <= 330)."""
+    rs = np.random.default_rng(713)
+    T, Cn, L, blank = 713, 45, 12, 0
+    classes = list(range(1, Cn))
+    rows = [_labels(rs, L, classes), _labels(rs, 7, classes)]
+    ids, nids = _pack(rows, L)
+    return dict(name="T 713 by the LDS rule", lp=_posteriors(rs, T, 2, Cn), lens=[T, T - 60], ids=ids, nids=nids, Lmax=L, blank=blank,
+                entries=[sampled_entries(L, Cn, blank, rs, 100), sampled_entries(7, Cn, blank, rs, 50)])
+
+
 def class_case(Cn, blank):
     rs = np.random.default_rng(1000 * Cn + blank)
     labels = [k for k in range(Cn) if k != blank]
@@ -461,6 +475,15 @@ def test_exhaustive_small(blank):
 @pytest.mark.parametrize("L", LANE_L)
 def test_lattice_lane_ownership_and_general_lattice(L):
     check_case(lane_case(L))
+
+
+@pytest.mark.gpu
+def test_general_lattice_through_the_lds_rule():
+    case = lds_case()
+    T, B, Cn = case["lp"].shape
+    assert _lib().mdd_ctc_variants_workspace_bytes(T, B, Cn, case["Lmax"]) == 8 * 2 * B * T * (2 * case["Lmax"] + 1)      # the general form's rows
+    assert _lib().mdd_ctc_variants_workspace_bytes(T - 1, B, Cn, case["Lmax"]) == 16 * B * (T - 1) * 2 * (case["Lmax"] + 1)
+    check_case(case)
 
 
 @pytest.mark.gpu
