@@ -35,14 +35,12 @@
 // so every sum has a term near 1.  No atomics: the same bits on every call.
 #include <math.h>
 
+#include "ctc_confnet.h"
 #include "ctc_host.h"
 #include "ctc_lse.h"
 #include "ctc_wave.h"
 
 namespace mdd {
-
-static constexpr int CN_WAVES = 16;
-static constexpr size_t CN_LDS_LIMIT = 159 * 1024;       // dynamic LDS; the last KB of the CU's 160 stays with the kernel's static 256 bytes
 
 struct ConfnetArgs {
     const float *logp; int T, B, C;
@@ -51,10 +49,6 @@ struct ConfnetArgs {
     double *total, *post; int *status;
     double *ws; size_t ws_utt;      // E_t of every frame, [T, J, C] per utterance (doubles)
 };
-
-// doubles of LDS for J slots: three [J, C] rows, what the waves publish of their blocks ([waves, C] and [waves]), skip / all / apre [J],
-// pre / tail / end [J + 1]
-static size_t confnet_lds_doubles(int C, int J) { return (size_t)3 * J * C + (size_t)CN_WAVES * (C + 1) + (size_t)6 * J + 8; }
 
 __device__ __forceinline__ double wave_max(double v) {
     for (int o = 32; o; o >>= 1) v = fmax(v, __shfl_xor(v, o));

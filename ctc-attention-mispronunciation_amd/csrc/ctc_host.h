@@ -1,4 +1,4 @@
-// The host shape of a CTC lattice entry (mdd_ctc_loss, mdd_ctc_align, mdd_ctc_variants, mdd_ctc_confnet, the beam entries), host code only:
+// The host shape of a CTC lattice entry (mdd_ctc_loss, mdd_ctc_align, mdd_ctc_variants, mdd_ctc_confnet, mdd_ctc_confnet_best, the beam entries), host code only:
 //   1. refuse    every bad argument by name, then a caller workspace that is too small (refuse_workspace) -- before any HIP call;
 //   2. attributes the kernels' LDS budgets, once per device (once_per_device, mdd_internal.h);
 //   3. workspace the caller's, or one allocated on the stream for the call (StreamWorkspace);

@@ -1,4 +1,4 @@
-// Wave-level device helpers of the CTC lattice kernels (ctc.hip, ctc_align.hip, ctc_confnet.hip), beside ctc_lse.h.
+// Wave-level device helpers of the CTC lattice kernels (ctc.hip, ctc_align.hip, ctc_confnet.hip, ctc_confnet_best.hip), beside ctc_lse.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -36,6 +36,24 @@ __device__ __forceinline__ float wave_sum_dpp(float x) {
     const int xi = __builtin_bit_cast(int, x);
     return __builtin_bit_cast(float, __builtin_amdgcn_readlane(xi, 0)) + __builtin_bit_cast(float, __builtin_amdgcn_readlane(xi, 16)) +
            __builtin_bit_cast(float, __builtin_amdgcn_readlane(xi, 32)) + __builtin_bit_cast(float, __builtin_amdgcn_readlane(xi, 48));
+}
+// wave_max_dpp: the maximum of a double over the 64 lanes, every lane returning the same bits, by wave_sum_dpp's route (rows of 16 by DPP,
+// then the four row maxima).  A maximum does not depend on the order, so it is the butterfly's value without its twelve ds_bpermutes.
+template <int CTRL>
+__device__ __forceinline__ double wave_dpp_all(double v) {      // CTRL must name a source for every lane (quad_perm, row mirrors)
+    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, true);
+    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, true);
+    return __hiloint2double(hi, lo);
+}
+__device__ __forceinline__ double wave_max_dpp(double x) {
+    x = fmax(x, wave_dpp_all<0xB1>(x));     // quad_perm [1,0,3,2]
+    x = fmax(x, wave_dpp_all<0x4E>(x));     // quad_perm [2,3,0,1]
+    x = fmax(x, wave_dpp_all<0x141>(x));    // row_half_mirror
+    x = fmax(x, wave_dpp_all<0x140>(x));    // row_mirror
+    const int lo = __double2loint(x), hi = __double2hiint(x);
+    double r[4];
+    for (int q = 0; q < 4; q++) r[q] = __hiloint2double(__builtin_amdgcn_readlane(hi, 16 * q), __builtin_amdgcn_readlane(lo, 16 * q));
+    return fmax(fmax(r[0], r[1]), fmax(r[2], r[3]));
 }
 // wave_sum_butterfly: __shfl_xor over distances 32, 16, .., 1.  The bits of ctc_confnet_kernel's log-adds (lse_all, excl_all) depend on this
 // order, not wave_sum_dpp's.

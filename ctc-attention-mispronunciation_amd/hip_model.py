@@ -159,7 +159,7 @@ class HipModel(object):
 
 
 class _CtcCall(object):
-    """What the four CTC lattice functions share: ``logp`` contiguous fp32 [T,B,C] on its device, conversion of the other arrays to that
+    """What the five CTC lattice functions share: ``logp`` contiguous fp32 [T,B,C] on its device, conversion of the other arrays to that
     device, and one call of an entry that ends ``..., workspace_dev, workspace_bytes, stream``."""
 
     def __init__(self, logp):
@@ -284,3 +284,32 @@ def ctc_confnet(logp, lens, w, nslots, blank=0, max_slots=None, want_post=True):
     c.workspace(_lib.lib().mdd_ctc_confnet_workspace_bytes, max(Jmax, 0), 1 if want_post else 0)
     c(_lib.lib().mdd_ctc_confnet, c.ptr(lens), c.ptr(w, stride), stride, c.ptr(nslots), Jmax, blank, c.ptr(total), c.ptr(post, stride), c.ptr(status))
     return ConfnetResult(total, post, status)
+
+
+ConfnetBestResult = collections.namedtuple("ConfnetBestResult", "score reading status path seg")
+
+
+def ctc_confnet_best(logp, lens, w, nslots, blank=0, max_slots=None, want_path=True, want_segments=True):
+    """The best reading of an error network with its alignment (mdd_ctc_confnet_best): the max-product sweep over ``ctc_confnet``'s network.
+
+    Arguments as ``ctc_confnet`` takes them.  Returns ``ConfnetBestResult(score [B] f64, reading [B,stride] i32, status [B] i32, path
+    [B,T] i32 | None, seg [B,stride,2] i32 | None)``: score is the largest sum of a reading's weights and one CTC path's log-posteriors
+    (the best pair of reading and alignment, not the reading of the largest summed likelihood); reading[b,j] the entry slot j takes
+    (``blank``: it emits nothing); path[b,t] the slot whose label frame t emits or -1; seg[b,j] the first and one-past-last frame of slot
+    j's label, -1, -1 where it emits nothing.  Rows past nslots[b] are -1 up to ``max_slots`` and not written beyond it.  Nothing
+    synchronises."""
+    c = _CtcCall(logp)
+    B = c.B
+    lens, w, nslots = c.to(lens, torch.int32), c.to(w, torch.float32), c.to(nslots, torch.int32)
+    if w.dim() != 3 or w.shape[0] != B or w.shape[2] != c.C or lens.shape != (B,) or nslots.shape != (B,):
+        raise ValueError("ctc_confnet_best: lens [B], w [B, stride, C], nslots [B]")
+    stride = w.shape[1]
+    Jmax = stride if max_slots is None else int(max_slots)
+    score, status = c.empty((B,), torch.float64), c.empty((B,), torch.int32)
+    reading = c.empty((B, stride), torch.int32)
+    path = c.empty((B, c.T), torch.int32, want_path)
+    seg = c.empty((B, stride, 2), torch.int32, want_segments)
+    c.workspace(_lib.lib().mdd_ctc_confnet_best_workspace_bytes, max(Jmax, 0))
+    c(_lib.lib().mdd_ctc_confnet_best, c.ptr(lens), c.ptr(w, stride), stride, c.ptr(nslots), Jmax, blank, c.ptr(score), c.ptr(reading, stride),
+      c.ptr(status), c.ptr(path), c.ptr(seg, stride))
+    return ConfnetBestResult(score, reading, status, path, seg)

@@ -3,7 +3,7 @@
 
     python -m ctc_attention_mispronunciation_amd.infer --conf CONF --wav_transcript_path DIR [-p cmudict] [-f cmu]
         [--cmvn PATH] [--cmudict PATH] [--precision f32x6|f32|bf16x3] [--decode_seq PATH] [--timestamps] [--posteriors] [--pronunciations] [--nbest N]
-        [--joint_posteriors [--error_prior P]]
+        [--joint_posteriors] [--joint_diagnosis] [--error_prior P]
 
 The conf YAML is read as ``infer_init`` reads it (AA/infer.py:211-261): the checkpoint
 ``checkpoint_dir/exp_name/ctc_best_model.pkl``, ``vocab_file``, ``decode_type``, ``beam_width``, ``lm_path``, ``lm_alpha``,
@@ -68,9 +68,15 @@ def parse_args(argv=None):
                     help="add a 'jpost  :' line to each block, in the format of 'post   :': the same per-phoneme figures as marginals over the "
                          "error network of the canonical phones -- every phoneme kept, substituted or deleted and every gap empty or filled "
                          "at once -- so two errors in one word no longer count against each other")
+    ap.add_argument("--joint_diagnosis", action="store_true",
+                    help="add a 'jdiag  :' line to each block: the single most probable combination of kept (ph), substituted (ph>alt), deleted "
+                         "(ph>-) and inserted (+ph) phonemes -- decoding constrained to the error network of the canonical phones -- with its "
+                         "number of edits, its score and its probability among all readings; with --timestamps a 'jtime  :' line follows with "
+                         "the seconds each emitted phoneme occupies.  Needs --error_prior")
     ap.add_argument("--error_prior", type=float, default=None, metavar="P",
-                    help="with --joint_posteriors: prior probability of an error per slot, 0 < P < 1 (a position keeps its phoneme with 1 - P "
-                         "and spreads P over the C - 1 other entries; a gap stays empty with 1 - P).  Default: every entry weighs the same")
+                    help="with --joint_posteriors and / or --joint_diagnosis (required by the latter; they share P): prior probability of an "
+                         "error per slot, 0 < P < 1 (a position keeps its phoneme with 1 - P and spreads P over the C - 1 other entries; a "
+                         "gap stays empty with 1 - P).  Default, --joint_posteriors only: every entry weighs the same")
     return ap.parse_args(argv)
 
 
@@ -160,9 +166,11 @@ def main(argv=None):
     if args.phonetic_format != "cmu":
         refuse("-f %s needs the IPA tables of phonemizer / espeak, which are not available offline; use -f cmu"
                % args.phonetic_format)
+    if args.joint_diagnosis and args.error_prior is None:
+        refuse("--joint_diagnosis needs --error_prior P: under the uniform prior a substitution ties with a deletion plus an insertion")
     if args.error_prior is not None:
-        if not args.joint_posteriors:
-            refuse("--error_prior: only with --joint_posteriors")
+        if not (args.joint_posteriors or args.joint_diagnosis):
+            refuse("--error_prior: only with --joint_posteriors or --joint_diagnosis")
         if not 0.0 < args.error_prior < 1.0:
             refuse("--error_prior %r: P must lie strictly between 0 and 1" % args.error_prior)
     t0 = time.time()
@@ -212,7 +220,8 @@ def main(argv=None):
     device = torch.device("cuda", torch.cuda.current_device())
     c1, c2, c3 = infer(phonetic, word_dict, loader, device, model, decoder, vocab, transcripts, False,
                        decode_seq_path=args.decode_seq, timestamps=args.timestamps, posteriors=args.posteriors, pronunciations=args.pronunciations,
-                       nbest=args.nbest or 0, joint_posteriors=args.joint_posteriors, error_prior=args.error_prior)
+                       nbest=args.nbest or 0, joint_posteriors=args.joint_posteriors, error_prior=args.error_prior,
+                       joint_diagnosis=args.joint_diagnosis)
     print(c1, c2, c3)
     end = time.time()
     total = max(total_wav_time, 1e-9)

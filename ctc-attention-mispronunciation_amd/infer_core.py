@@ -204,6 +204,53 @@ def posterior_line(d, label="post   : "):
     return label + " ".join(toks)
 
 
+def _joint_name(k, names, to_display=None):
+    ph = names[k]
+    return to_display.get(ph.upper(), ph) if to_display is not None else ph
+
+
+def joint_diagnosis_line(diag, ids, names, blank=0, to_display=None):
+    """The ``jdiag  :`` line of a block from one utterance's ``ctcDecoder.joint_diagnosis`` result ``(positions, gaps, score,
+    posterior)`` over the canonical ``ids``: ``jdiag  : <tokens> | edits <n> | score <%.4f> | p <%.4f>``.  The tokens run over the canonical
+    ids (``names[id]``, passed through ``to_display`` as the other lines' are) with the gaps interleaved: ``ph`` kept, ``ph>alt``
+    substituted by alt, ``ph>-`` deleted, ``+ph`` inserted; edits counts the tokens that are not plain.  ``jdiag  : -`` where the utterance
+    has no result (``diag`` is None)."""
+    if diag is None:
+        return "jdiag  : -"
+    positions, gaps, score, posterior = diag
+    if len(positions) != len(ids) or len(gaps) != len(ids) + 1:
+        raise ValueError("joint_diagnosis_line: %d positions and %d gaps for %d canonical phonemes" % (len(positions), len(gaps), len(ids)))
+    toks, edits = [], 0
+    for i in range(len(ids) + 1):
+        if gaps[i][0] != blank:
+            toks.append("+" + _joint_name(gaps[i][0], names, to_display))
+            edits += 1
+        if i == len(ids):
+            break
+        own, k = int(ids[i]), positions[i][0]
+        ph = _joint_name(own, names, to_display)
+        if k == own:
+            toks.append(ph)
+        else:
+            toks.append(ph + ">" + ("-" if k == blank else _joint_name(k, names, to_display)))
+            edits += 1
+    return "jdiag  : %s | edits %d | score %.4f | p %.4f" % (" ".join(toks), edits, score, posterior)
+
+
+def joint_time_line(diag, names, seconds_per_frame, blank=0, to_display=None):
+    """The ``jtime  :`` line behind ``jdiag  :`` with ``timestamps``: ``jtime  : <ph> <start>-<end> ...`` over the labels the best reading
+    emits, in slot order, in seconds as ``time   :`` prints them (nominal frame starts); ``jtime  : -`` where the utterance has no result."""
+    if diag is None:
+        return "jtime  : -"
+    positions, gaps = diag[0], diag[1]
+    toks = []
+    for i in range(len(gaps)):
+        for k, s, e in (gaps[i],) + ((positions[i],) if i < len(positions) else ()):
+            if k != blank:
+                toks.append("%s %.2f-%.2f" % (_joint_name(k, names, to_display), s * seconds_per_frame, e * seconds_per_frame))
+    return "jtime  : " + " ".join(toks)
+
+
 def seconds_per_frame(test_loader, cnn_time_stride):
     """Seconds between posterior frames: the fbank's frame shift x the loader's ``n_skip_frame`` x the CNN's time stride (0.04 s in
     the reference configuration)."""
@@ -249,7 +296,8 @@ def nbest_lines(records, canonical, decoder, to_display=None):
 
 
 def infer(phonetic, word_dict, test_loader, device, model, decoder, vocab, test_transcipt_dict, use_ipa, out=None,
-          decode_seq_path=None, timestamps=False, posteriors=False, pronunciations=False, nbest=0, joint_posteriors=False, error_prior=None):
+          decode_seq_path=None, timestamps=False, posteriors=False, pronunciations=False, nbest=0, joint_posteriors=False, error_prior=None,
+          joint_diagnosis=False):
     """AA/infer.py:282-372.  Per batch ``(inputs, input_sizes, _, _, trans, trans_sizes, utt_list)``: ``model(inputs, trans)``,
     frame counts ``(input_sizes * T').long()``, ``decoder.decode``, then per utterance the 'sil' strip, 'err' removal, ``wer``,
     alignment, fault lists and score (``diagnose``), printed as the reference's 13-line block to ``out`` (stdout by default).
@@ -286,15 +334,27 @@ def infer(phonetic, word_dict, test_loader, device, model, decoder, vocab, test_
     sequence -- every position kept, substituted or deleted and every gap empty or filled AT ONCE, not one edit with the rest taken as
     canonical (``ctcDecoder.joint_phoneme_posteriors``, one call per batch).  ``error_prior`` (0 < P < 1) is the prior probability of an
     error per slot; ``None`` weights every entry of every slot alike.  It reads only the posteriors, so it serves both model classes;
-    with ``pronunciations`` the line is the chosen candidate's.  Without it nothing changes."""
-    if error_prior is not None and not (joint_posteriors and 0.0 < error_prior < 1.0):
-        raise ValueError("error_prior needs joint_posteriors and 0 < error_prior < 1")
+    with ``pronunciations`` the line is the chosen candidate's.  Without it nothing changes.
+
+    ``joint_diagnosis=True`` (no reference counterpart; needs ``error_prior``, which it shares with ``joint_posteriors``) adds one line,
+    ``jdiag  :`` (``joint_diagnosis_line``), directly behind ``jpost`` / ``post`` and in front of ``nbest`` / ``pron``: the single most
+    probable combination of kept, substituted, deleted and inserted phonemes -- the best reading of the same error network with its
+    alignment (``ctcDecoder.joint_diagnosis``, one call per batch) -- with its number of edits, its score and its probability among all
+    readings.  With ``timestamps`` a ``jtime  :`` line (``joint_time_line``) follows it: the frames of every emitted phoneme in seconds.
+    It reads only the posteriors, so it serves both model classes; with ``pronunciations`` the lines are the chosen candidate's.
+    Without it nothing changes."""
+    if error_prior is not None and not ((joint_posteriors or joint_diagnosis) and 0.0 < error_prior < 1.0):
+        raise ValueError("error_prior needs joint_posteriors or joint_diagnosis and 0 < error_prior < 1")
+    if joint_diagnosis and error_prior is None:
+        raise ValueError("joint_diagnosis needs error_prior")
     if nbest and not (hasattr(decoder, "decode_nbest") and 1 <= nbest <= decoder.beam_width):
         raise ValueError("nbest needs a BeamDecoder and 1 <= nbest <= beam_width")
     if posteriors:
         from .utils.ctcDecoder import phoneme_posteriors
     if joint_posteriors:
         from .utils.ctcDecoder import joint_phoneme_posteriors
+    if joint_diagnosis:
+        from .utils.ctcDecoder import joint_diagnosis as joint_diagnosis_of
     if pronunciations:
         from .hip_model import ctc_variants
     out = sys.stdout if out is None else out
@@ -332,6 +392,8 @@ def infer(phonetic, word_dict, test_loader, device, model, decoder, vocab, test_
                         r["post"] = phoneme_posteriors(probs, frame_lens, trans, trans_sizes, decoder.blank_index)
                     if joint_posteriors:
                         r["jpost"] = joint_phoneme_posteriors(probs, frame_lens, trans, trans_sizes, decoder.blank_index, error_prior)
+                    if joint_diagnosis:
+                        r["jdiag"] = joint_diagnosis_of(probs, frame_lens, trans, trans_sizes, decoder.blank_index, error_prior=error_prior)
                     if pronunciations:
                         r["loglik"] = ctc_variants(probs, frame_lens, trans.to(torch.int32), trans_sizes.to(torch.int32), decoder.blank_index,
                                                    want_ins=False).base.cpu().tolist()
@@ -371,6 +433,11 @@ def infer(phonetic, word_dict, test_loader, device, model, decoder, vocab, test_
                         dp = diagnose_posterior(decoded[x], canonical, None if post[x] is None else post[x][0], decoder, vocab.index2word,
                                                 to_display)
                         block[-1:-1] = [posterior_line(dp, "jpost  : ")]
+                    if joint_diagnosis:
+                        own = trans[x][:trans_sizes[x]]
+                        block[-1:-1] = [joint_diagnosis_line(r["jdiag"][x], own, vocab.index2word, decoder.blank_index, to_display)]
+                        if timestamps:
+                            block[-1:-1] = [joint_time_line(r["jdiag"][x], vocab.index2word, spf, decoder.blank_index, to_display)]
                     if nbest:
                         block[-1:-1] = nbest_lines(r["nbest"][x], canonical, decoder, to_display)
                     if pronunciations:

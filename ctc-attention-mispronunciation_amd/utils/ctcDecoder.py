@@ -273,6 +273,51 @@ def joint_phoneme_posteriors(prob_tensor, frame_seq_len, ids, nids, blank=0, err
     return _posterior_tuples(r.post.cpu().numpy(), r.total.cpu().numpy(), r.status.cpu().numpy(), ids_h, n, blank)
 
 
+def joint_diagnosis(prob_tensor, frame_seq_len, ids, nids, blank=0, *, error_prior):
+    """The single most probable combination of kept, substituted, deleted and inserted phonemes of the canonical ``ids`` / ``nids``
+    ([B, stride] / [B]) with the frames each phoneme occupies: the best reading of ``error_network(ids, error_prior)`` and its alignment
+    (mdd_ctc_confnet_best).  ``error_prior`` is required, 0 < P < 1: under the uniform prior a substitution ties exactly with a deletion
+    plus an insertion, and the tie rule alone would decide.  Per utterance ``None`` (ids that are no valid targets, or a network without
+    any alignment) or ``(positions, gaps, score, posterior)``:
+      positions[i] = (entry, start, end)   entry ids[i]: kept, ``blank``: deleted, else the substitute; the frames [start, end) of what
+                                           was emitted, -1, -1 for a deletion
+      gaps[g]      = (entry, start, end)   for 0 <= g <= nids[b]; ``blank``: nothing inserted before position g
+      score        the reading's weights plus the log-posteriors of its best path (float64)
+      posterior    exp(sum_j w[j, r_j] + log P_CTC(labels) - total): the reading's probability among all readings of the network, over
+                   all of its alignments (one ``ctc_variants`` base on the reading's labels, one ``ctc_confnet`` total), float64."""
+    from ..hip_model import ctc_confnet, ctc_confnet_best, ctc_variants
+    if error_prior is None or not 0.0 < error_prior < 1.0:
+        raise ValueError("joint_diagnosis: 0 < error_prior < 1")
+    lp, T, B, Cn, lens = _posteriors_and_lens(prob_tensor, frame_seq_len)
+    ids_h, n = torch.as_tensor(ids).cpu().numpy(), torch.as_tensor(nids).cpu().numpy()
+    valid = [0 <= int(n[b]) <= ids_h.shape[1] and all(0 <= int(v) < Cn and int(v) != blank for v in ids_h[b, :max(int(n[b]), 0)])
+             for b in range(B)]
+    Lmax = min(max(int(n.max()), 0), ids_h.shape[1]) if B else 0           # no slots past the longest row
+    w, nslots = error_network(torch.as_tensor(ids)[:, :Lmax], torch.as_tensor(nids), Cn, blank, error_prior)
+    nslots = torch.where(torch.as_tensor(valid), nslots.cpu(), torch.full((B,), -1, dtype=torch.int32))       # not a target: BAD_TARGET
+    r = ctc_confnet_best(lp, lens, w, nslots, blank=blank, want_path=False)
+    total = ctc_confnet(lp, lens, w, nslots, blank=blank, want_post=False).total.cpu().numpy()
+    status, reading, seg, score = r.status.cpu().numpy(), r.reading.cpu().numpy(), r.seg.cpu().numpy(), r.score.cpu().numpy()
+    w_h = w.cpu().numpy().astype(np.float64)
+    # log P_CTC of each reading's labels: one base per utterance
+    labels = [[int(k) for k in reading[b, :2 * int(n[b]) + 1] if k != blank] if status[b] == 0 else [] for b in range(B)]
+    lab = np.full((B, max(1, max((len(v) for v in labels), default=0))), 1 if blank == 0 else 0, dtype=np.int32)   # padding: a label, never read
+    for b, v in enumerate(labels):
+        lab[b, :len(v)] = v
+    base = ctc_variants(lp, lens, torch.from_numpy(lab), torch.tensor([len(v) for v in labels], dtype=torch.int32), blank=blank,
+                        want_ins=False).base.cpu().numpy()
+    out = []
+    for b in range(B):
+        if status[b] != 0:
+            out.append(None)
+            continue
+        L = int(n[b])
+        slots = [(int(reading[b, j]), int(seg[b, j, 0]), int(seg[b, j, 1])) for j in range(2 * L + 1)]
+        prior = float(sum(w_h[b, j, k] for j, (k, _, _) in enumerate(slots)))
+        out.append((slots[1::2], slots[0::2], float(score[b]), float(np.exp(prior + float(base[b]) - float(total[b])))))
+    return out
+
+
 def nbest_posteriors(loglik):
     """Float64 softmax over one utterance's N log-likelihoods: the share of probability each listed hypothesis holds AMONG THE LISTED
     ONES, not an absolute probability (what the list leaves out is not counted).  ``-inf`` entries get 0; ``None`` when every entry

@@ -370,6 +370,37 @@ int mdd_ctc_confnet(const float *logp_dev, int32_t T, int32_t B, int32_t C, cons
                     double *total_dev, double *post_dev, int32_t *status_dev,
                     void *workspace_dev, int64_t workspace_bytes, void *stream);
 
+/* ---- Best reading of an error network (no reference counterpart): decoding constrained to the network of mdd_ctc_confnet, the
+ * max-product sweep with a backtrace (csrc/ctc_confnet_best.hip, DESIGN.md "Best reading").  Inputs, accepted shapes (C in 2..256, Jmax <=
+ * mdd_ctc_confnet_max_slots(C)) and the meaning of w_dev / nslots_dev are exactly mdd_ctc_confnet's.  The call finds
+ *     max over readings r and over CTC paths pi of r's labels of   sum_j w[j, r_j] + sum_{t < len} logp[t, pi_t]
+ * -- the best PAIR of reading and alignment, NOT the reading with the largest likelihood summed over its alignments.  Outputs:
+ *   score_dev [B]                 fp64, that maximum
+ *   reading_dev [B,slot_stride]   the entry slot j takes (the blank entry: it emits nothing); rows nslots[b] <= j < Jmax are -1, rows
+ *                                 >= Jmax are not written
+ *   status_dev [B]                mdd_align_status
+ *   path_dev [B,T]                (nullable) written whole: the slot whose label frame t emits, -1 for a blank frame and for t >= len
+ *   seg_dev [B,slot_stride,2]     (nullable) first frame and one past the last frame of the label slot j emits (its frames are
+ *                                 contiguous); -1, -1 for a slot that emits nothing and for rows up to Jmax; rows >= Jmax are not written
+ * path_dev / seg_dev as NULL leave the other outputs' bits unchanged.  len = 0: only the all-empty reading has a path, its score the sum
+ * of the skips.  Frames >= len are never read.
+ * MDD_ALIGN_INFEASIBLE: no reading has a path; score -inf, reading and path -1, seg -1, -1.  MDD_ALIGN_BAD_TARGET (nslots[b] outside
+ * [0,Jmax], a NaN or +inf weight in a slot in use): score NaN, the rest as for infeasible.  Other utterances are unaffected by either.
+ * Arithmetic: fp64 additions and comparisons of the fp32 inputs, no exp or log.  Exactly equal values are resolved by a fixed priority:
+ *   staying in a label wins over entering it; coming from the nearer slot wins over skipping that slot (also at the end: ending in slot
+ *   j wins over skipping it); among classes the lower one wins.  Values that differ only by the rounding of a differently ordered sum are
+ *   not ties.  No atomics: the same bits on every call.
+ * workspace_dev: caller-owned scratch of at least mdd_ctc_confnet_best_workspace_bytes(T,B,C,Jmax) bytes (16-byte aligned; the
+ *   backpointers, 2 ceil(C / 64) + 1 64-bit words per frame and slot: 8 T B Jmax (2 ceil(C / 64) + 1) bytes), NULL = the library allocates
+ *   stream-ordered for the call.  Nothing synchronises.
+ * Bad host arguments (a required pointer NULL, T/B/C <= 0, C > 256, blank outside [0,C), Jmax < 0, > slot_stride or >
+ *   mdd_ctc_confnet_max_slots(C), a caller workspace that is too small) return MDD_ERR_ARG before any device work. */
+int64_t mdd_ctc_confnet_best_workspace_bytes(int32_t T, int32_t B, int32_t C, int32_t Jmax);
+int mdd_ctc_confnet_best(const float *logp_dev, int32_t T, int32_t B, int32_t C, const int32_t *len_dev,
+                         const float *w_dev, int32_t slot_stride, const int32_t *nslots_dev, int32_t Jmax, int32_t blank,
+                         double *score_dev, int32_t *reading_dev, int32_t *status_dev, int32_t *path_dev, int32_t *seg_dev,
+                         void *workspace_dev, int64_t workspace_bytes, void *stream);
+
 /* ---- A10: Decoder.wer core = _edit_distance + printChanges (AA/utils/ctcDecoder.py:118-184), host.
  * a = hypothesis tokens, b = canonical tokens; ops (capacity >= na+nb): 0 '-', 1 'S', 2 'I', 3 'D'.
  * Either side empty -> MDD_ERR_EMPTY (reference: TypeError). */
