@@ -9,6 +9,8 @@
 // of tests/fbank_reference.py under its per-element conditioning model (noise, impulses, tones, Nyquist, DC, the floor,
 // frame-count edges, recorded words; the batched kernel's stacking against float64 rows, not against fbank_kernel);
 // tests/test_fbank_reference.py pins that restatement to oracle/oracle.py's and shows what the bound catches.
+// tests/test_train_wav.py holds the train-time forms to these kernels' own rows: the masked batch (mdd_fbank_batch_aug) bit for bit,
+// the global CMVN statistics (mdd_cmvn_accumulate) to their float64 sums.
 //
 // One wave per frame, four frames per workgroup.  A frame is 400 samples = 1.6 KB: the work is a 512-point FFT in LDS
 // (9 radix-2 stages, 4 butterflies per lane and stage, wave-synchronous), 80 short dot products and a row store --
@@ -17,6 +19,7 @@
 #include <mutex>
 #include <vector>
 
+#include "ctc_host.h"
 #include "mdd_internal.h"
 
 namespace mdd {
@@ -136,10 +139,31 @@ __global__ __launch_bounds__(256) void fbank_kernel(const float *__restrict__ wa
 // stacked row s when s lies in [kept_b, T_out) -- the even-pad row of data_loader.py:138-142 and the batch padding -- so every
 // element of out [B, T_out, (right + 1) * 81] is written exactly once by this launch.  The grid's x extent covers
 // max(T_raw_b) <= T_out * skip and T_out.
+//
+// AUG (mdd_fbank_batch_aug): SpecAugment's masks (AA/utils/tools.py:229-255) on the utterance's own [T_raw, 81] matrix, after CMVN and
+// before the stacking, where SpeechDataset.__getitem__ applies them (AA/utils/data_loader.py:132-137).  The wave holds the frame's 81
+// columns in registers, so a mask is a few compares in front of the stores: a masked value becomes +0.0f in every slot that reads it,
+// the edge repeats of the last frame included.  The spans only ever predicate; no device value reaches an address.  The instantiation
+// without AUG never reads `mk` and is mdd_fbank_batch's kernel as it was.
+struct FbankMasks {
+    const int32_t *f, *t;      // [B, nf, 2] column spans and [B, nt, 2] raw-frame spans, (start, width) each
+    int nf, nt;
+};
+
+// Is x inside span (start, width) cut to [0, limit)?  width <= 0 is empty; the end is summed in 64 bits.
+__device__ __forceinline__ bool fbank_in_span(int x, int start, int width, int limit) {
+    if (width <= 0) return false;
+    const int64_t lo = start > 0 ? start : 0;
+    int64_t hi = (int64_t)start + (int64_t)width;
+    if (hi > limit) hi = limit;
+    return (int64_t)x >= lo && (int64_t)x < hi;
+}
+
+template <bool AUG>
 __global__ __launch_bounds__(256) void fbank_batch_kernel(const float *__restrict__ wav, const int64_t *__restrict__ offsets,
                                                           int T_out, FbankTables tb, const float *__restrict__ cscale,
                                                           const float *__restrict__ coffset, int right, int skip,
-                                                          float *__restrict__ out) {
+                                                          float *__restrict__ out, FbankMasks mk) {
     __shared__ float2 buf[4][FB_P];
     __shared__ float raw[4][FB_N];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -156,6 +180,23 @@ __global__ __launch_bounds__(256) void fbank_batch_kernel(const float *__restric
     if (s >= T_raw) return;                        // wave-uniform: waves never meet at a workgroup barrier
     float mel[2], energy;
     fbank_frame(wav + offsets[b] + (size_t)s * FB_S, tb, cscale, coffset, buf[wave], raw[wave], lane, mel, energy);
+    if (AUG) {
+        bool m0 = false, m1 = false, me = false;   // columns 1 + lane, 65 + lane and 0
+        for (int j = 0; j < mk.nt; j++) {
+            const int32_t *sp = mk.t + ((size_t)b * mk.nt + j) * 2;
+            if (fbank_in_span(s, sp[0], sp[1], T_raw)) m0 = m1 = me = true;
+        }
+        for (int j = 0; j < mk.nf; j++) {
+            const int32_t *sp = mk.f + ((size_t)b * mk.nf + j) * 2;
+            const int st = sp[0], wd = sp[1];
+            m0 |= fbank_in_span(1 + lane, st, wd, FB_D);
+            m1 |= fbank_in_span(65 + lane, st, wd, FB_D);
+            me |= fbank_in_span(0, st, wd, FB_D);
+        }
+        if (m0) mel[0] = 0.f;
+        if (m1) mel[1] = 0.f;
+        if (me) energy = 0.f;
+    }
     for (int r = 0; r <= right; r++) {
         // rows i with i * skip + r == s, or, for the last frame, every i * skip + r >= s (the edge repeat)
         int i0, i1;
@@ -169,6 +210,67 @@ __global__ __launch_bounds__(256) void fbank_batch_kernel(const float *__restric
         if (i1 >= T_out) i1 = T_out - 1;           // a T_out below the batch's stack length loses rows, never writes past them
         for (int i = i0; i <= i1; i++) fbank_store_row(ub + (size_t)i * W + r * FB_D, lane, mel, energy);
     }
+}
+
+// Global CMVN statistics (Kaldi's compute-cmvn-stats, which AA/steps/make_feat.sh:24-39 runs over the training set): the sums and
+// sums of squares of the un-normalised rows.  Workgroup (x, b) walks the strip of CMVN_STRIP raw frames starting at x * CMVN_STRIP of
+// utterance b; wave w takes frames w, w + 4, ... of the strip in rising order and keeps per-lane fp64 running sums (lane l: column
+// 1 + l; lanes < 16 also column 65 + l; lane 0 also column 0).  The four waves meet at ONE workgroup barrier, so no wave returns early:
+// the frame work is predicated (wave-uniform) and every wave reaches the barrier.  Their sums are added through LDS in wave order
+// into one partial [2, 82] per workgroup; cmvn_reduce_kernel adds the partials to the statistics in index order.  No atomics: the
+// same inputs give the same bits on every call.
+constexpr int CMVN_STRIP = 64, CMVN_N = 2 * (FB_D + 1);
+
+__global__ __launch_bounds__(256) void cmvn_partial_kernel(const float *__restrict__ wav, const int64_t *__restrict__ offsets,
+                                                           FbankTables tb, double *__restrict__ part) {
+    __shared__ float2 buf[4][FB_P];
+    __shared__ float raw[4][FB_N];
+    __shared__ double red[4][CMVN_N];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int b = blockIdx.y, strip0 = blockIdx.x * CMVN_STRIP;
+    const int64_t n = offsets[b + 1] - offsets[b];
+    const int64_t frames = n < FB_N ? 0 : 1 + (n - FB_N) / FB_S;
+    const int T_raw = frames > INT32_MAX ? INT32_MAX : (int)frames;
+    double s0 = 0.0, q0 = 0.0, s1 = 0.0, q1 = 0.0, se = 0.0, qe = 0.0;
+    for (int k = wave; k < CMVN_STRIP; k += 4) {
+        const int f = strip0 + k;
+        if (f < T_raw) {                           // wave-uniform; the wave goes on to the barrier either way
+            float mel[2], energy;
+            fbank_frame(wav + offsets[b] + (size_t)f * FB_S, tb, nullptr, nullptr, buf[wave], raw[wave], lane, mel, energy);
+            const double a = (double)mel[0], c = (double)mel[1], e = (double)energy;
+            s0 += a; q0 += a * a;
+            s1 += c; q1 += c * c;
+            se += e; qe += e * e;
+            FB_WAVE_SYNC();                        // the next frame overwrites the scratch this one's mel sums read
+        }
+    }
+    red[wave][1 + lane] = s0;
+    red[wave][FB_D + 1 + 1 + lane] = q0;
+    if (lane < FB_BINS - 64) { red[wave][65 + lane] = s1; red[wave][FB_D + 1 + 65 + lane] = q1; }
+    if (lane == 0) {
+        red[wave][0] = se;
+        red[wave][FB_D + 1] = qe;
+        red[wave][FB_D] = 0.0;                     // the count is set below, once per workgroup
+        red[wave][CMVN_N - 1] = 0.0;
+    }
+    __syncthreads();
+    const int idx = threadIdx.x;
+    if (idx < CMVN_N) {
+        double acc = ((red[0][idx] + red[1][idx]) + red[2][idx]) + red[3][idx];
+        if (idx == FB_D) {
+            const int left = T_raw - strip0;
+            acc = (double)(left <= 0 ? 0 : (left < CMVN_STRIP ? left : CMVN_STRIP));
+        }
+        part[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * CMVN_N + idx] = acc;
+    }
+}
+
+__global__ __launch_bounds__(256) void cmvn_reduce_kernel(const double *__restrict__ part, int64_t parts, double *__restrict__ stats) {
+    const int idx = threadIdx.x;
+    if (idx >= CMVN_N) return;
+    double acc = stats[idx];
+    for (int64_t p = 0; p < parts; p++) acc += part[p * CMVN_N + idx];
+    stats[idx] = acc;
 }
 
 static std::mutex g_fb_mutex;
@@ -268,25 +370,82 @@ extern "C" int32_t mdd_fbank_batch_len(const int64_t *n_samples, int32_t B, int3
     return t_out;
 }
 
-extern "C" int mdd_fbank_batch(const float *wav_dev, const int64_t *offsets_dev, int32_t B, int32_t T_out,
-                               const float *cmvn_scale_dev, const float *cmvn_offset_dev, int32_t right, int32_t skip,
-                               int32_t n_down, float *out_dev, void *stream) {
+// mdd_fbank_batch and mdd_fbank_batch_aug: one set of refusals, one launch; `mk` null launches the kernel without the masks
+static int fbank_batch_entry(const char *entry, const float *wav_dev, const int64_t *offsets_dev, int32_t B, int32_t T_out,
+                             const float *cmvn_scale_dev, const float *cmvn_offset_dev, int32_t right, int32_t skip, int32_t n_down,
+                             float *out_dev, const FbankMasks *mk, void *stream) {
     if (B <= 0 || T_out < 0 || right < 0 || skip < 1 || n_down < 1 ||
         ((cmvn_scale_dev == nullptr) != (cmvn_offset_dev == nullptr))) {
-        set_error("mdd_fbank_batch: bad argument (B=%d T_out=%d right=%d skip=%d n_down=%d, cmvn pointers must come as a pair)",
+        set_error("%s: bad argument (B=%d T_out=%d right=%d skip=%d n_down=%d, cmvn pointers must come as a pair)", entry,
                   B, T_out, right, skip, n_down);
         return MDD_ERR_ARG;
     }
+    if (mk) {
+        if (mk->nf < 0 || mk->nf > 8 || mk->nt < 0 || mk->nt > 8) {
+            set_error("%s: bad argument (NF=%d NT=%d, each must lie in 0..8)", entry, mk->nf, mk->nt);
+            return MDD_ERR_ARG;
+        }
+        if ((mk->nf > 0 && !mk->f) || (mk->nt > 0 && !mk->t)) {
+            set_error("%s: null %s with %s > 0", entry, mk->nf > 0 && !mk->f ? "fmask_dev" : "tmask_dev",
+                      mk->nf > 0 && !mk->f ? "NF" : "NT");
+            return MDD_ERR_ARG;
+        }
+    }
     if (T_out == 0) return MDD_OK;
-    if (!wav_dev || !offsets_dev || !out_dev) { set_error("mdd_fbank_batch: null buffer"); return MDD_ERR_ARG; }
-    if ((int64_t)T_out * skip > INT32_MAX - 4 || B > 65535) { set_error("mdd_fbank_batch: batch too large"); return MDD_ERR_ARG; }
+    if (!wav_dev || !offsets_dev || !out_dev) { set_error("%s: null buffer", entry); return MDD_ERR_ARG; }
+    if ((int64_t)T_out * skip > INT32_MAX - 4 || B > 65535) { set_error("%s: batch too large", entry); return MDD_ERR_ARG; }
     int dev = 0;
     MDD_HIP_CHECK(hipGetDevice(&dev));
     FbankTables tb;
     if (int rc = fbank_tables(dev, &tb)) return rc;
     const int rows = T_out * skip > T_out ? T_out * skip : T_out;   // covers every raw frame (T_raw_b <= T_out * skip) and row
-    hipLaunchKernelGGL(fbank_batch_kernel, dim3((rows + 3) / 4, B), dim3(256), 0, (hipStream_t)stream, wav_dev, offsets_dev,
-                       T_out, tb, cmvn_scale_dev, cmvn_offset_dev, right, skip, out_dev);
+    if (mk)
+        hipLaunchKernelGGL(fbank_batch_kernel<true>, dim3((rows + 3) / 4, B), dim3(256), 0, (hipStream_t)stream, wav_dev, offsets_dev,
+                           T_out, tb, cmvn_scale_dev, cmvn_offset_dev, right, skip, out_dev, *mk);
+    else
+        hipLaunchKernelGGL(fbank_batch_kernel<false>, dim3((rows + 3) / 4, B), dim3(256), 0, (hipStream_t)stream, wav_dev, offsets_dev,
+                           T_out, tb, cmvn_scale_dev, cmvn_offset_dev, right, skip, out_dev, FbankMasks{nullptr, nullptr, 0, 0});
+    MDD_LAUNCH_CHECK();
+    return MDD_OK;
+}
+
+extern "C" int mdd_fbank_batch(const float *wav_dev, const int64_t *offsets_dev, int32_t B, int32_t T_out,
+                               const float *cmvn_scale_dev, const float *cmvn_offset_dev, int32_t right, int32_t skip,
+                               int32_t n_down, float *out_dev, void *stream) {
+    return fbank_batch_entry("mdd_fbank_batch", wav_dev, offsets_dev, B, T_out, cmvn_scale_dev, cmvn_offset_dev, right, skip, n_down,
+                             out_dev, nullptr, stream);
+}
+
+extern "C" int mdd_fbank_batch_aug(const float *wav_dev, const int64_t *offsets_dev, int32_t B, int32_t T_out,
+                                   const float *cmvn_scale_dev, const float *cmvn_offset_dev, int32_t right, int32_t skip,
+                                   int32_t n_down, float *out_dev, const int32_t *fmask_dev, int32_t NF, const int32_t *tmask_dev,
+                                   int32_t NT, void *stream) {
+    const FbankMasks mk{fmask_dev, tmask_dev, NF, NT};
+    return fbank_batch_entry("mdd_fbank_batch_aug", wav_dev, offsets_dev, B, T_out, cmvn_scale_dev, cmvn_offset_dev, right, skip,
+                             n_down, out_dev, &mk, stream);
+}
+
+extern "C" int mdd_cmvn_accumulate(const float *wav_dev, const int64_t *offsets_dev, int32_t B, int64_t max_samples, double *stats_dev,
+                                   void *stream) {
+    if (B <= 0 || B > 65535 || max_samples < 0) {
+        set_error("mdd_cmvn_accumulate: bad argument (B=%d, 1..65535; max_samples=%lld)", B, (long long)max_samples);
+        return MDD_ERR_ARG;
+    }
+    if (!wav_dev || !offsets_dev || !stats_dev) { set_error("mdd_cmvn_accumulate: null buffer"); return MDD_ERR_ARG; }
+    const int64_t frames = max_samples < FB_N ? 0 : 1 + (max_samples - FB_N) / FB_S;
+    if (frames > INT32_MAX - CMVN_STRIP) { set_error("mdd_cmvn_accumulate: max_samples too large"); return MDD_ERR_ARG; }
+    if (frames == 0) return MDD_OK;                                    // nothing reaches one window: nothing to add
+    int dev = 0;
+    MDD_HIP_CHECK(hipGetDevice(&dev));
+    FbankTables tb;
+    if (int rc = fbank_tables(dev, &tb)) return rc;
+    const int strips = (int)((frames + CMVN_STRIP - 1) / CMVN_STRIP);
+    const int64_t parts = (int64_t)strips * B;
+    StreamWorkspace ws;
+    if (int rc = ws.acquire(nullptr, parts * CMVN_N * (int64_t)sizeof(double), (hipStream_t)stream)) return rc;
+    hipLaunchKernelGGL(cmvn_partial_kernel, dim3(strips, B), dim3(256), 0, (hipStream_t)stream, wav_dev, offsets_dev, tb, ws.as<double>());
+    MDD_LAUNCH_CHECK();
+    hipLaunchKernelGGL(cmvn_reduce_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, ws.as<double>(), parts, stats_dev);
     MDD_LAUNCH_CHECK();
     return MDD_OK;
 }

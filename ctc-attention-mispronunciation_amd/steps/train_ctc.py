@@ -9,9 +9,14 @@
   ``end_adjust_acc``) resets the patience; ten epochs inside the band, or one outside it, restore the best state, multiply the rate
   by ``decay`` and count an adjustment; eight adjustments stop training.
 * ``build_training(...)``  model + ``CTCLoss(reduction='sum')`` + ``Adam(lr, weight_decay)`` as :184-187 wires them.
+* ``main(conf)`` (:111-291) and ``python -m ctc_attention_mispronunciation_amd.steps.train_ctc --conf CONF``: the program -- seeds, data (the
+  reference's ark route, or WAVs through ``TrainWavLoader`` with the CMVN statistics computed on the GPU if the file is absent), model from
+  the conf, epoch loop, ``ctc_best_model.pkl``.
 The arithmetic of every step runs in libmdd_hip (train.py); this file is host control flow only.
 """
 import copy
+import os
+import sys
 
 import torch
 
@@ -127,6 +132,7 @@ class LrSchedule(object):
         self.adjust_rate_count = 0
         self.acc_best = 0
         self.model_state = self.op_state = self.best_model_state = self.best_op_state = None
+        self.printed_count = self.printed_time = 0     # what train_ctc.py:256 prints: the counters before an adjustment resets them
 
     def begin_epoch(self):
         if self.stop_train or self.count >= self.num_epoches:
@@ -157,6 +163,7 @@ class LrSchedule(object):
         if acc > self.acc_best:
             self.acc_best = acc
             self.best_model_state, self.best_op_state = self._snapshot()
+        self.printed_count, self.printed_time = self.adjust_rate_count, self.adjust_time
         if self.adjust_rate_count == 10:
             self.adjust_rate_flag = True
             self.adjust_time += 1
@@ -178,3 +185,211 @@ class LrSchedule(object):
 def build_training(model, init_lr=1e-3, weight_decay=5e-4):
     """(loss_fn, optimizer) as train_ctc.py:186-187 creates them."""
     return CTCLoss(reduction='sum'), Adam(model.parameters(), lr=init_lr, weight_decay=weight_decay)
+
+
+# ---------------------------------------------------------------------------------------------------------------- the program
+SUPPORTED_RNN = ("nn.LSTM", "nn.GRU", "nn.RNN")
+SUPPORTED_ACTIVATE = ("relu", "tanh", "sigmoid")
+
+
+class Config(object):
+    batch_size = 4
+    dropout = 0.1
+
+
+def refuse(msg):
+    print(msg, file=sys.stderr)
+    sys.exit(2)
+
+
+def check_conf(conf):
+    """The data route of a conf -- "ark" (``train_scp_path`` / ``valid_scp_path``: Kaldi features somebody made, the reference's
+    route) or "wav" (``train_wav_scp`` / ``valid_wav_scp``: '<utt> <path.wav>' lines, the wav.scp of the reference's local/
+    scripts) -- or a refusal (status 2, one line on stderr) for a conf with neither pair, both, half of one, or a file that is
+    not there.  Before any data is read or the device is touched."""
+    ark = [k for k in ("train_scp_path", "valid_scp_path") if conf.get(k)]
+    wav = [k for k in ("train_wav_scp", "valid_wav_scp") if conf.get(k)]
+    if ark and wav:
+        refuse("conf names both data routes (%s and %s): keep the ark pair or the WAV pair" % (", ".join(ark), ", ".join(wav)))
+    if not ark and not wav:
+        refuse("conf names no training data: set train_scp_path / valid_scp_path (Kaldi features) or train_wav_scp / valid_wav_scp (WAVs)")
+    if len(ark or wav) != 2:
+        refuse("conf has %s without its partner: a route needs its train and its valid file" % (ark or wav)[0])
+    route = "wav" if wav else "ark"
+    needed = (ark or wav) + ["train_lab_path", "train_trans_path", "valid_lab_path", "valid_trans_path", "vocab_file"]
+    for k in needed:
+        if not conf.get(k):
+            refuse("conf lacks %s" % k)
+        if not os.path.isfile(conf[k]):
+            refuse("%s: no file at %s" % (k, conf[k]))
+    if route == "wav" and not conf.get("cmvn_path"):
+        refuse("the WAV route needs cmvn_path: the global CMVN statistics, computed from the training WAVs and written there if absent")
+    return route
+
+
+def read_table(path):
+    """'<key> <rest of line>' lines -> ordered (key, rest) pairs; keys as SpeechDataset reads them (cut at the first '.')."""
+    rows = []
+    with open(path, "r") as rf:
+        for line in rf:
+            if line.strip():
+                key, rest = line.strip().split(" ", 1)
+                rows.append((key.split(".")[0], rest.strip()))
+    return rows
+
+
+def wav_items(scp_path, lab_path, trans_path):
+    """TrainWavLoader items of one split: (utt, WAV path, canonical phones, annotated phones), in the scp's order."""
+    scp = read_table(scp_path)
+    labels, trans = (dict(read_table(p)) for p in (lab_path, trans_path))
+    for utt, _ in scp:
+        if utt not in labels or utt not in trans:
+            refuse("%s: no %s line for %s" % (scp_path, "label" if utt not in labels else "transcript", utt))
+    return [(utt, path, trans[utt], labels[utt]) for utt, path in scp]
+
+
+def wav_cmvn(items, path, batch_size):
+    """The (scale, offset) pair of the global CMVN file at ``path``; a file that is not there is first computed from the training
+    WAVs on the GPU (``fbank.cmvn_stats``) and written -- the compute-cmvn-stats step of AA/steps/make_feat.sh:24-39."""
+    from ..utils import fbank
+    if not os.path.exists(path):
+        def batches():
+            for start in range(0, len(items), batch_size):
+                read = [fbank.read_wav(it[1], with_format=True) for it in items[start:start + batch_size]]
+                wavs = [fbank.quantize_pcm16(x) if rate == fbank.SAMPLE_RATE and not pcm16 else x for x, rate, pcm16 in read]
+                if all(rate == fbank.SAMPLE_RATE for _, rate, _ in read):
+                    for w in wavs:
+                        yield w
+                else:
+                    yield fbank.resample_batch(wavs, [rate for _, rate, _ in read])
+        stats = fbank.cmvn_stats(batches(), batch_size=batch_size)
+        if os.path.dirname(path):
+            os.makedirs(os.path.dirname(path), exist_ok=True)
+        fbank.write_cmvn_stats(path, stats)
+        print("CMVN statistics of %d training utterances (%d frames) written to %s" % (len(items), int(stats[0, -1]), path))
+    return fbank.cmvn_scale_offset(fbank.read_cmvn_stats(path))
+
+
+def main(conf):
+    """AA/steps/train_ctc.py:111-291 over run_epoch / LrSchedule / build_training: seeds, Vocab, the two loaders, the model from the
+    conf's rnn_* and CNN keys, the epoch loop with the reference's printed lines, the best-accuracy state into
+    ``checkpoint_dir/exp_name/ctc_best_model.pkl`` -- the checkpoint ``infer.load_model`` reads.  New conf keys: ``train_wav_scp`` /
+    ``valid_wav_scp`` + ``cmvn_path`` (the WAV route, ``TrainWavLoader``), ``speed_perturb`` (a list of factors for it),
+    ``train_precision`` ("f32", "bf16x3" or "f32x6").  Every rank reads the whole data: sharding it is not built."""
+    route = check_conf(conf)
+    import ast
+    import time
+
+    import numpy as np
+    import torch.nn as nn
+    from ..models.model_ctc import CTC_Model
+    from ..utils.data_loader import SpeechDataLoader, SpeechDataset, TrainWavLoader, Vocab
+    opts = Config()
+    for k, v in conf.items():
+        setattr(opts, k, v)
+        print('{:50}:{}'.format(k, v))
+    if opts.rnn_type not in SUPPORTED_RNN or opts.activation_function not in SUPPORTED_ACTIVATE:
+        refuse("rnn_type must be one of %s and activation_function one of %s" % (SUPPORTED_RNN, SUPPORTED_ACTIVATE))
+    precision = getattr(opts, "train_precision", None)
+    if precision is not None and precision not in ("f32", "bf16x3", "f32x6"):
+        refuse("train_precision %r: f32, bf16x3 or f32x6" % (precision,))
+
+    device = torch.device('cuda:0') if opts.use_gpu else torch.device('cpu')
+    torch.manual_seed(opts.seed)
+    np.random.seed(opts.seed)
+    if opts.use_gpu:
+        torch.cuda.manual_seed(opts.seed)
+
+    vocab = Vocab(opts.vocab_file)
+    n_downsample = getattr(opts, "n_downsample", 2)
+    if route == "ark":
+        for k in ("train_scp_path", "train_lab_path", "train_trans_path", "valid_scp_path", "valid_lab_path", "valid_trans_path"):
+            print(getattr(opts, k))
+        train_dataset = SpeechDataset(vocab, opts.train_scp_path, opts.train_lab_path, opts.train_trans_path, opts, True)
+        dev_dataset = SpeechDataset(vocab, opts.valid_scp_path, opts.valid_lab_path, opts.valid_trans_path, opts)
+        train_loader = SpeechDataLoader(train_dataset, batch_size=opts.batch_size, shuffle=opts.shuffle_train, num_workers=opts.num_workers)
+        dev_loader = SpeechDataLoader(dev_dataset, batch_size=opts.batch_size, shuffle=False, num_workers=opts.num_workers)
+    else:
+        for k in ("train_wav_scp", "train_lab_path", "train_trans_path", "valid_wav_scp", "valid_lab_path", "valid_trans_path"):
+            print(getattr(opts, k))
+        if getattr(opts, "left_ctx", 0) != 0:
+            refuse("the WAV route stacks right context only (left_ctx: 0, as every conf of the reference has it)")
+        train_items = wav_items(opts.train_wav_scp, opts.train_lab_path, opts.train_trans_path)
+        dev_items = wav_items(opts.valid_wav_scp, opts.valid_lab_path, opts.valid_trans_path)
+        cmvn = wav_cmvn(train_items, opts.cmvn_path, opts.batch_size)
+        geometry = dict(cmvn=cmvn, right_ctx=opts.right_ctx, n_skip_frame=opts.n_skip_frame, n_downsample=n_downsample)
+        train_loader = TrainWavLoader(train_items, vocab, opts.batch_size, train=True, shuffle=opts.shuffle_train,
+                                      speeds=getattr(opts, "speed_perturb", None), **geometry)
+        dev_loader = TrainWavLoader(dev_items, vocab, opts.batch_size, train=False, shuffle=False, **geometry)
+
+    rnn_type = getattr(nn, opts.rnn_type.split(".", 1)[1])
+    rnn_param = {"rnn_input_size": opts.rnn_input_size, "rnn_hidden_size": opts.rnn_hidden_size, "rnn_layers": opts.rnn_layers,
+                 "rnn_type": rnn_type, "bidirectional": opts.bidirectional, "batch_norm": opts.batch_norm}
+    num_class = vocab.n_words
+    opts.output_class_dim = vocab.n_words
+    channel, kernel_size, stride, padding, pooling = (ast.literal_eval(getattr(opts, k)) for k in
+                                                      ("channel", "kernel_size", "stride", "padding", "pooling"))
+    activation = {"relu": nn.ReLU, "tanh": nn.Tanh, "sigmoid": nn.Sigmoid}[opts.activation_function]
+    cnn_param = {"batch_norm": opts.batch_norm, "activate_function": activation,
+                 "layer": [[channel[n], kernel_size[n], stride[n], padding[n], pooling[n] if pooling is not None else None]
+                           for n in range(opts.layers)]}
+    model = CTC_Model(add_cnn=opts.add_cnn, cnn_param=cnn_param, rnn_param=rnn_param, num_class=num_class, drop_out=opts.drop_out)
+    model = model.to(device)
+    if precision is not None:
+        model.train_precision = precision
+    print("Number of parameters %d" % sum(p.numel() for p in model.parameters()))
+    for idx, m in enumerate(model.children()):
+        print(idx, m)
+
+    params = {'num_epoches': opts.num_epoches, 'end_adjust_acc': opts.end_adjust_acc, 'mel': opts.mel, 'seed': opts.seed,
+              'decay': opts.lr_decay, 'learning_rate': opts.init_lr, 'weight_decay': opts.weight_decay, 'batch_size': opts.batch_size,
+              'feature_type': opts.feature_type, 'n_feats': opts.feature_dim}
+    print(params)
+    loss_fn, optimizer = build_training(model, init_lr=opts.init_lr, weight_decay=opts.weight_decay)
+    schedule = LrSchedule(model, optimizer, opts.init_lr, opts.lr_decay, opts.end_adjust_acc, opts.num_epoches)
+    start_time = time.time()
+    loss_results, dev_loss_results, dev_cer_results = [], [], []
+    while schedule.begin_epoch():
+        count = schedule.count
+        print("Start training epoch: %d, learning_rate: %.5f" % (count, schedule.learning_rate))
+        _, loss = run_epoch(count, model, train_loader, loss_fn, device, optimizer=optimizer, print_every=opts.verbose_step, is_training=True)
+        loss_results.append(loss)
+        acc, dev_loss = run_epoch(count, model, dev_loader, loss_fn, device, optimizer=None, print_every=opts.verbose_step, is_training=False)
+        dev_loss_results.append(dev_loss)
+        dev_cer_results.append(acc)
+        schedule.end_epoch(acc, dev_loss)
+        print("adjust_rate_count:" + str(schedule.printed_count) + ' adjust_time:' + str(schedule.printed_time))
+        print("epoch %d done, cv acc is: %.4f, time_used: %.4f minutes" % (count, acc, (time.time() - start_time) / 60))
+        print('dev loss:', dev_loss, 'loss_best:', schedule.loss_best)
+        print('\n')
+    print("End training, best dev loss is: %.4f, acc is: %.4f" % (schedule.loss_best, schedule.acc_best))
+    schedule.finish()
+    save_dir = os.path.join(opts.checkpoint_dir, opts.exp_name)
+    os.makedirs(save_dir, exist_ok=True)
+    best_path = os.path.join(save_dir, 'ctc_best_model.pkl')
+    params['epoch'] = schedule.count
+    torch.save(CTC_Model.save_package(model, optimizer=optimizer, epoch=params, loss_results=loss_results, dev_loss_results=dev_loss_results,
+                                      dev_cer_results=dev_cer_results), best_path)
+    return best_path
+
+
+def cli(argv=None):
+    import argparse
+    ap = argparse.ArgumentParser(description="train the CNN + BiLSTM + attention CTC model on the MI355X path")
+    ap.add_argument("--conf", default="conf/ctc_config.yaml", help="conf file with the arguments of the model and the training")
+    args = ap.parse_args(argv)
+    import yaml
+    try:
+        with open(args.conf, "r") as f:
+            conf = yaml.safe_load(f)
+    except (OSError, yaml.YAMLError):
+        print("No input config or config file missing, please check.")
+        sys.exit(1)
+    if not isinstance(conf, dict):
+        refuse("%s: not a mapping of conf keys" % args.conf)
+    main(conf)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(cli())

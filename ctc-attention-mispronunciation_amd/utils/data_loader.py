@@ -3,6 +3,8 @@ reference (AA/utils/data_loader.py) for the parts the path needs: ``Vocab`` (uni
 blank = 0, UNK = 1; :13-52), the context-stack / frame-skip / even-pad of one utterance (:138-142,
 done on the GPU by mdd_stack_skip) and the zero-padding collate with its float32 length fractions
 (``create_input``, :151-181).  Reading Kaldi ark files is upstream of the path.
+``WavBatchLoader`` (inference) and ``TrainWavLoader`` (training, with the reference's augmentation) build the same batches
+straight from WAVs on the GPU.
 """
 import numpy as np
 import torch
@@ -199,3 +201,103 @@ class WavBatchLoader(object):
             trans, trans_sizes = self._collate_ids([it[2] for it in chunk])
             batch = (inputs, input_sizes, trans.clone(), trans_sizes.clone(), trans, trans_sizes, [it[0] for it in chunk])
             yield batch + (self.candidate_sets(chunk),) if self.pronunciations else batch
+
+
+def speed_rate(rate, speed):
+    """The rate an utterance recorded at ``rate`` Hz is declared to have so that resampling it to 16 kHz plays it ``speed`` times
+    as fast (Kaldi-style speed perturbation on the existing resampler): int(round(rate * speed))."""
+    return int(round(rate * speed))
+
+
+class TrainWavLoader(object):
+    """Training (and validation) batches straight from WAVs, in the shape and order of ``SpeechDataLoader(SpeechDataset(...,
+    train), batch_size, shuffle, num_workers=0)`` as AA/steps/train_ctc.py:131-134 builds them -- the features never exist on
+    the host: fbank, CMVN, SpecAugment, context stack, frame skip and padding of a batch are one kernel launch
+    (``fbank.fbank_batch``; any rate other than 16 kHz first goes through ``fbank.resample_batch``).
+
+    ``items``: (utt, samples [int16 scale] or the path of a WAV, canonical phones, annotated phones[, sample rate, default 16000]);
+    phones are space-separated strings (or lists of names).  A path is read with ``read_wav`` when its batch is formed (its rate
+    comes from the file; a 16 kHz file that is not 16-bit PCM is quantised as ``infer.collect`` does).  Each batch is the
+    reference's 7-tuple (inputs, input_sizes, labels, label_sizes, trans, trans_sizes, utt_list) with the annotated phones as the
+    labels; ids are looked up as SpeechDataset does (unknown -> 'UNK') and padded as create_input pads them.
+
+    Order: torch's own samplers behind a DataLoader over the item indices (RandomSampler or SequentialSampler + BatchSampler, the
+    last batch kept), so under one ``torch.manual_seed`` the batches are SpeechDataLoader's.  With ``train=True`` every item gets,
+    in batch order, the draws ``tools.augment_item`` makes for it: ``draw_spec_augment(T_raw, 81)`` -- T_raw from the length the
+    host already knows -- then ``data_enhancement`` on every canonical id; the spans are applied by the kernel.  ``speeds`` (train
+    only), e.g. (0.9, 1.0, 1.1): one factor per item by ``random.choice``, before that item's other draws; an item at rate r and
+    speed s is declared to be at ``speed_rate(r, s)`` Hz, so the resampler stretches it, and its T_raw follows ``resample_len``.
+    A batch whose declared rates are all 16000 skips the resampler.
+
+    All GPU work goes onto the current stream: no side stream, no thread that launches kernels.  The bf16x3 training step runs
+    persistent layer kernels whose workgroups wait on each other; a front-end kernel running beside them could keep one of their
+    workgroups off the chip."""
+
+    def __init__(self, items, vocab, batch_size, cmvn=None, right_ctx=2, n_skip_frame=2, n_downsample=2, train=False, shuffle=False,
+                 speeds=None):
+        self.items = list(items)
+        self.vocab = vocab
+        self.batch_size = int(batch_size)
+        self.cmvn = cmvn
+        self.right_ctx, self.n_skip_frame, self.n_downsample = right_ctx, n_skip_frame, n_downsample
+        self.train = bool(train)
+        self.speeds = list(speeds) if speeds else None
+        self._index_batches = DataLoader(range(len(self.items)), batch_size=self.batch_size, shuffle=bool(shuffle), num_workers=0,
+                                         collate_fn=list)
+
+    def __len__(self):
+        return len(self._index_batches)
+
+    def _ids(self, phones):
+        unk = self.vocab.word2index["UNK"]
+        return [self.vocab.word2index.get(c, unk) for c in (phones.split() if isinstance(phones, str) else phones)]
+
+    @staticmethod
+    def _pad(rows):
+        n_max = max(len(r) for r in rows)
+        ids, sizes = torch.zeros(len(rows), n_max), torch.zeros(len(rows))
+        for i, r in enumerate(rows):
+            ids[i, :len(r)] = torch.tensor(r, dtype=torch.float32)
+            sizes[i] = len(r)
+        return ids.long(), sizes.long()
+
+    def __iter__(self):
+        import random
+        from .fbank import NUM_COLS, SAMPLE_RATE, fbank_batch, quantize_pcm16, read_wav, resample_batch, resample_len
+        from .tools import data_enhancement, draw_spec_augment
+        L = _lib.lib()
+        for index in self._index_batches:
+            wavs, rates, labels, trans, utts, fmask, tmask = [], [], [], [], [], [], []
+            for k in index:
+                it = self.items[int(k)]
+                samples, rate = it[1], int(it[4]) if len(it) > 4 else SAMPLE_RATE
+                if isinstance(samples, (str, bytes)) or hasattr(samples, "__fspath__"):
+                    samples, rate, pcm16 = read_wav(samples, with_format=True)
+                    if rate == SAMPLE_RATE and not pcm16:
+                        samples = quantize_pcm16(samples)
+                n = samples.numel() if torch.is_tensor(samples) else np.asarray(samples).size
+                can = self._ids(it[2])
+                if self.train:
+                    if self.speeds:
+                        rate = speed_rate(rate, random.choice(self.speeds))
+                    t_raw = L.mdd_fbank_num_frames(resample_len(n, rate))
+                    if t_raw == 0:
+                        raise ValueError("TrainWavLoader: %s is shorter than one 400-sample window at 16 kHz" % it[0])
+                    fs, ts = draw_spec_augment(t_raw, NUM_COLS)
+                    fmask.append(fs)
+                    tmask.append(ts)
+                    can = sum([data_enhancement(t) for t in can], [])
+                wavs.append(samples)
+                rates.append(rate)
+                labels.append(self._ids(it[3]))
+                trans.append(can)
+                utts.append(it[0])
+            kw = dict(cmvn=self.cmvn, right_ctx=self.right_ctx, n_skip_frame=self.n_skip_frame, n_downsample=self.n_downsample)
+            if self.train:
+                kw.update(fmask=fmask, tmask=tmask)
+            if all(r == SAMPLE_RATE for r in rates):
+                inputs, input_sizes = fbank_batch(wavs, **kw)
+            else:
+                wav, offsets = resample_batch(wavs, rates)
+                inputs, input_sizes = fbank_batch(wav, offsets=offsets, **kw)
+            yield (inputs, input_sizes) + self._pad(labels) + self._pad(trans) + (utts,)

@@ -90,6 +90,18 @@ def read_cmvn_stats(path):
     return np.array([[float(v) for v in r] for r in rows], dtype=np.float64)
 
 
+def write_cmvn_stats(path, stats):
+    """float64 [2, D+1] -> the Kaldi text matrix ``read_cmvn_stats`` reads (`` [`` / two rows / `` ]``), every value with 17
+    significant digits, so that reading it back gives the same float64 bits."""
+    stats = np.asarray(stats, dtype=np.float64)
+    if stats.ndim != 2 or stats.shape[0] != 2:
+        raise ValueError("write_cmvn_stats: expected a [2, D+1] matrix, got %s" % (stats.shape,))
+    with open(path, "w") as f:
+        f.write(" [\n")
+        for r, row in enumerate(stats):
+            f.write("  " + " ".join("%.17g" % v for v in row) + (" ]\n" if r == 1 else "\n"))
+
+
 def cmvn_scale_offset(stats, norm_vars=True):
     """(scale, offset) float32 vectors of ``apply-cmvn`` with global stats: out = feat * scale + offset."""
     D = stats.shape[1] - 1
@@ -172,7 +184,25 @@ def load_mat(spec):
         return np.frombuffer(f.read(4 * rows * cols), dtype="<f4").reshape(rows, cols).copy()
 
 
-def fbank_batch(wavs, cmvn=None, right_ctx=2, n_skip_frame=2, n_downsample=2, out=None, offsets=None):
+MAX_MASKS = 8                    # spans per utterance and kind that mdd_fbank_batch_aug takes
+CMVN_STRIP = 64                  # raw frames one workgroup of the statistics kernel walks (csrc/fbank.hip)
+
+
+def _span_table(spans, B, name):
+    """Per-utterance (start, width) lists (or an int array [B, N, 2]) -> int32 [B, N, 2], short lists padded with empty spans."""
+    rows = [np.asarray(r, dtype=np.int64).reshape(-1, 2) for r in spans]
+    if len(rows) != B:
+        raise ValueError("fbank_batch: %s has %d entries for %d utterances" % (name, len(rows), B))
+    N = max([r.shape[0] for r in rows] + [0])
+    if N > MAX_MASKS:
+        raise ValueError("fbank_batch: %s holds %d spans for one utterance, at most %d" % (name, N, MAX_MASKS))
+    table = np.zeros((B, N, 2), dtype=np.int64)
+    for b, r in enumerate(rows):
+        table[b, :r.shape[0]] = r
+    return np.clip(table, -2 ** 31, 2 ** 31 - 1).astype(np.int32)      # (the kernel cuts spans to the matrix anyway)
+
+
+def fbank_batch(wavs, cmvn=None, right_ctx=2, n_skip_frame=2, n_downsample=2, out=None, offsets=None, fmask=None, tmask=None):
     """B utterances -> the padded model input the reference's infer.py batches from them, in one kernel launch (mdd_fbank_batch):
     fbank + CMVN per utterance, make_context(., 0, right_ctx) + skip_feat(., n_skip_frame) + zero rows up to a multiple of
     n_downsample (AA/utils/data_loader.py:138-142), zero-padded to the longest (create_input, :151-181).
@@ -183,7 +213,11 @@ def fbank_batch(wavs, cmvn=None, right_ctx=2, n_skip_frame=2, n_downsample=2, ou
     ``compute_fbank_feats`` of that utterance.  ``out`` (optional) is written whole, padding included.
 
     With ``offsets`` ([B+1] int64, host), ``wavs`` is instead one 1-D float32 CUDA tensor holding the B utterances back to back,
-    utterance b at [offsets[b], offsets[b+1]) -- what ``resample_batch`` returns; the samples stay on the device."""
+    utterance b at [offsets[b], offsets[b+1]) -- what ``resample_batch`` returns; the samples stay on the device.
+
+    ``fmask`` / ``tmask`` (train time; both None: the call above, through mdd_fbank_batch): per utterance a list of (start, width)
+    spans, as ``tools.draw_spec_augment`` returns them -- columns and raw frames of the utterance's own [T_raw, 81] matrix that are
+    zeroed after CMVN and before the stacking, where SpeechDataset applies ``spec_augment`` (mdd_fbank_batch_aug, same launch)."""
     if offsets is not None:
         offsets = np.asarray(offsets.cpu().numpy() if torch.is_tensor(offsets) else offsets, dtype=np.int64).reshape(-1)
         if not (torch.is_tensor(wavs) and wavs.is_cuda and wavs.dtype == torch.float32 and wavs.dim() == 1):
@@ -197,6 +231,9 @@ def fbank_batch(wavs, cmvn=None, right_ctx=2, n_skip_frame=2, n_downsample=2, ou
         host = [np.asarray(w.detach().cpu().numpy() if torch.is_tensor(w) else w, dtype=np.float32).reshape(-1) for w in wavs]
         n = np.array([h.size for h in host], dtype=np.int64)
     B = len(n)
+    if fmask is not None or tmask is not None:
+        ft = _span_table(fmask if fmask is not None else [[]] * B, B, "fmask")
+        tt = _span_table(tmask if tmask is not None else [[]] * B, B, "tmask")
     L = _lib.lib()
     t_out = L.mdd_fbank_batch_len(n.ctypes.data_as(C.POINTER(C.c_int64)), B, n_skip_frame, n_downsample)
     if t_out < 0:
@@ -224,13 +261,67 @@ def fbank_batch(wavs, cmvn=None, right_ctx=2, n_skip_frame=2, n_downsample=2, ou
         of = torch.as_tensor(cmvn[1]).to(dev, torch.float32).contiguous()
         if sc.numel() != NUM_COLS or of.numel() != NUM_COLS:
             raise ValueError("cmvn vectors must have %d entries" % NUM_COLS)
-    _lib.check(L.mdd_fbank_batch(_lib.ptr(wav), _lib.ptr(off), B, t_out, _lib.ptr(sc), _lib.ptr(of), right_ctx, n_skip_frame, n_downsample,
-                                 _lib.ptr(out), _lib.current_stream_ptr()))
+    if fmask is None and tmask is None:
+        _lib.check(L.mdd_fbank_batch(_lib.ptr(wav), _lib.ptr(off), B, t_out, _lib.ptr(sc), _lib.ptr(of), right_ctx, n_skip_frame, n_downsample,
+                                     _lib.ptr(out), _lib.current_stream_ptr()))
+    else:
+        spans = torch.from_numpy(np.concatenate([ft.reshape(-1), tt.reshape(-1)])).to(dev)     # one copy for both tables
+        fd = spans[:ft.size] if ft.size else None
+        td = spans[ft.size:] if tt.size else None
+        _lib.check(L.mdd_fbank_batch_aug(_lib.ptr(wav), _lib.ptr(off), B, t_out, _lib.ptr(sc), _lib.ptr(of), right_ctx, n_skip_frame,
+                                         n_downsample, _lib.ptr(out), _lib.ptr(fd), ft.shape[1], _lib.ptr(td), tt.shape[1],
+                                         _lib.current_stream_ptr()))
     lens = [L.mdd_stack_len(L.mdd_fbank_num_frames(int(k)), n_skip_frame, n_downsample) for k in n]
     sizes = torch.zeros(B)
     for b in range(B):
         sizes[b] = lens[b] / t_out          # a Python true division stored into float32, as create_input does (:177)
     return out, sizes
+
+
+def cmvn_stats(wavs_or_batches, batch_size=32, stats=None):
+    """Global CMVN statistics of a set of utterances on the GPU (mdd_cmvn_accumulate) -- Kaldi's ``compute-cmvn-stats`` over the
+    un-normalised fbank rows, which the reference runs once over its training set (AA/steps/make_feat.sh:24-39): float64 [2, 82],
+    row 0 the column sums and the frame count, row 1 the sums of squares and 0; ``cmvn_scale_offset`` takes it, ``write_cmvn_stats``
+    stores it.
+
+    ``wavs_or_batches``: an iterable (a generator will do) whose entries are 16 kHz utterances (1-D sample arrays / tensors on the
+    int16 scale; gathered ``batch_size`` to a launch) and / or whole batches ``(samples, offsets)`` as ``resample_batch`` returns
+    them, the samples on the device.  ``stats``: earlier statistics to go on from.  An utterance shorter than one window adds nothing.
+    The sums are fp64 in a fixed order: the same utterances in the same order and batches give the same bits."""
+    _lib.require_gpu()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    acc = torch.zeros((2, NUM_COLS + 1), dtype=torch.float64, device=dev)
+    if stats is not None:
+        acc.copy_(torch.as_tensor(np.asarray(stats, dtype=np.float64).reshape(2, NUM_COLS + 1)))
+
+    def add(wav, offsets):
+        n = np.diff(offsets)
+        if n.size == 0 or offsets[0] != 0 or np.any(n < 0) or offsets[-1] > wav.numel():
+            raise ValueError("cmvn_stats: offsets must rise from 0 to at most %d" % wav.numel())
+        off = torch.from_numpy(offsets).to(dev)
+        _lib.check(_lib.lib().mdd_cmvn_accumulate(_lib.ptr(wav), _lib.ptr(off), len(n), int(n.max()), _lib.ptr(acc), _lib.current_stream_ptr()))
+
+    def flush(host):
+        if host:
+            offsets = np.concatenate([[0], np.cumsum([h.size for h in host])]).astype(np.int64)
+            add(torch.from_numpy(np.concatenate(host)).to(dev), offsets)
+
+    host = []
+    for entry in wavs_or_batches:
+        if isinstance(entry, tuple) and len(entry) == 2 and torch.is_tensor(entry[0]) and entry[0].is_cuda:
+            flush(host)
+            host = []
+            wav, offsets = entry
+            if wav.dtype != torch.float32 or wav.dim() != 1 or wav.device != dev:
+                raise ValueError("cmvn_stats: a batch's samples must be one 1-D float32 tensor on the current device")
+            add(wav.contiguous(), np.asarray(offsets.cpu().numpy() if torch.is_tensor(offsets) else offsets, dtype=np.int64).reshape(-1))
+        else:
+            host.append(np.asarray(entry.detach().cpu().numpy() if torch.is_tensor(entry) else entry, dtype=np.float32).reshape(-1))
+            if len(host) == batch_size:
+                flush(host)
+                host = []
+    flush(host)
+    return acc.cpu().numpy()
 
 
 RESAMPLE_MIN_RATE, RESAMPLE_MAX_RATE = 1000, 384000

@@ -72,6 +72,36 @@ def spec_augment(mel_spectrogram, frequency_mask_num=1, time_mask_num=1, frequen
     return out
 
 
+def draw_spec_augment(tau, v, frequency_mask_num=1, time_mask_num=1, frequency_masking_para=2, time_masking_para=5):
+    """The masks ``spec_augment`` would apply to a [tau, v] matrix, without the matrix: (fspans, tspans), lists of (start, width)
+    over columns and over frames.  The same generator calls in the same order -- ``np.random.uniform`` then ``random.randint`` per
+    mask, frequency masks first -- so after the same seeds the draws are ``spec_augment``'s and both generators end in the same
+    state; where ``spec_augment`` raises (``randint`` on an empty range: a tau below the drawn width), so does this.  The spans
+    go to the GPU front end (``fbank.fbank_batch(fmask=, tmask=)``), which masks the frames while it holds them."""
+    fspans, tspans = [], []
+    for _ in range(max(frequency_mask_num, 0)):
+        f = int(np.random.uniform(low=0.0, high=frequency_masking_para))
+        fspans.append((random.randint(0, v - f), f))
+    for _ in range(max(time_mask_num, 0)):
+        t = int(np.random.uniform(low=0.0, high=time_masking_para))
+        tspans.append((random.randint(0, tau - t), t))
+    return fspans, tspans
+
+
+def apply_spans(x, fspans, tspans):
+    """A copy of x [tau, v] with the (start, width) spans zeroed as mdd_fbank_batch_aug zeroes them: columns for fspans, whole frames
+    for tspans; width <= 0 is empty and any other span is cut to the matrix (for tests)."""
+    out = np.array(x)
+    tau, v = out.shape
+    for start, width in fspans:
+        if width > 0:
+            out[:, max(int(start), 0):max(min(int(start) + int(width), v), 0)] = 0
+    for start, width in tspans:
+        if width > 0:
+            out[max(int(start), 0):max(min(int(start) + int(width), tau), 0), :] = 0
+    return out
+
+
 def data_enhancement(phone, mutation_prob=0.1, enhancement_type=1, phone_num=44):
     """One canonical phoneme id -> a one-element list holding the (possibly mutated) id."""
     out = phone

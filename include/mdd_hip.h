@@ -436,6 +436,29 @@ int32_t mdd_fbank_batch_len(const int64_t *n_samples, int32_t B, int32_t skip, i
 int mdd_fbank_batch(const float *wav_dev, const int64_t *offsets_dev, int32_t B, int32_t T_out,
                     const float *cmvn_scale_dev, const float *cmvn_offset_dev,
                     int32_t right, int32_t skip, int32_t n_down, float *out_dev, void *stream);
+/* The train-time form of the batched front end: SpecAugment's masks (AA/utils/tools.py:229-255) applied to each utterance's own
+ * [T_raw, 81] matrix after CMVN and before the stacking, where SpeechDataset.__getitem__ applies them (AA/utils/data_loader.py:132-137).
+ * fmask_dev [B, NF, 2] and tmask_dev [B, NT, 2] (int32, device) hold (start, width) spans: an fmask span zeroes columns
+ *   start <= c < start + width of every frame, a tmask span all 81 columns of raw frames start <= s < start + width.  A zeroed value
+ *   is stored as +0.0f in every stacked slot that reads it (a zeroed last frame in each of its edge repeats).  width <= 0 is empty;
+ *   any other value is intersected with the valid range (sums in 64 bits) and none leads to an access: the spans only predicate.
+ *   NF = NT = 0 gives mdd_fbank_batch's bits; every value that is not masked has mdd_fbank's bits.
+ *   Refused (MDD_ERR_ARG before any device call): what mdd_fbank_batch refuses, NF or NT outside 0..8, a count > 0 with a NULL
+ *   pointer. */
+int mdd_fbank_batch_aug(const float *wav_dev, const int64_t *offsets_dev, int32_t B, int32_t T_out,
+                        const float *cmvn_scale_dev, const float *cmvn_offset_dev,
+                        int32_t right, int32_t skip, int32_t n_down, float *out_dev,
+                        const int32_t *fmask_dev /* [B,NF,2] */, int32_t NF,
+                        const int32_t *tmask_dev /* [B,NT,2] */, int32_t NT, void *stream);
+/* Global CMVN statistics on the GPU (Kaldi's compute-cmvn-stats, AA/steps/make_feat.sh:24-39): adds the sums of the un-normalised
+ * fbank rows (mdd_fbank's bits) of the B utterances, laid out as for mdd_fbank_batch, to stats_dev [2, 82] (double, device):
+ *   stats[0][c] += sum x_c, stats[0][81] += frames, stats[1][c] += sum x_c^2, stats[1][81] stays as it is (0).
+ *   Squares and sums in fp64, no atomics, a fixed order: the same inputs give the same bits on every call.  max_samples is the
+ *   host's bound on the longest utterance and sizes the grid (frames past it are not counted).  An utterance shorter than one
+ *   window adds nothing.  The partial sums live in memory allocated on `stream` for the call.
+ *   Refused (MDD_ERR_ARG before any device call): B outside 1..65535, max_samples < 0 or beyond 2^31 frames, a NULL pointer. */
+int mdd_cmvn_accumulate(const float *wav_dev, const int64_t *offsets_dev, int32_t B, int64_t max_samples,
+                        double *stats_dev /* [2,82] */, void *stream);
 
 /* ---- Any-rate input -> 16 kHz PCM16 in front of the fbank: the reference resamples every WAV that is not 16 kHz and writes it
  * back as a 16-bit WAV (`librosa.resample(data, orig_sr=fs, target_sr=16000)` = resampy kaiser_best, then `sf.write`,
