@@ -58,5 +58,8 @@ __attribute__((visibility("hidden"))) void launch_beam_generic(const BeamCall &c
 __attribute__((visibility("hidden"))) void launch_beam_fast(const BeamCall &c, const BeamPlan &p, const double *lpw, const unsigned char *flags);
 __attribute__((visibility("hidden"))) int init_beam_generic_attributes();
 __attribute__((visibility("hidden"))) int init_beam_fast_attributes();
+// beam.hip -> beam_wide.hip (mdd_beam_wide): the wide kernel on the workspace the plan laid out, whose head the pre-pass has filled
+__attribute__((visibility("hidden"))) void launch_beam_wide(const BeamCall &c, const BeamWidePlan &p, unsigned char *ws);
+__attribute__((visibility("hidden"))) int init_beam_wide_attributes();
 
 }  // namespace mdd

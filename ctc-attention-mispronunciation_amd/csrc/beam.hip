@@ -1,5 +1,6 @@
 // CTC decoders on the GPU: prefix beam search (greedy: greedy.hip).  The frame pre-pass and the host path of the beam entries; the two
 // search kernels are in beam_generic.hip and beam_fast.hip, what they share in beam.h, the LDS limits and the route in plan.h (beam_plan).
+// mdd_beam_wide (beam <= 256, any T up to 38400) is a third kernel behind its own entry: beam_wide.hip, laid out by plan.h's beam_wide_plan.
 //
 // Reference: BeamDecoder.decode -> ctcBeamSearch.decode (AA/utils/ctcDecoder.py:215-226, AA/utils/BeamSearch.py:73-153).
 // A serial scan over the posterior frames of one utterance; it is latency-bound, not bandwidth- or flop-bound (180 B read per frame).
@@ -85,6 +86,49 @@ extern "C" int mdd_beam_nbest(const float *logp_dev, int32_t T, int32_t B, int32
                               int32_t *nids_dev, int32_t *status_dev, double *score_dev, void *stream) {
     return beam_search({"mdd_beam_nbest", true, false, logp_dev, T, B, C, len_dev, beam, blank, lm_dev, lm_alpha, nbest, ids_dev, nids_dev, status_dev,
                         score_dev, nullptr, (hipStream_t)stream});
+}
+
+// Whether mdd_beam / mdd_beam_nbest accept the shape now: their argument ranges and their plan's limits, under the switches they would read
+extern "C" int32_t mdd_beam_fits(int32_t T, int32_t B, int32_t C, int32_t beam) {
+    if (!beam_shape_ok(T, B, C, beam)) return 0;
+    return beam_plan(T, B, C, beam, false, read_beam_switches()).over == BeamLimit::Ok ? 1 : 0;
+}
+
+// bytes of workspace mdd_beam_wide needs for these shapes (beam_wide_plan): the pre-pass's outputs and one slice per utterance
+extern "C" int64_t mdd_beam_wide_workspace_bytes(int32_t T, int32_t B, int32_t C, int32_t beam) {
+    if (!beam_wide_shape_ok(T, B, C, beam)) return 0;
+    return (int64_t)beam_wide_plan(T, B, C, beam).bytes;
+}
+
+// The wide entry, in the order of ctc_host.h.  No switches: one kernel, chosen by nothing but the plan's LDS placement.
+extern "C" int mdd_beam_wide(const float *logp_dev, int32_t T, int32_t B, int32_t C, const int32_t *len_dev, int32_t beam, int32_t blank,
+                             const double *lm_dev, double lm_alpha, int32_t nbest, int32_t *ids_dev, int32_t *nids_dev,
+                             int32_t *status_dev, double *score_dev, void *workspace_dev, int64_t workspace_bytes, void *stream) {
+    const char *what = !logp_dev ? "logp_dev is NULL" : !len_dev ? "len_dev is NULL" : !lm_dev ? "lm_dev is NULL" : !ids_dev ? "ids_dev is NULL"
+                     : !nids_dev ? "nids_dev is NULL" : !status_dev ? "status_dev is NULL" : !score_dev ? "score_dev is NULL"
+                     : (T < 1 || T > kBeamWideMaxT) ? "need 1<=T<=38400" : B < 1 ? "B < 1" : (C < 2 || C > 256) ? "need 2<=C<=256"
+                     : (beam < 1 || beam > kBeamWideMax) ? "need 1<=beam<=256" : (blank < 0 || blank >= C) ? "blank outside [0, C)"
+                     : (nbest < 1 || nbest > beam) ? "need 1<=nbest<=beam" : nullptr;
+    if (what) { set_error("mdd_beam_wide: bad argument (%s)", what); return MDD_ERR_ARG; }
+    const BeamWidePlan p = beam_wide_plan(T, B, C, beam);
+    if (workspace_dev && workspace_bytes < (int64_t)p.bytes)
+        return refuse_workspace("mdd_beam_wide", "mdd_beam_wide_workspace_bytes", workspace_bytes, (int64_t)p.bytes);
+    hipStream_t st = (hipStream_t)stream;
+    static OncePerDevice once;
+    if (int rc = once_per_device(once, init_beam_wide_attributes)) return rc;
+    StreamWorkspace ws;
+    if (int rc = ws.acquire(workspace_dev, (int64_t)p.bytes, st)) return rc;
+    unsigned char *w = ws.as<unsigned char>();
+    const size_t n = (size_t)T * B * C;
+    int grid = (int)((n + 255) / 256);
+    if (grid > 2048) grid = 2048;
+    hipLaunchKernelGGL(beam_prep_kernel, dim3(grid), dim3(256), 0, st, logp_dev, T, B, C, blank, reinterpret_cast<double *>(w), w + p.off_flags);
+    const BeamCall c{"mdd_beam_wide", true, false, logp_dev, T, B, C, len_dev, beam, blank, lm_dev, lm_alpha, nbest, ids_dev, nids_dev, status_dev,
+                     score_dev, nullptr, st};
+    launch_beam_wide(c, p, w);
+    const hipError_t le = hipGetLastError();
+    if (le != hipSuccess) { set_error("mdd_beam_wide: kernel launch failed: %s", hipGetErrorString(le)); return MDD_ERR_HIP; }
+    return MDD_OK;
 }
 
 // Diagnostic: mdd_beam through the stamped instantiation of the single-wave kernel, its phase cycle sums into the caller's own

@@ -327,4 +327,57 @@ static inline BeamPlan beam_plan(int T, int B, int C, int beam, bool nbest_entry
     return p;
 }
 
+// ---- The wide beam entry (beam_wide.hip: mdd_beam_wide): beam <= 256 at any T mdd_greedy takes.  One workgroup of kBeamWideThreads per
+// utterance; the per-beam state of 2 x 256 entries is static LDS (about 45 KB), the candidate totals and the compacted list are dynamic LDS
+// while they fit kBeamWideLdsBudget and lie in the utterance's slice of the workspace beyond it; everything whose size grows with T is in the workspace.
+// beam_wide_plan is the one place the byte counts and offsets come from: the host path, the kernel's arguments and
+// mdd_beam_wide_workspace_bytes all read it.  The entry has no environment switches.
+constexpr int kBeamWideMax = 256;          // beams of the wide kernel
+constexpr int kBeamWideThreads = 512;      // its workgroup: at least kBeamWideMax threads hold maxima in the selection
+constexpr int kBeamWideMaxT = 38400;       // mdd_greedy's bound on T
+// Dynamic LDS of the wide kernel.  With its static 45 KB this stays under the 160 KB of a CU; one workgroup per CU either way.
+constexpr size_t kBeamWideLdsBudget = 112 * 1024;
+struct BeamWidePlan {
+    int Tcap;              // a prefix row: T ids + 1, in whole words
+    size_t n;              // candidate slots of a frame: beam * C
+    int tot_in_lds;        // the candidate totals (8 n bytes) are dynamic LDS
+    size_t list_cap;       // entries of the compacted list (12 bytes each) the rest of the budget holds, at most n; a frame whose list is
+                           //   longer (exact ties) writes it to the workspace instead
+    size_t smem;           // dynamic LDS of the launch: tot [n] f64 (if in LDS) | cl_v [list_cap] f64 | cl_o [list_cap] i32
+    // the workspace: lp [T,B,C] fp64 | flags [T,B] u8 | B utterance slices of `utt` bytes; every part starts on a multiple of 16 bytes
+    size_t off_flags, off_utt, utt;
+    // inside a slice: live [T] i32 (the live frames, t * 2 + repeat bit) | pref [2][beam][Tcap] u8 | tot [n] f64 where not in LDS |
+    // cl_v [n] f64, cl_o [n] i32 where list_cap < n (the offsets of absent parts are 0 and unused)
+    size_t u_pref, u_tot, u_clv, u_clo;
+    size_t bytes;          // the whole workspace
+};
+MDD_PLAN_HD inline size_t beam_wide_round16(size_t v) { return (v + 15) & ~(size_t)15; }
+static inline BeamWidePlan beam_wide_plan(int T, int B, int C, int beam) {
+    BeamWidePlan p{};
+    p.Tcap = (T + 1 + 3) & ~3;
+    p.n = (size_t)beam * C;
+    p.tot_in_lds = sizeof(double) * p.n <= kBeamWideLdsBudget;
+    const size_t tot_lds = p.tot_in_lds ? sizeof(double) * p.n : 0;
+    p.list_cap = (kBeamWideLdsBudget - tot_lds) / (sizeof(double) + sizeof(int));
+    p.list_cap &= ~(size_t)1;                                       // cl_o starts on 8 bytes either way
+    if (p.list_cap > p.n) p.list_cap = p.n;
+    p.smem = tot_lds + (sizeof(double) + sizeof(int)) * p.list_cap;
+    p.off_flags = beam_wide_round16(sizeof(double) * (size_t)T * B * C);
+    p.off_utt = p.off_flags + beam_wide_round16((size_t)T * B);
+    size_t u = beam_wide_round16(sizeof(int) * (size_t)T);
+    p.u_pref = u;
+    u += beam_wide_round16((size_t)2 * beam * p.Tcap);
+    if (!p.tot_in_lds) { p.u_tot = u; u += beam_wide_round16(sizeof(double) * p.n); }
+    if (p.list_cap < p.n) {
+        p.u_clv = u; u += beam_wide_round16(sizeof(double) * p.n);
+        p.u_clo = u; u += beam_wide_round16(sizeof(int) * p.n);
+    }
+    p.utt = u;
+    p.bytes = p.off_utt + (size_t)B * p.utt;
+    return p;
+}
+// The argument ranges of mdd_beam_wide, and of mdd_beam / mdd_beam_nbest (mdd_beam_fits)
+inline bool beam_wide_shape_ok(int T, int B, int C, int beam) { return T >= 1 && T <= kBeamWideMaxT && B >= 1 && C >= 2 && C <= 256 && beam >= 1 && beam <= kBeamWideMax; }
+inline bool beam_shape_ok(int T, int B, int C, int beam) { return T >= 1 && B >= 1 && C >= 2 && C <= 256 && beam >= 1 && beam <= kBeamMax; }
+
 }  // namespace mdd

@@ -383,7 +383,9 @@ class BeamDecoder(Decoder):
         return self._tables[key]
 
     def _search(self, entry, prob_tensor, frame_seq_len, N, *nbest):
-        """mdd_beam (``nbest`` empty, N = 1) or mdd_beam_nbest (``nbest`` = (N,)): (ids [N,B,T], nids [N,B], status [B], score [N,B])."""
+        """mdd_beam (``nbest`` empty, N = 1) or mdd_beam_nbest (``nbest`` = (N,)): (ids [N,B,T], nids [N,B], status [B], score [N,B]).
+        A shape those two refuse on size (mdd_beam_fits: beam_width over 64, or state past their LDS limits) goes to mdd_beam_wide with the
+        same N, which has their outputs and takes beam_width up to 256 at any length; it refuses what is left by its own message."""
         lp, T, B, Cn, lens = _posteriors_and_lens(prob_tensor, frame_seq_len)
         ids = torch.empty((N, B, T), dtype=torch.int32, device=lp.device)
         nids = torch.empty((N, B), dtype=torch.int32, device=lp.device)
@@ -391,8 +393,12 @@ class BeamDecoder(Decoder):
         score = torch.empty((N, B), dtype=torch.float64, device=lp.device)
         lm, p = self._lm_table(Cn, lp.device), _lib.ptr
         with torch.cuda.device(lp.device):
-            _lib.check(entry(p(lp), T, B, Cn, p(lens), self.beam_width, self.blank_index, p(lm), float(self.lm_alpha), *nbest,
-                             p(ids), p(nids), p(status), p(score), _lib.current_stream_ptr()))
+            if _lib.lib().mdd_beam_fits(T, B, Cn, self.beam_width):
+                _lib.check(entry(p(lp), T, B, Cn, p(lens), self.beam_width, self.blank_index, p(lm), float(self.lm_alpha), *nbest,
+                                 p(ids), p(nids), p(status), p(score), _lib.current_stream_ptr()))
+            else:
+                _lib.check(_lib.lib().mdd_beam_wide(p(lp), T, B, Cn, p(lens), self.beam_width, self.blank_index, p(lm), float(self.lm_alpha), N,
+                                                    p(ids), p(nids), p(status), p(score), None, 0, _lib.current_stream_ptr()))
         return ids, nids, status, score
 
     def decode_ids(self, prob_tensor, frame_seq_len=None):

@@ -265,6 +265,33 @@ int mdd_beam_nbest(const float *logp_dev, int32_t T, int32_t B, int32_t C, const
                    int32_t *ids_dev    /* [nbest,B,T] */, int32_t *nids_dev /* [nbest,B] */,
                    int32_t *status_dev /* [B] */,         double *score_dev /* [nbest,B], required */, void *stream);
 
+/* ---- A9, wide: the same search past the LDS limits of the two entries above, as the reference's own has none (a dict and a sort).
+ * mdd_beam_fits: host only, no other effect.  1 where mdd_beam / mdd_beam_nbest would accept (T, B, C, beam) at this moment -- their
+ *   argument ranges and their LDS limits, under MDD_BEAM_GENERIC / MDD_BEAM_W as they read them -- else 0.  A caller routes on it: 1, the
+ *   entries above; 0, mdd_beam_wide.
+ * mdd_beam_wide: 1 <= beam <= 256, 2 <= C <= 256, 1 <= T <= 38400 (mdd_greedy's bound), B >= 1, 0 <= blank < C, 1 <= nbest <= beam; every
+ *   shape mdd_beam accepts is among them.  Inputs, outputs (hypothesis-major, score_dev required), status codes and the ordering of the
+ *   slices are mdd_beam_nbest's; nbest = 1 is the winner.  On a shape both accept, ids, nids, status and score are mdd_beam_nbest's bits:
+ *   the kernel (beam_wide_kernel, csrc/beam_wide.hip) computes every total in the generic kernel's order and selects under the same
+ *   total order.  One workgroup of eight waves per utterance; the state of 2 x 256 beams in LDS, the candidate totals and the compacted
+ *   candidate list in LDS up to 112 KB (8 beam C for the totals, 12 bytes per list entry in what is left) and in the workspace beyond,
+ *   prefix rows (2 beam rows of Tcap bytes) in the workspace.  No environment switches.
+ *   Cost to know: on inputs whose candidates tie exactly the compacted list is the whole candidate set and the rank count is quadratic
+ *   in it (beam C)^2 / 512 comparisons per thread and frame.
+ * workspace_dev: caller scratch of at least mdd_beam_wide_workspace_bytes(T, B, C, beam) bytes, 16-byte aligned, which holds all the call
+ *   needs beyond its outputs (the pre-pass's fp64 log-probs and flags, and per utterance the live-frame list, the prefix rows and what
+ *   of the candidate arrays is not in LDS); NULL = the library allocates stream-ordered for the call.  The count is one host function,
+ *   beam_wide_plan in csrc/plan.h; mdd_beam_wide_workspace_bytes returns 0 for a shape outside the ranges above.
+ * Bad arguments (a range above, a required pointer NULL, nbest outside [1, beam], a caller workspace that is too small) return
+ *   MDD_ERR_ARG before any device work, with nothing written; the message starts with mdd_beam_wide. */
+int32_t mdd_beam_fits(int32_t T, int32_t B, int32_t C, int32_t beam);
+int64_t mdd_beam_wide_workspace_bytes(int32_t T, int32_t B, int32_t C, int32_t beam);
+int mdd_beam_wide(const float *logp_dev, int32_t T, int32_t B, int32_t C, const int32_t *len_dev, int32_t beam, int32_t blank,
+                  const double *lm_dev, double lm_alpha, int32_t nbest,
+                  int32_t *ids_dev    /* [nbest,B,T] */, int32_t *nids_dev /* [nbest,B] */,
+                  int32_t *status_dev /* [B] */,         double *score_dev /* [nbest,B], required */,
+                  void *workspace_dev, int64_t workspace_bytes, void *stream);
+
 /* ---- A12: nn.CTCLoss(reduction='sum') pieces (AA/steps/train_ctc.py:72,186): alpha/beta lattice.
  * logp_dev [T,B,C], targets_dev [B,Lmax] int64 (padded), in_len_dev/tgt_len_dev [B] int64 ->
  * nll_dev [B] (per-utterance negative log-likelihood; the reference's loss is their sum; +inf for an utterance with no
