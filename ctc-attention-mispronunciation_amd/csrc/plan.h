@@ -380,4 +380,46 @@ static inline BeamWidePlan beam_wide_plan(int T, int B, int C, int beam) {
 inline bool beam_wide_shape_ok(int T, int B, int C, int beam) { return T >= 1 && T <= kBeamWideMaxT && B >= 1 && C >= 2 && C <= 256 && beam >= 1 && beam <= kBeamWideMax; }
 inline bool beam_shape_ok(int T, int B, int C, int beam) { return T >= 1 && B >= 1 && C >= 2 && C <= 256 && beam >= 1 && beam <= kBeamMax; }
 
+// ---- Minimum Bayes risk over an N-best list (mbr.hip: mdd_nbest_mbr): every pairwise edit distance of an utterance's N hypotheses by the
+// bit-vector recurrence (mbr.h).  A pattern's vertical deltas are `words` 64-bit words; the kernel is instantiated for 1, 2, 4, 8 and 16 of
+// them, so max_len is rounded up to the next of 64, 128, 256, 512, 1024.  The call first packs the ids it has range-checked, one byte each,
+// into the workspace: per utterance [Lp / 4][NP] 32-bit words, word (jq, r) holding ids 4 jq .. 4 jq + 3 of row r -- the N hypotheses and,
+// in column N, the reference -- so that the 64 lanes of a wave, each walking another row, read consecutive words.  A workgroup of
+// kMbrWaves waves takes kMbrRowsPerBlock patterns of one utterance, a wave one pattern at a time with its match table peq [C][words] in LDS;
+// in the one-word form the workgroup also holds the utterance's packed list in LDS, in the others the lanes read it from the workspace.
+// mbr_plan is the one place these counts come from: the host path, the kernels' arguments and mdd_nbest_mbr_workspace_bytes read it.
+constexpr int kMbrMaxN = kBeamWideMax;     // hypotheses of a list: the wide beam entry's bound
+constexpr int kMbrMaxLen = 1024;           // ids of a hypothesis: 16 words
+constexpr int kMbrWaves = 4;               // waves of a workgroup of the distance kernel, one pattern each at a time
+constexpr int kMbrRowsPerBlock = 16;       // patterns of a workgroup: four per wave, so that the list is staged 16 times less often than read
+constexpr size_t kMbrLdsMax = 160 * 1024;
+struct MbrPlan {
+    int words;          // 64-bit words of a pattern: 1, 2, 4, 8 or 16
+    int Lp;             // ids of a packed row: 64 * words
+    int NP;             // columns of the packed list: N + 1 (the reference) rounded up to 16 words = 64 bytes
+    int text_in_lds;    // the one-word form: the workgroup's copy of the packed list
+    size_t peq_bytes;   // the match tables of a workgroup: kMbrWaves * C * words u64
+    size_t text_bytes;  // the LDS copy of the list: [16][NP] u32, or 0
+    size_t smem;        // dynamic LDS of the distance kernel: peq | text
+    size_t utt;         // workspace bytes of one utterance: [Lp / 4][NP] u32
+    size_t bytes;       // the whole workspace
+};
+inline bool mbr_shape_ok(int N, int B, int C, int max_len) {
+    return N >= 1 && N <= kMbrMaxN && B >= 1 && C >= 2 && C <= 256 && max_len >= 1 && max_len <= kMbrMaxLen;
+}
+static inline MbrPlan mbr_plan(int N, int B, int C, int max_len) {
+    MbrPlan p{};
+    p.words = 1;
+    while (64 * p.words < max_len) p.words *= 2;
+    p.Lp = 64 * p.words;
+    p.NP = (N + 1 + 15) & ~15;
+    p.text_in_lds = p.words == 1;
+    p.peq_bytes = sizeof(unsigned long long) * (size_t)kMbrWaves * C * p.words;
+    p.text_bytes = p.text_in_lds ? sizeof(unsigned) * (size_t)(p.Lp / 4) * p.NP : 0;
+    p.smem = p.peq_bytes + p.text_bytes;
+    p.utt = sizeof(unsigned) * (size_t)(p.Lp / 4) * p.NP;
+    p.bytes = (size_t)B * p.utt;
+    return p;
+}
+
 }  // namespace mdd

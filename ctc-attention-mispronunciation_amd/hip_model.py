@@ -313,3 +313,57 @@ def ctc_confnet_best(logp, lens, w, nslots, blank=0, max_slots=None, want_path=T
     c(_lib.lib().mdd_ctc_confnet_best, c.ptr(lens), c.ptr(w, stride), stride, c.ptr(nslots), Jmax, blank, c.ptr(score), c.ptr(reading, stride),
       c.ptr(status), c.ptr(path), c.ptr(seg, stride))
     return ConfnetBestResult(score, reading, status, path, seg)
+
+
+MBR_MAX_LEN = 1024          # include/mdd_hip.h: mdd_nbest_mbr's bound on max_len (16 words of 64 pattern positions)
+
+
+def nbest_mbr(ids, nids, status, weights, num_class, max_len=None, ref=None, ref_len=None, want_dist=False):
+    """Minimum-Bayes-risk decode of an N-best list on the GPU (mdd_nbest_mbr): every pairwise edit distance inside each utterance's list,
+    each hypothesis' expected distance under the list's own weights, and the hypothesis that minimises it.
+
+    ids [N,B,pitch] / nids [N,B] int32 as ``BeamDecoder.decode_nbest_ids`` returns them (int32 CUDA tensors pass through with no copy),
+    status [B] or None (non-zero: skip the utterance), weights [N,B] float64, finite and >= 0 (``nbest_posteriors``' shares; they need
+    not sum to 1).  ``max_len`` bounds nids (default: the ids' row length clipped to the limit of 1024, so the call needs no sync); a
+    bound of at most 64 runs the kernel's one-word form.  ``ref`` [B,ref_pitch] / ``ref_len`` [B]: a reference sequence per utterance,
+    both or neither.  Returns device tensors ``(best [B] i32, risk [N,B] f64, flag [B] i32, dist [B,N,N] i32 | None, ref_dist [N,B] i32 |
+    None, ref_risk [B] f64 | None)``: risk[n,b] = sum_m weights[m,b] d(h_n, h_m); best[b] the lowest n with a weight above 0 and the
+    least risk; ref_dist[n,b] = d(h_n, ref_b) and ref_risk[b] their weighted sum.  flag[b] = 1 (skipped: status, or no weight above 0)
+    or 2 (a length outside [0, max_len] or an id outside [0, num_class)) gives best -1, NaN risks and -1 distances.  Nothing
+    synchronises."""
+    ids = torch.as_tensor(ids)
+    if not ids.is_cuda:
+        _lib.require_gpu()
+    ids = _lib.to_gpu(ids, torch.int32)
+    dev = ids.device
+
+    def to(x, dtype):
+        return None if x is None else torch.as_tensor(x).to(dev, dtype).contiguous()
+
+    nids, status, weights, ref, ref_len = to(nids, torch.int32), to(status, torch.int32), to(weights, torch.float64), to(ref, torch.int32), to(ref_len, torch.int32)
+    if ids.dim() != 3 or nids.shape != ids.shape[:2] or weights.shape != ids.shape[:2] or (status is not None and status.shape != ids.shape[1:2]):
+        raise ValueError("nbest_mbr: ids [N, B, pitch], nids [N, B], status [B], weights [N, B]")
+    N, B, pitch = ids.shape
+    if (ref is None) != (ref_len is None) or (ref is not None and (ref.dim() != 2 or ref.shape[0] != B or ref_len.shape != (B,))):
+        raise ValueError("nbest_mbr: ref [B, ref_pitch] and ref_len [B], both or neither")
+    L = min(pitch, MBR_MAX_LEN) if max_len is None else int(max_len)
+    has_ref = ref is not None
+    ref_pitch = ref.shape[1] if has_ref else 0
+    if has_ref and ref_pitch == 0:           # an empty [B, 0] reference: every length must be 0; one never-read column stands in
+        ref, ref_pitch = torch.zeros((B, 1), dtype=torch.int32, device=dev), 1
+
+    def empty(shape, dtype, want=True):
+        return torch.empty(shape, dtype=dtype, device=dev) if want else None
+
+    best, risk, flag = empty((B,), torch.int32), empty((N, B), torch.float64), empty((B,), torch.int32)
+    dist = empty((B, N, N), torch.int32, want_dist)
+    ref_dist, ref_risk = empty((N, B), torch.int32, has_ref), empty((B,), torch.float64, has_ref)
+    L_ = _lib.lib()
+    nws = L_.mdd_nbest_mbr_workspace_bytes(N, B, int(num_class), L)
+    ws = torch.empty((max(nws, 16) + 7) // 8, dtype=torch.float64, device=dev)      # torch's caching allocator: no hipMalloc per call
+    p = _lib.ptr
+    with torch.cuda.device(dev):
+        _lib.check(L_.mdd_nbest_mbr(p(ids), pitch, p(nids), p(status), p(weights), N, B, int(num_class), L, p(ref), p(ref_len), ref_pitch,
+                                    p(best), p(risk), p(dist), p(ref_dist), p(ref_risk), p(flag), p(ws), ws.numel() * 8,
+                                    _lib.current_stream_ptr()))
+    return best, risk, flag, dist, ref_dist, ref_risk

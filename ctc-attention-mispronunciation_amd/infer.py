@@ -3,7 +3,7 @@
 
     python -m ctc_attention_mispronunciation_amd.infer --conf CONF --wav_transcript_path DIR [-p cmudict] [-f cmu]
         [--cmvn PATH] [--cmudict PATH] [--precision f32x6|f32|bf16x3] [--decode_seq PATH] [--timestamps] [--posteriors] [--pronunciations] [--nbest N]
-        [--joint_posteriors] [--joint_diagnosis] [--error_prior P]
+        [--mbr N] [--joint_posteriors] [--joint_diagnosis] [--error_prior P]
 
 The conf YAML is read as ``infer_init`` reads it (AA/infer.py:211-261): the checkpoint
 ``checkpoint_dir/exp_name/ctc_best_model.pkl``, ``vocab_file``, ``decode_type``, ``beam_width``, ``lm_path``, ``lm_alpha``,
@@ -64,6 +64,12 @@ def parse_args(argv=None):
                     help="add N 'nbest  :' lines to each block: the N best final hypotheses of the beam search with their beam score, exact CTC "
                          "log-likelihood, share of probability among the N listed (not an absolute probability) and Comp.; needs "
                          "decode_type Beam and 1 <= N <= beam_width")
+    ap.add_argument("--mbr", type=int, default=None, metavar="N",
+                    help="add an 'mbr    :' line to each block: the minimum-Bayes-risk hypothesis of the N best final hypotheses of the beam "
+                         "search -- the one with the least expected edit distance to the list under the list's own CTC posterior -- with its "
+                         "rank, its expected number of phoneme errors (risk), the same for the decoded string (risk1), the list's expected edit "
+                         "distance to the canonical phones (exp) and Comp.; the block itself stays the 1-best's.  Needs decode_type Beam and "
+                         "2 <= N <= beam_width; independent of --nbest")
     ap.add_argument("--joint_posteriors", action="store_true",
                     help="add a 'jpost  :' line to each block, in the format of 'post   :': the same per-phoneme figures as marginals over the "
                          "error network of the canonical phones -- every phoneme kept, substituted or deleted and every gap empty or filled "
@@ -190,6 +196,13 @@ def main(argv=None):
             refuse("--nbest %d: N must be at least 1" % args.nbest)
         if args.nbest > opts.beam_width:
             refuse("--nbest %d: the search keeps beam_width = %d hypotheses; N cannot exceed it" % (args.nbest, opts.beam_width))
+    if args.mbr is not None:
+        if opts.decode_type == "Greedy":
+            refuse("--mbr: the greedy decoder keeps one hypothesis; set decode_type to Beam")
+        if args.mbr < 2:
+            refuse("--mbr %d: N must be at least 2 (the risk of a list of one is 0)" % args.mbr)
+        if args.mbr > opts.beam_width:
+            refuse("--mbr %d: the search keeps beam_width = %d hypotheses; N cannot exceed it" % (args.mbr, opts.beam_width))
     if not os.path.exists(args.cmvn):
         refuse("CMVN stats not found at %s (pass --cmvn)" % args.cmvn)
     print(args.wav_transcript_path, False, args.phonetic)
@@ -221,7 +234,7 @@ def main(argv=None):
     c1, c2, c3 = infer(phonetic, word_dict, loader, device, model, decoder, vocab, transcripts, False,
                        decode_seq_path=args.decode_seq, timestamps=args.timestamps, posteriors=args.posteriors, pronunciations=args.pronunciations,
                        nbest=args.nbest or 0, joint_posteriors=args.joint_posteriors, error_prior=args.error_prior,
-                       joint_diagnosis=args.joint_diagnosis)
+                       joint_diagnosis=args.joint_diagnosis, mbr=args.mbr or 0)
     print(c1, c2, c3)
     end = time.time()
     total = max(total_wav_time, 1e-9)

@@ -295,9 +295,27 @@ def nbest_lines(records, canonical, decoder, to_display=None):
     return lines
 
 
+def mbr_line(record, canonical, decoder, to_display=None):
+    """The ``mbr    :`` line of a block from one utterance's ``BeamDecoder.decode_mbr`` record ``(string, rank, risk, risk_of_rank_0,
+    expected_errors_vs_canonical)``: ``mbr    : <rank> <phones> | risk <%.4f> | risk1 <%.4f> | exp <%.4f> | Comp. <correct>/<total>``.
+    rank is the place of the minimum-Bayes-risk hypothesis in the N-best list, 1-based as ``nbest  :`` prints ranks; risk its expected
+    number of phoneme errors against the list, risk1 the same for rank 1 (the block's decoded string), exp the list's expected edit
+    distance to the block's canonical phones ('-' without them) and Comp. what ``diagnose`` counts for that hypothesis ('-' where
+    ``wer`` has nothing to align).  ``mbr    : -`` where the utterance has no result (``record`` is None)."""
+    if record is None:
+        return "mbr    : -"
+    hyp, rank, risk, risk1, exp = record
+    try:
+        d = diagnose(hyp, canonical, decoder, to_display)
+        comp = "%d/%d" % (d["correct"], d["correct"] + d["del_sub"])
+    except TypeError:                    # an empty side after the 'sil' strip: Decoder.wer raises, as the reference's does
+        comp = "-"
+    return "mbr    : %d %s | risk %.4f | risk1 %.4f | exp %s | Comp. %s" % (rank + 1, hyp, risk, risk1, "-" if exp is None else "%.4f" % exp, comp)
+
+
 def infer(phonetic, word_dict, test_loader, device, model, decoder, vocab, test_transcipt_dict, use_ipa, out=None,
           decode_seq_path=None, timestamps=False, posteriors=False, pronunciations=False, nbest=0, joint_posteriors=False, error_prior=None,
-          joint_diagnosis=False):
+          joint_diagnosis=False, mbr=0):
     """AA/infer.py:282-372.  Per batch ``(inputs, input_sizes, _, _, trans, trans_sizes, utt_list)``: ``model(inputs, trans)``,
     frame counts ``(input_sizes * T').long()``, ``decoder.decode``, then per utterance the 'sil' strip, 'err' removal, ``wer``,
     alignment, fault lists and score (``diagnose``), printed as the reference's 13-line block to ``out`` (stdout by default).
@@ -342,13 +360,22 @@ def infer(phonetic, word_dict, test_loader, device, model, decoder, vocab, test_
     alignment (``ctcDecoder.joint_diagnosis``, one call per batch) -- with its number of edits, its score and its probability among all
     readings.  With ``timestamps`` a ``jtime  :`` line (``joint_time_line``) follows it: the frames of every emitted phoneme in seconds.
     It reads only the posteriors, so it serves both model classes; with ``pronunciations`` the lines are the chosen candidate's.
-    Without it nothing changes."""
+    Without it nothing changes.
+
+    ``mbr=N`` (no reference counterpart; needs a ``BeamDecoder`` with ``beam_width >= N >= 2``; independent of ``nbest``) adds one line,
+    ``mbr    :`` (``mbr_line``), behind the ``nbest`` lines and in front of ``pron``: the minimum-Bayes-risk hypothesis of the N best --
+    the one with the least expected edit distance to the list under the list's own CTC posterior (``decode_mbr``, one call per batch) --
+    with its rank, its expected number of phoneme errors, the same figure for the block's decoded string and the list's expected edit
+    distance to the canonical phones.  The block's decoded string, alignment and diagnosis stay the 1-best's.  It reads only the
+    posteriors, so it serves both model classes; with ``pronunciations`` the line is the chosen candidate's.  With 0 nothing changes."""
     if error_prior is not None and not ((joint_posteriors or joint_diagnosis) and 0.0 < error_prior < 1.0):
         raise ValueError("error_prior needs joint_posteriors or joint_diagnosis and 0 < error_prior < 1")
     if joint_diagnosis and error_prior is None:
         raise ValueError("joint_diagnosis needs error_prior")
     if nbest and not (hasattr(decoder, "decode_nbest") and 1 <= nbest <= decoder.beam_width):
         raise ValueError("nbest needs a BeamDecoder and 1 <= nbest <= beam_width")
+    if mbr and not (hasattr(decoder, "decode_mbr") and 2 <= mbr <= decoder.beam_width):
+        raise ValueError("mbr needs a BeamDecoder and 2 <= mbr <= beam_width")
     if posteriors:
         from .utils.ctcDecoder import phoneme_posteriors
     if joint_posteriors:
@@ -388,6 +415,8 @@ def infer(phonetic, word_dict, test_loader, device, model, decoder, vocab, test_
                         r["decoded"] = decoder.decode(probs, frame_lens)
                     if nbest:
                         r["nbest"] = decoder.decode_nbest(probs, frame_lens, nbest)
+                    if mbr:
+                        r["mbr"] = decoder.decode_mbr(probs, frame_lens, mbr, trans, trans_sizes)
                     if posteriors:
                         r["post"] = phoneme_posteriors(probs, frame_lens, trans, trans_sizes, decoder.blank_index)
                     if joint_posteriors:
@@ -440,6 +469,8 @@ def infer(phonetic, word_dict, test_loader, device, model, decoder, vocab, test_
                             block[-1:-1] = [joint_time_line(r["jdiag"][x], vocab.index2word, spf, decoder.blank_index, to_display)]
                     if nbest:
                         block[-1:-1] = nbest_lines(r["nbest"][x], canonical, decoder, to_display)
+                    if mbr:
+                        block[-1:-1] = [mbr_line(r["mbr"][x], canonical, decoder, to_display)]
                     if pronunciations:
                         phones = [" ".join(vocab.index2word[num] for num in per_set[p]["trans"][x][:per_set[p]["trans_sizes"][x]]) for p in range(count)]
                         block[-1:-1] = [pronunciation_line(phones, loglik, chosen)]

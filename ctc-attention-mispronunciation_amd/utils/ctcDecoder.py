@@ -462,6 +462,53 @@ class BeamDecoder(Decoder):
                          None if post is None else float(post[n])) for n in range(N)])
         return out
 
+    def decode_mbr(self, prob_tensor, frame_seq_len=None, nbest=None, canonical_ids=None, canonical_lens=None):
+        """The minimum-Bayes-risk ("consensus") hypothesis of the N-best list: among the ``nbest`` (default ``beam_width``) final
+        hypotheses the one with the least expected edit distance to the others, each weighted by its share of the list's exact CTC
+        likelihood -- ``decode_nbest_ids`` -> ``nbest_loglik`` -> ``nbest_posteriors`` -> ``hip_model.nbest_mbr`` (mdd_nbest_mbr).  The
+        phoneme error rate is an edit distance, so this is the listed hypothesis that minimises the expected number of phoneme errors
+        under the list's own posterior; ties go to the better rank, so a list that agrees with itself keeps ``decode``'s answer.
+        Per utterance ``(string, rank, risk, risk_of_rank_0, expected_errors_vs_canonical | None)``: the hypothesis and its place in the
+        list (0 is ``decode``'s string), its expected number of phoneme errors against the list, the same figure for rank 0, and --
+        with ``canonical_ids`` [B, L] / ``canonical_lens`` [B] -- the list's expected edit distance to the canonical phones.  ``None``
+        for an utterance the kernel flags: no listed hypothesis is a CTC path of the posteriors (all weights 0), or an id is outside
+        the classes.  The exceptions are ``decode``'s; a hypothesis or canonical row longer than 1024 ids raises ``ValueError``."""
+        from ..hip_model import MBR_MAX_LEN, nbest_mbr
+        lp, T, B, Cn, lens = _posteriors_and_lens(prob_tensor, frame_seq_len)
+        ids, nids, status, _ = self.decode_nbest_ids(lp, lens, nbest)
+        N = ids.shape[0]
+        self._strings(ids[0], nids[0], status)                      # rank 0 as decode builds it: raises decode's exception
+        ids_h, nids_h = ids.cpu().numpy(), nids.cpu().numpy()      # one download of the list; a string is built for the chosen rank alone
+        longest = int(nids_h.max())
+        ref = ref_len = None
+        if canonical_ids is not None:
+            ref, ref_len = torch.as_tensor(canonical_ids), torch.as_tensor(canonical_lens)
+            longest = max(longest, int(ref_len.max()) if ref_len.numel() else 0)
+        if longest > MBR_MAX_LEN:
+            raise ValueError("decode_mbr: a sequence of %d ids; mdd_nbest_mbr takes at most %d" % (longest, MBR_MAX_LEN))
+        mbr_ids = ids
+        if longest > ids.shape[2]:       # a canonical row longer than the T frames a hypothesis row holds: max_len bounds both, so widen the rows
+            mbr_ids = torch.nn.functional.pad(ids, (0, longest - ids.shape[2]))
+        loglik = self.nbest_loglik(lp, lens, ids, nids, max_len=int(nids_h.max()))
+        weights = np.zeros((N, B), dtype=np.float64)
+        for b in range(B):
+            post = nbest_posteriors(loglik[:, b])
+            if post is not None:
+                weights[:, b] = post
+        best, risk, flag, _, _, ref_risk = nbest_mbr(mbr_ids, nids, status, torch.from_numpy(weights), Cn, max_len=max(longest, 1), ref=ref,
+                                                     ref_len=ref_len)
+        best, risk, flag = best.cpu().numpy(), risk.cpu().numpy(), flag.cpu().numpy()
+        ref_risk = None if ref_risk is None else ref_risk.cpu().numpy()
+        out = []
+        for b in range(B):
+            if flag[b] != 0:
+                out.append(None)
+                continue
+            k = int(best[b])
+            string = " ".join(self.int_to_char[int(i)] for i in ids_h[k, b, :nids_h[k, b]])
+            out.append((string, k, float(risk[k, b]), float(risk[0, b]), None if ref_risk is None else float(ref_risk[b])))
+        return out
+
     def _strings(self, ids, nids, status):
         ids, nids, status = ids.cpu().numpy(), torch.as_tensor(nids).cpu().numpy(), status.cpu().numpy()
         bad = np.nonzero(status)[0]

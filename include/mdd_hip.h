@@ -292,6 +292,49 @@ int mdd_beam_wide(const float *logp_dev, int32_t T, int32_t B, int32_t C, const 
                   int32_t *status_dev /* [B] */,         double *score_dev /* [nbest,B], required */,
                   void *workspace_dev, int64_t workspace_bytes, void *stream);
 
+/* ---- Minimum-Bayes-risk decode of an N-best list (no reference counterpart: the reference sorts its final list and keeps `[0]`,
+ * AA/utils/BeamSearch.py:148): every pairwise edit distance inside an utterance's list, the expected distance of each hypothesis under
+ * the list's own weights, and the hypothesis that minimises it (csrc/mbr.hip, DESIGN.md "Minimum Bayes risk").
+ * Inputs: ids_dev [N,B,pitch] / nids_dev [N,B], hypothesis-major: mdd_beam_nbest's and mdd_beam_wide's outputs as they are; h_n of
+ *   utterance b is the first nids[n,b] ids of row (n,b).  status_dev [B] (nullable): non-zero = skip the utterance.  weight_dev [N,B]
+ *   fp64, finite and >= 0, e.g. each hypothesis' share of the list's CTC likelihood; they need not sum to 1.  Optionally a reference
+ *   sequence per utterance (the canonical ids): ref_dev [B,ref_pitch] / ref_len_dev [B]; both NULL or both set, ref_pitch >= 1 where set.
+ * d(x, y) is the unit-cost Levenshtein distance: the `dist` of mdd_align, and the other side's length where a side is empty.  Outputs:
+ *   dist_dev [B,N,N]   (nullable) dist[b,n,m] = d(h_n, h_m)
+ *   risk_dev [N,B]     fp64, risk[n,b] = sum_m weight[m,b] d(h_n, h_m); written for every n, also where weight[n,b] = 0
+ *   best_dev [B]       the lowest n with weight[n,b] > 0 that minimises risk[n,b]: ties go to the lower rank, so a list that agrees with
+ *                      itself keeps mdd_beam's answer
+ *   ref_dist_dev [N,B] (nullable) d(h_n, ref_b);   ref_risk_dev [B] (nullable) fp64, sum_n weight[n,b] d(h_n, ref_b).  Either without the
+ *                      reference is an argument error
+ *   flag_dev [B]       0 fine.  1 skipped: status[b] != 0, or no weight of the utterance is above 0.  2: a length outside [0, max_len]
+ *                      (the reference's: outside [0, min(max_len, ref_pitch)]) or, within a row's length, an id outside [0, C) -- the
+ *                      reference row included.  Looked at in this order: a skipped utterance by status is not read at all, and a bad
+ *                      length or id is flag 2 whatever the weights are.  A flagged utterance has best -1, risk and ref_risk NaN, dist
+ *                      and ref_dist -1, and changes nothing in its neighbours.
+ * Ids past a row's length are never read.  No id is used as an index before it is range-checked: the call first packs the checked ids,
+ *   one byte each, into the workspace, and the distance kernel reads only that.
+ * Ranges: 1 <= N <= 256 (mdd_beam_wide's bound), B >= 1, 2 <= C <= 256, 1 <= max_len <= min(pitch, 1024).  max_len bounds nids and picks
+ *   the kernel's form: 64-bit words of vertical deltas per pattern, 1, 2, 4, 8 or 16 of them for max_len up to 64, 128, 256, 512, 1024
+ *   (the bit-vector recurrence of Myers / Hyyro, csrc/mbr.h).  The one-word form is the fast one: a workgroup keeps the utterance's packed
+ *   list and four match tables in LDS (8 C x 4 + 64 (N + 1 rounded up to 16) bytes); the others read the list from the workspace and keep four
+ *   tables of 8 C words bytes (128 KB at C = 256, 16 words).  The counts are one host function, mbr_plan in csrc/plan.h.
+ * Arithmetic: the distances are integers and exact; risk in fp64, each lane of a wave adding weight[m] d for its texts m = lane, lane + 64,
+ *   .. in that order, then a butterfly over the 64 lanes: no floating-point atomics, the same bits on every call.
+ * workspace_dev: caller scratch of at least mdd_nbest_mbr_workspace_bytes(N, B, C, max_len) bytes (16-byte aligned; the packed lists:
+ *   B x 64 words x (N + 1 rounded up to 16) bytes), NULL = the library allocates stream-ordered for the call.
+ *   mdd_nbest_mbr_workspace_bytes returns 0 for a shape outside the ranges above.  Nothing synchronises.
+ * Bad arguments (a range above, a required pointer NULL, the reference given in part, a ref_* output without the reference, a caller
+ *   workspace that is too small) return MDD_ERR_ARG before any device work, with nothing written; the message starts with mdd_nbest_mbr
+ *   and names the argument. */
+int64_t mdd_nbest_mbr_workspace_bytes(int32_t N, int32_t B, int32_t C, int32_t max_len);
+int mdd_nbest_mbr(const int32_t *ids_dev /* [N,B,pitch] */, int32_t pitch, const int32_t *nids_dev /* [N,B] */,
+                  const int32_t *status_dev /* [B], nullable */, const double *weight_dev /* [N,B] */,
+                  int32_t N, int32_t B, int32_t C, int32_t max_len,
+                  const int32_t *ref_dev /* [B,ref_pitch], nullable */, const int32_t *ref_len_dev /* [B] */, int32_t ref_pitch,
+                  int32_t *best_dev /* [B] */, double *risk_dev /* [N,B] */, int32_t *dist_dev /* [B,N,N], nullable */,
+                  int32_t *ref_dist_dev /* [N,B], nullable */, double *ref_risk_dev /* [B], nullable */, int32_t *flag_dev /* [B] */,
+                  void *workspace_dev, int64_t workspace_bytes, void *stream);
+
 /* ---- A12: nn.CTCLoss(reduction='sum') pieces (AA/steps/train_ctc.py:72,186): alpha/beta lattice.
  * logp_dev [T,B,C], targets_dev [B,Lmax] int64 (padded), in_len_dev/tgt_len_dev [B] int64 ->
  * nll_dev [B] (per-utterance negative log-likelihood; the reference's loss is their sum; +inf for an utterance with no
