@@ -40,7 +40,7 @@ inline int refuse_workspace(const char *entry, const char *bytes_fn, int64_t giv
     return MDD_ERR_ARG;
 }
 
-// consecutive labels a lane owns in the wave forms of the lattice (ctc_wave_kernel, ctc_align_wave_kernel): 64 NL >= Lmax + 1 up to Lmax = 255
-inline int ctc_labels_per_lane(int Lmax) { return Lmax <= 63 ? 1 : (Lmax <= 127 ? 2 : 4); }
+// ctc_labels_per_lane(Lmax), the consecutive labels a lane owns in the wave forms of the lattice, is plan.h's (through mdd_internal.h): the
+// host-only plan of mdd_ctc_nbest reads it too.
 
 }  // namespace mdd

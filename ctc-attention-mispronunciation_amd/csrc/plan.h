@@ -58,7 +58,8 @@
 // launches carry no diagnostics, and its f32x6 products stay on the 192-row tile.
 //
 // The beam entries take no handle: their two switches (MDD_BEAM_GENERIC, MDD_BEAM_W) are read at every call by read_beam_switches(), and
-// beam_plan() below is their selection, the same kind of pure function.
+// beam_plan() below is their selection, the same kind of pure function.  mdd_ctc_nbest's two (MDD_CTC_NBEST_WAVES, MDD_CTC_NBEST_HPB: the
+// handles of its timing sweep) are read at every call by read_ctc_nbest_switches() for ctc_nbest_plan().
 #pragma once
 #include <stddef.h>
 #include <stdlib.h>
@@ -419,6 +420,72 @@ static inline MbrPlan mbr_plan(int N, int B, int C, int max_len) {
     p.smem = p.peq_bytes + p.text_bytes;
     p.utt = sizeof(unsigned) * (size_t)(p.Lp / 4) * p.NP;
     p.bytes = (size_t)B * p.utt;
+    return p;
+}
+
+// ---- Rescoring an N-best list (ctc_nbest.hip: mdd_ctc_nbest): the exact CTC log-likelihood of every hypothesis of every utterance in one
+// launch.  A workgroup of `waves` waves takes one utterance and hyps_per_block consecutive ranks: it stages the utterance's log-prob
+// block [T][C] fp32 into LDS once, then every wave runs the alpha scans of its ranks on its own (labels and lattice in registers: no LDS
+// per wave, no barrier behind the staging).  ctc_nbest_plan is the one place the counts come from: the entry, the launch and
+// mdd_ctc_nbest_fits read it.
+// consecutive labels a lane owns in the wave forms of the lattice (ctc_wave_kernel, ctc_align_wave_kernel, ctc_nbest_kernel): 64 NL >= Lmax + 1
+// up to Lmax = 255
+inline int ctc_labels_per_lane(int Lmax) { return Lmax <= 63 ? 1 : (Lmax <= 127 ? 2 : 4); }
+constexpr int kCtcNbestMaxN = kBeamWideMax;    // hypotheses of a list: the wide beam entry's bound
+constexpr int kCtcNbestMaxLen = 255;           // labels of a hypothesis: 64 lanes x 4 labels hold 2 max_len + 1 states
+constexpr int kCtcNbestMaxWaves = 16;          // waves of a workgroup the kernel is built for (its launch bounds)
+// Waves of a workgroup, a scan each at a time, and the ranks a workgroup takes.  A scan is bound by its SIMD's issue rate, not by waiting:
+// at B = 64, N = 10 a fifth scanning wave on a CU's four SIMDs lengthens the call from 0.086 to 0.119 ms (profiles/ctc_nbest_notes.txt),
+// and staging the block again costs far less than that.  So while
+// the list has no more scans than the device has SIMDs, a workgroup takes four ranks, one per SIMD of its CU (its other four waves only
+// help staging); beyond, ten, which stages less often and was the best or within 10 % of it at every full-device shape of the sweep,
+// also where a block over 80 KiB leaves a CU one workgroup.  The ranks are then dealt evenly over the groups (10 ranks as 5 + 5, not
+// 8 + 2).  The results do not depend on any of this.  MDD_CTC_NBEST_WAVES = w (1..16) and MDD_CTC_NBEST_HPB = h (1..256), read at every
+// call and taken as they are, are the sweep's handles.
+constexpr int kCtcNbestWaves = 8;
+constexpr int kCtcNbestSimds = 256 * 4;        // of an MI355X
+constexpr int kCtcNbestRanksSpread = 4, kCtcNbestRanksFull = 10;
+// The log-prob block of a launch.  At most 160 KiB is a CU's; this bound is lower for the bits' sake: mdd_ctc_loss runs ctc_wave_kernel,
+// whose nll the entry reproduces, while its block and 11.1 KiB of its own arrays (at C = 256, NL = 4) fit 128 KiB, and its general kernel
+// with other roundings beyond.  Every shape accepted here is one mdd_ctc_loss gives to ctc_wave_kernel.
+constexpr size_t kCtcNbestLdsMax = 116 * 1024;
+struct CtcNbestPlan {
+    int waves;            // waves of a workgroup
+    int hyps_per_block;   // consecutive ranks of a workgroup: wave w scans first + w, first + w + waves, ..
+    int NL;               // labels per lane: the instantiation
+    size_t smem;          // dynamic LDS: lpt [T][C] f32 (the waves keep nothing else there)
+    int groups;           // the grid is (groups, B): ceil(N / hyps_per_block)
+};
+inline bool ctc_nbest_fits(int T, int C, int max_len) {
+    return T >= 1 && C >= 2 && C <= 256 && max_len >= 0 && max_len <= kCtcNbestMaxLen && sizeof(float) * (size_t)T * C <= kCtcNbestLdsMax;
+}
+struct CtcNbestSwitches {
+    int waves = 0;   // MDD_CTC_NBEST_WAVES (0: unset)
+    int hpb = 0;     // MDD_CTC_NBEST_HPB (0: unset)
+};
+static inline CtcNbestSwitches read_ctc_nbest_switches() {
+    CtcNbestSwitches s;
+    const char *e = getenv("MDD_CTC_NBEST_WAVES");
+    int v = e ? atoi(e) : 0;
+    if (v >= 1 && v <= kCtcNbestMaxWaves) s.waves = v;
+    e = getenv("MDD_CTC_NBEST_HPB");
+    v = e ? atoi(e) : 0;
+    if (v >= 1 && v <= kCtcNbestMaxN) s.hpb = v;
+    return s;
+}
+static inline CtcNbestPlan ctc_nbest_plan(int T, int B, int C, int N, int max_len, const CtcNbestSwitches &sw = CtcNbestSwitches()) {
+    CtcNbestPlan p{};
+    p.waves = sw.waves ? sw.waves : kCtcNbestWaves;
+    p.NL = ctc_labels_per_lane(max_len);
+    p.smem = sizeof(float) * (size_t)T * C;
+    if (sw.hpb) {
+        p.hyps_per_block = sw.hpb;
+    } else {
+        const bool spread = 2 * p.smem <= 160 * 1024 && (long long)N * B <= kCtcNbestSimds;
+        const int target = spread ? kCtcNbestRanksSpread : kCtcNbestRanksFull, groups = (N + target - 1) / target;
+        p.hyps_per_block = (N + groups - 1) / groups;
+    }
+    p.groups = (N + p.hyps_per_block - 1) / p.hyps_per_block;
     return p;
 }
 

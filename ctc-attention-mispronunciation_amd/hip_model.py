@@ -159,8 +159,8 @@ class HipModel(object):
 
 
 class _CtcCall(object):
-    """What the five CTC lattice functions share: ``logp`` contiguous fp32 [T,B,C] on its device, conversion of the other arrays to that
-    device, and one call of an entry that ends ``..., workspace_dev, workspace_bytes, stream``."""
+    """What the six CTC lattice functions share: ``logp`` contiguous fp32 [T,B,C] on its device, conversion of the other arrays to that
+    device, and one call of an entry that ends ``..., workspace_dev, workspace_bytes, stream`` (``ctc_nbest``'s: ``..., stream``)."""
 
     def __init__(self, logp):
         assert logp.is_cuda and logp.dtype == torch.float32
@@ -185,8 +185,11 @@ class _CtcCall(object):
         return _lib.ptr(t if rows or t is None else self.ws)
 
     def __call__(self, entry, *args):
+        """``entry(logp, T, B, C, *args, workspace_dev, workspace_bytes, stream)``; an entry without a workspace (no ``workspace`` call
+        before this one: mdd_ctc_nbest) ends ``..., stream``."""
+        tail = () if self.ws is None else (self.ptr(self.ws), self.ws.numel() * 8)
         with torch.cuda.device(self.dev):
-            _lib.check(entry(self.ptr(self.logp), self.T, self.B, self.C, *args, self.ptr(self.ws), self.ws.numel() * 8, _lib.current_stream_ptr()))
+            _lib.check(entry(self.ptr(self.logp), self.T, self.B, self.C, *args, *tail, _lib.current_stream_ptr()))
 
 
 def ctc_loss(logp, targets, in_len, tgt_len, blank=0, want_grad=True):
@@ -198,6 +201,32 @@ def ctc_loss(logp, targets, in_len, tgt_len, blank=0, want_grad=True):
     c.workspace(_lib.lib().mdd_ctc_workspace_bytes, tg.shape[1], 1 if want_grad else 0)
     c(_lib.lib().mdd_ctc_loss, c.ptr(tg), tg.shape[1], c.ptr(il), c.ptr(tl), blank, c.ptr(nll), c.ptr(grad))
     return nll, grad
+
+
+def ctc_nbest_fits(T, C, max_len):
+    """Whether ``ctc_nbest`` takes posteriors of T frames and C classes with hypotheses of up to ``max_len`` ids (mdd_ctc_nbest_fits: at
+    most 255 ids, and the [T, C] fp32 block of an utterance within the kernel's LDS bound).  Host only."""
+    return bool(_lib.lib().mdd_ctc_nbest_fits(int(T), int(C), int(max_len)))
+
+
+def ctc_nbest(logp, lens, ids, nids, blank=0, max_len=None):
+    """Exact CTC log-likelihood of every hypothesis of an N-best list in one launch (mdd_ctc_nbest).
+
+    logp [T,B,C] fp32 CUDA, lens [B]; ids [N,B,pitch] / nids [N,B] as ``BeamDecoder.decode_nbest_ids`` returns them (int32 CUDA tensors
+    pass through with no copy).  ``max_len`` bounds nids (default: the ids' row length, so the call needs no sync); the shape must be one
+    ``ctc_nbest_fits`` accepts.  Returns ``loglik [N,B]`` float64 on the device: ``(-loglik).float()`` has the bits of ``ctc_loss``'s nll
+    for ``ids[n]``, so -inf where a hypothesis is no CTC path of the frames and NaN where one of its ids is outside the classes.  Nothing
+    synchronises."""
+    c = _CtcCall(logp)
+    lens, ids, nids = c.to(lens, torch.int32), c.to(ids, torch.int32), c.to(nids, torch.int32)
+    if ids.dim() != 3 or ids.shape[1] != c.B or lens.shape != (c.B,) or nids.shape != ids.shape[:2]:
+        raise ValueError("ctc_nbest: lens [B], ids [N, B, pitch], nids [N, B]")
+    N, _, pitch = ids.shape
+    Lmax = pitch if max_len is None else int(max_len)
+    loglik = c.empty((N, c.B), torch.float64)
+    # (rows of no ids at all: nothing is read through ids_dev, which must still be an address)
+    c(_lib.lib().mdd_ctc_nbest, c.ptr(lens), c.ptr(ids if pitch else nids), pitch, c.ptr(nids), N, Lmax, blank, c.ptr(loglik))
+    return loglik
 
 
 AlignResult = collections.namedtuple("AlignResult", "score status path seg seg_logp")

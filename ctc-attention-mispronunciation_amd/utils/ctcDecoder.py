@@ -430,14 +430,19 @@ class BeamDecoder(Decoder):
 
     def nbest_loglik(self, prob_tensor, frame_seq_len, ids, nids, max_len=None):
         """Exact CTC log-likelihood of every hypothesis of ``decode_nbest_ids``' ``ids [N,B,T]`` / ``nids [N,B]`` over its utterance's
-        frames, as a float64 numpy array [N,B]: one ``hip_model.ctc_loss`` call without gradient per slice (the fp32 nll of the training
-        lattice, negated), ``-inf`` where the lattice finds no path.  ``max_len`` bounds nids (default: the ids' row length); a tight
-        bound lets the lattice run in its one-wave form."""
-        from ..hip_model import ctc_loss
-        lp, T, B, _, lens = _posteriors_and_lens(prob_tensor, frame_seq_len)
+        frames, as a float64 numpy array [N,B]: the fp32 nll of the training lattice, negated, ``-inf`` where the lattice finds no path.
+        ``max_len`` bounds nids (default: the ids' row length); a tight bound lets the lattice keep fewer labels per lane.  Where
+        ``hip_model.ctc_nbest_fits`` takes the shape, all ranks are one ``hip_model.ctc_nbest`` launch, rounded through fp32 as the nll
+        is; otherwise (hypotheses past 255 ids, posteriors past the launch's LDS bound) one ``hip_model.ctc_loss`` call without
+        gradient per slice.  The same bytes either way."""
+        from .. import hip_model
+        lp, T, B, Cn, lens = _posteriors_and_lens(prob_tensor, frame_seq_len)
         lens = lens.clamp(0, T)
         width = ids.shape[2] if max_len is None else max(min(int(max_len), ids.shape[2]), 1)
-        nll = [ctc_loss(lp, ids[n, :, :width], lens, nids[n], blank=self.blank_index, want_grad=False)[0] for n in range(ids.shape[0])]
+        if 1 <= ids.shape[0] <= 256 and hip_model.ctc_nbest_fits(T, Cn, width):
+            loglik = hip_model.ctc_nbest(lp, lens, ids, nids, blank=self.blank_index, max_len=min(width, ids.shape[2]))
+            return -(-loglik).float().double().cpu().numpy()
+        nll = [hip_model.ctc_loss(lp, ids[n, :, :width], lens, nids[n], blank=self.blank_index, want_grad=False)[0] for n in range(ids.shape[0])]
         return -torch.stack(nll).double().cpu().numpy()
 
     def decode_nbest(self, prob_tensor, frame_seq_len=None, nbest=None, rescore=True):

@@ -335,6 +335,29 @@ int mdd_nbest_mbr(const int32_t *ids_dev /* [N,B,pitch] */, int32_t pitch, const
                   int32_t *ref_dist_dev /* [N,B], nullable */, double *ref_risk_dev /* [B], nullable */, int32_t *flag_dev /* [B] */,
                   void *workspace_dev, int64_t workspace_bytes, void *stream);
 
+/* ---- Rescoring an N-best list (no reference counterpart): the exact CTC log-likelihood of every hypothesis of every utterance in one
+ * launch (csrc/ctc_nbest.hip, DESIGN.md "N-best rescoring"), where one mdd_ctc_loss call per rank staged the same log-probs N times.
+ * Inputs: logp_dev [T,B,C] fp32, len_dev [B] (clamped to [0,T]); ids_dev [N,B,pitch] / nids_dev [N,B], hypothesis-major int32:
+ *   mdd_beam_nbest's and mdd_beam_wide's outputs as they are.  nids is clamped to [0, max_len]; ids past a row's length are never read.
+ * Output: loglik_dev [N,B] fp64, every element written.  (float)(-loglik[n,b]) has the bits of mdd_ctc_loss's nll for row (n, b) -- the
+ *   kernel restates ctc_wave_kernel's alpha scan step for step: finite, -inf where the hypothesis is no CTC path of the frames (also an
+ *   utterance without frames and a hypothesis with ids), 0 for an empty hypothesis of an utterance without frames, the sum of the blank
+ *   column for an empty hypothesis, and NaN for that (n, b) alone where a label within the row's length is outside [0, C).
+ * Ranges: 1 <= N <= 256 (mdd_beam_wide's bound), 1 <= B <= 65535 (the grid), 2 <= C <= 256, 0 <= blank < C, 0 <= max_len <= min(pitch,
+ *   255), T >= 1 with the utterance's log-prob block in LDS: 4 T C <= 116 KiB (T <= 659 at C = 45, 116 at C = 256).  The bound is where
+ *   mdd_ctc_loss still runs the kernel whose bits the entry reproduces; a caller routes on mdd_ctc_nbest_fits (host only, 1 / 0) and
+ *   takes mdd_ctc_loss per rank otherwise.  One workgroup of eight waves per utterance and group of ranks (four while the list has no
+ *   more scans than the device has SIMDs, ten beyond), a scan per wave at a time; the counts are one host function, ctc_nbest_plan in
+ *   csrc/plan.h.  MDD_CTC_NBEST_WAVES = w (1..16) and MDD_CTC_NBEST_HPB = h (1..256), read at every call, set the waves and the ranks of
+ *   a workgroup for timing sweeps (tools/time_ctc_nbest.py); the results do not depend on them.
+ * One launch on the caller's stream, no workspace, nothing synchronises; the same call gives the same bits every time.
+ * Bad arguments (a range above, a pointer NULL, a shape mdd_ctc_nbest_fits refuses) return MDD_ERR_ARG before any device work, with
+ *   nothing written; the message starts with mdd_ctc_nbest and names the argument. */
+int mdd_ctc_nbest_fits(int32_t T, int32_t C, int32_t max_len);         /* 1 / 0, host only */
+int mdd_ctc_nbest(const float *logp_dev /* [T,B,C] */, int32_t T, int32_t B, int32_t C, const int32_t *len_dev /* [B] */,
+                  const int32_t *ids_dev /* [N,B,pitch] */, int32_t pitch, const int32_t *nids_dev /* [N,B] */,
+                  int32_t N, int32_t max_len, int32_t blank, double *loglik_dev /* [N,B] */, void *stream);
+
 /* ---- A12: nn.CTCLoss(reduction='sum') pieces (AA/steps/train_ctc.py:72,186): alpha/beta lattice.
  * logp_dev [T,B,C], targets_dev [B,Lmax] int64 (padded), in_len_dev/tgt_len_dev [B] int64 ->
  * nll_dev [B] (per-utterance negative log-likelihood; the reference's loss is their sum; +inf for an utterance with no
