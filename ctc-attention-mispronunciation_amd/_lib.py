@@ -17,7 +17,7 @@ MDD_ERR_EMPTY = -5   # include/mdd_hip.h: an empty sequence where the reference 
 EXPORTS = (
     "mdd_last_error", "mdd_version", "mdd_create", "mdd_create_ctc", "mdd_is_ctc_only", "mdd_destroy", "mdd_load_weight", "mdd_finalize_weights",
     "mdd_set_precision", "mdd_get_precision", "mdd_stack_len", "mdd_stack_skip", "mdd_len_frames", "mdd_forward", "mdd_forward_fused", "mdd_forward_candidates", "mdd_forward_raw", "mdd_forward_num_stages", "mdd_forward_profile", "mdd_tap", "mdd_tap_copy", "mdd_enable_taps", "mdd_sync",
-    "mdd_greedy", "mdd_beam", "mdd_beam_nbest", "mdd_beam_fits", "mdd_beam_wide_workspace_bytes", "mdd_beam_wide", "mdd_nbest_mbr_workspace_bytes", "mdd_nbest_mbr", "mdd_ctc_nbest_fits", "mdd_ctc_nbest", "mdd_ctc_loss", "mdd_ctc_workspace_bytes", "mdd_ctc_align", "mdd_ctc_align_workspace_bytes", "mdd_ctc_variants", "mdd_ctc_variants_workspace_bytes", "mdd_ctc_confnet", "mdd_ctc_confnet_workspace_bytes", "mdd_ctc_confnet_max_slots", "mdd_ctc_confnet_best", "mdd_ctc_confnet_best_workspace_bytes", "mdd_align", "mdd_align_batch", "mdd_eval_batch", "mdd_fbank_num_frames", "mdd_fbank", "mdd_fbank_batch_len", "mdd_fbank_batch",
+    "mdd_greedy", "mdd_beam", "mdd_beam_nbest", "mdd_beam_fits", "mdd_beam_wide_workspace_bytes", "mdd_beam_wide", "mdd_nbest_mbr_workspace_bytes", "mdd_nbest_mbr", "mdd_ctc_nbest_fits", "mdd_ctc_nbest", "mdd_ctc_nbest_grad_fits", "mdd_ctc_nbest_grad_workspace_bytes", "mdd_ctc_nbest_grad", "mdd_nbest_risk", "mdd_ctc_loss", "mdd_ctc_workspace_bytes", "mdd_ctc_align", "mdd_ctc_align_workspace_bytes", "mdd_ctc_variants", "mdd_ctc_variants_workspace_bytes", "mdd_ctc_confnet", "mdd_ctc_confnet_workspace_bytes", "mdd_ctc_confnet_max_slots", "mdd_ctc_confnet_best", "mdd_ctc_confnet_best_workspace_bytes", "mdd_align", "mdd_align_batch", "mdd_eval_batch", "mdd_fbank_num_frames", "mdd_fbank", "mdd_fbank_batch_len", "mdd_fbank_batch",
     "mdd_fbank_batch_aug", "mdd_cmvn_accumulate",
     "mdd_resample_len", "mdd_resample_filter", "mdd_resample_batch",
     "mdd_train_create", "mdd_train_destroy", "mdd_train_num_tensors", "mdd_train_tensor_info", "mdd_train_num_masks", "mdd_train_mask_bytes",
@@ -98,6 +98,13 @@ def lib():
         L.mdd_ctc_nbest_fits.argtypes = [i32, i32, i32]
         L.mdd_ctc_nbest_fits.restype = i32
         L.mdd_ctc_nbest.argtypes = [vp, i32, i32, i32, vp, vp, i32, vp, i32, i32, i32, vp, vp]
+    if hasattr(L, "mdd_ctc_nbest_grad"):   # (a build of an earlier commit under MDD_LIB_PATH lacks the entry)
+        L.mdd_ctc_nbest_grad_fits.argtypes = [i32, i32, i32]
+        L.mdd_ctc_nbest_grad_fits.restype = i32
+        L.mdd_ctc_nbest_grad_workspace_bytes.argtypes = [i32, i32, i32, i32, i32]
+        L.mdd_ctc_nbest_grad_workspace_bytes.restype = C.c_int64
+        L.mdd_ctc_nbest_grad.argtypes = [vp, i32, i32, i32, vp, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, C.c_int64, vp]
+        L.mdd_nbest_risk.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]
     L.mdd_ctc_loss.argtypes =[vp, i32, i32, i32, vp, i32, vp, vp, i32, vp, vp, vp, C.c_int64, vp]
     L.mdd_ctc_workspace_bytes.argtypes = [i32, i32, i32, i32, i32]
     L.mdd_ctc_workspace_bytes.restype = C.c_int64

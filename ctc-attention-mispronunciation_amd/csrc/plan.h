@@ -489,4 +489,50 @@ static inline CtcNbestPlan ctc_nbest_plan(int T, int B, int C, int N, int max_le
     return p;
 }
 
+// ---- MWER training (ctc_nbest_grad.hip: mdd_ctc_nbest_grad): sum_n coef[n,b] * (the gradient mdd_ctc_loss deposits for hypothesis n) in one
+// call.  A workgroup of eight waves takes one utterance and `ranks` consecutive ranks, one after the other: alpha on wave 0, beta on wave 1,
+// then all waves turn frames into occupancy rows and add them into an LDS accumulator.  Its LDS is ctc_wave_kernel's with the accumulator
+// beside the block:  lpt [T][C] f32 | acc [T][C] f32 | lab [LC] i32 | cls_off [C + 1] i32 | cls_idx [LC] i32 | gam [8][LC] f32  (LC = 64 NL),
+// rounded up to 16 bytes, at most kCtcNbestGradLdsMax (a CU's 160 KiB less the kernel's few static bytes); the block is then at most
+// 80 KiB, so every shape accepted here is one mdd_ctc_nbest_fits accepts and one mdd_ctc_loss gives to ctc_wave_kernel.
+// With 90 KiB and more a CU holds one workgroup, and a rank is a chain of T dependent steps: the ranks are spread over as many groups as
+// leave the launch within one workgroup per CU (kCtcNbestGradCus / B, at least one), dealt evenly (10 ranks over 8 groups as 5 x 2).
+// The workspace:  rows [groups * B][2][T][SP] f64 (SP = 2 (max_len + 1): a workgroup's alpha and beta rows, reused from rank to rank) and,
+// with more than one group, slabs [groups][T][B][C] f32 (each group's partial sum) and gflag [groups][B] i32.  No switch is read: the
+// counts, and with them the bits, follow from the shape alone.
+constexpr int kCtcNbestGradWaves = 8;
+constexpr int kCtcNbestGradCus = 256;          // of an MI355X
+constexpr size_t kCtcNbestGradLdsMax = 160 * 1024 - 256;
+struct CtcNbestGradPlan {
+    int NL;               // labels per lane: the instantiation
+    int ranks;            // consecutive ranks of a workgroup
+    int groups;           // the grid is (groups, B): ceil(N / ranks)
+    int SP;               // pitch of a lattice row in doubles
+    size_t smem;          // dynamic LDS
+    size_t rows_bytes, slab_bytes, flag_bytes, bytes;      // the workspace's three parts and their sum
+};
+inline size_t ctc_nbest_grad_smem(int T, int C, int NL) {
+    const size_t LC = 64 * (size_t)NL;
+    return (2 * sizeof(float) * (size_t)T * C + 4 * LC + 4 * ((size_t)C + 1) + 4 * LC + 4 * kCtcNbestGradWaves * LC + 15) & ~(size_t)15;
+}
+inline bool ctc_nbest_grad_fits(int T, int C, int max_len) {
+    return T >= 1 && T <= (1 << 20) && C >= 2 && C <= 256 && max_len >= 0 && max_len <= kCtcNbestMaxLen &&
+           ctc_nbest_grad_smem(T, C, ctc_labels_per_lane(max_len)) <= kCtcNbestGradLdsMax;
+}
+static inline CtcNbestGradPlan ctc_nbest_grad_plan(int T, int B, int C, int N, int max_len) {
+    CtcNbestGradPlan p{};
+    p.NL = ctc_labels_per_lane(max_len);
+    p.smem = ctc_nbest_grad_smem(T, C, p.NL);
+    int groups = kCtcNbestGradCus / B;
+    groups = groups < 1 ? 1 : (groups > N ? N : groups);
+    p.ranks = (N + groups - 1) / groups;
+    p.groups = (N + p.ranks - 1) / p.ranks;
+    p.SP = 2 * (max_len + 1);
+    p.rows_bytes = sizeof(double) * (size_t)p.groups * B * 2 * T * p.SP;
+    p.slab_bytes = p.groups > 1 ? sizeof(float) * (size_t)p.groups * T * B * C : 0;
+    p.flag_bytes = p.groups > 1 ? sizeof(int32_t) * (size_t)p.groups * B : 0;
+    p.bytes = p.rows_bytes + p.slab_bytes + p.flag_bytes;
+    return p;
+}
+
 }  // namespace mdd

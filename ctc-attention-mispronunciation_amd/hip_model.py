@@ -229,7 +229,60 @@ def ctc_nbest(logp, lens, ids, nids, blank=0, max_len=None):
     return loglik
 
 
-AlignResult = collections.namedtuple("AlignResult", "score status path seg seg_logp")
+def ctc_nbest_grad_fits(T, C, max_len):
+    """Whether ``ctc_nbest_grad`` takes posteriors of T frames and C classes with hypotheses of up to ``max_len`` ids
+    (mdd_ctc_nbest_grad_fits: at most 255 ids, and the [T, C] block, an accumulator of its size and the lattice's arrays within a
+    workgroup's LDS; every shape it accepts ``ctc_nbest_fits`` accepts).  Host only."""
+    return bool(_lib.lib().mdd_ctc_nbest_grad_fits(int(T), int(C), int(max_len)))
+
+
+def ctc_nbest_grad(logp, lens, ids, nids, coef, blank=0, max_len=None, want_loglik=False):
+    """``grad[t,b,c] = sum_n coef[n,b] g_n[t,b,c]`` in one call (mdd_ctc_nbest_grad), g_n the tensor ``ctc_loss`` deposits on the log-probs
+    for hypothesis n as target: the gradient of the MWER objective with ``nbest_risk``'s coefficients.
+
+    logp, lens, ids, nids, max_len as ``ctc_nbest`` takes them; coef [N,B] float64.  A rank with ``coef == 0`` is not scanned.  The shape
+    must be one ``ctc_nbest_grad_fits`` accepts.  Returns device tensors ``(grad [T,B,C] f32, flag [B] i32, loglik [N,B] f64 | None)``:
+    flag 1 where a rank with a non-zero coef is no CTC path of the frames, 2 where one has an id outside the classes or a coef is not
+    finite -- such an utterance has all-zero rows; loglik has ``ctc_nbest``'s bits on scanned ranks and NaN on skipped ones.  Nothing
+    synchronises."""
+    c = _CtcCall(logp)
+    lens, ids, nids, coef = c.to(lens, torch.int32), c.to(ids, torch.int32), c.to(nids, torch.int32), c.to(coef, torch.float64)
+    if ids.dim() != 3 or ids.shape[1] != c.B or lens.shape != (c.B,) or nids.shape != ids.shape[:2] or coef.shape != ids.shape[:2]:
+        raise ValueError("ctc_nbest_grad: lens [B], ids [N, B, pitch], nids [N, B], coef [N, B]")
+    N, _, pitch = ids.shape
+    Lmax = pitch if max_len is None else int(max_len)
+    grad, flag = torch.empty_like(c.logp), c.empty((c.B,), torch.int32)
+    loglik = c.empty((N, c.B), torch.float64, want_loglik)
+    c.workspace(_lib.lib().mdd_ctc_nbest_grad_workspace_bytes, N, Lmax)
+    c(_lib.lib().mdd_ctc_nbest_grad, c.ptr(lens), c.ptr(ids if pitch else nids), pitch, c.ptr(nids), N, Lmax, blank, c.ptr(coef), c.ptr(loglik),
+      c.ptr(grad), c.ptr(flag))
+    return grad, flag, loglik
+
+
+def nbest_risk(loglik, cost, status=None):
+    """Posteriors, risk and MWER coefficients of an N-best list (mdd_nbest_risk): loglik [N,B] float64 (``ctc_nbest``'s), cost [N,B] int32
+    (``nbest_mbr``'s ref_dist), status [B] or None.  Returns device tensors ``(post [N,B] f64, risk [B] f64, coef [N,B] f64, flag [B]
+    i32)``: post the softmax over the ranks with a finite loglik, risk = sum post cost, coef = post (risk - cost) = d risk / d nll.
+    flag 1 (status non-zero, or no finite rank) or 2 (a negative cost) gives post and coef 0 and risk NaN.  Nothing synchronises."""
+    loglik = torch.as_tensor(loglik)
+    if not loglik.is_cuda:
+        _lib.require_gpu()
+    loglik = _lib.to_gpu(loglik, torch.float64)
+    dev = loglik.device
+    cost = torch.as_tensor(cost).to(dev, torch.int32).contiguous()
+    status = None if status is None else torch.as_tensor(status).to(dev, torch.int32).contiguous()
+    if loglik.dim() != 2 or cost.shape != loglik.shape or (status is not None and status.shape != loglik.shape[1:]):
+        raise ValueError("nbest_risk: loglik [N, B], cost [N, B], status [B]")
+    N, B = loglik.shape
+    post, coef = torch.empty_like(loglik), torch.empty_like(loglik)
+    risk, flag = torch.empty((B,), dtype=torch.float64, device=dev), torch.empty((B,), dtype=torch.int32, device=dev)
+    p = _lib.ptr
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().mdd_nbest_risk(p(loglik), p(cost), p(status), N, B, p(post), p(risk), p(coef), p(flag), _lib.current_stream_ptr()))
+    return post, risk, coef, flag
+
+
+AlignResult =collections.namedtuple("AlignResult", "score status path seg seg_logp")
 ALIGN_OK, ALIGN_INFEASIBLE, ALIGN_BAD_TARGET = 0, 1, 2      # include/mdd_hip.h: mdd_align_status
 
 

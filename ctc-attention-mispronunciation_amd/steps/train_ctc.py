@@ -227,6 +227,31 @@ def check_conf(conf):
     return route
 
 
+def check_mwer(conf):
+    """The MWER and fine-tuning keys of a conf: ``mwer_nbest`` (N hypotheses, 2..256; absent or 0: off), ``mwer_weight`` (1.0),
+    ``mwer_ctc_weight`` (0.01), ``mwer_beam_width`` (``max(N, 10)``, at most 256) and ``init_model`` (a package of
+    ``CTC_Model.save_package`` whose weights the run starts from; with or without ``mwer_nbest``).  Returns ``(N, beam_width)``, N = 0 for
+    off, or refuses (status 2, one line on stderr) before any data is read or the device is touched."""
+    init = conf.get("init_model")
+    if init and not os.path.isfile(init):
+        refuse("init_model: no file at %s" % init)
+    n = conf.get("mwer_nbest") or 0
+    if not n:
+        return 0, 0
+    if not isinstance(n, int) or not 2 <= n <= 256:
+        refuse("mwer_nbest %r: the N-best list of the MWER loss takes 2..256 hypotheses" % (n,))
+    beam = conf.get("mwer_beam_width") or max(n, 10)
+    if not isinstance(beam, int) or not 1 <= beam <= 256:
+        refuse("mwer_beam_width %r: the beam search takes a width of 1..256" % (beam,))
+    if n > beam:
+        refuse("mwer_nbest %d exceeds mwer_beam_width %d: the search lists at most its beam" % (n, beam))
+    if not conf.get("lm_path"):
+        refuse("mwer_nbest needs lm_path: the beam search that makes the list reads its bigram table from there")
+    if not os.path.isfile(conf["lm_path"]):
+        refuse("lm_path: no file at %s" % conf["lm_path"])
+    return n, beam
+
+
 def read_table(path):
     """'<key> <rest of line>' lines -> ordered (key, rest) pairs; keys as SpeechDataset reads them (cut at the first '.')."""
     rows = []
@@ -275,8 +300,10 @@ def main(conf):
     conf's rnn_* and CNN keys, the epoch loop with the reference's printed lines, the best-accuracy state into
     ``checkpoint_dir/exp_name/ctc_best_model.pkl`` -- the checkpoint ``infer.load_model`` reads.  New conf keys: ``train_wav_scp`` /
     ``valid_wav_scp`` + ``cmvn_path`` (the WAV route, ``TrainWavLoader``), ``speed_perturb`` (a list of factors for it),
-    ``train_precision`` ("f32", "bf16x3" or "f32x6").  Every rank reads the whole data: sharding it is not built."""
+    ``train_precision`` ("f32", "bf16x3" or "f32x6"), ``init_model`` and the ``mwer_*`` keys (``check_mwer``: fine-tuning towards the
+    phoneme error rate with ``train.MWERLoss`` on the training epochs; needs ``lm_path``, reads ``lm_alpha``).  Every rank reads the whole data: sharding it is not built."""
     route = check_conf(conf)
+    mwer_nbest, mwer_beam = check_mwer(conf)
     import ast
     import time
 
@@ -334,6 +361,9 @@ def main(conf):
                  "layer": [[channel[n], kernel_size[n], stride[n], padding[n], pooling[n] if pooling is not None else None]
                            for n in range(opts.layers)]}
     model = CTC_Model(add_cnn=opts.add_cnn, cnn_param=cnn_param, rnn_param=rnn_param, num_class=num_class, drop_out=opts.drop_out)
+    if getattr(opts, "init_model", None):                    # fine-tuning: the weights of an earlier run's package
+        model.load_state_dict(torch.load(opts.init_model, map_location="cpu", weights_only=False)["state_dict"])
+        print("Initial weights from %s" % opts.init_model)
     model = model.to(device)
     if precision is not None:
         model.train_precision = precision
@@ -346,13 +376,20 @@ def main(conf):
               'feature_type': opts.feature_type, 'n_feats': opts.feature_dim}
     print(params)
     loss_fn, optimizer = build_training(model, init_lr=opts.init_lr, weight_decay=opts.weight_decay)
+    train_loss_fn = loss_fn
+    if mwer_nbest:       # the training epochs alone: the validation epoch keeps the CTC loss, so dev_loss, the schedule and the best checkpoint keep their meaning
+        from ..train import MWERLoss
+        from ..utils.ctcDecoder import BeamDecoder
+        decoder = BeamDecoder(vocab.index2word, beam_width=mwer_beam, lm_path=opts.lm_path, lm_alpha=getattr(opts, "lm_alpha", 0.01))
+        train_loss_fn = MWERLoss(decoder, mwer_nbest, ctc_weight=getattr(opts, "mwer_ctc_weight", 0.01), mwer_weight=getattr(opts, "mwer_weight", 1.0))
+        print("MWER training: %d-best of beam %d, mwer_weight %g, ctc_weight %g" % (mwer_nbest, mwer_beam, train_loss_fn.mwer_weight, train_loss_fn.ctc_weight))
     schedule = LrSchedule(model, optimizer, opts.init_lr, opts.lr_decay, opts.end_adjust_acc, opts.num_epoches)
     start_time = time.time()
     loss_results, dev_loss_results, dev_cer_results = [], [], []
     while schedule.begin_epoch():
         count = schedule.count
         print("Start training epoch: %d, learning_rate: %.5f" % (count, schedule.learning_rate))
-        _, loss = run_epoch(count, model, train_loader, loss_fn, device, optimizer=optimizer, print_every=opts.verbose_step, is_training=True)
+        _, loss = run_epoch(count, model, train_loader, train_loss_fn, device, optimizer=optimizer, print_every=opts.verbose_step, is_training=True)
         loss_results.append(loss)
         acc, dev_loss = run_epoch(count, model, dev_loader, loss_fn, device, optimizer=None, print_every=opts.verbose_step, is_training=False)
         dev_loss_results.append(dev_loss)

@@ -6,6 +6,9 @@
 * ``model_forward_train(model, x, x1, masks=None)``   what ``CTC_Model.forward`` calls in train mode; differentiable w.r.t. every
   parameter (autograd Function; the model's BatchNorm running statistics are updated in place, as nn.BatchNorm does).
 * ``CTCLoss``       drop-in for ``nn.CTCLoss`` (same constructor / call signature, train_ctc.py:72,186) over mdd_ctc_loss.
+* ``MWERLoss``      the expected number of phoneme errors over the beam search's N-best list, interpolated with the CTC loss; called like
+  ``CTCLoss`` (mdd_beam_nbest -> mdd_ctc_nbest -> mdd_nbest_mbr -> mdd_nbest_risk -> mdd_ctc_nbest_grad); torch only
+  weights and adds the two gradient tensors and sums the per-utterance scalars.
 * ``Adam``          ``torch.optim.Adam``-compatible optimizer (lr, betas, eps, weight_decay, state_dict) over mdd_adam_step.
 PyTorch supplies device memory, streams and the autograd tape; no torch operator computes anything on this path.
 """
@@ -157,17 +160,7 @@ class CTCLoss(torch.nn.Module):
         dev = log_probs.device
         il = torch.as_tensor(input_lengths, dtype=torch.int64)
         tl = torch.as_tensor(target_lengths, dtype=torch.int64)
-        tg = torch.as_tensor(targets)
-        if tg.dim() == 1:                                           # concatenated targets -> padded [B, Lmax]
-            B, Lm = tl.numel(), int(tl.max()) if tl.numel() else 0
-            pad = torch.zeros((B, max(Lm, 1)), dtype=torch.int64)
-            off = 0
-            tgc = tg.cpu()
-            for b in range(B):
-                n = int(tl[b])
-                pad[b, :n] = tgc[off:off + n]
-                off += n
-            tg = pad
+        tg = _padded_targets(targets, tl)                           # concatenated targets -> padded [B, Lmax]
         nll = _CTCLossFn.apply(log_probs, tg.to(dev), il.to(dev), tl.to(dev), self.blank)
         if self.zero_infinity:
             nll = torch.where(torch.isinf(nll), torch.zeros_like(nll), nll)
@@ -176,6 +169,121 @@ class CTCLoss(torch.nn.Module):
         if self.reduction == "sum":
             return nll.sum()
         return (nll / tl.to(dev).clamp(min=1).to(nll.dtype)).mean()
+
+
+def _padded_targets(targets, target_lengths):
+    """Targets as a padded 2-D int64 tensor [B, Lmax] (concatenated 1-D targets are cut at the lengths, as ``CTCLoss.forward`` does)."""
+    tl = torch.as_tensor(target_lengths, dtype=torch.int64)
+    tg = torch.as_tensor(targets)
+    if tg.dim() != 1:
+        return tg
+    B, Lm = tl.numel(), int(tl.max()) if tl.numel() else 0
+    pad = torch.zeros((B, max(Lm, 1)), dtype=torch.int64)
+    off, tgc = 0, tg.cpu()
+    for b in range(B):
+        n = int(tl[b])
+        pad[b, :n] = tgc[off:off + n]
+        off += n
+    return pad
+
+
+class _MWERLossFn(torch.autograd.Function):
+    """The whole chain on ``log_probs.detach()``; the gradient is made in ``forward`` and scaled by the upstream scalar in ``backward``."""
+
+    @staticmethod
+    def forward(ctx, log_probs, targets, input_lengths, target_lengths, mod):
+        from . import hip_model
+        lp = log_probs.detach()
+        want_grad = log_probs.requires_grad
+        T, B, Cn = lp.shape
+        blank, N = mod.blank, mod.nbest
+        lens = input_lengths.to(lp.device, torch.int32).clamp(0, T)
+        nll, grad_ctc = hip_model.ctc_loss(lp, targets, input_lengths, target_lengths, blank=blank, want_grad=want_grad)
+        # 1. the list; its longest hypothesis bounds the lattices (one host synchronisation: a tight bound is a quarter of the scan's work)
+        ids, nids, status, _ = mod.decoder.decode_nbest_ids(lp, lens, N)
+        pitch = ids.shape[2]
+        width = max(int(nids.max().item()), 1)
+        one_launch = hip_model.ctc_nbest_fits(T, Cn, width)
+        fused = not mod.per_rank and one_launch and hip_model.ctc_nbest_grad_fits(T, Cn, width)
+        per_rank = None
+        if not one_launch or (want_grad and not fused):
+            per_rank = [hip_model.ctc_loss(lp, ids[n, :, :width], lens, nids[n], blank=blank, want_grad=want_grad) for n in range(N)]
+        # 2. exact log-likelihoods, fp64 as the kernel leaves them (the per-rank route has the same values rounded through fp32)
+        if one_launch:
+            loglik = hip_model.ctc_nbest(lp, lens, ids, nids, blank=blank, max_len=width)
+        else:
+            loglik = -torch.stack([r[0] for r in per_rank]).double()
+        # 3. edit distances to the annotated phones (uniform weights: only ref_dist is used)
+        ref = targets.to(lp.device, torch.int32)
+        L_mbr = max(pitch, ref.shape[1], 1)
+        if L_mbr > hip_model.MBR_MAX_LEN:
+            raise ValueError("MWERLoss: a sequence of %d ids; mdd_nbest_mbr takes at most %d" % (L_mbr, hip_model.MBR_MAX_LEN))
+        mbr_ids = ids if L_mbr == pitch else torch.nn.functional.pad(ids, (0, L_mbr - pitch))
+        uniform = torch.full((N, B), 1.0 / N, dtype=torch.float64, device=lp.device)
+        ref_dist = hip_model.nbest_mbr(mbr_ids, nids, status, uniform, Cn, max_len=L_mbr, ref=ref, ref_len=target_lengths)[4]
+        # 4. posteriors, risk, coefficients
+        post, risk, coef, flag = hip_model.nbest_risk(loglik, ref_dist, status)
+        # 5. the gradient of the risk
+        grad = None
+        if want_grad:
+            if fused:
+                grad, gflag, _ = hip_model.ctc_nbest_grad(lp, lens, ids, nids, coef, blank=blank, max_len=width)
+            else:
+                grad = torch.zeros_like(lp)
+                gflag = torch.zeros_like(flag)
+                for n, (nll_n, g_n) in enumerate(per_rank):
+                    live = coef[n] != 0
+                    gflag = torch.where(live & ~torch.isfinite(nll_n), torch.ones_like(gflag), gflag)
+                    k = coef[n].float().view(1, B, 1)
+                    grad = grad + torch.where(live.view(1, B, 1), k * g_n, torch.zeros_like(g_n))
+            flag = torch.maximum(flag, gflag)
+            flagged = (flag != 0).view(1, B, 1)
+            grad = torch.where(flagged, torch.zeros_like(grad), grad) * mod.mwer_weight + grad_ctc * mod.ctc_weight
+        risk = torch.where(flag != 0, torch.zeros_like(risk), risk)
+        mod.last = dict(ids=ids, nids=nids, status=status, loglik=loglik, ref_dist=ref_dist, post=post, risk=risk, coef=coef, flag=flag,
+                        nll=nll, fused=fused)
+        ctx.save_for_backward(grad if grad is not None else torch.empty(0))
+        return (mod.mwer_weight * risk.sum() + mod.ctc_weight * nll.double().sum()).float()
+
+    @staticmethod
+    def backward(ctx, gout):
+        (grad,) = ctx.saved_tensors
+        return grad * gout, None, None, None, None
+
+
+class MWERLoss(torch.nn.Module):
+    """Minimum-word-error-rate training (Prabhavalkar et al. 2018) on phonemes: the expected number of phoneme errors over the N-best
+    list the beam search returns, interpolated with the CTC loss --
+    ``mwer_weight * sum_b R_b + ctc_weight * sum_b nll_b``,  ``R_b = sum_n P_n d(h_n, targets_b)``,  ``P = softmax_n(loglik_n)``.
+
+    ``decoder``: a ``BeamDecoder`` (its ``decode_nbest_ids`` makes the list; ``nbest <= decoder.beam_width``).  Called like ``CTCLoss``
+    with ``(log_probs [T,B,C], targets, input_lengths, target_lengths)``; the value is a sum over the batch (``reduction='sum'``: the
+    training loop's ``/ batch_size`` applies unchanged).  Inside one autograd Function, on ``log_probs.detach()``:
+    ``decoder.decode_nbest_ids`` -> ``hip_model.ctc_nbest`` (fp64, no round trip through fp32) -> ``hip_model.nbest_mbr`` with the
+    targets as reference and uniform weights (for ``ref_dist`` alone) -> ``hip_model.nbest_risk`` -> ``hip_model.ctc_nbest_grad``; the
+    saved gradient is scaled by the upstream scalar in ``backward``.  The list is a constant of the step: no gradient flows through the
+    search.  An utterance the chain flags (a search status, no hypothesis that is a CTC path, a target id outside the classes) adds 0
+    to the risk term and zero rows to its gradient; the CTC term is ``CTCLoss``'s for every utterance.  Where ``ctc_nbest_fits`` or
+    ``ctc_nbest_grad_fits`` refuses the shape (or with ``per_rank=True``) the log-likelihoods and the gradient come from one
+    ``hip_model.ctc_loss`` call per rank with the same coefficients.  ``ctc_weight`` 0.01 is the paper's interpolation weight: a default,
+    not a claim about this model.  ``last`` keeps the step's device tensors (list, loglik, ref_dist, post, risk, coef, flag, nll).
+
+    Out of scope: adding the annotated sequence to the list when the search did not find it; sampled lists; length-normalised
+    posteriors."""
+
+    def __init__(self, decoder, nbest, ctc_weight=0.01, mwer_weight=1.0, blank=0, per_rank=False):
+        super(MWERLoss, self).__init__()
+        if not 2 <= int(nbest) <= min(256, decoder.beam_width):
+            raise ValueError("MWERLoss: nbest must be in [2, min(256, beam_width = %d)]" % decoder.beam_width)
+        self.decoder, self.nbest, self.ctc_weight, self.mwer_weight, self.blank = decoder, int(nbest), float(ctc_weight), float(mwer_weight), blank
+        self.per_rank, self.last = per_rank, None
+
+    def forward(self, log_probs, targets, input_lengths, target_lengths):
+        dev = log_probs.device
+        il = torch.as_tensor(input_lengths, dtype=torch.int64).to(dev)
+        tl = torch.as_tensor(target_lengths, dtype=torch.int64).to(dev)
+        tg = _padded_targets(targets, target_lengths).to(dev)
+        return _MWERLossFn.apply(log_probs, tg, il, tl, self)
 
 
 class Adam(torch.optim.Optimizer):

@@ -358,6 +358,52 @@ int mdd_ctc_nbest(const float *logp_dev /* [T,B,C] */, int32_t T, int32_t B, int
                   const int32_t *ids_dev /* [N,B,pitch] */, int32_t pitch, const int32_t *nids_dev /* [N,B] */,
                   int32_t N, int32_t max_len, int32_t blank, double *loglik_dev /* [N,B] */, void *stream);
 
+/* ---- MWER training (no reference counterpart; Prabhavalkar et al. 2018): the expected number of phoneme errors over the N-best list as a
+ * training objective (csrc/ctc_nbest_grad.hip, DESIGN.md "MWER training").  With nll_n the CTC negative log-likelihood of hypothesis n,
+ * g_n the tensor mdd_ctc_loss deposits on the log-probs for it as target, and cost[n,b] its edit distance to the annotated phones
+ * (mdd_nbest_mbr's ref_dist):  P = softmax_n(-nll_n),  R_b = sum_n P_n cost_n,  dR_b/dnll_n = P_n (R_b - cost_n) =: coef[n,b], and the
+ * tensor R_b deposits on the log-probs is sum_n coef[n,b] g_n.
+ *
+ * mdd_nbest_risk: loglik_dev [N,B] fp64 (mdd_ctc_nbest's output), cost_dev [N,B] int32, status_dev [B] or NULL -> post_dev [N,B] (the
+ *   fp64 softmax over the ranks whose loglik is finite; -inf, +inf and NaN ranks get 0), risk_dev [B] = sum post cost, coef_dev [N,B] =
+ *   post (risk - cost), flag_dev [B].  One wave per utterance, lanes take ranks lane, lane + 64, .. and a butterfly adds them: the same
+ *   bits on every call.  flag 1: status[b] != 0, or no rank is finite; flag 2: a negative cost (the -1 of a row mdd_nbest_mbr flagged);
+ *   status is looked at first, then the costs.  A flagged utterance has post and coef 0 and risk NaN.  N = 1 gives coef exactly 0.
+ *   Ranges: 1 <= N <= 256, B >= 1.
+ *
+ * mdd_ctc_nbest_grad: grad_dev [T,B,C] = sum_n coef[n,b] g_n[t,b,c], every element written, frames >= len zeros.  Inputs as mdd_ctc_nbest
+ *   takes them (len clamped to [0,T], nids to [0,max_len], ids past a row's length never read, no id an index before its range check).
+ *   A rank with coef == 0 is not scanned and contributes nothing whatever its ids are: a list with one live hypothesis costs one lattice.
+ *   The exp(lp) term is added once, as exp(lp) * sum_n coef (the sum in fp64, ascending n).  Lattice values are fp64 with fp32
+ *   increments, as mdd_ctc_loss keeps them; with N = 1 and coef = 1 the output has the bits of mdd_ctc_loss's gradient.
+ *   loglik_dev [N,B] (nullable): written for every rank; a scanned rank has the bits of mdd_ctc_nbest's value for that (n, b) (NaN where
+ *   a label is outside [0, C), 0 / -inf for an utterance without frames), a skipped rank (coef == 0) NaN.
+ *   flag_dev [B]: 0 fine; 1 a rank with coef != 0 is no CTC path of the frames (nll = +inf: also an utterance without frames and a live
+ *   hypothesis with ids); 2 a rank with coef != 0 has a label outside [0, C), or a coef is not finite (2 wins over 1).  A flagged
+ *   utterance gets all-zero gradient rows and changes nothing in its neighbours.
+ *   Ranges: mdd_ctc_nbest's (1 <= N <= 256, 1 <= B <= 65535, 2 <= C <= 256, 0 <= blank < C, 0 <= max_len <= min(pitch, 255), T >= 1), and
+ *   the workgroup's LDS -- the log-prob block, an accumulator of its size and ctc_wave_kernel's arrays, 8 T C + 2560 NL + 4 (C + 1) bytes
+ *   within 160 KiB less 256: T <= 425 at C = 45 and max_len 255 -- which mdd_ctc_nbest_grad_fits answers (host only, 1 / 0); every shape
+ *   it accepts mdd_ctc_nbest_fits accepts.  A caller takes mdd_ctc_loss per rank otherwise.
+ *   Grid (groups of ranks, B), eight waves; a workgroup runs its ranks in ascending order, alpha and beta side by side on two waves,
+ *   then all waves add coef * occupancy into an LDS accumulator whose every element has one owning lane.  With several groups each
+ *   stores a partial slab and a second kernel adds the slabs in ascending group order.  No floating-point atomics, no switch: the same
+ *   call gives the same bits.  The counts are one host function, ctc_nbest_grad_plan in csrc/plan.h.
+ *   workspace_dev: mdd_ctc_nbest_grad_workspace_bytes (0 outside the ranges) or more, or NULL (allocated on the stream for the call).
+ * Both entries launch on the caller's stream and synchronise nothing.  Bad arguments (a range above, a required pointer NULL, a refused
+ *   shape, a caller workspace that is too small) return MDD_ERR_ARG before any device work, with nothing written; the message starts
+ *   with the entry's name and names the argument. */
+int mdd_nbest_risk(const double *loglik_dev /* [N,B] */, const int32_t *cost_dev /* [N,B] */, const int32_t *status_dev /* [B], nullable */,
+                   int32_t N, int32_t B, double *post_dev /* [N,B] */, double *risk_dev /* [B] */, double *coef_dev /* [N,B] */,
+                   int32_t *flag_dev /* [B] */, void *stream);
+int mdd_ctc_nbest_grad_fits(int32_t T, int32_t C, int32_t max_len);    /* 1 / 0, host only */
+int64_t mdd_ctc_nbest_grad_workspace_bytes(int32_t T, int32_t B, int32_t C, int32_t N, int32_t max_len);
+int mdd_ctc_nbest_grad(const float *logp_dev /* [T,B,C] */, int32_t T, int32_t B, int32_t C, const int32_t *len_dev /* [B] */,
+                       const int32_t *ids_dev /* [N,B,pitch] */, int32_t pitch, const int32_t *nids_dev /* [N,B] */,
+                       int32_t N, int32_t max_len, int32_t blank, const double *coef_dev /* [N,B] */,
+                       double *loglik_dev /* [N,B], nullable */, float *grad_dev /* [T,B,C] */, int32_t *flag_dev /* [B] */,
+                       void *workspace_dev, int64_t workspace_bytes, void *stream);
+
 /* ---- A12: nn.CTCLoss(reduction='sum') pieces (AA/steps/train_ctc.py:72,186): alpha/beta lattice.
  * logp_dev [T,B,C], targets_dev [B,Lmax] int64 (padded), in_len_dev/tgt_len_dev [B] int64 ->
  * nll_dev [B] (per-utterance negative log-likelihood; the reference's loss is their sum; +inf for an utterance with no
