@@ -150,7 +150,7 @@ def lib():
     L.mdd_train_sync.argtypes = [vp, vp]
     L.mdd_train_set_precision.argtypes = [vp, C.c_int32]
     L.mdd_diag_gemm_ops.argtypes = [C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
-    L.mdd_adam_step.argtypes = [vp, vp, vp, vp, vp, i32, i32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, vp]
+    L.mdd_adam_step.argtypes = [vp, vp, vp, vp, vp, i32, i32, C.c_float, C.c_double, C.c_double, C.c_float, C.c_float, vp]    # the betas travel as doubles
     _lib = L
     return L
 

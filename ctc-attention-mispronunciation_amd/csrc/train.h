@@ -57,9 +57,9 @@ template <class F> int sum_parts(DeviceBuf &part, int parts, size_t n, float *ou
     if (int rc = partials(part.p)) return rc;
     return launch_reduce_parts(part.p, parts, n, out, st);
 }
-int launch_adam_multi(float *const *p, float *const *g, float *const *m, float *const *v, const int64_t *numel, int n, float lr, float b1, float b2, float eps,
+int launch_adam_multi(float *const *p, float *const *g, float *const *m, float *const *v, const int64_t *numel, int n, float lr, double b1, double b2, float eps,
                       float wd, int step, hipStream_t st);
-int launch_adam(float *p, const float *g, float *m, float *v, size_t n, float lr, float b1, float b2, float eps, float wd, int step, hipStream_t st);
+int launch_adam(float *p, const float *g, float *m, float *v, size_t n, float lr, double b1, double b2, float eps, float wd, int step, hipStream_t st);
 
 // ---- lstm_step.hip: the generic step kernels saving gates and cell states, the weight layouts, the per-step backward
 struct LstmBwdArgs {

@@ -122,29 +122,34 @@ int launch_reduce_parts(const float *part, int parts, size_t n, float *out, hipS
 
 // ------------------------------------------------------------------------------------------------ Adam (torch.optim.Adam semantics, L2 weight decay)
 // g' = g + wd * p;  m = b1 m + (1-b1) g';  v = b2 v + (1-b2) g'^2;  p -= lr / (1 - b1^t) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
-__global__ void adam_kernel(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m, float *__restrict__ v, size_t n, float lr, float b1,
-                            float b2, float eps, float wd, float bc1, float bc2_sqrt) {
+// The betas arrive as doubles and everything that depends on them alone is formed in double on the host and rounded ONCE, as torch does
+// (1 - beta2 reaches ATen as the double 0.001 and becomes 0.001f): 1.f - 0.999f is 0.0009999871, -1.29e-5 relative, which exp_avg_sq carried.
+struct AdamCoef { float b1, b2, omb1, omb2, bc1, bc2_sqrt; };       // beta, 1 - beta, 1 - beta1^step, sqrt(1 - beta2^step)
+static AdamCoef adam_coef(double b1, double b2, int step) {
+    return {(float)b1, (float)b2, (float)(1.0 - b1), (float)(1.0 - b2), (float)(1.0 - std::pow(b1, (double)step)), (float)std::sqrt(1.0 - std::pow(b2, (double)step))};
+}
+__global__ void adam_kernel(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m, float *__restrict__ v, size_t n, float lr, AdamCoef c,
+                            float eps, float wd) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         const float gi = g[i] + wd * p[i];
-        const float mi = b1 * m[i] + (1.f - b1) * gi;
-        const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+        const float mi = c.b1 * m[i] + c.omb1 * gi;
+        const float vi = c.b2 * v[i] + c.omb2 * gi * gi;
         m[i] = mi; v[i] = vi;
-        p[i] -= (lr / bc1) * (mi / (sqrtf(vi) / bc2_sqrt + eps));
+        p[i] -= (lr / c.bc1) * (mi / (sqrtf(vi) / c.bc2_sqrt + eps));
     }
 }
-int launch_adam(float *p, const float *g, float *m, float *v, size_t n, float lr, float b1, float b2, float eps, float wd, int step, hipStream_t st) {
-    const float bc1 = 1.f - powf(b1, (float)step), bc2s = sqrtf(1.f - powf(b2, (float)step));
-    hipLaunchKernelGGL(adam_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 2048)), dim3(256), 0, st, p, g, m, v, n, lr, b1, b2, eps, wd, bc1, bc2s);
+int launch_adam(float *p, const float *g, float *m, float *v, size_t n, float lr, double b1, double b2, float eps, float wd, int step, hipStream_t st) {
+    hipLaunchKernelGGL(adam_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 2048)), dim3(256), 0, st, p, g, m, v, n, lr, adam_coef(b1, b2, step), eps, wd);
     MDD_LAUNCH_CHECK();
     return MDD_OK;
 }
 
-// The same update over up to 48 tensors in ONE launch (the model has 55 parameter tensors, most of them small: one launch each was a
+// The same update over up to 48 tensors in ONE launch (the reference model has 43 parameter tensors -- and 12 buffers, which Adam never sees --, most of them small: one launch each was a
 // quarter millisecond of launches per step).  The table travels in the kernel arguments; workgroup w works on 1024-element chunk
 // w - first[t] of tensor t (first[] = running chunk counts).
 constexpr int ADAM_MT = 48;
 struct AdamTable { float *p[ADAM_MT]; const float *g[ADAM_MT]; float *m[ADAM_MT]; float *v[ADAM_MT]; unsigned long long n[ADAM_MT]; int first[ADAM_MT + 1]; int count; };
-__global__ __launch_bounds__(256) void adam_multi_kernel(AdamTable tb, float lr, float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt) {
+__global__ __launch_bounds__(256) void adam_multi_kernel(AdamTable tb, float lr, AdamCoef c, float eps, float wd) {
     int t = 0;
     while (t + 1 < tb.count && (int)blockIdx.x >= tb.first[t + 1]) t++;            // (uniform per workgroup; <= 48 steps)
     const size_t i0 = (size_t)((int)blockIdx.x - tb.first[t]) * 1024;
@@ -155,16 +160,16 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(AdamTable tb, float lr,
         const size_t i = i0 + threadIdx.x + 256 * k;
         if (i < tb.n[t]) {
             const float gi = g[i] + wd * p[i];
-            const float mi = b1 * m[i] + (1.f - b1) * gi;
-            const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+            const float mi = c.b1 * m[i] + c.omb1 * gi;
+            const float vi = c.b2 * v[i] + c.omb2 * gi * gi;
             m[i] = mi; v[i] = vi;
-            p[i] -= (lr / bc1) * (mi / (sqrtf(vi) / bc2_sqrt + eps));
+            p[i] -= (lr / c.bc1) * (mi / (sqrtf(vi) / c.bc2_sqrt + eps));
         }
     }
 }
-int launch_adam_multi(float *const *p, float *const *g, float *const *m, float *const *v, const int64_t *numel, int n, float lr, float b1, float b2, float eps,
+int launch_adam_multi(float *const *p, float *const *g, float *const *m, float *const *v, const int64_t *numel, int n, float lr, double b1, double b2, float eps,
                       float wd, int step, hipStream_t st) {
-    const float bc1 = 1.f - powf(b1, (float)step), bc2s = sqrtf(1.f - powf(b2, (float)step));
+    const AdamCoef coef = adam_coef(b1, b2, step);
     int i = 0;
     while (i < n) {
         AdamTable tb;
@@ -176,7 +181,7 @@ int launch_adam_multi(float *const *p, float *const *g, float *const *m, float *
             tb.first[c + 1] = tb.first[c] + (int)((numel[i] + 1023) / 1024);
         }
         if (tb.count == 0) break;
-        hipLaunchKernelGGL(adam_multi_kernel, dim3((unsigned)tb.first[tb.count]), dim3(256), 0, st, tb, lr, b1, b2, eps, wd, bc1, bc2s);
+        hipLaunchKernelGGL(adam_multi_kernel, dim3((unsigned)tb.first[tb.count]), dim3(256), 0, st, tb, lr, coef, eps, wd);
         MDD_LAUNCH_CHECK();
     }
     return MDD_OK;

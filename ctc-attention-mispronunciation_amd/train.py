@@ -288,7 +288,8 @@ class MWERLoss(torch.nn.Module):
 
 class Adam(torch.optim.Optimizer):
     """torch.optim.Adam's update (no amsgrad) with the arithmetic in mdd_adam_step: g += weight_decay * p; biased first and
-    second moments; bias-corrected step.  State keys ('step', 'exp_avg', 'exp_avg_sq') follow torch's, so a state_dict saved
+    second moments; bias-corrected step (the betas reach the library as the Python doubles they are: 1 - beta and the bias corrections are
+    rounded to fp32 once, as torch rounds them, so exp_avg_sq stays fp32-close to torch's).  State keys ('step', 'exp_avg', 'exp_avg_sq') follow torch's, so a state_dict saved
     by either loads into the other (save_package keeps 'optim_dict', model_ctc.py:262)."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0):
@@ -321,6 +322,6 @@ class Adam(torch.optim.Optimizer):
                 with torch.cuda.device(grp[0].device):
                     _lib.check(L.mdd_adam_step(arr(grp), arr([p.grad for p in grp]), arr([self.state[p]["exp_avg"] for p in grp]),
                                                arr([self.state[p]["exp_avg_sq"] for p in grp]), numel, n, step, C.c_float(group["lr"]),
-                                               C.c_float(group["betas"][0]), C.c_float(group["betas"][1]), C.c_float(group["eps"]),
+                                               C.c_double(group["betas"][0]), C.c_double(group["betas"][1]), C.c_float(group["eps"]),
                                                C.c_float(group["weight_decay"]), _lib.current_stream_ptr()))
         return loss

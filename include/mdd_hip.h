@@ -644,6 +644,9 @@ int mdd_eval_batch(const int32_t *dec, const int32_t *dec_len, const int32_t *la
  *                               backward or forward; without one, mdd_train_backward returns MDD_ERR_ARG ("forward first") and
  *                               writes nothing -- also for a second backward on the same forward (autograd's retain_graph).
  *   mdd_adam_step               torch.optim.Adam over n tensors (train_ctc.py:187: lr 1e-3, weight_decay 5e-4 added to the gradient)
+ *                               beta1, beta2 in [0, 1) are DOUBLES: 1 - beta, 1 - beta1^step and sqrt(1 - beta2^step) are formed in double on the
+ *                               host and rounded to float once, as torch rounds them (1.f - 0.999f would be 1.3e-5 off, and exp_avg_sq with it).
+ *                               Entries with a NULL parameter or gradient or numel <= 0 are passed over; step counts from 1.
  * Arithmetic: three modes, chosen per handle by mdd_train_set_precision (or MDD_TRAIN_PRECISION at create) and read by the next FORWARD:
  * the saved forward remembers its mode (and its conv1 path), and its backward follows that, whatever the handle's mode is by then.  They differ only in how the
  * LARGE CONTRACTIONS of the step run -- the BiLSTM and text-encoder input projections, dW_ih, the dW_hh products and dX:
@@ -673,7 +676,7 @@ int mdd_train_forward(mdd_train_ws *w, float *const *tensors, const float *x_dev
 int mdd_train_backward(mdd_train_ws *w, float *const *tensors, const float *dlogp_dev, float *const *grads, void *stream);
 int mdd_train_sync(mdd_train_ws *w, void *stream);
 int mdd_adam_step(float *const *params, float *const *grads, float *const *exp_avg, float *const *exp_avg_sq, const int64_t *numel, int32_t n,
-                  int32_t step, float lr, float beta1, float beta2, float eps, float weight_decay, void *stream);
+                  int32_t step, float lr, double beta1, double beta2, float eps, float weight_decay, void *stream);
 
 /* ---- Diagnostics (test and measurement aid; no reference counterpart).
  * mdd_diag_gemm_ph8: race screen of the 8-phase projection GEMM -- the same pseudo-random operands through the single-barrier
